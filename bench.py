@@ -14,7 +14,14 @@ configs[1]: "3D U-Net ICL 96^3, num_classes=2, batch=2, 1xMI355X"); forward of b
 5-term loss, backward, gradient all-reduce over RCCL when N>1, SGD(momentum, wd).  Dropout p=0.3 and
 DropPath 0.02 are active as in training.  value = volumes processed by all ranks / max-over-ranks time.
 
-Extra objects on the JSON line (tier contract ④):
+A plain run sets up, warms up, times the K steps and prints the JSON line; nothing else runs on the GPU (--feed and --loop reference
+add their own timings when asked for).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed (its loss terms, and the model's parameters
+and buffers, large tensors as a fixed sample) to DIR/*.npy; the inputs are seeded, so two builds can be compared output for output.
+--full adds what takes runs of its own: the objects below, config.exact_fp32_mfma_convolutions, config.other_workloads and
+config.ddp_phases (each can still be turned off with its --no-* option).
+
+Extra objects on the JSON line with --full (tier contract ④):
   roofline      dominant kernel = the forward/input-gradient convolution instantiation with the largest total time
                 (named exactly as rocprofv3 --stats lists it; the C ABI reports which template its launcher picked):
                 algorithmic FLOPs of its launches / their HIP-event durations (events on the launch stream), against the
@@ -258,6 +265,36 @@ def hbm_traffic(kernel: str):
         return None
 
 
+DUMP_SAMPLE = 1 << 16      # elements kept of a larger tensor by --dump-outputs
+DUMP_LIMIT = 64 << 20      # bytes of one dump
+
+
+def dump_outputs(out_dir: str, losses, model):
+    """--dump-outputs: what a caller of the timed step holds after its last step — the loss terms ``ICLTrainer.step`` returned and the
+    model's updated parameters and buffers (state_dict names) — as DIR/loss.<term>.npy and DIR/state.<name>.npy.  A tensor of more
+    than DUMP_SAMPLE elements is written flat, as the elements at DUMP_SAMPLE positions drawn by a generator seeded with the CRC of its
+    name: the same positions in every run and every build.  float32 / float64 tensors keep their type, integer ones become float64."""
+    import zlib
+    import numpy as np
+    named = [(f"loss.{k}", v) for k, v in losses.items()] + [(f"state.{k}", v) for k, v in model.state_dict().items()]
+    arrays = {}
+    for name, t in named:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, flat.numel(), DUMP_SAMPLE))
+            a = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        else:
+            a = flat.cpu().numpy().reshape(tuple(t.shape))
+        arrays[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit; nothing was written")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays, {total / 2**20:.1f} MB -> {out_dir}", file=sys.stderr, flush=True)
+
+
 def self_launch(args, argv) -> int:
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start torch.distributed.run as a child process (one rank per
     GPU, rendezvous on 127.0.0.1) BEFORE anything initialises the GPU in this process — `torch.cuda.device_count()` does not — and
@@ -316,6 +353,13 @@ def main():
     ap.add_argument("--num-classes", type=int, default=2)
     ap.add_argument("--model", default="unet_3D_icl", choices=["unet_3D_icl", "swinunetr_icl"],
                     help="unet_3D_icl = BASELINE configs[1] (the headline line); swinunetr_icl = configs[3]")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region also run what it does not need: the exact-fp32 comparison, the per-kernel roofline, "
+                         "config.other_workloads, the CPU baseline and (N > 1) config.ddp_phases; the --no-* options below turn single "
+                         "ones off again")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (loss terms; parameters and buffers, tensors above 65,536 elements as a "
+                         "fixed sample) to DIR/<name>.npy, float32 / float64, at most 64 MB")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--other-workload", default=None, metavar="MODEL:NC",
@@ -346,6 +390,8 @@ def main():
                     help="exercise ONLY the multi-rank plumbing (self-launch, rendezvous, barrier-bracketed timing, MAX over ranks, "
                          "rank-0 JSON relay) on a gloo group with a sleep as the step: no GPU, no kernels; used by tests/")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.other_workload:
         if not torch.cuda.is_available():
@@ -475,8 +521,11 @@ def main():
         dt = float(t.item())
     volumes = 2 * world * args.steps
     value = volumes / dt
+    if args.dump_outputs and rank == 0:
+        # before anything below steps the trainer again
+        dump_outputs(args.dump_outputs, last, trainer.model)
     ddp_phases = None
-    if use_ddp and graphed and trainer.graph_update is not None:
+    if args.full and use_ddp and graphed and trainer.graph_update is not None:
         # where a data-parallel step spends its time (five more steps, after the timed region; MAX over ranks per phase): the first real
         # scaling record explains itself — backward is compute, exposed_collective is what xGMI adds, update grows with the gathered rows
         trainer.time_phases = True
@@ -558,7 +607,7 @@ def main():
                     "icl_trainer_eager_ms_per_step": round(eager_ms, 3)}
 
     exact = None
-    if rank == 0 and world == 1 and not args.no_exact_compare and os.environ.get("ICL_CONV_SPLIT", "1") != "0":
+    if args.full and rank == 0 and world == 1 and not args.no_exact_compare and os.environ.get("ICL_CONV_SPLIT", "1") != "0":
         # the same step with every convolution on the exact-fp32 MFMA kernels (ICL_CONV_SPLIT=0), for reference: a second model and
         # trainer (own capture), timed the same way, after the headline region
         os.environ["ICL_CONV_SPLIT"] = "0"
@@ -588,7 +637,7 @@ def main():
             os.environ["ICL_CONV_SPLIT"] = "1"
 
     roof = None
-    if rank == 0 and not args.no_kernel_timer:
+    if args.full and rank == 0 and not args.no_kernel_timer:
         trainer.graph = trainer.graph_forward = trainer.graph_update = None   # per-kernel HIP-event timing needs eager launches ...
         trainer.ddp = None                              # ... of this rank's step alone: the other ranks are done
         side_was = ops.SideStream.enabled
@@ -729,7 +778,7 @@ def main():
                        **({"feed": feed} if feed else {})},
             "roofline": roof,
         }
-        if world == 1 and not use_ddp and not args.no_other_workloads and args.model == "unet_3D_icl" and nc == 2:
+        if args.full and world == 1 and not use_ddp and not args.no_other_workloads and args.model == "unet_3D_icl" and nc == 2:
             # BASELINE.json configs[4] and configs[3] on this GPU, after the headline region and before the CPU baseline
             del trainer, model
             trainer = model = None
@@ -738,7 +787,7 @@ def main():
             for key, (mname, mnc) in (("unet3d_icl_nc16", ("unet_3D_icl", 16)), ("swinunetr_icl_nc2", ("swinunetr_icl", 2))):
                 other[key] = other_workload_child(mname, mnc, 10, args.warmup)
             out["config"]["other_workloads"] = other
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             trainer = model = None
             torch.cuda.empty_cache()
             out["cpu_baseline"] = cpu_baseline(nc, args.model)

@@ -10,10 +10,10 @@ cd "$(dirname "$0")/.." || exit 1
 O=gpurun_out; R=${ROUND:-r6}; mkdir -p $O
 export ICL_BENCH_SHARE_GPU=1 ICL_BENCH_BACKEND=gloo
 for n in 2 4 8; do
-  timeout 1500 python bench.py --gpus $n --steps 3 --warmup 2 --no-cpu-baseline --no-exact-compare --no-kernel-timer --no-other-workloads > $O/${R}_ddp_rehearsal_${n}_ranks_nc2.json 2> $O/${R}_ddp_rehearsal_${n}_ranks_nc2.err
+  timeout 1500 python bench.py --full --gpus $n --steps 3 --warmup 2 --no-cpu-baseline --no-exact-compare --no-kernel-timer --no-other-workloads > $O/${R}_ddp_rehearsal_${n}_ranks_nc2.json 2> $O/${R}_ddp_rehearsal_${n}_ranks_nc2.err
   echo "ranks=$n nc=2 rc=$?"; tail -c 400 $O/${R}_ddp_rehearsal_${n}_ranks_nc2.json
 done
-ICL_DDP_SHARD_ROWS=768 timeout 2400 python bench.py --gpus 8 --steps 3 --warmup 2 --num-classes 16 --no-cpu-baseline --no-exact-compare --no-kernel-timer --no-other-workloads > $O/${R}_ddp_rehearsal_8_ranks_nc16.json 2> $O/${R}_ddp_rehearsal_8_ranks_nc16.err
+ICL_DDP_SHARD_ROWS=768 timeout 2400 python bench.py --full --gpus 8 --steps 3 --warmup 2 --num-classes 16 --no-cpu-baseline --no-exact-compare --no-kernel-timer --no-other-workloads > $O/${R}_ddp_rehearsal_8_ranks_nc16.json 2> $O/${R}_ddp_rehearsal_8_ranks_nc16.err
 echo "ranks=8 nc=16 rc=$?"; tail -c 400 $O/${R}_ddp_rehearsal_8_ranks_nc16.json
 unset ICL_BENCH_SHARE_GPU ICL_BENCH_BACKEND
 for nc in 2 16; do

@@ -49,7 +49,7 @@ PY
     critical-path) python tools/critical_path.py 2>&1 | tail -${TAIL:-24} ;;
     timeline)
         ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d "$O/tl_prof" -o b --output-format csv -- python3 "$R/bench.py" \
-            --no-cpu-baseline --no-exact-compare --no-other-workloads --launch graph --steps 8 --warmup 2 > /dev/null 2>&1 )
+            --full --no-cpu-baseline --no-exact-compare --no-other-workloads --launch graph --steps 8 --warmup 2 > /dev/null 2>&1 )
         T=$(find "$O/tl_prof" -name "*kernel_trace.csv" | head -1)
         python3 tools/timeline.py "$T" 3 0.25 > "$O/timeline.txt" 2>&1
         python3 tools/queue_tail.py "$T" 70 > "$O/queue_tails.txt" 2>&1      # the tails of the backward chains, per hardware queue

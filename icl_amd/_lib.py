@@ -125,6 +125,8 @@ _SIGNATURES = {
     "icl_loss_bwd_multi": (c_int, [P, I, P]),
     "icl_qchain_stage": (c_int, [P, P]),
     "icl_qchain_wgrad": (c_int, [P, P, P, P, P, P, P, P, I, P]),
+    "icl_seg_metrics_ws_bytes": (c_int64, [I, I, I, I]),
+    "icl_seg_metrics": (c_int, [P, I, P, I, I, I, I, I, I, P, P, P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -23,6 +23,7 @@
 #include "kernels/gemm.h"
 #include "kernels/datafeed.h"
 #include "kernels/qchain.h"
+#include "kernels/metrics.h"
 
 #ifdef ICL_TWO_UNITS
 // product build: this instantiation lives in icl_hip_noslp.hip (compiled with -fno-slp-vectorize; the reason is in that file's header)
@@ -2361,3 +2362,101 @@ int icl_qchain_wgrad(const void* const* g, const void* const* x, void* const* dw
   ICL_LAUNCH(icl::qc_wgrad_kernel, dim3(grid_for(most, 256, 1024), count), dim3(256), 0, (hipStream_t)stream, j);
   return check_launch("qc_wgrad");
 }
+
+// ---------------------------------------------------------------- validation Dice / HD95 counts and order statistics (kernels/metrics.h)
+namespace {
+
+struct SegWs {
+  unsigned* cnt; int* box; unsigned* flags; unsigned* hist; unsigned char* bp; unsigned char* bg; int* da; int* db;
+  int64_t zero_bytes, total;
+};
+
+inline int64_t seg_align(int64_t b) { return (b + 255) / 256 * 256; }
+
+SegWs seg_layout(char* base, int n0, int n1, int n2, int nc) {
+  SegWs w{};
+  const int64_t v = (int64_t)n0 * n1 * n2;
+  const int64_t nbins = (int64_t)(n0 - 1) * (n0 - 1) + (int64_t)(n1 - 1) * (n1 - 1) + (int64_t)(n2 - 1) * (n2 - 1) + 1;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += seg_align(bytes); return p; };
+  w.cnt = (unsigned*)take((int64_t)nc * icl::kSegCnt * 4);
+  w.flags = (unsigned*)take((int64_t)2 * nc * (n0 + n1 + n2) * 4);
+  w.hist = (unsigned*)take(nbins * 4);
+  w.zero_bytes = off;                       // counters, presence flags and histogram start at zero
+  w.box = (int*)take((int64_t)nc * 16 * 4);
+  w.bp = (unsigned char*)take(v);
+  w.bg = (unsigned char*)take(v);
+  w.da = (int*)take(v * 4);
+  w.db = (int*)take(v * 4);
+  w.total = off;
+  return w;
+}
+
+bool seg_shape_ok(int n0, int n1, int n2, int nc) {
+  if (n0 < 1 || n1 < 1 || n2 < 1 || nc < 2 || nc > icl::kSegMaxClasses) return false;
+  const int64_t v = (int64_t)n0 * n1 * n2;
+  const int64_t nbins = (int64_t)(n0 - 1) * (n0 - 1) + (int64_t)(n1 - 1) * (n1 - 1) + (int64_t)(n2 - 1) * (n2 - 1) + 1;
+  return v <= 0x7fffffffLL && nbins < (int64_t)icl::kSegInf;      // 32-bit counters and squared distances
+}
+
+template <typename TP, typename TG>
+void seg_border_launch(const void* pred, const void* gt, const SegWs& w, int n0, int n1, int n2, int nc, int all_border, hipStream_t st) {
+  ICL_LAUNCH((icl::seg_border_kernel<TP, TG>), dim3(grid_for((long)n0 * n1 * n2, 256)), dim3(256), 0, st, (const TP*)pred, (const TG*)gt, w.bp,
+             w.bg, w.cnt, w.flags, n0, n1, n2, nc, all_border);
+}
+
+template <typename TP>
+int seg_border_dispatch_gt(const void* pred, const void* gt, int gt_dtype, const SegWs& w, int n0, int n1, int n2, int nc, int all_border,
+                           hipStream_t st) {
+  switch (gt_dtype) {
+    case 1: seg_border_launch<TP, uint8_t>(pred, gt, w, n0, n1, n2, nc, all_border, st); return 0;
+    case 8: seg_border_launch<TP, long long>(pred, gt, w, n0, n1, n2, nc, all_border, st); return 0;
+    default: return -1;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t icl_seg_metrics_ws_bytes(int n0, int n1, int n2, int num_classes) {
+  if (!seg_shape_ok(n0, n1, n2, num_classes)) return -1;
+  return seg_layout(nullptr, n0, n1, n2, num_classes).total;
+}
+
+int icl_seg_metrics(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int n0, int n1, int n2, int num_classes, int all_border,
+                    int64_t* out, void* ws, void* stream) {
+  if (!pred || !gt || !out || !ws || !seg_shape_ok(n0, n1, n2, num_classes))
+    return fail(-1, "seg_metrics: bad argument (2 <= num_classes <= %d, n0 n1 n2 <= 2^31 - 1 voxels, workspace of icl_seg_metrics_ws_bytes)",
+                icl::kSegMaxClasses);
+  const int nc = num_classes;
+  hipStream_t st = (hipStream_t)stream;
+  const SegWs w = seg_layout((char*)ws, n0, n1, n2, nc);
+  ICL_MEMSET_ASYNC(ws, 0, (size_t)w.zero_bytes, st);
+  int rc;
+  switch (pred_dtype) {
+    case 1: rc = seg_border_dispatch_gt<uint8_t>(pred, gt, gt_dtype, w, n0, n1, n2, nc, all_border ? 1 : 0, st); break;
+    case 8: rc = seg_border_dispatch_gt<long long>(pred, gt, gt_dtype, w, n0, n1, n2, nc, all_border ? 1 : 0, st); break;
+    default: rc = -1;
+  }
+  if (rc) return fail(-1, "seg_metrics: label element size must be 1 (uint8) or 8 (int64)");
+  if (int e = check_launch("seg_border")) return e;
+  ICL_LAUNCH(icl::seg_bbox_kernel, dim3(nc), dim3(256), 0, st, (const unsigned*)w.cnt, (const unsigned*)w.flags, w.box, n0, n1, n2, nc);
+  if (int e = check_launch("seg_bbox")) return e;
+  const dim3 grid(grid_for((long)n0 * n1 * n2, 256));      // enough for the largest region; workgroups past a class's region exit at once
+  for (int k = 1; k < nc; ++k) {
+    for (int dir = 0; dir < 2; ++dir) {      // 0: distances from dP to dG (features dG, queries dP); 1: the other way round
+      const unsigned char* feat = dir ? w.bp : w.bg;
+      const unsigned char* query = dir ? w.bg : w.bp;
+      ICL_LAUNCH(icl::seg_edt_axis2_kernel, grid, dim3(256), 0, st, feat, (const int*)w.box, w.da, k, dir, n1, n2);
+      ICL_LAUNCH(icl::seg_edt_axis1_kernel, grid, dim3(256), 0, st, (const int*)w.da, (const int*)w.box, w.db, k, dir);
+      ICL_LAUNCH(icl::seg_edt_axis0_hist_kernel, grid, dim3(256), 0, st, (const int*)w.db, query, (const int*)w.box, w.hist, k, dir, n1, n2);
+    }
+    ICL_LAUNCH(icl::seg_select_kernel, dim3(1), dim3(icl::kSegSelectThreads), 0, st, (const unsigned*)w.cnt, (const int*)w.box, w.hist,
+               (long long*)out, k);
+    if (int e = check_launch("seg_edt / seg_select")) return e;
+  }
+  return 0;
+}
+
+}  // extern "C"

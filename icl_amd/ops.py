@@ -2727,3 +2727,49 @@ def soft_dice_loss(a: torch.Tensor, b: torch.Tensor):
 def softmax_mse(a: torch.Tensor, b: torch.Tensor):
     """mean((softmax(a,1) - softmax(b,1))^2) — one scale of softmax_mse_loss (losses.py:82-87); target detached."""
     return _FusedLoss.apply(a, b.detach(), None, 3, False)[0]
+
+
+# --------------------------------------------------------------------------------------
+# Validation metrics — cal_metric / calculate_metric_percase of every foreground class (val_3D.py:85-97, val_2D.py:10-22)
+# --------------------------------------------------------------------------------------
+
+_SEG_DTYPES = {torch.uint8: 1, torch.bool: 1, torch.int64: 8}
+
+
+def seg_metrics_shape(t: torch.Tensor):
+    """(n0, n1, n2, all_border) for a label map the metric kernels take: 3-D, or 3-D after leading axes of length 1 (the AMOS path scores
+    [1, D, H, W] arrays: under the N-D connectivity-1 erosion such an axis makes every voxel of a class a surface voxel).  None otherwise."""
+    shape = tuple(t.shape)
+    if len(shape) < 3 or any(s != 1 for s in shape[:-3]):
+        return None
+    return shape[-3], shape[-2], shape[-1], int(len(shape) > 3)
+
+
+def seg_metrics(pred: torch.Tensor, gt: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """Per-class integer records of Dice and HD95 (include/icl_hip.h icl_seg_metrics): int64 [num_classes - 1, 6] on the device of the
+    maps, row c - 1 = (|P|, |G|, |P & G|, n, s0, s1) for P = pred == c, G = gt == c; n = number of surface voxels of both, s0 / s1 the
+    squared surface distances at ranks floor(0.95 (n - 1)) and the next one (-1 when P or G is empty).  Asynchronous on the current
+    stream; the maps stay where they are.  Label dtypes: uint8 / bool (h5 labels) and int64 (argmax); pred and gt may differ."""
+    if pred.shape != gt.shape:
+        raise ValueError(f"seg_metrics: shapes differ {tuple(pred.shape)} vs {tuple(gt.shape)}")
+    geo = seg_metrics_shape(pred)
+    if geo is None:
+        raise ValueError(f"seg_metrics: needs a 3-D label map (leading axes of length 1 allowed), got {tuple(pred.shape)}")
+    for t in (pred, gt):
+        if t.dtype not in _SEG_DTYPES:
+            raise TypeError(f"seg_metrics: unsupported label dtype {t.dtype}")
+        if not t.is_cuda and not _lib.host_pointers_ok():
+            raise RuntimeError("icl_amd: HIP kernels need device tensors (no CPU fallback)")
+    if pred.device != gt.device:
+        raise ValueError("seg_metrics: pred and gt on different devices")
+    n0, n1, n2, all_border = geo
+    pred, gt = pred.contiguous(), gt.contiguous()
+    L = _lib.lib()
+    nbytes = L.icl_seg_metrics_ws_bytes(n0, n1, n2, int(num_classes))
+    if nbytes < 0:
+        raise ValueError(f"seg_metrics: shape {(n0, n1, n2)} / num_classes {num_classes} not supported (2 <= num_classes <= 256)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    out = torch.empty((int(num_classes) - 1, 6), dtype=torch.int64, device=pred.device)
+    _lib.check(L.icl_seg_metrics(_ptr(pred), _SEG_DTYPES[pred.dtype], _ptr(gt), _SEG_DTYPES[gt.dtype], n0, n1, n2, int(num_classes), all_border,
+                                 _ptr(out), _ptr(ws), _stream(pred)), "seg_metrics")
+    return out

@@ -133,3 +133,31 @@ def synthetic_labels(shape, seed: int, num_classes: int, device="cpu") -> torch.
     else:
         lab = torch.clamp((u * num_classes).to(torch.int64), 0, num_classes - 1)
     return lab.view(*shape)
+
+
+def synthetic_segmentation(shape, num_classes: int, seed: int, speckle: float = 0.01, scatter: float = 0.0):
+    """Seeded (gt, pred) label maps (numpy uint8 / int64 [shape]) for the validation metrics: per foreground class an ellipsoid in the
+    ground truth and a shifted, resized one in the prediction, both with speckle noise (a fraction ``speckle`` of each ellipsoid's
+    bounding box flipped) so that the surfaces are ragged.  Class c is painted after c - 1 and may cover part of it.  ``scatter``: that
+    fraction of the prediction's voxels, drawn over the WHOLE volume, gets a random foreground class (an early-training prediction:
+    every class's border then spans the volume)."""
+    rng = np.random.default_rng(seed)
+    gt = np.zeros(shape, np.uint8)
+    pred = np.zeros(shape, np.int64)
+    for c in range(1, num_classes):
+        big = num_classes <= 2
+        radii = np.array([s * (rng.uniform(0.2, 0.35) if big else rng.uniform(0.05, 0.12)) for s in shape])
+        center = np.array([rng.uniform(r + 1, s - r - 1) for s, r in zip(shape, radii)])
+        for m, shift, scale in ((gt, 0.0, 1.0), (pred, rng.uniform(-0.15, 0.15, 3) * radii, rng.uniform(0.85, 1.15, 3))):
+            cen, rad = center + shift, radii * scale
+            lo = [max(int(math.floor(a - r)) - 1, 0) for a, r in zip(cen, rad)]
+            hi = [min(int(math.ceil(a + r)) + 2, s) for a, r, s in zip(cen, rad, shape)]
+            idx = np.ogrid[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+            inside = sum(((i - a) / r) ** 2 for i, a, r in zip(idx, cen, rad)) <= 1.0
+            inside ^= rng.random(inside.shape) < speckle
+            sub = m[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]]
+            sub[inside] = c
+    if scatter:
+        hit = rng.random(shape) < scatter
+        pred[hit] = rng.integers(1, num_classes, int(hit.sum()))
+    return gt, pred

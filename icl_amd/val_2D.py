@@ -6,7 +6,8 @@ is resized to ``patch_size`` with ``scipy.ndimage.zoom(order=0)``, pushed throug
 back — but pushes ``slices_per_batch`` slices per forward (eval-mode networks are per-sample: BatchNorm uses its running statistics,
 so batching does not change any slice's logits; the reference runs one slice per forward).  The nearest-neighbour resize stays
 scipy's, so the index mapping is the reference's bit for bit.  Metrics: Dice + HD95 with the reference's empty-mask conventions
-(``icl_amd.val_3D.cal_metric``; HD95 parity unpinned — MedPy is not installed in the build image).
+(``icl_amd.val_3D.cal_metric``; HD95 parity unpinned — MedPy is not installed in the build image), scored for every class at once by
+the metric kernels when the net is on a HIP device (``val_3D.cal_metric_multiclass``; ``ICL_VAL_METRICS=host``: numpy).
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import numpy as np
 import torch
 from scipy.ndimage import zoom
 
-from .val_3D import binary_dice, binary_hd95
+from .val_3D import _upload_label, binary_dice, binary_hd95, cal_metric_multiclass, val_metrics_mode
 
 
 def calculate_metric_percase(pred, gt):
@@ -45,12 +46,23 @@ def _predict_volume(image, net, patch_size, inference_kw, slices_per_batch):
     return prediction
 
 
+def _score_volume(prediction, label, net, classes):
+    """``[calculate_metric_percase(prediction == i, label == i) for i in 1..classes-1]``; with the net on a HIP device both maps go up
+    once and every class is scored by the metric kernels (the same values and types: Dice and HD95 are symmetric in their arguments)."""
+    dev = next(net.parameters()).device
+    if dev.type == "cuda" and val_metrics_mode() == "device" and 2 <= classes <= 256:
+        gt = _upload_label(label, dev)
+        if gt is not None and gt.shape == prediction.shape:
+            return cal_metric_multiclass(gt, torch.from_numpy(prediction).to(dev), classes)
+    return [calculate_metric_percase(prediction == i, label == i) for i in range(1, classes)]
+
+
 def test_single_volume_ours(image, label, net, writer=None, iter_num=0, classes=4, patch_size=(224, 224), slices_per_batch=16):
     """val_2D.py:35-54: ``image`` / ``label`` are [1, slices, H, W] tensors (one case of the validation loader)."""
     image = image.squeeze(0).cpu().detach().numpy()
     label = label.squeeze(0).cpu().detach().numpy()
     prediction = _predict_volume(image, net, patch_size, {"inference": True}, slices_per_batch)
-    return [calculate_metric_percase(prediction == i, label == i) for i in range(1, classes)]
+    return _score_volume(prediction, label, net, classes)
 
 
 def test_single_volume(image, label, net, classes, patch_size=(256, 256), slices_per_batch=16):
@@ -58,4 +70,4 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), slices
     image = image.squeeze(0).cpu().detach().numpy()
     label = label.squeeze(0).cpu().detach().numpy()
     prediction = _predict_volume(image, net, patch_size, {}, slices_per_batch)
-    return [calculate_metric_percase(prediction == i, label == i) for i in range(1, classes)]
+    return _score_volume(prediction, label, net, classes)

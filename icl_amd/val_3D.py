@@ -13,6 +13,7 @@ build image, so the HD95 half is "parity unpinned" (DESIGN.md §2).
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -22,6 +23,15 @@ import torch
 def test_single_case_base(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_batch=4,
                           return_score=False):
     """image: numpy [W,H,D] (the reference's h5 layout).  Returns the label map (numpy int64 [W,H,D])."""
+    label_map, score = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes, windows_per_batch)
+    if return_score:
+        return label_map.cpu().numpy(), score.cpu().numpy()
+    return label_map.cpu().numpy()
+
+
+@torch.no_grad()
+def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_batch=4):
+    """``test_single_case_base`` up to the copy to the host: (label map int64 [W,H,D], score [C,W,H,D]) on the net's device."""
     dev = next(net.parameters()).device
     w, h, d = image.shape
     pads = []
@@ -62,9 +72,7 @@ def test_single_case_base(net, net_type, image, stride_xy, stride_z, patch_size,
         sl = tuple(slice(a, a + n) for (a, _), n in zip(pads, (w, h, d)))
         label_map = label_map[sl]
         score = score[(slice(None),) + sl]
-    if return_score:
-        return label_map.cpu().numpy(), score.cpu().numpy()
-    return label_map.cpu().numpy()
+    return label_map, score
 
 
 def binary_dice(pred, gt) -> float:
@@ -107,6 +115,87 @@ def cal_metric(gt, pred):
     return 1, 0
 
 
+# --------------------------------------------------------------------------------------------------------------------
+# All foreground classes at once on the device (kernels/metrics.h, include/icl_hip.h icl_seg_metrics)
+# --------------------------------------------------------------------------------------------------------------------
+
+def val_metrics_mode() -> str:
+    """``ICL_VAL_METRICS``: ``device`` (default) scores label maps that are on a HIP device with the metric kernels, ``host`` forces the
+    numpy path of ``cal_metric`` (A/B runs).  Host data always take the numpy path."""
+    mode = os.environ.get("ICL_VAL_METRICS", "device")
+    if mode not in ("device", "host"):
+        raise ValueError(f"ICL_VAL_METRICS must be 'device' or 'host', got {mode!r}")
+    return mode
+
+
+def hd95_from_order_stats(n: int, sq0: int, sq1: int) -> float:
+    """``np.percentile(x, 95)`` of n >= 2 distances given the SQUARED distances at ranks k0 = floor(0.95 (n - 1)) and k0 + 1 of the sorted
+    set — numpy's ``linear`` method step for step (virtual index (n - 1) * 0.95, gamma its fractional part, ``_lerp``) in float64.
+    sqrt of an exact integer is correctly rounded, so this is bit-equal to the percentile of the distance transform's values."""
+    v = (n - 1) * np.true_divide(95, 100)
+    gamma = v - np.floor(v)
+    a, b = np.sqrt(np.float64(sq0)), np.sqrt(np.float64(sq1))
+    diff = b - a
+    return float(b - diff * (1 - gamma) if gamma >= 0.5 else a + diff * gamma)
+
+
+def _metric_from_record(rec):
+    """One row of ``ops.seg_metrics`` -> what ``cal_metric`` returns for that class (values and types)."""
+    np_, ng, inter, n, sq0, sq1 = (int(v) for v in rec)
+    if np_ > 0 and ng > 0:
+        return 2.0 * inter / float(np_ + ng), hd95_from_order_stats(n, sq0, sq1)
+    if np_ > 0 or ng > 0:
+        return 0, 373.128664
+    return 1, 0
+
+
+def _cal_metric_kernels(gt, pred, num_classes):
+    from . import ops
+    return [_metric_from_record(r) for r in ops.seg_metrics(pred, gt, num_classes).cpu().tolist()]
+
+
+def _device_metrics_apply(gt, pred, num_classes) -> bool:
+    from . import ops
+    return (torch.is_tensor(gt) and torch.is_tensor(pred) and gt.is_cuda and pred.is_cuda and val_metrics_mode() == "device"
+            and 2 <= num_classes <= 256
+            and gt.shape == pred.shape and gt.dtype in ops._SEG_DTYPES and pred.dtype in ops._SEG_DTYPES
+            and ops.seg_metrics_shape(pred) is not None)
+
+
+def cal_metric_multiclass(gt, pred, num_classes):
+    """``[cal_metric(gt == c, pred == c) for c in 1..num_classes-1]`` with identical values and types.  Label maps on a HIP device
+    (uint8 / bool or int64; 3-D, or with leading axes of length 1) are scored by the metric kernels and stay there — six
+    integers per class come back; anything else (and num_classes outside 2..256) takes the numpy path unchanged
+    (``ICL_VAL_METRICS=host`` forces it)."""
+    if _device_metrics_apply(gt, pred, num_classes):
+        return _cal_metric_kernels(gt, pred, num_classes)
+    if torch.is_tensor(gt) and gt.is_cuda:
+        gt = gt.cpu().numpy()
+    if torch.is_tensor(pred) and pred.is_cuda:
+        pred = pred.cpu().numpy()
+    return [cal_metric(gt == c, pred == c) for c in range(1, num_classes)]
+
+
+def _upload_label(label, device):
+    """A host label map as a device tensor of a dtype the metric kernels read (uint8 / bool or int64), or None: the numpy path.
+    Floating label maps (MONAI's ``LoadImaged`` yields float32 labels to the AMOS loop) are taken when every value is an integer, for
+    which ``label == c`` on the floats and on the integers agree; a map holding any other value (a fraction, NaN, beyond +-2^62) is
+    None."""
+    label = np.asarray(label.cpu() if torch.is_tensor(label) else label)
+    if label.dtype.kind == "f":
+        if label.size == 0 or not np.array_equal(label, np.rint(label)):
+            return None
+        lo, hi = float(label.min()), float(label.max())
+        if lo < -2.0 ** 62 or hi > 2.0 ** 62:
+            return None
+        label = label.astype(np.uint8 if lo >= 0 and hi <= 255 else np.int64)
+    elif label.dtype.kind not in "biu":
+        return None
+    if label.dtype not in (np.bool_, np.uint8, np.int64):
+        label = label.astype(np.int64)
+    return torch.as_tensor(np.ascontiguousarray(label), device=device)
+
+
 def test_all_case_base(net, net_type, base_dir, test_list="full_test.list", num_classes=4, patch_size=(48, 160, 160),
                        stride_xy=32, stride_z=24, cases=None):
     """val_3D.py:100-118.  ``cases`` (iterable of (image, label) numpy pairs) replaces the h5 files when given; otherwise
@@ -122,7 +211,15 @@ def test_all_case_base(net, net_type, base_dir, test_list="full_test.list", num_
                     yield h5f["image"][:], h5f["label"][:]
         cases = _gen()
     metric_cal = [[] for _ in range(num_classes - 1)]
+    dev = next(net.parameters()).device
+    on_device = dev.type == "cuda" and val_metrics_mode() == "device" and 2 <= num_classes <= 256
     for image, label in cases:
+        gt = _upload_label(label, dev) if on_device else None
+        if gt is not None:      # the label map stays on the device; the ground truth goes up once per case
+            prediction, _ = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes)
+            for i, m in enumerate(cal_metric_multiclass(gt, prediction, num_classes)):
+                metric_cal[i].append(m)
+            continue
         prediction = test_single_case_base(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=num_classes)
         for i in range(1, num_classes):
             metric_cal[i - 1].append(cal_metric(label == i, prediction == i))
@@ -192,6 +289,13 @@ def test_all_case_amos(net, net_type, val_loader, num_classes=4):
         image, label = batch["image"].to(dev), batch["label"].squeeze(0)
         kw = {"inference": True} if net_type in ("unet_3D_icl", "swinunetr_icl") else {}
         logits = sliding_window_inference(image, (96, 96, 96), 4, net, **kw)
+        if dev.type == "cuda" and val_metrics_mode() == "device":
+            prediction = torch.argmax(logits, dim=1)
+            gt = _upload_label(label, dev)
+            if gt is not None and _device_metrics_apply(gt, prediction, num_classes):
+                for i, m in enumerate(cal_metric_multiclass(gt, prediction, num_classes)):
+                    metric_cal[i].append(m)
+                continue
         prediction = torch.argmax(logits, dim=1).cpu().numpy()
         label = np.asarray(label.cpu() if torch.is_tensor(label) else label)
         for i in range(1, num_classes):

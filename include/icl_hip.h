@@ -459,6 +459,21 @@ int icl_qchain_stage(const IclQcStage* stage, void* stream);
 int icl_qchain_wgrad(const void* const* g, const void* const* x, void* const* dw, void* const* db, const int32_t* rows, const int32_t* n,
                      const int32_t* k, const int32_t* kind, int count, void* stream);
 
+/* ---- validation metrics: Dice and HD95 counts of every foreground class (val_3D.py:85-97, val_2D.py:10-22: cal_metric /
+ * calculate_metric_percase -> medpy.metric.binary.dc / hd95 on `label == c`, `prediction == c`; restated in icl_amd/val_3D.py).
+ * pred / gt: dense [n0][n1][n2] label maps (axis 2 fastest), element size pred_dtype / gt_dtype: 1 = uint8 (h5 labels), 8 = int64 (argmax); a
+ * voxel belongs to class c (1 <= c < num_classes) when its label equals c, other labels belong to no class.  all_border = 1: the maps
+ * carry further axes of length 1 (the AMOS path scores [1, D, H, W] arrays), so every voxel of a class is a surface voxel.
+ * out: DEVICE int64 [num_classes - 1][6], row c - 1 = {|P|, |G|, |P & G|, n = |dP| + |dG|, s0, s1}: dP / dG the border voxels
+ * (S ^ binary_erosion(S, connectivity 1), voxels on the volume faces included), s0 / s1 the squared surface distances of ranks
+ * k0 = floor(0.95 (n - 1)) and k0 + 1 in the sorted union of both directed sets (-1 when |P| = 0 or |G| = 0).  Exact integers: the host
+ * forms dice = 2 |P & G| / (|P| + |G|) and hd95 = numpy's linear interpolation between sqrt(s0) and sqrt(s1) (bit-equal to
+ * np.percentile(np.hstack((a, b)), 95)).  2 <= num_classes <= 256; ws: icl_seg_metrics_ws_bytes bytes (-1: shape not supported),
+ * about 10 bytes per voxel.  About 7 (num_classes - 1) + 3 launches, no synchronisation. */
+int64_t icl_seg_metrics_ws_bytes(int n0, int n1, int n2, int num_classes);
+int icl_seg_metrics(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int n0, int n1, int n2, int num_classes, int all_border,
+                    int64_t* out, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

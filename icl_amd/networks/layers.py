@@ -170,19 +170,12 @@ class BatchNormAct(nn.Module):
         self.register_buffer("running_var", torch.ones(c, device=device))
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long, device=device))
 
-    # ICLTrainer collects the ``num_batches_tracked += 1`` of all BatchNorm layers of a step (18 one-element launches in the
-    # 3-D ICL model) into one multi-tensor add: ``deferred`` maps id(counter) -> [counter, increments] while a step is open.
-    deferred = None
+    # An open step collects the ``num_batches_tracked += 1`` of all BatchNorm layers (18 one-element launches in the 3-D ICL model)
+    # into one multi-tensor add (flush_counters, from StepScope.close): ``deferred`` (StepScope.bn_counters) maps id(counter) -> [counter, increments].
+    deferred = ops.ScopeField("bn_counters")
 
     @classmethod
-    def defer_counters(cls):
-        cls.deferred = {}
-
-    @classmethod
-    def flush_counters(cls):
-        pending, cls.deferred = cls.deferred, None
-        if not pending:
-            return
+    def flush_counters(cls, pending):
         pool = cls._shared
         if pool is not None and all(k in pool["index"] for k in pending):
             # all counters live in one int64 vector (share_counters): one add of a cached increment vector

@@ -14,6 +14,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from .step_scope import BackwardEnd, DeferredBiasGrads, DeferredWgradReduce, FactoredGrads, ScopeField, StepScope, WgradLane  # noqa: F401
 
 _vp = ctypes.c_void_p
 
@@ -144,156 +145,6 @@ class SideStream:
 
 
 
-class BackwardEnd:
-    """End-of-backward work of a step scope that is NOT driven by ICLTrainer (FusedSGD's scope inside the unchanged reference loop).
-    The lane of the deep levels' weight gradients is joined and the deferred bias / LayerNorm gradients are reduced when the autograd
-    pass that produced them FINISHES (engine.queue_callback, armed by the first backward node that defers something), not in
-    ``optimizer.step()``: code between ``loss.backward()`` and ``step()`` — ``clip_grad_norm_``, gradient logging, a GradScaler — then
-    sees complete ``.grad`` tensors on the caller's stream.  ``hook`` is None unless such a scope is open."""
-    hook = None
-    _armed = False
-
-    @classmethod
-    def arm(cls):
-        if cls.hook is None or cls._armed:
-            return
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(cls._fire)
-            cls._armed = True
-        except RuntimeError:      # not inside a backward pass (a Function.backward called by hand): the scope's close does the work
-            pass
-
-    @classmethod
-    def _fire(cls):
-        cls._armed = False
-        h = cls.hook
-        if h is not None:
-            h()
-
-
-class WgradLane:
-    """Weight gradients of the deep levels on a second stream.  From `up3` down (24^3, 12^3, 6^3) a layer's input-gradient and weight-gradient
-    launches occupy 54-144 workgroups each on a chip of 256 CUs, and nothing else runs in that part of the backward pass (the aligner
-    branches are done: tools/critical_path.py).  The weight gradient is a leaf of the graph — only the optimiser reads it — so inside
-    ICLTrainer's step (``open``) `_Conv3d.backward` launches it on a lane ordered after the producer of dY and goes on with the input
-    gradient on its own stream; ``join()`` (ICLTrainer, after backward) orders the step's stream after the lane.  Captured steps: the lane
-    is a parallel branch of the hipGraph.  ``ICL_WGRAD_LANE=0`` keeps everything in line."""
-    enabled = os.environ.get("ICL_WGRAD_LANE", "1") != "0"
-    max_voxels = int(os.environ.get("ICL_WGRAD_LANE_MAX_VOXELS", str(24 ** 3)))
-    open = False
-    _stream = None
-    _used = False
-    # forward uses of every weight whose gradient may take the lane, counted while the step is open (ICLTrainer resets it per step).
-    # The lane's only join is after loss.backward(), so a gradient computed there must reach the optimiser untouched: autograd has to
-    # ADOPT the returned tensor (weight.grad is None, one use per step, no hooks on the parameter).  Anything else — a weight applied
-    # twice, a .grad left from an earlier backward, parameter hooks — reads or adds to the gradient on the step's own stream during
-    # backward; ``adoptable`` is False then and the caller orders its stream after the lane before it returns the gradient.
-    uses = None
-
-    @classmethod
-    def begin_step(cls):
-        cls.uses = {}
-        cls.open = False
-
-    @classmethod
-    def note_use(cls, weight):
-        if cls.uses is not None and weight is not None:
-            cls.uses[id(weight)] = cls.uses.get(id(weight), 0) + 1
-
-    @classmethod
-    def adoptable(cls, weight) -> bool:
-        if cls.uses is None or cls.uses.get(id(weight), 0) != 1 or weight.grad is not None:
-            return False
-        if getattr(weight, "_backward_hooks", None) or getattr(weight, "_post_accumulate_grad_hooks", None):
-            return False
-        return True
-
-    @classmethod
-    def sync_to_current(cls, like: torch.Tensor):
-        """Order the current stream after everything queued on the lane (a gradient that is not simply adopted)."""
-        torch.cuda.current_stream(like.device).wait_stream(cls._stream)
-
-    @classmethod
-    def wants(cls, x: torch.Tensor, voxels: int) -> bool:
-        return cls.enabled and cls.open and x.is_cuda and voxels <= cls.max_voxels
-
-    @classmethod
-    def fork_point(cls, like: torch.Tensor):
-        """Order the lane after everything queued so far on the current stream (call where dY is complete, BEFORE the input gradient
-        is queued, so that the two gradients of the layer run side by side)."""
-        dev = like.device
-        if cls._stream is None or cls._stream.device != dev:
-            # an aligner lane if there is one (idle in this part of the backward pass, and known to run beside the step's stream)
-            cls._stream = SideStream._streams.get((dev.index, 1)) or torch.cuda.Stream(device=dev)
-        cls._stream.wait_stream(torch.cuda.current_stream(dev))
-        cls._used = True
-        BackwardEnd.arm()
-
-    @classmethod
-    def on_lane(cls, *tensors):
-        for t in tensors:
-            if t is not None:
-                t.record_stream(cls._stream)
-        return torch.cuda.stream(cls._stream)
-
-    @classmethod
-    def join(cls):
-        if cls._used:
-            torch.cuda.current_stream(cls._stream.device).wait_stream(cls._stream)
-            cls._used = False
-
-class DeferredWgradReduce:
-    """While open (a step scope: ICLTrainer, or FusedSGD's from the model's forward hook), the slab sums of the convolution weight
-    gradients are not launched behind their kernels: `_Conv3d.backward` runs the weight-gradient kernel only (icl_conv3d_wgrad_slabs),
-    hands autograd the still-unwritten gradient tensor and queues (slabs, gradient); ``flush()`` sums all of them in ONE launch
-    (icl_conv3d_wgrad_reduce_multi) when the backward pass has ended and the weight-gradient lane is joined.  Only for a gradient that
-    autograd ADOPTS untouched (one use of the weight in the step, no .grad yet, no hooks: WgradLane.adoptable) — anything that reads or
-    accumulates the gradient during backward gets it complete, as before.  ``ICL_WGRAD_DEFER_REDUCE=0`` keeps every sum in line."""
-    enabled = os.environ.get("ICL_WGRAD_DEFER_REDUCE", "1") != "0"
-    pending = None
-
-    @classmethod
-    def begin(cls):
-        cls.pending = [] if cls.enabled else None
-
-    @classmethod
-    def wants(cls, weight) -> bool:
-        return cls.pending is not None and isinstance(weight, torch.nn.Parameter) and WgradLane.adoptable(weight)
-
-    @classmethod
-    def defer(cls, ws, gw, cout, cin, ks, nslabs, weight=None):
-        # an ALIAS of the gradient's memory, not the tensor autograd is handed: AccumulateGrad adopts a gradient only while nobody else
-        # holds it (use count) and clones it otherwise — it would clone the unwritten bytes and the sum would land in the original
-        # (its STORAGE and address: a view would keep `gw` itself alive through `_base`)
-        cls.pending.append((ws, (gw.untyped_storage(), gw.data_ptr(), gw.device, weight, tuple(gw.shape)), cout, cin, ks, nslabs))
-        BackwardEnd.arm()
-
-    @classmethod
-    def flush(cls, keep_open: bool = False):
-        items, cls.pending = cls.pending, ([] if (keep_open and cls.enabled) else None)
-        if not items:
-            return
-        dev = items[0][1][2]
-        here = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-        n = len(items)
-        arr, iarr = _vp * n, ctypes.c_int32 * n
-        if here is not None:
-            for ws, _gw, *_ in items:
-                ws.record_stream(here)      # (the gradients themselves live until the optimiser has read them on this stream)
-        def target(rec):
-            # belt and braces: should autograd have CLONED the unwritten tensor after all (a condition `adoptable` does not foresee),
-            # the parameter's .grad is that clone — the only gradient it has (it had none before): the sum goes there
-            _st, ptr, _dev, weight, shape = rec
-            g = getattr(weight, "grad", None) if weight is not None else None
-            if g is not None and g.data_ptr() != ptr and tuple(g.shape) == shape and g.is_contiguous() and g.dtype == torch.float32:
-                return g.data_ptr()
-            return ptr
-        _lib.check(_lib.lib().icl_conv3d_wgrad_reduce_multi(arr(*[it[0].data_ptr() for it in items]), arr(*[target(it[1]) for it in items]),
-                                                           iarr(*[it[2] for it in items]), iarr(*[it[3] for it in items]),
-                                                           iarr(*[it[4] for it in items]), iarr(*[it[5] for it in items]), n,
-                                                           _vp(here.cuda_stream) if here is not None else None), "wgrad_reduce_multi")
-
-
 class KernelTimer:
     """HIP-event timing of individual kernel launches on the stream they are launched on (bench.py roofline).
     Usage: ``with KernelTimer() as kt: step()``; ``kt.summary()`` -> {name: (launches, ms_total, flops, bytes)}."""
@@ -395,16 +246,15 @@ def pack_weights(w: torch.Tensor, mode: int) -> torch.Tensor:
 
 class PackedWeights:
     """Step-level cache of the packed convolution weights (forward + dgrad layout).  The weights only change in the optimiser
-    step, so ICLTrainer brackets its iteration with ``begin_step()`` / ``end_step()``: the first iteration packs per call (as a
-    bare module does) and records which Parameters asked; every later ``begin_step()`` packs all of them in ONE launch into
-    persistent buffers (fixed addresses: the launch is part of the captured hipGraph).  Outside the bracket nothing is cached."""
-    current: Optional["PackedWeights"] = None
+    step, so a step scope brackets the iteration with ``begin_step()`` / ``end_step()`` of its owner's cache (``StepScope.open(packed)``):
+    the first iteration packs per call (as a bare module does) and records which Parameters asked; every later ``begin_step()`` packs
+    all of them in ONE launch into persistent buffers (fixed addresses: the launch is part of the captured hipGraph).  Else no cache."""
+    current = ScopeField("packed")      # the cache of the open step
 
     def __init__(self):
         self.entries = {}     # id(parameter) -> [parameter, wp, wpt, valid, wsplit_fwd, wsplit_dgrad, planes valid, wants planes]
 
     def begin_step(self):
-        PackedWeights.current = self
         live = list(self.entries.values())
         if not live:
             return
@@ -446,7 +296,7 @@ class PackedWeights:
     @staticmethod
     def split_of(weight):
         """(fwd planes, dgrad planes) of a weight whose packs were split by this step's ``begin_step()``; (None, None) otherwise."""
-        cache = PackedWeights.current if isinstance(weight, torch.nn.Parameter) else None
+        cache = getattr(StepScope.current, "packed", None) if isinstance(weight, torch.nn.Parameter) else None
         e = cache.entries.get(id(weight)) if cache is not None else None
         if e is None or e[0] is not weight or not e[3] or not e[6]:
             return None, None
@@ -455,15 +305,13 @@ class PackedWeights:
     def end_step(self):
         for e in self.entries.values():
             e[3] = e[6] = False
-        if PackedWeights.current is self:
-            PackedWeights.current = None
 
     @staticmethod
     def get(weight):
         """(wp, wpt) of ``weight`` (contiguous [Cout, Cin, k, k, k]), packed now unless this step's begin_step() already did."""
         L = _lib.lib()
         cout, cin, ks = weight.shape[0], weight.shape[1], weight.shape[2]
-        cache = PackedWeights.current if isinstance(weight, torch.nn.Parameter) else None
+        cache = getattr(StepScope.current, "packed", None) if isinstance(weight, torch.nn.Parameter) else None
         e = cache.entries.get(id(weight)) if cache is not None else None
         if e is not None and e[0] is not weight:
             e = None
@@ -487,7 +335,7 @@ class PackedWeights:
         """Called by the convolution with the size of the volume it runs on: weights that meet a volume of the split-product
         kernels (>= 6^3 voxels — the launcher decides per shape — unless ICL_CONV_SPLIT_MIN says otherwise) get their bf16 planes from
         the next begin_step() on."""
-        cache = PackedWeights.current if isinstance(weight, torch.nn.Parameter) else None
+        cache = getattr(StepScope.current, "packed", None) if isinstance(weight, torch.nn.Parameter) else None
         e = cache.entries.get(id(weight)) if cache is not None else None
         if e is not None and e[0] is weight and voxels >= int(os.environ.get("ICL_CONV_SPLIT_MIN", 6 ** 3)):
             e[7] = True
@@ -653,7 +501,7 @@ class _Conv3d(torch.autograd.Function):
                 # fresh view so that AccumulateGrad adopts it instead of cloning a tensor it sees other references to.
                 # Only inside ICLTrainer's step bracket, where FusedSGD is the sole consumer of the gradient; anywhere else (stock
                 # optimisers, user code writing into .grad) every bias gets its own zero tensor.
-                gb = _cached_zeros(cout, x.device).view(cout) if PackedWeights.current is not None else x.new_zeros(cout)
+                gb = _cached_zeros(cout, x.device).view(cout) if getattr(StepScope.current, "packed", None) is not None else x.new_zeros(cout)
                 gb_arg = None
             flops = 2.0 * ks ** 3 * cin * cout * s * n
             nbytes = 4.0 * (n * s * (cin + cout) + 2 * ks ** 3 * cin * cout)
@@ -1704,70 +1552,6 @@ def _tall_atb(a: torch.Tensor, b: torch.Tensor, want_colsum: bool):
     return out, colsum
 
 
-class DeferredBiasGrads:
-    """While open (ICLTrainer brackets forward/backward with ``begin()`` / ``flush()``), the Linear layers that know their module
-    (``owner``) and see few rows do not reduce their bias gradient inside backward: they queue (bias, dY) and ``flush()`` computes
-    all column sums in ONE launch and assigns (or accumulates into) ``bias.grad``.  Closed, every bias gradient is reduced on
-    the spot as usual."""
-    pending = None
-    producers = None      # the streams the queued tensors were produced on (the aligner lanes): flush() orders its stream after them
-
-    @classmethod
-    def begin(cls):
-        cls.pending = []
-        cls.producers = set()
-
-    @classmethod
-    def note_producer(cls, t):
-        """The queued tensor is written by work on the CURRENT stream; flush() runs on the step's stream.  Autograd joins the streams of
-        the AccumulateGrad nodes that ran — a lane whose parameters are all deferred or adopted is none of them — so the flush orders
-        itself after every producing stream explicitly (round 5)."""
-        if cls.producers is not None and t.is_cuda:
-            cls.producers.add(torch.cuda.current_stream(t.device))
-
-    @classmethod
-    def defer(cls, bias, g2) -> bool:
-        if cls.pending is None or not isinstance(bias, torch.nn.Parameter) or g2.shape[0] >= LINEAR_WGRAD_MIN_ROWS:
-            return False
-        g2 = g2.contiguous()
-        cls.pending.append((bias, g2))
-        cls.note_producer(g2)
-        BackwardEnd.arm()
-        return True
-
-    @classmethod
-    def flush(cls, keep_open: bool = False):
-        """``keep_open``: reduce what is queued and stay open for the next backward pass of the same step scope (BackwardEnd)."""
-        items, cls.pending = cls.pending, ([] if keep_open else None)
-        producers, cls.producers = cls.producers, (set() if keep_open else None)
-        if not items:
-            return
-        if producers:
-            here = torch.cuda.current_stream(items[0][1].device)
-            for s in producers:
-                if s != here:
-                    here.wait_stream(s)
-            for _, g in items:
-                g.record_stream(here)
-        L = _lib.lib()
-        n = len(items)
-        sizes = [g.shape[1] for _, g in items]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=items[0][1].device)
-        outs, off = [], 0
-        for c in sizes:
-            outs.append(flat[off:off + c])
-            off += c
-        arr = ctypes.c_void_p * n
-        iarr = ctypes.c_int32 * n
-        _lib.check(L.icl_colsum_multi(arr(*[g.data_ptr() for _, g in items]), arr(*[o.data_ptr() for o in outs]),
-                                      iarr(*[g.shape[0] for _, g in items]), iarr(*sizes), n, _stream(flat)), "colsum_multi")
-        for (bias, _), o in zip(items, outs):
-            if bias.grad is None:
-                bias.grad = o
-            else:
-                bias.grad = bias.grad + o      # a bias used by several calls of the step
-
-
 class _Linear(torch.autograd.Function):
     """y = x W^T + b.  Forward and dx: csrc/kernels/gemm.h (fp32 MFMA; the weight is streamed once for skinny inputs); dW/db of TALL
     inputs (>= 2048 rows: the Swin token grids) use csrc/kernels/linear_wgrad.h, of short ones the k-strided tiled product."""
@@ -1799,7 +1583,7 @@ class _Linear(torch.autograd.Function):
         gx = gw = gb = None
         g2 = gy.reshape(-1, o).contiguous()
         need_b = ctx.has_bias and ctx.needs_input_grad[2]
-        if need_b and ctx.bias_param is not None and DeferredBiasGrads.defer(ctx.bias_param, g2):
+        if need_b and ctx.bias_param is not None and g2.shape[0] < LINEAR_WGRAD_MIN_ROWS and DeferredBiasGrads.defer(ctx.bias_param, g2):
             need_b = False      # reduced with all the other bias gradients of the step (DeferredBiasGrads.flush)
         if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and g2.shape[0] <= 32 and LINEAR_BWD_ONE_LAUNCH:
             # few rows (the aligner's query-side layers): input gradient and weight gradient in ONE launch — these layers sit on the
@@ -1869,45 +1653,6 @@ class _ConvTransposeGemm(torch.autograd.Function):
         return gx, gw
 
 
-class FactoredGrads:
-    """Switch for keeping the weight gradient of HUGE Linear layers factored (ICLTrainer turns it on around its step).
-
-    The four 13,824^2 ``Class_Decoder.mlp2`` weights are 97 % of the ICL model and their gradient is a sum of
-    M = batch*classes*heads outer products, dW = g^T x.  With the switch on, backward does not form dW (764 MB each): it
-    appends the pair (g [M, out], x [M, in]) to ``weight._icl_factors`` and leaves ``weight.grad`` as None;
-    ``icl_amd.optim.FusedSGD`` applies the update straight from the factors (csrc/kernels/optim.h) and
-    ``icl_amd.ddp.GradientReducer`` all-gathers the ~1 MB factors instead of all-reducing the matrix.
-    Off (the default), ``weight.grad`` is a dense tensor as usual, e.g. for ``torch.optim.SGD`` in the reference trainers."""
-
-    enabled = False
-    min_elems = 1 << 21      # the four 13,824^2 and the four 1,728^2 token-axis matrices of the 3-D ICL models
-    max_rows = 512           # rows of ONE backward call
-    # Data-parallel crossover: the ranks all-gather the factor rows, so the update every rank applies has rows * world rows and is
-    # MFMA-bound beyond a few hundred (tools/sgd_probe.py, 13,824^2: 0.54 ms at 16 rows, 0.80 at 128, 2.1 at 512, 4.0 at 1024,
-    # 5.9 at 1536 — ~100 TFLOP/s).  The dense alternative costs the 764 MB gradient (0.5 ms to form), its all-reduce (>= 5 ms at the
-    # ~150 GB/s of one xGMI link per ring hop) and the 20 B/parameter update (0.64 ms): above ~1536 gathered rows the layer's
-    # gradient is formed densely instead.  ICLTrainer sets `world`.
-    world = 1
-    max_rows_gathered = 1536
-    # Single rank: the factors of a layer are complete when its backward runs, so the optimiser step of a weight that is used ONCE
-    # per step can ride on the pass that computes the input gradient (csrc/kernels/gemm.h linear_dgrad_sgd_kernel: the 764 MB
-    # matrix is read once for gx AND the update instead of twice).  ICLTrainer sets `fused_optimizer` (its FusedSGD) and resets the
-    # use counts at the start of each step; None = the update stays in FusedSGD.step().
-    fused_optimizer = None
-    uses = None
-
-    def __init__(self, on: bool = True):
-        self.on = on
-
-    def __enter__(self):
-        self.prev = FactoredGrads.enabled
-        FactoredGrads.enabled = self.on
-        return self
-
-    def __exit__(self, *a):
-        FactoredGrads.enabled = self.prev
-
-
 class _LinearFactored(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, owner):
@@ -1926,10 +1671,12 @@ class _LinearFactored(torch.autograd.Function):
         g2 = gy.reshape(-1, o).contiguous()
         param = ctx.owner.weight
         gb = None
-        if ctx.has_bias and ctx.needs_input_grad[2] and not DeferredBiasGrads.defer(getattr(ctx.owner, "bias", None), g2):
+        if ctx.has_bias and ctx.needs_input_grad[2] and not (g2.shape[0] < LINEAR_WGRAD_MIN_ROWS
+                                                             and DeferredBiasGrads.defer(getattr(ctx.owner, "bias", None), g2)):
             gb = g2.sum(0)
-        opt = FactoredGrads.fused_optimizer
-        if (opt is not None and ctx.needs_input_grad[0] and FactoredGrads.uses is not None and FactoredGrads.uses.get(id(param)) == 1
+        scope = StepScope.current
+        opt = scope.fused_optimizer if scope is not None else None
+        if (opt is not None and ctx.needs_input_grad[0] and scope.factor_uses.get(id(param)) == 1
                 and weight.data_ptr() == param.data_ptr() and opt.can_update_in_backward(param, g2.shape[0])):
             # input gradient from the old weight and the SGD step of the weight, one pass over the matrix
             return opt.update_in_backward(param, g2, x2).view(ctx.x_shape), None, gb, None
@@ -1942,14 +1689,16 @@ class _LinearFactored(torch.autograd.Function):
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], owner=None, lane_wgrad: bool = False) -> torch.Tensor:
     """F.linear.  ``owner``: the module whose ``.weight`` this is — lets the gradient stay factored (see FactoredGrads)."""
-    if FactoredGrads.uses is not None:
+    scope = StepScope.current
+    if scope is not None and scope.factor_uses is not None:
         # every use of a weight in this step, whichever autograd path it takes below: the update-inside-backward of
         # _LinearFactored is only legal for a weight that is read exactly once per step
         key = id(owner.weight) if owner is not None and getattr(owner, "weight", None) is not None else id(weight)
-        FactoredGrads.uses[key] = FactoredGrads.uses.get(key, 0) + 1
+        scope.factor_uses[key] = scope.factor_uses.get(key, 0) + 1
     if (owner is not None and FactoredGrads.enabled and weight.requires_grad and weight.numel() >= FactoredGrads.min_elems
             and x.numel() // x.shape[-1] <= FactoredGrads.max_rows
-            and (x.numel() // x.shape[-1]) * FactoredGrads.world <= FactoredGrads.max_rows_gathered
+            and (x.numel() // x.shape[-1]) * (1 if scope is None else scope.world)
+            <= (FactoredGrads.max_rows_gathered if scope is None else scope.max_rows_gathered)
             and weight.shape[1] % 4 == 0 and torch.is_grad_enabled()):
         return _LinearFactored.apply(x, weight, bias, owner)
     return _Linear.apply(x, weight, bias, owner, lane_wgrad)
@@ -1987,7 +1736,8 @@ class _LayerNorm(torch.autograd.Function):
             ws = _ws(L.icl_layernorm_bwd_ws_bytes(rows, c), x)
             # inside ICLTrainer's step the chunk partials of all LayerNorm layers are summed by ONE launch at the end of backward
             # (DeferredBiasGrads.flush); elsewhere on the spot.  Either way in a fixed order: no float atomics.
-            defer = DeferredBiasGrads.pending is not None and ctx.params is not None
+            scope = StepScope.current
+            defer = scope is not None and scope.bias_grads is not None and ctx.params is not None
             if not defer:
                 dgb = torch.empty((2, c), dtype=torch.float32, device=x.device)
                 dg, db = dgb[0], dgb[1]
@@ -1995,8 +1745,8 @@ class _LayerNorm(torch.autograd.Function):
                                        _stream(x)), "layernorm_bwd")
         if defer:
             part = ws[:(ws.numel() // (2 * c)) * 2 * c].view(2, -1, c)
-            DeferredBiasGrads.pending.append((ctx.params[0], part[0]))
-            DeferredBiasGrads.pending.append((ctx.params[1], part[1]))
+            scope.bias_grads.append((ctx.params[0], part[0]))
+            scope.bias_grads.append((ctx.params[1], part[1]))
             DeferredBiasGrads.note_producer(part)
             BackwardEnd.arm()
         return gx, dg, db, None

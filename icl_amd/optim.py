@@ -14,6 +14,7 @@ import weakref
 import torch
 
 from . import _lib
+from .step_scope import StepScope
 
 _BIG = 1 << 20
 SPLIT_MIN_ROWS = 192    # factor rows from which d = g^T x runs on split products (tools/sgd_probe.py, 13,824^2: 128 rows 769 -> 720 us
@@ -68,8 +69,8 @@ def _load_no_hook():
 
 class FusedSGD(torch.optim.Optimizer):
     """``step_scope`` (default on): when the parameters belong to ONE icl_amd model built by ``net_factory_3d`` / ``net_factory``, the
-    optimiser opens — from a forward pre-hook of that model, in training mode with gradients enabled — the step-scoped machinery that
-    ``ICLTrainer`` opens around its iteration, and closes it in ``step()``: packed convolution weights (``ops.PackedWeights``), factored
+    optimiser opens — from a forward pre-hook of that model, in training mode with gradients enabled — the step scope (``ops.StepScope``)
+    that ``ICLTrainer`` opens around its iteration, and closes it in ``step()``: packed convolution weights (``ops.PackedWeights``), factored
     gradients of the token-axis matrices and their SGD step inside backward (``ops.FactoredGrads``), deferred bias gradients and
     BatchNorm counters, weight gradients of the deep levels on a lane (``ops.WgradLane``).  The unchanged reference loop
     (``outputs = model(..); ..; optimizer.zero_grad(); loss.backward(); optimizer.step()``,
@@ -83,11 +84,8 @@ class FusedSGD(torch.optim.Optimizer):
         if momentum <= 0:
             raise ValueError("FusedSGD implements the momentum form used by the ICL trainers")
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
-        self._scope_model = None
-        self._scope_open = False
         self._scope_update_in_backward = bool(update_in_backward)
         self._scope_packed = None
-        self._scope_hook = None
         # graph=True (round 5, needs the step scope): after `graph_warmup` eager training iterations the model's forward and backward
         # are captured into two hipGraphs (the step scope's bookkeeping inside them) and every later `model(x_lab, x_unlab)` /
         # `loss.backward()` of the UNCHANGED loop replays them; the losses, `optimizer.zero_grad()`, `optimizer.step()` and the
@@ -102,8 +100,7 @@ class FusedSGD(torch.optim.Optimizer):
             models = {id(m): m for m in (model_of(p) for g in self.param_groups for p in g["params"]) if m is not None}
             if len(models) == 1:
                 (model,) = models.values()
-                self._scope_model = weakref.ref(model)
-                self._scope_hook = model.register_forward_pre_hook(_ScopePreHook(self))
+                model.register_forward_pre_hook(_ScopePreHook(self))
                 if self._graph_on:
                     _install_graphed_forward(self, model)
         self.lr_dev = None   # optional device scalar read by the kernels instead of group['lr'] (hipGraph replay)
@@ -167,18 +164,19 @@ class FusedSGD(torch.optim.Optimizer):
             for p in group["params"]:
                 if getattr(p, "_icl_factors", None) is not None:
                     p._icl_factors = None
-        if self._scope_open:
-            self._close_scope(flush=False)
+        self._close_scope(flush=False)
 
-    # ---- step scope (see the class docstring)
+    # ---- step scope (see the class docstring; the state itself is an ops.StepScope)
     def _open_scope(self, module, capturing: bool = False):
         from . import ops
-        from .networks.layers import BatchNormAct
         if not module.training or not torch.is_grad_enabled():
             return
         if self._graph_state is not None and not capturing:
             return                       # the captured graphs carry the scope's work; nothing runs eagerly
-        if self._scope_open:
+        scope = StepScope.current
+        if scope is not None and scope.owner() is not self:
+            return                       # somebody else (ICLTrainer) has a step open
+        if scope is not None:
             # A second training forward before step(): gradient accumulation over micro-batches, or several forward
             # passes whose losses are summed before ONE backward.  The scope stays open — use counts, queued bias gradients and
             # factored gradients keep accumulating, exactly as `.grad` does — and the packed weights are refreshed (one launch; the
@@ -191,76 +189,29 @@ class FusedSGD(torch.optim.Optimizer):
                     "half-updated weights.  Call optimizer.step() after every loss.backward(), or build the optimiser with "
                     "update_in_backward=False for loops that accumulate gradients over several backward passes (or abandon_step() "
                     "to discard a failed iteration)")
-            self._scope_packed.begin_step()
+            scope.packed.begin_step()
             return
-        if ops.PackedWeights.current is not None or ops.FactoredGrads.uses is not None:
-            return                       # somebody else (ICLTrainer) has a step open
         if self._scope_packed is None:
             self._scope_packed = ops.PackedWeights()
-        self._scope_open = True
-        self._scope_packed.begin_step()
-        BatchNormAct.defer_counters()
-        multi = False
         try:
             import torch.distributed as dist
-            multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+            single = not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
         except Exception:                # noqa: BLE001
-            multi = False
-        ops.WgradLane.begin_step()
-        self._scope_prev_factored = ops.FactoredGrads.enabled
-        self._scope_multi = multi
-        if not multi:
-            # single process: weight gradients of the deep levels on a lane, bias / LayerNorm gradients reduced by one launch — both
-            # completed when the backward pass ENDS (ops.BackwardEnd), so `.grad` is whole when loss.backward() returns
-            ops.DeferredBiasGrads.begin()
-            ops.DeferredWgradReduce.begin()
-            ops.WgradLane.open = True    # (only backward functions consult it)
-            me = weakref.ref(self)
-            ops.BackwardEnd.hook = lambda: (me() is not None and me()._end_of_backward())
-            ops.FactoredGrads.enabled = True
-            ops.FactoredGrads.world = 1
-            ops.FactoredGrads.fused_optimizer = self if self._scope_update_in_backward else None
-            ops.FactoredGrads.uses = {} if self._scope_update_in_backward else None
-        # multi-process (a data-parallel wrapper around the unchanged loop): dense `.grad` tensors that pass through autograd's own
-        # accumulation — a wrapper's accumulator hooks fire for every parameter and bucket nothing that another stream is still
-        # writing — so neither the lane nor the bias deferral nor the factored gradients are opened; packed weights and the
+            single = True
+        # single process: weight gradients of the deep levels on a lane, bias / LayerNorm gradients reduced by one launch — both
+        # completed when the backward pass ENDS (ops.BackwardEnd), so `.grad` is whole when loss.backward() returns — and factored
+        # gradients.  Multi-process (a data-parallel wrapper around the unchanged loop): dense `.grad` tensors that pass through
+        # autograd's own accumulation — a wrapper's accumulator hooks fire for every parameter and bucket nothing that another stream
+        # is still writing — so neither the lane nor the deferrals nor the factored gradients are opened; packed weights and the
         # BatchNorm counters (forward-only) still are
-
-    def _end_of_backward(self):
-        """Runs when an autograd pass that used the scope's lane / deferrals finishes (on the stream of the caller of backward())."""
-        from . import ops
-        if not self._scope_open:
-            return
-        ops.WgradLane.join()
-        if ops.DeferredWgradReduce.pending is not None:
-            ops.DeferredWgradReduce.flush(keep_open=True)
-        if ops.DeferredBiasGrads.pending is not None:
-            ops.DeferredBiasGrads.flush(keep_open=True)
+        StepScope.open(self._scope_packed, owner=self, lane_open=single, deferrals=single, complete_at_backward_end=single,
+                       factored=True if single else None,
+                       fused_optimizer=weakref.proxy(self) if (single and self._scope_update_in_backward) else None)
 
     def _close_scope(self, flush: bool = True):
-        from . import ops
-        from .networks.layers import BatchNormAct
-        ops.BackwardEnd.hook = None
-        ops.WgradLane.join()
-        if ops.DeferredWgradReduce.pending is not None:
-            if flush:
-                ops.DeferredWgradReduce.flush()
-            ops.DeferredWgradReduce.pending = None
-        ops.WgradLane.open = False
-        ops.WgradLane.uses = None
-        ops.FactoredGrads.enabled = self._scope_prev_factored
-        ops.FactoredGrads.fused_optimizer = None
-        ops.FactoredGrads.uses = None
-        if flush:
-            BatchNormAct.flush_counters()
-            if ops.DeferredBiasGrads.pending is not None:
-                ops.DeferredBiasGrads.flush()
-        else:
-            BatchNormAct.deferred = None
-            ops.DeferredBiasGrads.pending = None
-            ops.DeferredBiasGrads.producers = None
-        self._scope_packed.end_step()
-        self._scope_open = False
+        scope = StepScope.current
+        if scope is not None and scope.owner() is self:
+            scope.close(flush)
 
     def _step_factored(self, L, p, factors, lr, mom, wd, narrow: int = 0):
         """dW = sum over entries of g^T x, applied without forming it (ops.FactoredGrads, csrc/kernels/optim.h)."""
@@ -473,8 +424,7 @@ class FusedSGD(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        if self._scope_open:
-            self._close_scope()                 # lane joined, deferred bias gradients assigned, packed weights released
+        self._close_scope()                     # lane joined, deferred bias gradients assigned, packed weights released
         if self._graph_state is not None and self.lr_dev is not None and not (
                 self.lr_dev.is_cuda and torch.cuda.is_current_stream_capturing()):
             # graph mode: a batch whose shape the graphs do not match ran eagerly — its update must not read the learning rate the
@@ -614,8 +564,7 @@ class _GraphedStep:
         from . import ops
         self.opt = weakref.ref(opt)
         dev = args[0].device
-        if opt._scope_open:
-            opt._close_scope(flush=False)       # the pre-hook opened an eager scope for this call: the captured one replaces it
+        opt._close_scope(flush=False)           # the pre-hook opened an eager scope for this call: the captured one replaces it
         params = [p for g in opt.param_groups for p in g["params"]]
         for p in params:
             p.grad = None
@@ -642,8 +591,7 @@ class _GraphedStep:
         self.gouts = [torch.zeros_like(t) for t in flat]
         with torch.cuda.graph(self.gb, pool=pool, stream=opt._cap_stream):
             torch.autograd.backward(flat, self.gouts)
-            if opt._scope_open:
-                opt._close_scope()
+            opt._close_scope()
             opt.flush_deferred(gate=True)
             if opt._update_stream_used:
                 torch.cuda.current_stream(dev).wait_stream(opt._update_stream)
@@ -719,8 +667,7 @@ def _install_graphed_forward(opt, model):
                 o._deferred = []
                 o._update_stream_used = False
                 o._updated_in_backward.clear()
-                if o._scope_open:
-                    o._close_scope(flush=False)
+                o._close_scope(flush=False)
                 for g_ in o.param_groups:
                     for p_ in g_["params"]:
                         p_.grad = None

@@ -108,41 +108,21 @@ class ICLTrainer:
     def _forward_backward(self, volume_batch, label_batch, boundary=None):
         """``boundary()`` (capture only) is called between the loss and ``loss.backward()``."""
         cfg = self.cfg
+        ddp = self.ddp if (self.ddp is not None and self.ddp.active) else None
         ops.StepRNG.begin_step()
-        self.packed.begin_step()        # every convolution weight packed once, in one launch (ops.PackedWeights)
-        self.optimizer.zero_grad(set_to_none=True)
-        BatchNormAct.defer_counters()
-        ops.DeferredBiasGrads.begin()
-        ops.WgradLane.begin_step()      # per-weight use counts of the step (a lane gradient must be adopted, not accumulated)
-        ops.DeferredWgradReduce.begin()  # (needs those counts: only adopted gradients are deferred)
-        try:
-            ops.FactoredGrads.world = self.ddp.world if (self.ddp is not None and self.ddp.active) else 1
-            rows_default = ops.FactoredGrads.max_rows_gathered
-            if self.ddp is not None and self.ddp.active:
-                ops.FactoredGrads.max_rows_gathered = self.ddp.max_rows_gathered      # this reducer's crossover, for this step only
-            # without gradient exchange the factors of a layer are final when its backward runs: update there (FusedSGD.update_in_backward)
-            fuse = cfg.factored_mlp2_grads and cfg.update_in_backward and not (self.ddp is not None and self.ddp.active)
-            ops.FactoredGrads.fused_optimizer = self.optimizer if fuse else None
-            ops.FactoredGrads.uses = {} if fuse else None
-            with ops.FactoredGrads(cfg.factored_mlp2_grads):
-                outputs = self.model(volume_batch[:cfg.labeled_bs], volume_batch[cfg.labeled_bs:])
-                loss, parts = self.compute_loss(outputs, label_batch)
-                if boundary is not None:
-                    boundary()
-                ops.WgradLane.open = True
-                loss.backward()
-                ops.WgradLane.join()
-                ops.DeferredWgradReduce.flush()      # the slab sums of every convolution weight gradient of the pass: one launch
-        finally:
-            ops.DeferredWgradReduce.pending = None
-            if "rows_default" in locals():
-                ops.FactoredGrads.max_rows_gathered = rows_default
-            ops.WgradLane.open = False
-            ops.WgradLane.uses = None
-            ops.FactoredGrads.fused_optimizer = None
-            ops.FactoredGrads.uses = None
-            BatchNormAct.flush_counters()     # all num_batches_tracked increments of the step in one launch
-            ops.DeferredBiasGrads.flush()     # all small-Linear bias gradients of the step in one launch
+        # without gradient exchange the factors of a layer are final when its backward runs: update there (FusedSGD.update_in_backward)
+        fuse = cfg.factored_mlp2_grads and cfg.update_in_backward and ddp is None
+        # leaving the block joins the lane and reduces what was deferred, one launch each — or drops it, if the step raised
+        with ops.StepScope.open(self.packed, factored=cfg.factored_mlp2_grads, world=ddp.world if ddp is not None else 1,
+                                max_rows_gathered=ddp.max_rows_gathered if ddp is not None else None,
+                                fused_optimizer=self.optimizer if fuse else None) as scope:
+            self.optimizer.zero_grad(set_to_none=True)
+            outputs = self.model(volume_batch[:cfg.labeled_bs], volume_batch[cfg.labeled_bs:])
+            loss, parts = self.compute_loss(outputs, label_batch)
+            if boundary is not None:
+                boundary()
+            scope.lane_open = True
+            loss.backward()
         parts = {k: v.detach() for k, v in parts.items()}
         parts["loss"] = loss.detach()
         return parts
@@ -156,7 +136,6 @@ class ICLTrainer:
         if part == "sharded":
             return
         self.optimizer.step()
-        self.packed.end_step()
         ops.StepRNG.end_step()
 
     def _step_body(self, volume_batch, label_batch, boundary=None):
@@ -165,7 +144,6 @@ class ICLTrainer:
         except BaseException:
             # an iteration that will not reach optimizer.step(): drop its queued updates, or every later zero_grad() raises
             self.optimizer.abandon_step()
-            self.packed.end_step()
             raise
         if self.ddp is not None and self.ddp.active:
             self.ddp.reduce_gradients()

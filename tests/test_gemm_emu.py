@@ -197,8 +197,7 @@ def test_fused_update_matches_optimizer_step_through_autograd():
         for step in range(2):
             x = _rand((6, 1536), 23 + step).requires_grad_()
             opt.zero_grad()
-            ops.FactoredGrads.fused_optimizer = opt if fuse else None
-            ops.FactoredGrads.uses = {} if fuse else None
+            scope = ops.StepScope.open(fused_optimizer=opt if fuse else None, deferrals=False)
             prev_min = ops.FactoredGrads.min_elems
             try:
                 with ops.FactoredGrads(True):
@@ -207,8 +206,7 @@ def test_fused_update_matches_optimizer_step_through_autograd():
                         y = y + ops.linear(x * 0.5, lin.weight, lin.bias, lin)
                     (y * _rand(tuple(y.shape), 30 + step)).sum().backward()
             finally:
-                ops.FactoredGrads.fused_optimizer = None
-                ops.FactoredGrads.uses = None
+                scope.close()
                 ops.FactoredGrads.min_elems = prev_min
             if fuse and not twice:
                 assert lin.weight.grad is None and not getattr(lin.weight, "_icl_factors", None)
@@ -242,8 +240,7 @@ def test_update_inside_backward_refuses_a_weight_with_another_use(monkeypatch):
         opt.can_update_in_backward = lambda p, rows: p.dim() == 2
         x = _rand((6, 512), 43).requires_grad_()
         xt = _rand((60, 512), 44)          # 60 rows > FactoredGrads.max_rows: ops.linear takes the dense _Linear path
-        ops.FactoredGrads.fused_optimizer = opt if fuse else None
-        ops.FactoredGrads.uses = {} if fuse else None
+        scope = ops.StepScope.open(fused_optimizer=opt if fuse else None, deferrals=False)
         try:
             with ops.FactoredGrads(True):
                 y = ops.linear(x, lin.weight, lin.bias, lin).sum()
@@ -253,8 +250,7 @@ def test_update_inside_backward_refuses_a_weight_with_another_use(monkeypatch):
                     y = y + F.linear(xt[:4], lin.weight, lin.bias).sum() * 0.01
                 y.backward()
         finally:
-            ops.FactoredGrads.fused_optimizer = None
-            ops.FactoredGrads.uses = None
+            scope.close()
         opt.step()
         return x.grad.clone(), lin.weight.detach().clone()
 

@@ -1418,16 +1418,16 @@ def test_wgrad_lane_gradient_of_a_weight_used_twice_is_ordered_before_its_accumu
     def run(lane):
         w.grad = w1.grad = None
         old = ops.WgradLane.enabled
-        ops.WgradLane.begin_step()
+        scope = ops.StepScope.open(deferrals=False)
         try:
             xin = x.clone().requires_grad_()
             y = ops.conv3d(ops.conv3d(ops.conv3d(xin, w, None), w1, None), w, None)
             seen = dict(twice=ops.WgradLane.adoptable(w), once=ops.WgradLane.adoptable(w1))
-            ops.WgradLane.enabled, ops.WgradLane.open = lane, True
+            ops.WgradLane.enabled, scope.lane_open = lane, True
             y.square().sum().backward()
-            ops.WgradLane.join()
         finally:
-            ops.WgradLane.open, ops.WgradLane.enabled, ops.WgradLane.uses = False, old, None
+            scope.close()      # (joins the lane)
+            ops.WgradLane.enabled = old
         torch.cuda.synchronize()
         return w.grad.clone(), w1.grad.clone(), seen
 
@@ -1436,7 +1436,6 @@ def test_wgrad_lane_gradient_of_a_weight_used_twice_is_ordered_before_its_accumu
     assert seen == dict(twice=False, once=True), seen
     assert torch.equal(a, b) and torch.equal(a1, b1)
     # a gradient left from an earlier backward is accumulated into, not replaced: not adoptable either
-    ops.WgradLane.begin_step()
-    ops.WgradLane.note_use(w1)
-    assert w1.grad is not None and not ops.WgradLane.adoptable(w1)
-    ops.WgradLane.uses = None
+    with ops.StepScope.open(deferrals=False):
+        ops.WgradLane.note_use(w1)
+        assert w1.grad is not None and not ops.WgradLane.adoptable(w1)

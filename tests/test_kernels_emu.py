@@ -562,9 +562,8 @@ def test_packed_weight_cache_repacks_all_weights_in_one_launch():
     cache = ops.PackedWeights()
     for step in range(3):
         ref = run()                                   # uncached: packs per call
-        cache.begin_step()
-        got = run()
-        cache.end_step()
+        with ops.StepScope.open(cache, deferrals=False):
+            got = run()
         assert ops.PackedWeights.current is None and len(cache.entries) == 3
         assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
         assert all(torch.equal(a, b) for a, b in zip(got[2], ref[2]))
@@ -591,10 +590,10 @@ def test_deferred_bias_gradients_match_immediate_ones():
     for p in (la.weight, la.bias, lb.weight, lb.bias):
         p.grad = None
     lb.bias.grad = torch.ones(7)                                               # pre-existing gradient: must be accumulated
-    ops.DeferredBiasGrads.begin()
+    scope = ops.StepScope.open()
     loss().backward()
     assert la.bias.grad is None and len(ops.DeferredBiasGrads.pending) == 3    # nothing reduced yet
-    ops.DeferredBiasGrads.flush()
+    scope.close()
     assert ops.DeferredBiasGrads.pending is None
     got = [la.weight.grad, la.bias.grad, lb.weight.grad, lb.bias.grad - 1.0]
     for a, b in zip(got, ref):
@@ -1038,7 +1037,6 @@ def test_fused_sgd_gradients_are_complete_after_backward_and_accumulate_over_mic
         assert sorted(clone.state_dict()) == sorted(model.state_dict())
     finally:
         ops.FactoredGrads.min_elems = old_min
-        ops.BackwardEnd.hook = None
 
 
 def test_unet_blocks_take_the_materialised_path_when_they_or_their_parents_are_hooked():
@@ -1128,13 +1126,12 @@ def test_deferred_instance_norm_equals_the_materialised_path(monkeypatch):
         packed = ops.PackedWeights()
         xin = x.clone().requires_grad_()
         for it in range(2):          # the second iteration runs with packed + split weights: the epilogue statistics exist
-            packed.begin_step()
-            for q in model.parameters():
-                q.grad = None
-            xin.grad = None
-            y, kinds = model(xin, p)
-            (y * _rand(tuple(y.shape), 22)).sum().backward()
-            packed.end_step()
+            with ops.StepScope.open(packed, deferrals=False):
+                for q in model.parameters():
+                    q.grad = None
+                xin.grad = None
+                y, kinds = model(xin, p)
+                (y * _rand(tuple(y.shape), 22)).sum().backward()
         return y.detach(), xin.grad.clone(), {k: q.grad.clone() for k, q in model.named_parameters() if q.grad is not None}, kinds
 
     for p in (0.3,):      # (without dropout: test_lazy_final_convolution_fused_kernels[0.0] and every GPU golden test)

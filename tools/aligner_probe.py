@@ -19,7 +19,6 @@ model.train()
 feats = [torch.randn(2, c, r, r, r, device=dev, requires_grad=True) for c, r in ((256, 6), (128, 12), (64, 24))]
 
 
-from icl_amd.networks.layers import BatchNormAct  # noqa: E402
 from icl_amd.trainer import ICLConfig, ICLTrainer  # noqa: E402
 
 tr = ICLTrainer(model, ICLConfig(num_classes=2, labeled_bs=1))
@@ -32,33 +31,21 @@ def forward():
     # the step-scoped machinery of ICLTrainer._forward_backward (factored mlp2 gradients, SGD step inside the backward pass, deferred
     # bias gradients), without the backbone
     ops.StepRNG.begin_step()
-    tr.packed.begin_step()
+    scope = ops.StepScope.open(tr.packed, factored=True, fused_optimizer=tr.optimizer)
     tr.optimizer.zero_grad(set_to_none=True)
     for f in feats:
         f.grad = None
-    BatchNormAct.defer_counters()
-    ops.DeferredBiasGrads.begin()
-    ops.FactoredGrads.world = 1
-    ops.FactoredGrads.fused_optimizer = tr.optimizer
-    ops.FactoredGrads.uses = {}
-    ctx = ops.FactoredGrads(True)
-    ctx.__enter__()
     with ops.SideStream(feats) as side:
         (maps_lab, qs_lab), (maps_con, _) = model.sspa.forward_labeled_pair(feats, 1)
         maps_un, _ = model.uscl([f[1:] for f in feats], qs_lab, "unlabeled")
     side.join(maps_lab + maps_un + maps_con)
-    return ctx, sum((m * m).mean() for m in maps_lab + maps_un + maps_con)
+    return scope, sum((m * m).mean() for m in maps_lab + maps_un + maps_con)
 
 
-def backward(ctx, loss):
+def backward(scope, loss):
     loss.backward()
-    ctx.__exit__(None, None, None)
-    ops.FactoredGrads.fused_optimizer = None
-    ops.FactoredGrads.uses = None
-    BatchNormAct.flush_counters()
-    ops.DeferredBiasGrads.flush()
+    scope.close()
     tr.optimizer.step()
-    tr.packed.end_step()
     ops.StepRNG.end_step()
 
 
@@ -72,9 +59,9 @@ torch.cuda.synchronize()
 pool = torch.cuda.graph_pool_handle()
 gf, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
 with torch.cuda.graph(gf, pool=pool):
-    ctx, loss = forward()
+    scope, loss = forward()
 with torch.cuda.graph(gb, pool=pool):
-    backward(ctx, loss)
+    backward(scope, loss)
 for _ in range(3):
     gf.replay(); gb.replay()
 torch.cuda.synchronize()

@@ -2276,6 +2276,55 @@ int icl_crop_rotflip(const void* const* images, const void* const* labels, const
   return check_launch("crop_rotflip");
 }
 
+int icl_slice_augment(const void* const* images, const void* const* labels, const int32_t* int_params, const double* double_params,
+                      int batch, float* image_out, uint8_t* label_out, int o0, int o1, void* stream) {
+  if (!images || !labels || !int_params || !double_params || !image_out || !label_out)
+    return fail(-1, "slice_augment: null pointer");
+  if (batch < 1 || batch > icl::kSliceMaxBatch) return fail(-1, "slice_augment: batch %d out of range (1 <= batch <= %d)", batch, icl::kSliceMaxBatch);
+  if (o0 < 2 || o1 < 2) return fail(-1, "slice_augment: output extents %d x %d (each must be >= 2)", o0, o1);
+  if ((long)o0 * o1 > 0x7fffffffL) return fail(-1, "slice_augment: output extents %d x %d (more than 2^31 - 1 pixels a sample)", o0, o1);
+  icl::SliceBatch sb{};
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* q = int_params + 5 * b;
+    const double* d = double_params + 8 * b;
+    icl::SliceSample& s = sb.s[b];
+    s.image = (const float*)images[b];
+    s.label = (const uint8_t*)labels[b];
+    s.n0 = q[0]; s.n1 = q[1]; s.branch = q[2]; s.k = q[3]; s.flip_axis = q[4];
+    s.m00 = d[0]; s.m01 = d[1]; s.m10 = d[2]; s.m11 = d[3]; s.off0 = d[4]; s.off1 = d[5]; s.z0 = d[6]; s.z1 = d[7];
+    if (!s.image || !s.label) return fail(-1, "slice_augment: sample %d: null slice pointer", b);
+    if (s.n0 < 1 || s.n1 < 1) return fail(-1, "slice_augment: sample %d: extents %d x %d (each must be >= 1)", b, s.n0, s.n1);
+    if (s.branch < icl::kSliceNone || s.branch > icl::kSliceRotate) return fail(-1, "slice_augment: sample %d: unknown branch %d", b, s.branch);
+    if (s.branch == icl::kSliceRotFlip && (s.k < 0 || s.k > 3)) return fail(-1, "slice_augment: sample %d: k = %d outside 0..3", b, s.k);
+    if (s.branch == icl::kSliceRotFlip && (s.flip_axis < 0 || s.flip_axis > 1))
+      return fail(-1, "slice_augment: sample %d: flip axis %d (0 or 1)", b, s.flip_axis);
+  }
+  ICL_LAUNCH(icl::slice_augment_kernel, dim3(grid_for((long)batch * o0 * o1, 256, 8192)), dim3(256), 0, (hipStream_t)stream, sb, image_out,
+             label_out, batch, o0, o1);
+  return check_launch("slice_augment");
+}
+
+int icl_slice_resize(const void* src, void* dst, int64_t batch, int n0, int n1, int o0, int o1, int elem_kind, void* stream) {
+  if (!src || !dst) return fail(-1, "slice_resize: null pointer");
+  if (batch < 1 || batch > (1 << 20)) return fail(-1, "slice_resize: batch %lld out of range", (long long)batch);
+  if (n0 < 1 || n1 < 1) return fail(-1, "slice_resize: source extents %d x %d (each must be >= 1)", n0, n1);
+  if (o0 < 2 || o1 < 2) return fail(-1, "slice_resize: output extents %d x %d (each must be >= 2)", o0, o1);
+  if ((long)o0 * o1 > 0x7fffffffL) return fail(-1, "slice_resize: output extents %d x %d (more than 2^31 - 1 pixels a slice)", o0, o1);
+  // scipy derives the factors from the extents: (n_in - 1) / (n_out - 1) in double
+  const double z0 = (double)(n0 - 1) / (double)(o0 - 1), z1 = (double)(n1 - 1) / (double)(o1 - 1);
+  const dim3 grid(grid_for((long)batch * o0 * o1, 256, 8192));
+  if (elem_kind == 0) {
+    ICL_LAUNCH(icl::slice_resize_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)src, (float*)dst, (int)batch, n0, n1, o0,
+               o1, z0, z1);
+  } else if (elem_kind == 1) {
+    ICL_LAUNCH(icl::slice_resize_kernel<long long>, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)src, (long long*)dst, (int)batch,
+               n0, n1, o0, o1, z0, z1);
+  } else {
+    return fail(-1, "slice_resize: unknown element kind %d (0 fp32, 1 int64)", elem_kind);
+  }
+  return check_launch("slice_resize");
+}
+
 int icl_linear_dgrad_sgd(const float* gy, const float* x, float* w, float* mom, float* gx, void* ws, int64_t rows, int in, int out,
                          float lr, float momentum, float weight_decay, int first, const float* lr_dev, void* stream) {
   if (!gy || !x || !w || !mom || !gx || !ws || rows < 1 || rows > 32 || in < 4 || out < 4 || (in & 3) || (out & 3))

@@ -4,17 +4,22 @@
 ``test_single_volume_ours(image, label, net, writer, iter_num, classes, patch_size)`` keeps the reference procedure — every slice
 is resized to ``patch_size`` with ``scipy.ndimage.zoom(order=0)``, pushed through ``net(x, inference=True)``, arg-maxed and resized
 back — but pushes ``slices_per_batch`` slices per forward (eval-mode networks are per-sample: BatchNorm uses its running statistics,
-so batching does not change any slice's logits; the reference runs one slice per forward).  The nearest-neighbour resize stays
-scipy's, so the index mapping is the reference's bit for bit.  Metrics: Dice + HD95 with the reference's empty-mask conventions
+so batching does not change any slice's logits; the reference runs one slice per forward).  With the net on a HIP device the case goes
+up once, both nearest-neighbour resizes are ONE launch each of the slice-resize kernel (``icl_slice_resize``: scipy's index mapping
+bit for bit, the zero last rows / columns of its ``mode='constant'`` included) and the prediction never leaves the device;
+``ICL_VAL_RESIZE=host`` (and every CPU net) keeps scipy on the host.  Metrics: Dice + HD95 with the reference's empty-mask conventions
 (``icl_amd.val_3D.cal_metric``; HD95 parity unpinned — MedPy is not installed in the build image), scored for every class at once by
 the metric kernels when the net is on a HIP device (``val_3D.cal_metric_multiclass``; ``ICL_VAL_METRICS=host``: numpy).
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 from scipy.ndimage import zoom
 
+from .dataloaders.dataset import resize_slices
 from .val_3D import _upload_label, binary_dice, binary_hd95, cal_metric_multiclass, val_metrics_mode
 
 
@@ -31,11 +36,35 @@ def calculate_metric_percase(pred, gt):
     return 1, 0
 
 
+def val_resize_mode() -> str:
+    """``ICL_VAL_RESIZE``: ``device`` (default) resizes the slices and the arg-max maps of a net on a HIP device with the slice-resize
+    kernel, ``host`` forces scipy's ``zoom`` on the host (A/B runs).  CPU nets always take the host path."""
+    mode = os.environ.get("ICL_VAL_RESIZE", "device")
+    if mode not in ("device", "host"):
+        raise ValueError(f"ICL_VAL_RESIZE must be 'device' or 'host', got {mode!r}")
+    return mode
+
+
+def _zoom_gives(n_in, n_out):
+    """scipy derives the output extent of ``zoom(x, n_out / n_in)`` as ``round(n_in * (n_out / n_in))``."""
+    return n_in >= 1 and n_out >= 2 and int(round(n_in * (n_out / n_in))) == n_out
+
+
 @torch.no_grad()
 def _predict_volume(image, net, patch_size, inference_kw, slices_per_batch):
+    """The prediction map [slices, H, W] int64: a numpy array from the host path, a device tensor from the device path."""
     dev = next(net.parameters()).device
     net.eval()
     n, x, y = image.shape
+    p0, p1 = int(patch_size[0]), int(patch_size[1])
+    if (dev.type == "cuda" and val_resize_mode() == "device" and n > 0 and image.dtype.kind in "fiu"
+            and _zoom_gives(x, p0) and _zoom_gives(y, p1) and _zoom_gives(p0, x) and _zoom_gives(p1, y)):
+        resized = resize_slices(torch.from_numpy(np.ascontiguousarray(image)).float().to(dev), (p0, p1))
+        maps = torch.empty((n, p0, p1), dtype=torch.int64, device=dev)
+        for lo in range(0, n, slices_per_batch):
+            logits = net(resized[lo:lo + slices_per_batch].unsqueeze(1), **inference_kw)
+            maps[lo:lo + logits.shape[0]] = torch.argmax(torch.softmax(logits, dim=1), dim=1)
+        return resize_slices(maps, (x, y))
     prediction = np.zeros((n, x, y), dtype=np.int64)
     resized = np.stack([zoom(image[i], (patch_size[0] / x, patch_size[1] / y), order=0) for i in range(n)])
     for lo in range(0, n, slices_per_batch):
@@ -48,12 +77,15 @@ def _predict_volume(image, net, patch_size, inference_kw, slices_per_batch):
 
 def _score_volume(prediction, label, net, classes):
     """``[calculate_metric_percase(prediction == i, label == i) for i in 1..classes-1]``; with the net on a HIP device both maps go up
-    once and every class is scored by the metric kernels (the same values and types: Dice and HD95 are symmetric in their arguments)."""
+    once (a device prediction stays where it is) and every class is scored by the metric kernels (the same values and types: Dice and
+    HD95 are symmetric in their arguments).  ``prediction``: a numpy array or a device tensor."""
     dev = next(net.parameters()).device
     if dev.type == "cuda" and val_metrics_mode() == "device" and 2 <= classes <= 256:
         gt = _upload_label(label, dev)
         if gt is not None and gt.shape == prediction.shape:
-            return cal_metric_multiclass(gt, torch.from_numpy(prediction).to(dev), classes)
+            return cal_metric_multiclass(gt, prediction if torch.is_tensor(prediction) else torch.from_numpy(prediction).to(dev), classes)
+    if torch.is_tensor(prediction):
+        prediction = prediction.cpu().numpy()
     return [calculate_metric_percase(prediction == i, label == i) for i in range(1, classes)]
 
 

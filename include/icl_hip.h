@@ -399,6 +399,21 @@ int icl_relpos_bias_bwd_sum(float* dbias, int chunks, const int32_t* inv, const 
 int icl_crop_rotflip(const void* const* images, const void* const* labels, const int32_t* params, int batch, float* image_out,
                      int64_t* label_out, int o0, int o1, int o2, void* stream);
 
+/* ---- on-device RandomGenerator of the 2-D trainers (dataloaders/dataset.py:147-166; composed at
+ * train_inherent_consistent_unet_2D.py:75 and ..._swinunet_2D.py): "maybe rot90 + flip, else maybe ndimage.rotate by an integer
+ * angle, then ndimage.zoom to the patch", all order 0, as ONE gather over slices resident in HBM, bit for bit scipy's result.
+ * images[b] / labels[b]: HOST arrays of device pointers to the fp32 [n0,n1] slice and its uint8 label; int_params: HOST int32
+ * [batch][5] = {n0, n1, branch (0 none, 1 rot90 + flip, 2 rotate), k (np.rot90 count, 0..3), flip axis (0, 1)}; double_params:
+ * HOST double [batch][8] = {M00, M01, M10, M11, off0, off1 (rotate: [[cos, sin], [-sin, cos]] and centre - M @ centre), z0, z1
+ * (zoom: (r - 1) / (o - 1) of the extents r after rot90)}, drawn by the caller with the reference's call sequence
+ * (icl_amd.dataloaders.dataset.draw_generator).  image_out [batch,1,o0,o1] fp32, label_out [batch,o0,o1] uint8.  batch <= 32. */
+int icl_slice_augment(const void* const* images, const void* const* labels, const int32_t* int_params, const double* double_params,
+                      int batch, float* image_out, uint8_t* label_out, int o0, int o1, void* stream);
+/* scipy.ndimage.zoom(slice, (o0 / n0, o1 / n1), order=0) of `batch` slices [n0,n1] -> [o0,o1] sharing one extent: both resizes of the
+ * 2-D validation loop (val_2D.py:41,48).  elem_kind 0: fp32 (the slices going in), 1: int64 (the arg-max maps going
+ * back).  Zero last rows / columns where scipy's coordinate overshoots the source extent are reproduced. */
+int icl_slice_resize(const void* src, void* dst, int64_t batch, int n0, int n1, int o0, int o1, int elem_kind, void* stream);
+
 /* ---- fused SGD(momentum, weight decay) step, torch.optim.SGD semantics (train_inherent_consistent_unet_3D_BraTS.py:85-86,115):
  * d = g + wd*p; m = first ? d : momentum*m + d; p -= lr*m.  The multi form takes HOST arrays of device pointers.
  * lr_dev (may be NULL): when given, the learning rate is read from this device scalar instead of `lr` (hipGraph replay). */

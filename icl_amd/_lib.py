@@ -103,6 +103,9 @@ _SIGNATURES = {
     "icl_window_attn_fwd": (c_int, [P, P, P, P, P, I, I, I, I, I, F, P]),
     "icl_window_attn_bwd": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, P]),
     "icl_window_attn_bwd_chunks": (c_int, [I, I, I, I, I]),
+    "icl_window_attn_fwd_drop": (c_int, [P, P, P, P, P, I, I, I, I, I, F, ctypes.c_uint32, F, P, P]),
+    "icl_window_attn_keep_probe": (c_int, [P, c_int64, I, ctypes.c_uint32, F, P, P]),
+    "icl_window_attn_bwd_drop": (c_int, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, ctypes.c_uint32, F, P, P]),
     "icl_relpos_bias_bwd_sum": (c_int, [P, I, P, P, P, L, I, I, P]),
     "icl_layernorm_fwd": (c_int, [P, P, P, P, P, P, L, I, F, P]),
     "icl_layernorm_bwd_ws_bytes": (c_int64, [L, I]),

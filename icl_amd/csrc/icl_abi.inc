@@ -681,16 +681,18 @@ static int winattn_geom(icl::WinAttnGeom& g, int b_, int n, int heads, int nw, i
 
 int64_t icl_window_attn_bias_elems_impl(int n, int heads) { return (int64_t)heads * n * ((n + 15) / 16 * 16); }
 
-template <int NKB, int DH>
+// The launchers take the kernels' optional trailing argument (const icl::WaDrop&, attention dropout) as a pack and hand it on: with the
+// pack empty they launch the p = 0 instantiations, with it the dropout ones — one kernel choice, one set of LDS sizes for both.
+template <int NKB, int DH, typename... DR>
 static int winattn_fwd_launch(const float* qkv, const float* bias, const int* regions, float* out, float* lse, const icl::WinAttnGeom& g,
-                              hipStream_t st) {
+                              hipStream_t st, const DR&... dr) {
   const size_t lds = ((size_t)2 * g.npad * icl::WaCfg<DH>::LD + g.npad) * 4;
   if (g.npad == NKB * 16) {
-    ICL_LAUNCH((icl::window_attn_fwd_kernel<NKB, DH, true>), dim3((unsigned)g.B_ * g.heads), dim3(icl::kWaThreads), lds, st, qkv, bias, regions, out, lse, g);
+    ICL_LAUNCH((icl::window_attn_fwd_kernel<NKB, DH, true>), dim3((unsigned)g.B_ * g.heads), dim3(icl::kWaThreads), lds, st, qkv, bias, regions, out, lse, g, dr...);
   } else {
-    ICL_LAUNCH((icl::window_attn_fwd_kernel<NKB, DH, false>), dim3((unsigned)g.B_ * g.heads), dim3(icl::kWaThreads), lds, st, qkv, bias, regions, out, lse, g);
+    ICL_LAUNCH((icl::window_attn_fwd_kernel<NKB, DH, false>), dim3((unsigned)g.B_ * g.heads), dim3(icl::kWaThreads), lds, st, qkv, bias, regions, out, lse, g, dr...);
   }
-  snprintf(g_kernel, sizeof(g_kernel), "window_attn_fwd_kernel<%d, %d>", NKB, DH);
+  snprintf(g_kernel, sizeof(g_kernel), "window_attn_fwd_kernel<%d, %d%s>", NKB, DH, sizeof...(DR) ? ", WaDrop" : "");
   return check_launch("window_attn_fwd");
 }
 
@@ -703,29 +705,78 @@ static int winattn_bias_chunks(const icl::WinAttnGeom& g) {
   return chunks < 1 ? 1 : chunks;
 }
 
-template <int NKB, int DH>
+template <int NKB, int DH, typename... DR>
 static int winattn_q_bias_launch(const float* qkv, const float* bias, const int* regions, const float* out, const float* lse,
-                                 const float* dout, float* dqkv, float* dbias, const icl::WinAttnGeom& g, hipStream_t st) {
+                                 const float* dout, float* dqkv, float* dbias, const icl::WinAttnGeom& g, hipStream_t st, const DR&... dr) {
   const size_t lds = ((size_t)2 * g.npad * icl::WaCfg<DH>::LD + g.npad) * 4;
   const int nkb = g.npad / 16, gx = (nkb + icl::kWaWaves - 1) / icl::kWaWaves;
   const int chunks = winattn_bias_chunks(g);
   if (g.npad == NKB * 16) {
     ICL_LAUNCH((icl::window_attn_bwd_q_bias_kernel<NKB, DH, true>), dim3(gx, g.heads, chunks), dim3(icl::kWaThreads), lds, st, qkv, bias,
-               regions, out, lse, dout, dqkv, dbias, g);
+               regions, out, lse, dout, dqkv, dbias, g, dr...);
   } else {
     ICL_LAUNCH((icl::window_attn_bwd_q_bias_kernel<NKB, DH, false>), dim3(gx, g.heads, chunks), dim3(icl::kWaThreads), lds, st, qkv, bias,
-               regions, out, lse, dout, dqkv, dbias, g);
+               regions, out, lse, dout, dqkv, dbias, g, dr...);
   }
   return check_launch("window_attn_bwd_q_bias");
 }
 
-template <int DH>
+template <int DH, typename... DR>
 static int winattn_kv_launch(const float* qkv, const float* bias, const int* regions, const float* out, const float* lse,
-                             const float* dout, float* dqkv, const icl::WinAttnGeom& g, hipStream_t st) {
+                             const float* dout, float* dqkv, const icl::WinAttnGeom& g, hipStream_t st, const DR&... dr) {
   const size_t lds = ((size_t)2 * g.npad * icl::WaCfg<DH>::LD + 3 * g.npad) * 4;
   ICL_LAUNCH((icl::window_attn_bwd_kv_kernel<DH>), dim3((unsigned)g.B_ * g.heads), dim3(icl::kWaThreads), lds, st, qkv, bias, regions, out,
-             lse, dout, dqkv, g);
+             lse, dout, dqkv, g, dr...);
   return check_launch("window_attn_bwd_kv");
+}
+
+// the forward of icl_window_attn_fwd and icl_window_attn_fwd_drop: which kernel, for p = 0 and for dropout alike
+template <typename... DR>
+static int winattn_fwd_dispatch(const float* qkv, const float* bias, const int* regions, float* out, float* lse, const icl::WinAttnGeom& g,
+                                int head_dim, hipStream_t st, const DR&... dr) {
+  const int nkb = g.npad / 16;
+  // ICL_WINATTN_ONLINE (default 1): online softmax over chunks of four key blocks, four waves per SIMD (kernels/winattn.h), for the
+  // 343- / 216-token windows of SwinUNETR; 0: the whole score row block of a wave in registers
+  const char* e_on = getenv("ICL_WINATTN_ONLINE");
+  // (measured, batch 2: 686 windows x 3 heads 420 -> 354 us, 128 x 6 heads 137 -> 122; with 192 workgroups or fewer the chip is not
+  // full either way and the extra rescaling costs 7 %: those stay on the register-resident form)
+  const int online = e_on ? atoi(e_on) : 1;             // 2: whatever the size (tests)
+  if (head_dim == 16 && ((nkb > 6 && (long)g.B_ * g.heads >= 512 && online == 1) || online == 2)) {
+    const size_t lds = ((size_t)2 * g.npad * (16 + 4) + g.npad) * 4;
+    ICL_SET_MAX_DYN_LDS((icl::window_attn_fwd_online_kernel<16, DR...>), 64 * 1024);
+    ICL_LAUNCH((icl::window_attn_fwd_online_kernel<16>), dim3((unsigned)g.B_ * g.heads), dim3(icl::kWaThreads), lds, st, qkv, bias, regions,
+               out, lse, g, dr...);
+    snprintf(g_kernel, sizeof(g_kernel), "window_attn_fwd_online_kernel<16%s>", sizeof...(DR) ? ", WaDrop" : "");
+    return check_launch("window_attn_fwd_online");
+  }
+  if (head_dim == 32) return winattn_fwd_launch<6, 32>(qkv, bias, regions, out, lse, g, st, dr...);
+  if (nkb > 14) return winattn_fwd_launch<22, 16>(qkv, bias, regions, out, lse, g, st, dr...);
+  if (nkb > 6) return winattn_fwd_launch<14, 16>(qkv, bias, regions, out, lse, g, st, dr...);
+  return winattn_fwd_launch<6, 16>(qkv, bias, regions, out, lse, g, st, dr...);
+}
+
+template <typename... DR>
+static int winattn_bwd_dispatch(const float* qkv, const float* bias, const int* regions, const float* out, const float* lse,
+                                const float* dout, float* dqkv, float* dbias, const icl::WinAttnGeom& g, int head_dim, hipStream_t st,
+                                const DR&... dr) {
+  if (int rc = head_dim == 32 ? winattn_kv_launch<32>(qkv, bias, regions, out, lse, dout, dqkv, g, st, dr...)
+                              : winattn_kv_launch<16>(qkv, bias, regions, out, lse, dout, dqkv, g, st, dr...))
+    return rc;
+  const int nkb = g.npad / 16;      // (dbias: icl_window_attn_bwd_chunks(...) slabs, every used element written: no memset)
+  if (head_dim == 32) return winattn_q_bias_launch<6, 32>(qkv, bias, regions, out, lse, dout, dqkv, dbias, g, st, dr...);
+  if (nkb > 14) return winattn_q_bias_launch<22, 16>(qkv, bias, regions, out, lse, dout, dqkv, dbias, g, st, dr...);
+  if (nkb > 6) return winattn_q_bias_launch<14, 16>(qkv, bias, regions, out, lse, dout, dqkv, dbias, g, st, dr...);
+  return winattn_q_bias_launch<6, 16>(qkv, bias, regions, out, lse, dout, dqkv, dbias, g, st, dr...);
+}
+
+// Attention dropout: seed / threshold / scale of one launch (the mask is regenerated from (seed, index) in every kernel).
+static int winattn_drop_spec(icl::WaDrop& d, uint32_t seed, float p, const uint32_t* seed_dev, const char* who) {
+  if (!(p > 0.f && p < 1.f)) return fail(-1, "%s: 0 < p < 1 required (p = 0 is the kernel without dropout)", who);
+  d.seed = (unsigned)seed;
+  d.thresh = (unsigned)((double)p * 4294967296.0);      // as icl_drop_path_add
+  d.scale = 1.f / (1.f - p);
+  d.seed_dev = (const unsigned*)seed_dev;
+  return 0;
 }
 
 // ---- dense products (kernels/gemm.h) ------------------------------------------------------------------------------
@@ -2032,26 +2083,7 @@ int icl_window_attn_fwd(const float* qkv, const float* bias, const int32_t* regi
   if (!qkv || !bias || !out || !lse) return fail(-1, "window_attn_fwd: null pointer");
   icl::WinAttnGeom g;
   if (int rc = winattn_geom(g, b_, n, heads, nw, head_dim, scale, "window_attn_fwd")) return rc;
-  const int nkb = g.npad / 16;
-  hipStream_t st = (hipStream_t)stream;
-  // ICL_WINATTN_ONLINE (default 1): online softmax over chunks of four key blocks, four waves per SIMD (kernels/winattn.h), for the
-  // 343- / 216-token windows of SwinUNETR; 0: the whole score row block of a wave in registers
-  const char* e_on = getenv("ICL_WINATTN_ONLINE");
-  // (measured, batch 2: 686 windows x 3 heads 420 -> 354 us, 128 x 6 heads 137 -> 122; with 192 workgroups or fewer the chip is not
-  // full either way and the extra rescaling costs 7 %: those stay on the register-resident form)
-  const int online = e_on ? atoi(e_on) : 1;             // 2: whatever the size (tests)
-  if (head_dim == 16 && ((nkb > 6 && (long)g.B_ * g.heads >= 512 && online == 1) || online == 2)) {
-    const size_t lds = ((size_t)2 * g.npad * (16 + 4) + g.npad) * 4;
-    ICL_SET_MAX_DYN_LDS((icl::window_attn_fwd_online_kernel<16>), 64 * 1024);
-    ICL_LAUNCH((icl::window_attn_fwd_online_kernel<16>), dim3((unsigned)g.B_ * g.heads), dim3(icl::kWaThreads), lds, st, qkv, bias, regions,
-               out, lse, g);
-    snprintf(g_kernel, sizeof(g_kernel), "window_attn_fwd_online_kernel<16>");
-    return check_launch("window_attn_fwd_online");
-  }
-  if (head_dim == 32) return winattn_fwd_launch<6, 32>(qkv, bias, regions, out, lse, g, st);
-  if (nkb > 14) return winattn_fwd_launch<22, 16>(qkv, bias, regions, out, lse, g, st);
-  if (nkb > 6) return winattn_fwd_launch<14, 16>(qkv, bias, regions, out, lse, g, st);
-  return winattn_fwd_launch<6, 16>(qkv, bias, regions, out, lse, g, st);
+  return winattn_fwd_dispatch(qkv, bias, regions, out, lse, g, head_dim, (hipStream_t)stream);
 }
 
 int icl_window_attn_bwd(const float* qkv, const float* bias, const int32_t* regions, const float* out, const float* lse,
@@ -2060,15 +2092,37 @@ int icl_window_attn_bwd(const float* qkv, const float* bias, const int32_t* regi
   if (!qkv || !bias || !out || !lse || !dout || !dqkv) return fail(-1, "window_attn_bwd: null pointer");
   icl::WinAttnGeom g;
   if (int rc = winattn_geom(g, b_, n, heads, nw, head_dim, scale, "window_attn_bwd")) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = head_dim == 32 ? winattn_kv_launch<32>(qkv, bias, regions, out, lse, dout, dqkv, g, st)
-                              : winattn_kv_launch<16>(qkv, bias, regions, out, lse, dout, dqkv, g, st))
-    return rc;
-  const int nkb = g.npad / 16;      // (dbias: icl_window_attn_bwd_chunks(...) slabs, every used element written: no memset)
-  if (head_dim == 32) return winattn_q_bias_launch<6, 32>(qkv, bias, regions, out, lse, dout, dqkv, dbias, g, st);
-  if (nkb > 14) return winattn_q_bias_launch<22, 16>(qkv, bias, regions, out, lse, dout, dqkv, dbias, g, st);
-  if (nkb > 6) return winattn_q_bias_launch<14, 16>(qkv, bias, regions, out, lse, dout, dqkv, dbias, g, st);
-  return winattn_q_bias_launch<6, 16>(qkv, bias, regions, out, lse, dout, dqkv, dbias, g, st);
+  return winattn_bwd_dispatch(qkv, bias, regions, out, lse, dout, dqkv, dbias, g, head_dim, (hipStream_t)stream);
+}
+
+// WindowAttention.attn_drop (swinunetr_icl.py:742-747) inside the fused kernels: the same dispatch with the dropout instantiations.
+int icl_window_attn_fwd_drop(const float* qkv, const float* bias, const int32_t* regions, float* out, float* lse, int b_, int n, int heads,
+                             int nw, int head_dim, float scale, uint32_t seed, float p, const uint32_t* seed_dev, void* stream) {
+  if (!qkv || !bias || !out || !lse) return fail(-1, "window_attn_fwd_drop: null pointer");
+  icl::WinAttnGeom g;
+  icl::WaDrop d;
+  if (int rc = winattn_geom(g, b_, n, heads, nw, head_dim, scale, "window_attn_fwd_drop")) return rc;
+  if (int rc = winattn_drop_spec(d, seed, p, seed_dev, "window_attn_fwd_drop")) return rc;
+  return winattn_fwd_dispatch(qkv, bias, regions, out, lse, g, head_dim, (hipStream_t)stream, d);
+}
+
+int icl_window_attn_bwd_drop(const float* qkv, const float* bias, const int32_t* regions, const float* out, const float* lse,
+                             const float* dout, float* dqkv, float* dbias, int b_, int n, int heads, int nw, int head_dim, float scale,
+                             uint32_t seed, float p, const uint32_t* seed_dev, void* stream) {
+  if (!qkv || !bias || !out || !lse || !dout || !dqkv) return fail(-1, "window_attn_bwd_drop: null pointer");
+  icl::WinAttnGeom g;
+  icl::WaDrop d;
+  if (int rc = winattn_geom(g, b_, n, heads, nw, head_dim, scale, "window_attn_bwd_drop")) return rc;
+  if (int rc = winattn_drop_spec(d, seed, p, seed_dev, "window_attn_bwd_drop")) return rc;
+  return winattn_bwd_dispatch(qkv, bias, regions, out, lse, dout, dqkv, dbias, g, head_dim, (hipStream_t)stream, d);
+}
+
+int icl_window_attn_keep_probe(int32_t* out, int64_t base, int count, uint32_t seed, float p, const uint32_t* seed_dev, void* stream) {
+  if (!out || count < 1 || base < 0) return fail(-1, "window_attn_keep_probe: bad argument");
+  icl::WaDrop d;
+  if (int rc = winattn_drop_spec(d, seed, p, seed_dev, "window_attn_keep_probe")) return rc;
+  ICL_LAUNCH(icl::window_attn_keep_probe_kernel, dim3(grid_for(count, 256)), dim3(256), 0, (hipStream_t)stream, (int*)out, (long)base, count, d);
+  return check_launch("window_attn_keep_probe");
 }
 
 int icl_window_attn_bwd_chunks(int b_, int n, int heads, int nw, int head_dim) {

@@ -125,7 +125,10 @@ struct DropSpec {
   const float* ss;      // != nullptr: the kernel's x operand is a RAW convolution output; relu(fma(x, scale, shift)) per (sample, channel) is
                         // applied on load, in front of the mask (deferred InstanceNorm + ReLU, norm.h norm_finalize_stats_kernel)
 };
-__device__ __forceinline__ unsigned drop_seed(const DropSpec& d) { return d.seed_dev ? mix32(d.seed ^ mix32(*d.seed_dev + 0x632BE5ABu)) : d.seed; }
+__device__ __forceinline__ unsigned drop_seed(unsigned seed, const unsigned* seed_dev) {
+  return seed_dev ? mix32(seed ^ mix32(*seed_dev + 0x632BE5ABu)) : seed;
+}
+__device__ __forceinline__ unsigned drop_seed(const DropSpec& d) { return drop_seed(d.seed, d.seed_dev); }
 __device__ __forceinline__ float drop_apply(float v, unsigned seed, unsigned thresh, float scale, long k) {
   const unsigned h = mix32((unsigned)k * 0x9E3779B1u + seed) ^ mix32((unsigned)(k >> 32) + seed * 0x85EBCA77u);
   return h >= thresh ? v * scale : 0.f;

@@ -26,6 +26,15 @@
 // (b) window_attn_bwd_q_bias — waves own a (head, query block) and walk over a slice of the windows (K, V staged per
 //     window, S^T layout): dQ of every window is written directly, and d(bias)[h, i, j] — the sum of dS over ALL windows of
 //     the batch — stays in a register-resident 16 x n slab that is added to HBM once at the end.
+//
+// Attention dropout (WindowAttention.attn_drop, swinunetr_icl.py:742-747) acts on the soft-max probabilities, which exist only in
+// registers here, so the mask is never stored: every kernel regenerates keep(k) = hash(seed, k) >= thresh — the decision of
+// dropout_kernel / drop_apply (misc.h) — for k = ((b_ * heads + h) * n + i) * n + j, the flat index of the reference's
+// [B_, heads, n, n] attention tensor.  Forward: Pd = keep * P / (1 - p), out = Pd V, the log-sum-exp is that of the undropped row.
+// Backward: dV = Pd^T dO, dP = keep / (1 - p) * (dO V^T), dS = P * (dP - D) with D_i = sum_j P_ij dP_ij = dO_i . out_i — the row term
+// computed from out and dO stays what it is.  The dropout variants are separate instantiations of the same kernel templates:
+// a launch that passes a trailing WaDrop argument instantiates <..., WaDrop> (DROP = true); without it the parameter pack is empty, the
+// kernel has the signature and the code it had before dropout existed, and every mask expression is a compile-time constant.
 #pragma once
 
 namespace icl {
@@ -42,6 +51,60 @@ struct WinAttnGeom {
   int B_, n, npad, heads, nW;      // B_ = batch * nW windows; window id of row b_ is b_ % nW (window_partition order)
   float scale;
 };
+
+// Attention dropout of one launch (DROP kernels only): seed / thresh / scale = 1 / (1 - p) as dropout_kernel's, seed_dev the optional
+// device-resident step counter hashed into the seed (drop_seed).
+struct WaDrop {
+  unsigned seed, thresh;
+  float scale;
+  const unsigned* seed_dev;
+};
+
+// keep(k) for the scores of one (window, head): k = base + off with base = (b_ * heads + h) * n * n in 64 bits and off = i * n + j < 2^17.
+// Constant per (window, head) and hoisted: the hash of the high word of k — two candidates, without and with the carry of the low
+// word's addition — and x0 = lo(base) * 0x9E3779B1 + seed; per score one multiply-add, mix32, a select, an xor and the compare.
+struct WaDropCtx {
+  unsigned x0, ncarry, h_hi, h_hi1, thresh;
+  __device__ __forceinline__ void init(const WaDrop& d, long bh, int n) {
+    init_base(d, bh * n * n);
+  }
+  __device__ __forceinline__ void init_base(const WaDrop& d, long base) {
+    const unsigned seed = drop_seed(d.seed, d.seed_dev);
+    const unsigned lo = (unsigned)base, hi = (unsigned)(base >> 32);
+    x0 = lo * 0x9E3779B1u + seed;
+    ncarry = lo ? 0u - lo : 0xFFFFFFFFu;      // lo + off wraps iff off >= 2^32 - lo
+    h_hi = mix32(hi + seed * 0x85EBCA77u);
+    h_hi1 = mix32(hi + 1u + seed * 0x85EBCA77u);
+    thresh = d.thresh;
+  }
+  __device__ __forceinline__ bool keep(unsigned off) const {
+    const unsigned h = mix32(x0 + off * 0x9E3779B1u) ^ (off >= ncarry ? h_hi1 : h_hi);
+    return h >= thresh;
+  }
+};
+
+// The decisions of one query against all keys of its window, one bit each (bit 4 kb + r of the lane = key 16 kb + 4 lg + r): the kernels
+// that hold a whole score row block or bias-gradient slab in registers (4 NKB of them) draw the row's decisions BEFORE that block goes
+// live and keep them in NKB / 8 registers.  The draw is a rolled loop on purpose: drawn in place, or unrolled here, the 4 NKB independent
+// hashes are scheduled side by side and the kernel spills.
+template <int NKB> struct WaKeepBits {
+  static constexpr int NW = (4 * NKB + 31) / 32;
+  unsigned w[NW];
+  __device__ __forceinline__ void draw(const WaDropCtx& dc, unsigned koff, int nkb) {
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+      const int nbits = 4 * nkb - 32 * i < 32 ? 4 * nkb - 32 * i : 32;      // (the key blocks past nkb of a general template stay 0)
+      unsigned acc = 0u;
+#pragma unroll 1
+      for (int b = 0; b < nbits; ++b) acc |= (dc.keep(koff + (unsigned)((8 * i + (b >> 2)) * 16 + (b & 3))) ? 1u : 0u) << b;
+      w[i] = acc;
+    }
+  }
+  __device__ __forceinline__ bool keep(int kb, int r) const { return (w[(4 * kb + r) >> 5] >> ((4 * kb + r) & 31)) & 1u; }
+};
+
+__device__ __forceinline__ WaDrop wa_drop_arg() { return WaDrop{0u, 0u, 1.f, nullptr}; }      // DROP = false: never read
+__device__ __forceinline__ WaDrop wa_drop_arg(const WaDrop& d) { return d; }
 
 // exp via v_exp_f32 (2^x): relative error ~1e-6 for |x| < 20, far inside the 1e-3 parity budget
 __device__ __forceinline__ float wa_exp(float x) { return icl_fast_exp(x); }
@@ -181,10 +244,12 @@ __global__ __launch_bounds__(256) void relpos_bias_gather_sum_kernel(const float
 // EXACT: the window has exactly NKB key blocks (343 tokens -> 22, 216 -> 14): the per-block guards compile away and the whole
 // query-block body becomes straight-line code, so the bias loads and K/V operand reads of later key blocks are issued under
 // the MFMAs of earlier ones (with the guards every key block was its own basic block: load, wait, four MFMAs).
-template <int NKB, int DH, bool EXACT>
+template <int NKB, int DH, bool EXACT, typename... DR>
 __global__ __launch_bounds__(kWaThreads) void window_attn_fwd_kernel(const float* __restrict__ qkv, const float* __restrict__ bias,
                                                               const int* __restrict__ regions, float* __restrict__ out,
-                                                              float* __restrict__ lse, WinAttnGeom g) {
+                                                              float* __restrict__ lse, WinAttnGeom g, DR... dr) {
+  constexpr bool DROP = sizeof...(DR) != 0;
+  const WaDrop d = wa_drop_arg(dr...);
   constexpr int LD = WaCfg<DH>::LD, DT = WaCfg<DH>::DT;
   ICL_DYN_LDS(float, lds);
   float* Ks = lds;
@@ -203,12 +268,16 @@ __global__ __launch_bounds__(kWaThreads) void window_attn_fwd_kernel(const float
   __syncthreads();
   const bool masked = regions != nullptr && mixed != 0;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
+  WaDropCtx dc;
+  if (DROP) dc.init(d, (long)b_ * g.heads + h, g.n);
   for (int qb = wid; qb < nkb; qb += kWaWaves) {
     const int query = qb * 16 + lr, qc = query < g.n ? query : g.n - 1;
     WaFrag<DH> qf;
     qf.load(base + (long)qc * rs, lg, g.scale);
     const int rq = rid[qc];
     const float* brow = bias + ((long)h * g.n + qc) * g.npad;
+    WaKeepBits<NKB> kbits;      // mask index of (query, key 4 lg) within the (window, head): qc * n + 4 lg
+    if (DROP) kbits.draw(dc, (unsigned)(qc * g.n + lg * 4), nkb);
     f32x4 s[NKB];
     float m = -3.0e38f;
 #pragma unroll
@@ -227,7 +296,7 @@ __global__ __launch_bounds__(kWaThreads) void window_attn_fwd_kernel(const float
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float p = wa_exp(s[kb][r] - m);
-          s[kb][r] = p;
+          s[kb][r] = (DROP && !kbits.keep(kb, r)) ? 0.f : p;      // the row sum is that of the undropped probabilities
           l += p;
         }
       }
@@ -235,7 +304,7 @@ __global__ __launch_bounds__(kWaThreads) void window_attn_fwd_kernel(const float
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
     if (lg == 0 && query < g.n) lse[((long)b_ * g.heads + h) * g.n + query] = m + logf(l);
-    const float inv = 1.0f / l;
+    const float inv = DROP ? d.scale / l : 1.0f / l;      // 1 / (1 - p) of the kept probabilities rides on the normalisation
     f32x4 o[DT];
 #pragma unroll
     for (int t = 0; t < DT; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -266,10 +335,12 @@ __global__ __launch_bounds__(kWaThreads) void window_attn_fwd_kernel(const float
 // maximum (two lane-group shuffles), rescale of the running sum and of the O accumulators by exp(m_old - m_new) — O rows are queries
 // 4 lg + r, the factor of query q lives in the lanes with lr = q: four shuffles —, P V (16 MFMAs).  Same outputs as
 // window_attn_fwd_kernel (out, lse = m + log l).
-template <int DH>
+template <int DH, typename... DR>
 __global__ __launch_bounds__(kWaThreads, 2) void window_attn_fwd_online_kernel(const float* __restrict__ qkv, const float* __restrict__ bias,
                                                                                const int* __restrict__ regions, float* __restrict__ out,
-                                                                               float* __restrict__ lse, WinAttnGeom g) {
+                                                                               float* __restrict__ lse, WinAttnGeom g, DR... dr) {
+  constexpr bool DROP = sizeof...(DR) != 0;
+  const WaDrop d = wa_drop_arg(dr...);
   constexpr int LD = WaCfg<DH>::LD, DT = WaCfg<DH>::DT, CH = 4;
   ICL_DYN_LDS(float, lds);
   float* Ks = lds;
@@ -288,12 +359,15 @@ __global__ __launch_bounds__(kWaThreads, 2) void window_attn_fwd_online_kernel(c
   __syncthreads();
   const bool masked = regions != nullptr && mixed != 0;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
+  WaDropCtx dc;
+  if (DROP) dc.init(d, (long)b_ * g.heads + h, g.n);
   for (int qb = wid; qb < nkb; qb += kWaWaves) {
     const int query = qb * 16 + lr, qc = query < g.n ? query : g.n - 1;
     WaFrag<DH> qf;
     qf.load(base + (long)qc * rs, lg, g.scale);
     const int rq = rid[qc];
     const float* brow = bias + ((long)h * g.n + qc) * g.npad;
+    const unsigned koff = DROP ? (unsigned)(qc * g.n + lg * 4) : 0u;
     float m = -3.0e38f, l = 0.f;
     f32x4 o[DT];
 #pragma unroll
@@ -330,7 +404,7 @@ __global__ __launch_bounds__(kWaThreads, 2) void window_attn_fwd_online_kernel(c
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float pv = wa_exp(s[k][r] - mn);
-            s[k][r] = pv;
+            s[k][r] = (DROP && !dc.keep(koff + (c0 + k) * 16 + r)) ? 0.f : pv;
             l += pv;
           }
         }
@@ -357,7 +431,7 @@ __global__ __launch_bounds__(kWaThreads, 2) void window_attn_fwd_online_kernel(c
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
     if (lg == 0 && query < g.n) lse[((long)b_ * g.heads + h) * g.n + query] = m + logf(l);
-    const float inv = 1.0f / l;
+    const float inv = DROP ? d.scale / l : 1.0f / l;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int q = qb * 16 + lg * 4 + r;
@@ -373,11 +447,13 @@ __global__ __launch_bounds__(kWaThreads, 2) void window_attn_fwd_online_kernel(c
 // dK and dV.  grid = B_ * heads; LDS = (2 * npad * (DH + 4) + 3 * npad) * 4 bytes (scale*Q, dO, log-sum-exp, delta, region ids of
 // every query of the window); waves own key blocks, their K / V rows come straight from HBM as MFMA operands.
 // S layout: lane -> query 4*lg + r of the block, key lr.  dqkv has the layout of qkv; only the k and v thirds are written here.
-template <int DH>
+template <int DH, typename... DR>
 __global__ __launch_bounds__(kWaThreads) void window_attn_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ bias,
                                                                  const int* __restrict__ regions, const float* __restrict__ out,
                                                                  const float* __restrict__ lse, const float* __restrict__ dout,
-                                                                 float* __restrict__ dqkv, WinAttnGeom g) {
+                                                                 float* __restrict__ dqkv, WinAttnGeom g, DR... dr) {
+  constexpr bool DROP = sizeof...(DR) != 0;
+  const WaDrop d = wa_drop_arg(dr...);
   constexpr int LD = WaCfg<DH>::LD, DT = WaCfg<DH>::DT, Q4 = WaCfg<DH>::Q4;
   ICL_DYN_LDS(float, lds);
   const int np = g.npad;
@@ -415,6 +491,8 @@ __global__ __launch_bounds__(kWaThreads) void window_attn_bwd_kv_kernel(const fl
   __syncthreads();
   const bool masked = regions != nullptr && mixed != 0;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
+  WaDropCtx dc;
+  if (DROP) dc.init(d, (long)b_ * g.heads + h, g.n);
   for (int kb = wid; kb < nkb; kb += kWaWaves) {
     const int key = kb * 16 + lr, kc = key < g.n ? key : g.n - 1;
     WaFrag<DH> kf, vf;
@@ -453,10 +531,13 @@ __global__ __launch_bounds__(kWaThreads) void window_attn_bwd_kv_kernel(const fl
         float sv = s[r];
         if (masked && rid[qc] != rk) sv += kWaMaskAdd;
         const float p = wa_exp(sv - Ls[q]);
-        const float ds = p * (dp[r] - Ds[q]);
+        // dropout: Pd = ksc * P feeds dV, dP = ksc * (dO V^T); (qc, key) is the forward's (query, key) — pad rows have p = 0
+        const float ksc = DROP ? (dc.keep((unsigned)(qc * g.n + key)) ? d.scale : 0.f) : 1.f;
+        const float ds = DROP ? p * (dp[r] * ksc - Ds[q]) : p * (dp[r] - Ds[q]);
+        const float pd = DROP ? p * ksc : p;
 #pragma unroll
         for (int t = 0; t < DT; ++t) {
-          dv[t] = icl_mfma_16x16x4(p, Gs[q * LD + t * 16 + lr], dv[t]);
+          dv[t] = icl_mfma_16x16x4(pd, Gs[q * LD + t * 16 + lr], dv[t]);
           dk[t] = icl_mfma_16x16x4(ds, Qs[q * LD + t * 16 + lr], dk[t]);
         }
       }
@@ -480,11 +561,14 @@ __global__ __launch_bounds__(kWaThreads) void window_attn_bwd_kv_kernel(const fl
 // in LDS, dS is recomputed (S^T layout), dQ of the 16 queries is written, and dS is added to a register-resident 16 x n slab
 // of d(bias), which is summed over all windows of the batch and added to HBM once at the end.
 // grid (ceil(nkb/kWaWaves), heads, chunks); LDS = (2 * npad * (DH + 4) + npad) * 4 bytes.  dbias [chunks, heads, n, npad] (may be NULL).
-template <int NKB, int DH, bool EXACT>
+template <int NKB, int DH, bool EXACT, typename... DR>
 __global__ __launch_bounds__(kWaThreads) void window_attn_bwd_q_bias_kernel(const float* __restrict__ qkv, const float* __restrict__ bias,
                                                                      const int* __restrict__ regions, const float* __restrict__ out,
                                                                      const float* __restrict__ lse, const float* __restrict__ dout,
-                                                                     float* __restrict__ dqkv, float* __restrict__ dbias, WinAttnGeom g) {
+                                                                     float* __restrict__ dqkv, float* __restrict__ dbias, WinAttnGeom g,
+                                                                     DR... dr) {
+  constexpr bool DROP = sizeof...(DR) != 0;
+  const WaDrop d = wa_drop_arg(dr...);
   constexpr int LD = WaCfg<DH>::LD, DT = WaCfg<DH>::DT;
   ICL_DYN_LDS(float, lds);
   float* Ks = lds;
@@ -526,6 +610,10 @@ __global__ __launch_bounds__(kWaThreads) void window_attn_bwd_q_bias_kernel(cons
     dl += __shfl_xor(dl, 32, 64);
     const float lq = qvalid ? lse[((long)b_ * g.heads + h) * g.n + qc] : 1.0e30f;
     const int rq = rid[qc];
+    WaDropCtx dc;
+    if (DROP) dc.init(d, (long)b_ * g.heads + h, g.n);
+    WaKeepBits<NKB> kbits;
+    if (DROP) kbits.draw(dc, (unsigned)(qc * g.n + lg * 4), nkb);
     f32x4 dq[DT];
 #pragma unroll
     for (int t = 0; t < DT; ++t) dq[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -541,7 +629,8 @@ __global__ __launch_bounds__(kWaThreads) void window_attn_bwd_q_bias_kernel(cons
         const f32x4 dp = wa_dot<DH>(vf, gf);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float ds = wa_exp(s[r] - lq) * (dp[r] - dl);
+          const float ds = DROP ? wa_exp(s[r] - lq) * ((kbits.keep(kb, r) ? dp[r] * d.scale : 0.f) - dl)
+                                : wa_exp(s[r] - lq) * (dp[r] - dl);
           acc[kb][r] += ds;
 #pragma unroll
           for (int t = 0; t < DT; ++t) dq[t] = icl_mfma_16x16x4(ds, Ks[(kb * 16 + lg * 4 + r) * LD + t * 16 + lr], dq[t]);
@@ -572,6 +661,14 @@ __global__ __launch_bounds__(kWaThreads) void window_attn_bwd_q_bias_kernel(cons
       }
     }
   }
+}
+
+// out[i] = keep(base + i) as the attention kernels draw it (WaDropCtx), for any 64-bit base: the unit check of the hoisted high-word
+// hashes and the carry rule against dropout_kernel's drop_apply — the models' own index never leaves 32 bits (686 * 3 * 343^2 = 2.4e8).
+__global__ __launch_bounds__(256) void window_attn_keep_probe_kernel(int* __restrict__ out, long base, int count, WaDrop d) {
+  WaDropCtx dc;
+  dc.init_base(d, base);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) out[i] = dc.keep((unsigned)i) ? 1 : 0;
 }
 
 }  // namespace icl

@@ -24,8 +24,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .aligner import LayerNorm, Linear
-from .layers import Conv3d
+from .aligner import DropPath, LayerNorm, Linear
+from .layers import Conv3d, Dropout3
 
 WINDOW = (7, 7, 7)
 
@@ -126,10 +126,13 @@ def merge_index(dims, slices, device):
 
 
 class WindowAttention(nn.Module):
-    """swinunetr_icl.py:644-750."""
+    """swinunetr_icl.py:644-750.  ``attn_drop`` (a plain float, the reference's ``attn_drop.p``) acts on the soft-max probabilities inside
+    the fused attention kernels (ops.window_attention); ``proj_drop`` follows the output projection (:748-749)."""
 
-    def __init__(self, dim, num_heads, window_size, device=None):
+    def __init__(self, dim, num_heads, window_size, attn_drop=0.0, proj_drop=0.0, device=None):
         super().__init__()
+        self.attn_drop = float(attn_drop)
+        self.proj_drop = Dropout3(proj_drop)
         self.dim, self.num_heads, self.window_size = dim, num_heads, tuple(window_size)
         self.scale = (dim // num_heads) ** -0.5
         ws = self.window_size
@@ -149,32 +152,50 @@ class WindowAttention(nn.Module):
     def forward(self, x, regions):
         """x [B*nW, n, C]; regions int32 [nW, n] or None (unshifted block)."""
         out = ops.window_attention(self.qkv(x), self.relative_position_bias_table, self.relative_position_index, regions,
-                                   self.num_heads, self.scale)
-        return self.proj(out)
+                                   self.num_heads, self.scale, self.attn_drop if self.training else 0.0)
+        return self.proj_drop(self.proj(out))
 
 
 class MLPBlock(nn.Module):
-    """MONAI MLPBlock(dropout 0): linear2(GELU(linear1(x)))."""
+    """MONAI MLPBlock(dropout_mode "swin"): drop2(linear2(drop1(GELU(linear1(x))))), two independent dropouts of the same rate."""
 
-    def __init__(self, dim, hidden, device=None):
+    def __init__(self, dim, hidden, dropout_rate=0.0, device=None):
         super().__init__()
         self.linear1 = Linear(dim, hidden, device=device)
         self.linear2 = Linear(hidden, dim, device=device)
+        self.drop1 = Dropout3(dropout_rate)
+        self.drop2 = Dropout3(dropout_rate)
 
     def forward(self, x):
-        return self.linear2(ops.gelu(self.linear1(x)))
+        return self.drop2(self.linear2(self.drop1(ops.gelu(self.linear1(x)))))
 
 
 class SwinTransformerBlock(nn.Module):
-    """swinunetr_icl.py:753-916 (drop_path == identity: net_factory_3d.py passes dropout_path_rate 0.0)."""
+    """swinunetr_icl.py:753-916:  x = shortcut + drop_path(part1(x));  x = x + drop_path(mlp(norm2(x)))  (:869,911-915).
 
-    def __init__(self, dim, num_heads, window_size, shift_size, device=None):
+    Stochastic sites, in the order in which a training-mode forward draws their seeds (``ops.StepRNG.next_seed()`` when it is enabled
+    for the device, torch's CPU generator otherwise; a site whose rate is 0, and every site in ``eval()``, draws nothing and launches
+    what the block launches without it):
+
+      1. ``attn.attn_drop``  — on the soft-max probabilities, inside the fused window-attention kernels, mask index
+                               ((window * heads + head) * n + query) * n + key (forward and both backward kernels regenerate it);
+      2. ``attn.proj_drop``  — element-wise on the projected attention output, windowed layout [B * nW, n, C];
+      3. ``drop_path``       — first residual: one decision per sample, res + keep / (1 - p) * part1 in one kernel (DropPath.add);
+      4. ``mlp.drop1``       — after the GELU, [B, D, H, W, 4C];
+      5. ``mlp.drop2``       — after linear2, [B, D, H, W, C];
+      6. ``drop_path``       — second residual, drawn independently of 3.
+
+    The modules are ``aligner.DropPath`` (``drop_prob``) and ``layers.Dropout3`` (``p``) — they own no parameters or buffers — so a
+    helper that switches stochastic layers off by those attributes reaches them; the attention rate is the float ``attn.attn_drop``."""
+
+    def __init__(self, dim, num_heads, window_size, shift_size, drop=0.0, attn_drop=0.0, drop_path=0.0, device=None):
         super().__init__()
         self.window_size, self.shift_size = tuple(window_size), tuple(shift_size)
         self.norm1 = LayerNorm(dim, device)
-        self.attn = WindowAttention(dim, num_heads, window_size, device)
+        self.attn = WindowAttention(dim, num_heads, window_size, attn_drop, drop, device)
+        self.drop_path = DropPath(drop_path)
         self.norm2 = LayerNorm(dim, device)
-        self.mlp = MLPBlock(dim, int(dim * 4.0), device)
+        self.mlp = MLPBlock(dim, int(dim * 4.0), drop, device)
 
     def forward_part1(self, x, regions):
         b, d, h, w, c = x.shape
@@ -189,8 +210,8 @@ class SwinTransformerBlock(nn.Module):
         return ops.gather_rows(win.view(b, -1, c), to_tok, to_win).view(b, d, h, w, c)
 
     def forward(self, x, regions):
-        x = x + self.forward_part1(x, regions)
-        return x + self.mlp(self.norm2(x))
+        x = self.drop_path.add(x, self.forward_part1(x, regions))
+        return self.drop_path.add(x, self.mlp(self.norm2(x)))
 
     def load_from(self, weights, n_block, layer):
         """swinunetr_icl.py:871-903: self-supervised checkpoints name the MLP ``fc1``/``fc2``."""
@@ -229,13 +250,14 @@ class BasicLayer(nn.Module):
     """swinunetr_icl.py:1019-1116.  Input and output are channels-last here; the reference's two ``rearrange`` calls
     per stage are folded into SwinTransformer.forward."""
 
-    def __init__(self, dim, depth, num_heads, window_size, device=None):
+    def __init__(self, dim, depth, num_heads, window_size, drop=0.0, attn_drop=0.0, drop_path=0.0, device=None):
         super().__init__()
         self.window_size = tuple(window_size)
         self.shift_size = tuple(i // 2 for i in window_size)
         no_shift = tuple(0 for _ in window_size)
-        self.blocks = nn.ModuleList([
-            SwinTransformerBlock(dim, num_heads, self.window_size, no_shift if i % 2 == 0 else self.shift_size, device)
+        self.blocks = nn.ModuleList([      # drop_path: the stage's slice of the linear schedule, one rate per block (:1075)
+            SwinTransformerBlock(dim, num_heads, self.window_size, no_shift if i % 2 == 0 else self.shift_size, drop, attn_drop,
+                                 drop_path[i] if isinstance(drop_path, (list, tuple)) else drop_path, device)
             for i in range(depth)])
         self.downsample = PatchMerging(dim, device)
 
@@ -266,11 +288,15 @@ class PatchEmbed(nn.Module):
 class SwinTransformer(nn.Module):
     """swinunetr_icl.py:1119-1235."""
 
-    def __init__(self, in_chans, embed_dim, window_size, depths, num_heads, device=None):
+    def __init__(self, in_chans, embed_dim, window_size, depths, num_heads, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0,
+                 device=None):
         super().__init__()
         self.patch_embed = PatchEmbed(in_chans, embed_dim, device)
+        self.pos_drop = Dropout3(drop_rate)
+        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, sum(depths))]      # stochastic depth decay rule (:1178)
         for i in range(4):
-            layer = BasicLayer(embed_dim * 2 ** i, depths[i], num_heads[i], window_size, device)
+            layer = BasicLayer(embed_dim * 2 ** i, depths[i], num_heads[i], window_size, drop_rate, attn_drop_rate,
+                               dpr[sum(depths[:i]):sum(depths[:i + 1])], device)
             setattr(self, f"layers{i + 1}", nn.ModuleList([layer]))
 
     @staticmethod
@@ -281,7 +307,7 @@ class SwinTransformer(nn.Module):
         return x.permute(0, 4, 1, 2, 3).contiguous()
 
     def forward(self, x, normalize=True):
-        x0 = self.patch_embed(x)
+        x0 = self.pos_drop(self.patch_embed(x))
         outs = [self.proj_out(x0, normalize)]
         cur = x0
         for i in range(4):
@@ -386,12 +412,19 @@ class SwinUNETRBackbone(nn.Module):
                 raise ValueError("input image size (img_size) should be divisible by stage-wise image resolution.")
         if feature_size % 12 != 0:
             raise ValueError("feature_size should be divisible by 12.")
-        if drop_rate or attn_drop_rate or dropout_path_rate:
-            raise NotImplementedError("SwinUNETR dropout / stochastic depth: the reference factory passes 0.0 for all three")
+        if not (0 <= drop_rate <= 1):
+            raise ValueError("dropout rate should be between 0 and 1.")
+        if not (0 <= attn_drop_rate <= 1):
+            raise ValueError("attention dropout rate should be between 0 and 1.")
+        if not (0 <= dropout_path_rate <= 1):
+            raise ValueError("drop path rate should be between 0 and 1.")
+        if 1 in (drop_rate, attn_drop_rate, dropout_path_rate):
+            # the reference's range admits 1 (everything dropped, 0 / 0 scaling); the mask kernels take p < 1
+            raise ValueError("icl_amd SwinUNETR: a dropout / drop path rate of exactly 1 is not supported (rates in [0, 1))")
         self.img_size = tuple(img_size)
         self.normalize = normalize
         f = feature_size
-        self.swinViT = SwinTransformer(in_channels, f, WINDOW, depths, num_heads, device)
+        self.swinViT = SwinTransformer(in_channels, f, WINDOW, depths, num_heads, drop_rate, attn_drop_rate, dropout_path_rate, device)
         self.encoder1 = UnetrBasicBlock(in_channels, f, device)
         self.encoder2 = UnetrBasicBlock(f, f, device)
         self.encoder3 = UnetrBasicBlock(2 * f, 2 * f, device)

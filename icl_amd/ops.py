@@ -1302,6 +1302,38 @@ def _step_seed(x, seed):
     return int(seed) & 0xFFFFFFFF, seed_dev
 
 
+def _mix32_np(x):
+    import numpy as np
+    x = x.astype(np.uint32, copy=True)
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x7FEB352D)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x846CA68B)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def dropout_keep_mask(seed: int, numel: int, p: float, group: int = 1, step: Optional[int] = None, start: int = 0):
+    """The keep / drop decisions of ``dropout_kernel`` / ``drop_apply`` (csrc/kernels/misc.h) restated on the host: a numpy bool array
+    [numel], True where element i is kept.  ``seed``: the 32-bit seed handed to the kernel; ``step``: the value of the ``StepRNG`` device
+    counter when one is in use (it is hashed into the seed as ``drop_seed`` does), None when the launch has no device counter;
+    ``group``: elements per decision (``icl_drop_path``: one decision per sample); ``start``: index of the first element (the decisions
+    of elements start .. start + numel - 1: a window of a tensor too large to enumerate).  Pure numpy, no GPU: the explicit mask against which
+    every stochastic site — the in-kernel attention dropout included — is checked."""
+    import numpy as np
+    seed = int(seed) & 0xFFFFFFFF
+    if step is not None:
+        seed = _mix32(seed ^ _mix32((int(step) + 0x632BE5AB) & 0xFFFFFFFF))
+    thresh = int(float(np.float32(p)) * 4294967296.0)      # (unsigned)((double)p * 2^32), p a C float
+    i = np.arange(int(numel), dtype=np.uint64) + np.uint64(start)
+    k = i // np.uint64(group) if group > 1 else i
+    lo = (k & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    hi = (k >> np.uint64(32)).astype(np.uint32)
+    with np.errstate(over="ignore"):
+        h = _mix32_np(lo * np.uint32(0x9E3779B1) + np.uint32(seed)) ^ _mix32_np(hi + np.uint32((seed * 0x85EBCA77) & 0xFFFFFFFF))
+    return h.astype(np.uint64) >= np.uint64(thresh)
+
+
 def drop_path_add(res: torch.Tensor, x: torch.Tensor, p: float, training: bool = True, seed: Optional[int] = None) -> torch.Tensor:
     """res + DropPath(p)(x) — the residual update of a transformer block — as one kernel in training (a plain add otherwise).
     Same per-sample mask and seeding as ``drop_path``."""
@@ -1982,7 +2014,7 @@ class _WindowAttention(torch.autograd.Function):
     table into the kernel's padded [heads, n, npad] layout by a small kernel (and its gradient scattered back)."""
 
     @staticmethod
-    def forward(ctx, qkv, table, index, regions, heads, scale):
+    def forward(ctx, qkv, table, index, regions, heads, scale, attn_drop=0.0, seed=0, seed_dev=None):
         _require(qkv, table, index, regions)
         L = _lib.lib()
         qkv = qkv.contiguous()
@@ -2002,10 +2034,16 @@ class _WindowAttention(torch.autograd.Function):
         lse = torch.empty((b_, heads, n), dtype=torch.float32, device=qkv.device)
         flops = 4.0 * b_ * heads * n * n * dh
         with _timed("window_attn_fwd_kernel", flops, 4.0 * (qkv.numel() + out.numel()), qkv):
-            _lib.check(L.icl_window_attn_fwd(_ptr(qkv), _ptr(bias_pad), _ptr(regions), _ptr(out), _ptr(lse), b_, n, heads, nw, dh,
-                                             scale, _stream(qkv)), "window_attn_fwd")
+            if attn_drop > 0.0:      # the dropout instantiations: the mask is regenerated in the kernels from (seed, index), never stored
+                _lib.check(L.icl_window_attn_fwd_drop(_ptr(qkv), _ptr(bias_pad), _ptr(regions), _ptr(out), _ptr(lse), b_, n, heads, nw, dh,
+                                                      scale, seed, attn_drop, _ptr(seed_dev), _stream(qkv)), "window_attn_fwd_drop")
+            else:
+                _lib.check(L.icl_window_attn_fwd(_ptr(qkv), _ptr(bias_pad), _ptr(regions), _ptr(out), _ptr(lse), b_, n, heads, nw, dh,
+                                                 scale, _stream(qkv)), "window_attn_fwd")
         ctx.save_for_backward(qkv, bias_pad, index, regions, out, lse)
         ctx.cfg = (heads, scale, nw, table.shape[0], dh)
+        ctx.drop = (attn_drop, seed)
+        ctx.seed_dev = seed_dev
         return out
 
     @staticmethod
@@ -2021,25 +2059,54 @@ class _WindowAttention(torch.autograd.Function):
         # one d(bias) slab per slice of windows (plain stores), summed in a fixed order below: no float atomics
         dbias = torch.empty((chunks,) + tuple(bias_pad.shape), dtype=torch.float32, device=qkv.device) if need_table else None
         flops = 14.0 * b_ * heads * n * n * dh
+        attn_drop, seed = ctx.drop
         with _timed("window_attn_bwd_kernel", flops, 4.0 * (2 * qkv.numel() + 2 * out.numel()), qkv):
-            _lib.check(L.icl_window_attn_bwd(_ptr(qkv), _ptr(bias_pad), _ptr(regions), _ptr(out), _ptr(lse), _ptr(gout), _ptr(dqkv),
-                                             _ptr(dbias), b_, n, heads, nw, dh, scale, _stream(qkv)), "window_attn_bwd")
+            if attn_drop > 0.0:
+                _lib.check(L.icl_window_attn_bwd_drop(_ptr(qkv), _ptr(bias_pad), _ptr(regions), _ptr(out), _ptr(lse), _ptr(gout), _ptr(dqkv),
+                                                      _ptr(dbias), b_, n, heads, nw, dh, scale, seed, attn_drop, _ptr(ctx.seed_dev),
+                                                      _stream(qkv)), "window_attn_bwd_drop")
+            else:
+                _lib.check(L.icl_window_attn_bwd(_ptr(qkv), _ptr(bias_pad), _ptr(regions), _ptr(out), _ptr(lse), _ptr(gout), _ptr(dqkv),
+                                                 _ptr(dbias), b_, n, heads, nw, dh, scale, _stream(qkv)), "window_attn_bwd")
         dtable = None
         if need_table:
             dtable = torch.empty((trows, heads), dtype=torch.float32, device=qkv.device)
             inv, offs = _relpos_inverse(index, n, trows)
             _lib.check(L.icl_relpos_bias_bwd_sum(_ptr(dbias), chunks, _ptr(inv), _ptr(offs), _ptr(dtable), trows, n, heads, _stream(qkv)),
                        "relpos_bias_bwd_sum")
-        return dqkv, dtable, None, None, None, None
+        return dqkv, dtable, None, None, None, None, None, None, None
 
 
 def window_attention(qkv: torch.Tensor, table: torch.Tensor, index: torch.Tensor, regions: Optional[torch.Tensor], heads: int,
-                     scale: float) -> torch.Tensor:
+                     scale: float, attn_drop: float = 0.0, seed: Optional[int] = None) -> torch.Tensor:
     """WindowAttention.forward core (swinunetr_icl.py:728-747).  qkv [B_, n, 3C] (q|k|v, each head-major); table
     ``relative_position_bias_table`` [T, heads] and index ``relative_position_index`` [343, 343] (the bias of a window with
     n tokens is table[index[:n, :n]] — also for clipped windows, as the reference does); regions int32 [nW, n] or None
-    (tokens of one window attend to each other iff their region ids match: the 0/-100 mask).  Returns [B_, n, C]."""
-    return _WindowAttention.apply(qkv, table, index, regions, heads, float(scale))
+    (tokens of one window attend to each other iff their region ids match: the 0/-100 mask).  Returns [B_, n, C].
+
+    ``attn_drop`` > 0 (the caller passes 0 outside training): dropout on the soft-max probabilities (:742-747) inside the fused kernels,
+    ``out = (keep * P / (1 - attn_drop)) @ v``.  The mask is the one ``dropout`` would draw on the reference's [B_, heads, n, n] attention
+    tensor — ``dropout_keep_mask(seed, B_ * heads * n * n, attn_drop)`` — and is regenerated by the backward kernels; ``seed`` follows the
+    protocol of ``dropout`` (None: ``StepRNG`` when enabled for the device, else torch's CPU generator).  ``attn_drop == 0`` draws no
+    seed and launches exactly the kernels without dropout."""
+    attn_drop = float(attn_drop)
+    if attn_drop == 0.0:
+        return _WindowAttention.apply(qkv, table, index, regions, heads, float(scale))
+    if not 0.0 < attn_drop < 1.0:
+        raise ValueError("icl_amd window attention: attn_drop must lie in [0, 1)")
+    seed, seed_dev = _step_seed(qkv, seed)
+    return _WindowAttention.apply(qkv, table, index, regions, heads, float(scale), attn_drop, seed, seed_dev)
+
+
+def window_attention_keep_probe(like: torch.Tensor, base: int, count: int, seed: int, p: float, seed_dev: Optional[torch.Tensor] = None):
+    """The keep decisions of the attention-dropout kernels for the flat indices base .. base + count - 1 of the attention tensor (bool
+    tensor on the device of ``like``), drawn by the kernels' own hoisted form of the hash: the unit check of its 64-bit index handling
+    (``base`` may exceed 2^32, which no model's attention tensor does) against ``dropout_keep_mask(..., start=base)``."""
+    _require(like)
+    out = torch.empty(count, dtype=torch.int32, device=like.device)
+    _lib.check(_lib.lib().icl_window_attn_keep_probe(_ptr(out), int(base), int(count), int(seed) & 0xFFFFFFFF, float(p), _ptr(seed_dev),
+                                                     _stream(like)), "window_attn_keep_probe")
+    return out != 0
 
 
 class _ProtoAttention(torch.autograd.Function):

@@ -381,6 +381,21 @@ int icl_window_attn_fwd(const float* qkv, const float* bias, const int32_t* regi
 int icl_window_attn_bwd(const float* qkv, const float* bias, const int32_t* regions, const float* out, const float* lse,
                         const float* dout, float* dqkv, float* dbias, int b_, int n, int heads, int nw, int head_dim, float scale,
                         void* stream);
+/* WindowAttention.attn_drop on the soft-max probabilities (swinunetr_icl.py:742-747: attn = self.attn_drop(attn) between the soft-max and
+ * attn @ v) inside the same fused kernels: out = (keep * P / (1 - p)) @ v.  The mask is never stored: forward and both backward kernels
+ * regenerate keep(k) = hash(seed, k) >= (unsigned)(p * 2^32) — the decision of icl_dropout / icl_drop_path for element k — with
+ * k = ((b_ * heads + h) * n + i) * n + j, the flat index of the reference's [B_, heads, n, n] attention tensor.  0 < p < 1; seed_dev as
+ * icl_drop_path (optional device-resident step counter hashed into the seed).  lse stays the log-sum-exp of the undropped scores; all
+ * other arguments, the kernel choice and the d(bias) slabs as icl_window_attn_fwd / _bwd (which remain the p = 0 entry points). */
+int icl_window_attn_fwd_drop(const float* qkv, const float* bias, const int32_t* regions, float* out, float* lse, int b_, int n, int heads,
+                             int nw, int head_dim, float scale, uint32_t seed, float p, const uint32_t* seed_dev, void* stream);
+int icl_window_attn_bwd_drop(const float* qkv, const float* bias, const int32_t* regions, const float* out, const float* lse,
+                             const float* dout, float* dqkv, float* dbias, int b_, int n, int heads, int nw, int head_dim, float scale,
+                             uint32_t seed, float p, const uint32_t* seed_dev, void* stream);
+/* Unit check of the attn_drop mask (swinunetr_icl.py:742-747).  out[i] = 1 where the attention kernels keep the probability whose flat index in [B_, heads, n, n] is base + i (0 <= i < count <= 2^17), 0
+ * where they drop it — their hoisted form of the hash (the high word of the 64-bit index hashed once per (window, head), with and without
+ * the carry of base + i) for ANY 64-bit base, so that it can be checked against icl_dropout's decisions beyond 2^32 elements. */
+int icl_window_attn_keep_probe(int32_t* out, int64_t base, int count, uint32_t seed, float p, const uint32_t* seed_dev, void* stream);
 /* d(bias) of icl_window_attn_bwd arrives as icl_window_attn_bwd_chunks(...) slabs [chunk][heads][n][npad] (one per slice of windows,
  * plain stores, every used element written: no zero fill).  icl_relpos_bias_bwd_sum adds them into the table gradient in a FIXED order —
  * inv: the padded positions i * npad + j of index[:n, :n] sorted by table row (stable), offs[t] .. offs[t + 1] the entries of row t —

@@ -132,6 +132,9 @@ _SIGNATURES = {
     "icl_qchain_wgrad": (c_int, [P, P, P, P, P, P, P, P, I, P]),
     "icl_seg_metrics_ws_bytes": (c_int64, [I, I, I, I]),
     "icl_seg_metrics": (c_int, [P, I, P, I, I, I, I, I, I, P, P, P]),
+    "icl_window_gather": (c_int, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "icl_window_accumulate": (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
+    "icl_window_finalize": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -24,6 +24,7 @@
 #include "kernels/datafeed.h"
 #include "kernels/qchain.h"
 #include "kernels/metrics.h"
+#include "kernels/window.h"
 
 #ifdef ICL_TWO_UNITS
 // product build: this instantiation lives in icl_hip_noslp.hip (compiled with -fno-slp-vectorize; the reason is in that file's header)
@@ -2560,6 +2561,122 @@ int icl_seg_metrics(const void* pred, int pred_dtype, const void* gt, int gt_dty
     if (int e = check_launch("seg_edt / seg_select")) return e;
   }
   return 0;
+}
+
+}  // extern "C"
+
+// ---- 3-D sliding window of the validation loops (kernels/window.h)
+namespace {
+
+// origins [n][3] -> kernel arguments; nullptr + message when n, or a window, does not fit
+const char* win_batch(const int32_t* origins, int n, int p0, int p1, int p2, int r0, int r1, int r2, icl::WinBatch& wb) {
+  static thread_local char msg[160];
+  if (n < 1 || n > icl::kWinMaxBatch) {
+    snprintf(msg, sizeof(msg), "%d windows (1 <= n <= %d)", n, icl::kWinMaxBatch);
+    return msg;
+  }
+  if (r0 < 1 || r1 < 1 || r2 < 1 || p0 < r0 || p1 < r1 || p2 < r2) {
+    snprintf(msg, sizeof(msg), "window %d x %d x %d does not fit the padded extent %d x %d x %d", r0, r1, r2, p0, p1, p2);
+    return msg;
+  }
+  const int pe[3] = {p0, p1, p2}, re[3] = {r0, r1, r2};
+  for (int w = 0; w < n; ++w)
+    for (int d = 0; d < 3; ++d) {
+      const int o = origins[3 * w + d];
+      if (o < 0 || o > pe[d] - re[d]) {
+        snprintf(msg, sizeof(msg), "window %d: origin %d on axis %d puts it outside the padded extent %d (window %d)", w, o, d, pe[d], re[d]);
+        return msg;
+      }
+      wb.o[w][d] = o;
+    }
+  return nullptr;
+}
+
+inline bool win_pads_ok(int s0, int s1, int s2, int a0, int a1, int a2, int p0, int p1, int p2) {
+  return s0 >= 1 && s1 >= 1 && s2 >= 1 && a0 >= 0 && a1 >= 0 && a2 >= 0 && (long)a0 + s0 <= p0 && (long)a1 + s1 <= p1 && (long)a2 + s2 <= p2;
+}
+
+constexpr int kWinMaxWgs = 2048;
+
+template <int NCMAX>
+void win_accumulate_launch(bool quad, dim3 grid, hipStream_t st, const float* logits, const float* imp, float* score, float* weight,
+                           const icl::WinBatch& wb, int n, int c, icl::WinExt p, icl::WinExt r, icl::WinExt lo, icl::WinExt ext, int softmax) {
+  if (quad) {
+    ICL_LAUNCH((icl::window_accumulate_kernel<NCMAX, 4>), grid, dim3(256), 0, st, logits, imp, score, weight, wb, n, c, p, r, lo, ext, softmax);
+  } else {
+    ICL_LAUNCH((icl::window_accumulate_kernel<NCMAX, 1>), grid, dim3(256), 0, st, logits, imp, score, weight, wb, n, c, p, r, lo, ext, softmax);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int icl_window_gather(const float* vol, float* out, const int32_t* origins, int n, int cin, int s0, int s1, int s2, int a0, int a1, int a2,
+                      int p0, int p1, int p2, int r0, int r1, int r2, void* stream) {
+  if (!vol || !out || !origins) return fail(-1, "window_gather: null pointer");
+  if (cin < 1 || !win_pads_ok(s0, s1, s2, a0, a1, a2, p0, p1, p2))
+    return fail(-1, "window_gather: bad extents (Cin %d, volume %d x %d x %d at %d, %d, %d of %d x %d x %d)", cin, s0, s1, s2, a0, a1, a2, p0, p1, p2);
+  icl::WinBatch wb{};
+  if (const char* m = win_batch(origins, n, p0, p1, p2, r0, r1, r2, wb)) return fail(-1, "window_gather: %s", m);
+  const icl::WinExt s{s0, s1, s2}, a{a0, a1, a2}, r{r0, r1, r2};
+  const bool quad = (r2 & 3) == 0 && aligned16(vol) && aligned16(out);
+  const long total = (long)cin * r0 * r1 * (quad ? r2 / 4 : r2);
+  const dim3 grid(grid_for(total, 256, kWinMaxWgs / n > 0 ? kWinMaxWgs / n : 1), n);
+  if (quad) {
+    ICL_LAUNCH(icl::window_gather_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, vol, out, wb, cin, s, a, r);
+  } else {
+    ICL_LAUNCH(icl::window_gather_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, vol, out, wb, cin, s, a, r);
+  }
+  return check_launch("window_gather");
+}
+
+int icl_window_accumulate(const float* logits, const float* importance, float* score, float* weight, const int32_t* origins, int n, int c,
+                          int p0, int p1, int p2, int r0, int r1, int r2, int softmax, void* stream) {
+  if (!logits || !score || !weight || !origins) return fail(-1, "window_accumulate: null pointer");
+  if (c < 1 || c > icl::kWinMaxClasses) return fail(-1, "window_accumulate: %d classes (1 <= C <= %d)", c, icl::kWinMaxClasses);
+  icl::WinBatch wb{};
+  if (const char* m = win_batch(origins, n, p0, p1, p2, r0, r1, r2, wb)) return fail(-1, "window_accumulate: %s", m);
+  const icl::WinExt p{p0, p1, p2}, r{r0, r1, r2};
+  int lo[3], hi[3];
+  bool quad = (p2 & 3) == 0 && (r2 & 3) == 0 && aligned16(logits) && aligned16(score) && aligned16(weight) && (!importance || aligned16(importance));
+  for (int d = 0; d < 3; ++d) { lo[d] = wb.o[0][d]; hi[d] = wb.o[0][d]; }
+  for (int w = 0; w < n; ++w) {
+    for (int d = 0; d < 3; ++d) {
+      if (wb.o[w][d] < lo[d]) lo[d] = wb.o[w][d];
+      if (wb.o[w][d] > hi[d]) hi[d] = wb.o[w][d];
+    }
+    if (wb.o[w][2] & 3) quad = false;
+  }
+  const icl::WinExt l{lo[0], lo[1], lo[2]}, ext{hi[0] - lo[0] + r0, hi[1] - lo[1] + r1, hi[2] - lo[2] + r2};      // the batch's bounding box
+  const long total = (long)ext.d0 * ext.d1 * (quad ? ext.d2 / 4 : ext.d2);
+  const dim3 grid(grid_for(total, 256, kWinMaxWgs));
+  hipStream_t st = (hipStream_t)stream;
+  const int sm = softmax ? 1 : 0;
+  if (c <= 4) win_accumulate_launch<4>(quad, grid, st, logits, importance, score, weight, wb, n, c, p, r, l, ext, sm);
+  else if (c <= 16) win_accumulate_launch<16>(quad, grid, st, logits, importance, score, weight, wb, n, c, p, r, l, ext, sm);
+  else win_accumulate_launch<0>(quad, grid, st, logits, importance, score, weight, wb, n, c, p, r, l, ext, sm);
+  return check_launch("window_accumulate");
+}
+
+int icl_window_finalize(const float* score, const float* weight, int64_t* label, float* quotients, int c, int p0, int p1, int p2, int a0,
+                        int a1, int a2, int s0, int s1, int s2, void* stream) {
+  if (!score || !weight || (!label && !quotients)) return fail(-1, "window_finalize: null pointer");
+  if (quotients == score && (s0 != p0 || s1 != p1 || s2 != p2))
+    return fail(-1, "window_finalize: the quotients can replace the score map only where nothing is cropped");
+  if (c < 1 || c > icl::kWinMaxClasses) return fail(-1, "window_finalize: %d classes (1 <= C <= %d)", c, icl::kWinMaxClasses);
+  if (!win_pads_ok(s0, s1, s2, a0, a1, a2, p0, p1, p2))
+    return fail(-1, "window_finalize: bad extents (volume %d x %d x %d at %d, %d, %d of %d x %d x %d)", s0, s1, s2, a0, a1, a2, p0, p1, p2);
+  const icl::WinExt p{p0, p1, p2}, a{a0, a1, a2}, s{s0, s1, s2};
+  const bool quad = (s2 & 3) == 0 && (p2 & 3) == 0 && (a2 & 3) == 0 && aligned16(score) && aligned16(weight) && (!label || aligned16(label)) &&
+                    (!quotients || aligned16(quotients));
+  const dim3 grid(grid_for((long)s0 * s1 * (quad ? s2 / 4 : s2), 256, kWinMaxWgs));
+  if (quad) {
+    ICL_LAUNCH(icl::window_finalize_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, score, weight, (long long*)label, quotients, c, p, a, s);
+  } else {
+    ICL_LAUNCH(icl::window_finalize_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, score, weight, (long long*)label, quotients, c, p, a, s);
+  }
+  return check_launch("window_finalize");
 }
 
 }  // extern "C"

@@ -2590,3 +2590,84 @@ def seg_metrics(pred: torch.Tensor, gt: torch.Tensor, num_classes: int) -> torch
     _lib.check(L.icl_seg_metrics(_ptr(pred), _SEG_DTYPES[pred.dtype], _ptr(gt), _SEG_DTYPES[gt.dtype], n0, n1, n2, int(num_classes), all_border,
                                  _ptr(out), _ptr(ws), _stream(pred)), "seg_metrics")
     return out
+
+
+# --------------------------------------------------------------------------------------
+# 3-D sliding window of the validation loops (val_3D.py:18-73, :128-132; csrc/kernels/window.h)
+# --------------------------------------------------------------------------------------
+
+def _window_origins(origins):
+    flat = [int(v) for o in origins for v in o]
+    if len(flat) != 3 * len(origins):
+        raise ValueError("window origins must be (o0, o1, o2) triples")
+    return (ctypes.c_int32 * max(len(flat), 1))(*flat), len(origins)
+
+
+def window_gather(vol: torch.Tensor, origins, roi, pads, padded, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``stack([pad(vol)[:, o0:o0 + r0, o1:o1 + r1, o2:o2 + r2] for o in origins]).contiguous()`` in one launch, bit-equal
+    (include/icl_hip.h icl_window_gather): vol fp32 [Cin, s0, s1, s2]; origins: up to 16 triples in the padded frame ``padded``, in which the
+    volume starts at ``pads`` = (a0, a1, a2); voxels outside the volume read as 0.  Returns [n, Cin, r0, r1, r2] (``out`` when given: a contiguous tensor of
+    that shape, e.g. a slice of a larger batch along its first axis).  Asynchronous on the current stream."""
+    _require(vol)
+    if vol.dtype != torch.float32 or vol.dim() != 4:
+        raise ValueError(f"window_gather: needs an fp32 [Cin, s0, s1, s2] volume, got {vol.dtype} {tuple(vol.shape)}")
+    vol = vol.contiguous()
+    arr, n = _window_origins(origins)
+    r, a, p = [int(v) for v in roi], [int(v) for v in pads], [int(v) for v in padded]
+    shape = (n, vol.shape[0], *r)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=vol.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != vol.device:
+        raise ValueError(f"window_gather: out must be a contiguous fp32 {shape} tensor on the volume's device")
+    _lib.check(_lib.lib().icl_window_gather(_ptr(vol), _ptr(out), arr, n, vol.shape[0], *vol.shape[1:], *a, *p, *r, _stream(vol)), "window_gather")
+    return out
+
+
+def window_accumulate(logits: torch.Tensor, origins, score: torch.Tensor, weight: torch.Tensor, importance: Optional[torch.Tensor] = None,
+                      softmax: bool = False) -> None:
+    """``score[:, window] += value`` and ``weight[window] += 1`` for every window of a batch, in the given order, in one launch
+    (icl_window_accumulate): logits fp32 [n, C, r0, r1, r2] (n <= 16, C <= 256), score fp32 [C, p0, p1, p2] and weight fp32 [p0, p1, p2],
+    updated in place.  ``softmax``: the value is softmax(logits, 1), else the logits.  ``importance`` fp32 [r0, r1, r2]: the value is
+    multiplied by it first (rounded, then added) and ``weight[window] += importance``."""
+    _require(logits, score, weight, importance)
+    if logits.dim() != 5 or score.dim() != 4 or weight.dim() != 3 or score.shape[0] != logits.shape[1] or score.shape[1:] != weight.shape:
+        raise ValueError(f"window_accumulate: shapes {tuple(logits.shape)}, {tuple(score.shape)}, {tuple(weight.shape)}")
+    for t in (logits, score, weight, importance):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"window_accumulate: fp32 only, got {t.dtype}")
+    if not (score.is_contiguous() and weight.is_contiguous()):
+        raise ValueError("window_accumulate: score and weight are updated in place and must be contiguous")
+    if importance is not None:
+        if importance.shape != logits.shape[2:]:
+            raise ValueError(f"window_accumulate: importance map {tuple(importance.shape)} for windows {tuple(logits.shape[2:])}")
+        importance = importance.contiguous()
+    logits = logits.contiguous()
+    arr, n = _window_origins(origins)
+    if n != logits.shape[0]:
+        raise ValueError(f"window_accumulate: {n} origins for {logits.shape[0]} windows")
+    _lib.check(_lib.lib().icl_window_accumulate(_ptr(logits), _ptr(importance), _ptr(score), _ptr(weight), arr, n, logits.shape[1],
+                                                *weight.shape, *logits.shape[2:], int(bool(softmax)), _stream(score)), "window_accumulate")
+
+
+def window_finalize(score: torch.Tensor, weight: torch.Tensor, pads, size, return_score: bool = False, label: bool = True):
+    """``argmax(score / weight, 0)`` cropped to the volume ``size`` = (s0, s1, s2) that starts at ``pads`` of the padded maps, in one pass
+    (icl_window_finalize): int64 [s0, s1, s2]; with ``return_score`` also the cropped quotients, fp32 [C, s0, s1, s2].  Where nothing is
+    cropped the quotients REPLACE the contents of ``score`` (division in place: no second class-by-volume tensor) and ``score`` itself is
+    returned for them.  ``label=False`` (with ``return_score``): the quotients alone are computed and returned."""
+    _require(score, weight)
+    if score.dim() != 4 or weight.dim() != 3 or score.shape[1:] != weight.shape or score.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise ValueError(f"window_finalize: needs fp32 score [C, p0, p1, p2] and weight [p0, p1, p2], got {tuple(score.shape)}, {tuple(weight.shape)}")
+    if not (label or return_score):
+        raise ValueError("window_finalize: nothing to compute")
+    if not (score.is_contiguous() and weight.is_contiguous()):
+        raise ValueError("window_finalize: score and weight must be contiguous")
+    a, s = [int(v) for v in pads], [int(v) for v in size]
+    lab = torch.empty(s, dtype=torch.int64, device=score.device) if label else None
+    quot = None
+    if return_score:
+        quot = score if tuple(s) == tuple(weight.shape) else torch.empty((score.shape[0], *s), dtype=torch.float32, device=score.device)
+    _lib.check(_lib.lib().icl_window_finalize(_ptr(score), _ptr(weight), _ptr(lab), _ptr(quot), score.shape[0], *weight.shape, *a, *s,
+                                              _stream(score)), "window_finalize")
+    if not label:
+        return quot
+    return (lab, quot) if return_score else lab

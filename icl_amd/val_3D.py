@@ -9,6 +9,11 @@ change any window's logits); the reference moves every window host->device->host
 published definition (``medpy.metric.binary.hd95``: 95th percentile of the symmetric surface distances, surfaces from a
 connectivity-1 erosion, distances from ``scipy.ndimage.distance_transform_edt``) — MedPy itself is not installed in the
 build image, so the HD95 half is "parity unpinned" (DESIGN.md §2).
+
+On a HIP device the stretch between the volume and the label map — window gather, soft-max, accumulation of the score and weight
+maps, division, arg-max, crop — runs on the window kernels (csrc/kernels/window.h, ``ops.window_*``; DESIGN.md §4.7) in both loops;
+``ICL_VAL_WINDOWS=aten`` keeps the ATen loops, which also serve host tensors.  ``mode="gaussian"`` blends overlapping windows with a
+Gaussian importance map on either path.
 """
 from __future__ import annotations
 
@@ -19,19 +24,100 @@ import numpy as np
 import torch
 
 
+def val_windows_mode() -> str:
+    """``ICL_VAL_WINDOWS``: ``device`` (default) runs the sliding window of both 3-D validation loops — window gather, soft-max and
+    accumulation, division, arg-max and crop — on the window kernels (csrc/kernels/window.h) when the volume is an fp32 tensor on a HIP
+    device; ``aten`` forces the ATen loop (A/B runs).  Host tensors and other dtypes always take the ATen loop."""
+    mode = os.environ.get("ICL_VAL_WINDOWS", "device")
+    if mode not in ("device", "aten"):
+        raise ValueError(f"ICL_VAL_WINDOWS must be 'device' or 'aten', got {mode!r}")
+    return mode
+
+
+_WINDOW_MAX_CLASSES = 256      # icl_window_accumulate / icl_window_finalize
+_WINDOW_MAX_BATCH = 16         # windows per launch
+
+
+def gaussian_importance_map(roi_size, sigma_scale=0.125) -> torch.Tensor:
+    """The window weights of ``mode="gaussian"``, fp32 [r0, r1, r2] on the host.  Built in float64, per axis: with c = r // 2 and
+    sigma = sigma_scale * r the factor is g(i) = exp(-(i - c)^2 / (2 sigma^2)); the map is the product of the three factors, divided by
+    its maximum, cast to fp32 and floored at 1e-3.  This FOLLOWS MONAI's Gaussian mode (``compute_importance_map``), which filters a delta
+    at the centre with an erf-integrated Gaussian kernel of the same sigma and floors the result likewise; MONAI is not installed in the build
+    image, so parity with its map is unpinned, like the window grid."""
+    roi = [int(r) for r in roi_size]
+    scales = [float(sigma_scale)] * len(roi) if np.isscalar(sigma_scale) else [float(v) for v in sigma_scale]
+    if len(scales) != len(roi):
+        raise ValueError(f"sigma_scale needs one value or {len(roi)}, got {sigma_scale!r}")
+    m = np.ones((), dtype=np.float64)
+    for r, sc in zip(roi, scales):
+        i = np.arange(r, dtype=np.float64)
+        sigma = sc * r
+        m = m[..., None] * np.exp(-((i - (r // 2)) ** 2) / (2.0 * sigma * sigma))
+    m = m / m.max()
+    return torch.from_numpy(m.astype(np.float32)).clamp_(min=1e-3)
+
+
+def _importance_map(mode, roi_size, sigma_scale, device):
+    """None for ``constant``, the Gaussian map on ``device`` for ``gaussian``; any other mode is a ValueError."""
+    if mode == "constant":
+        return None
+    if mode == "gaussian":
+        return gaussian_importance_map(roi_size, sigma_scale).to(device)
+    raise ValueError(f"sliding-window mode must be 'constant' or 'gaussian', got {mode!r}")
+
+
+def _window_kernels_apply(t, num_classes=1) -> bool:
+    return (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and 1 <= num_classes <= _WINDOW_MAX_CLASSES
+            and val_windows_mode() == "device")
+
+
 @torch.no_grad()
 def test_single_case_base(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_batch=4,
-                          return_score=False):
-    """image: numpy [W,H,D] (the reference's h5 layout).  Returns the label map (numpy int64 [W,H,D])."""
-    label_map, score = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes, windows_per_batch)
+                          return_score=False, mode="constant"):
+    """image: numpy [W,H,D] (the reference's h5 layout).  Returns the label map (numpy int64 [W,H,D]).  ``mode``: ``constant`` (the
+    reference's plain average over overlapping windows) or ``gaussian`` (``gaussian_importance_map`` at sigma_scale 0.125)."""
+    label_map, score = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes, windows_per_batch, mode,
+                                              return_score)
     if return_score:
         return label_map.cpu().numpy(), score.cpu().numpy()
     return label_map.cpu().numpy()
 
 
+def _single_case_kernels(net, icl, vol, pads, starts, patch_size, num_classes, windows_per_batch, imp, want_score):
+    """The window loop of ``_single_case_on_device`` on the window kernels: vol fp32 [W,H,D] on a HIP device (unpadded; the gather
+    zero-fills), ``starts`` in the padded frame.  Returns ((label map, cropped score or None), None) — or (None, logits of the first
+    batch) when the network's output is not fp32 [n, num_classes, *patch_size]: the caller's ATen loop then takes over with that
+    batch already computed, so the network sees every batch once."""
+    from . import ops
+    size = tuple(vol.shape)
+    a = tuple(p[0] for p in pads)
+    psize = tuple(n + p[0] + p[1] for n, p in zip(size, pads))
+    score = cnt = None
+    for i in range(0, len(starts), windows_per_batch):
+        chunk = starts[i:i + windows_per_batch]
+        batch = torch.empty((len(chunk), 1, *patch_size), dtype=torch.float32, device=vol.device)
+        for k in range(0, len(chunk), _WINDOW_MAX_BATCH):
+            ops.window_gather(vol.unsqueeze(0), chunk[k:k + _WINDOW_MAX_BATCH], patch_size, a, psize, out=batch[k:k + _WINDOW_MAX_BATCH])
+        logits = net(batch, inference=True) if icl else net(batch)
+        if score is None:
+            if tuple(logits.shape) != (len(chunk), num_classes, *patch_size) or logits.dtype != torch.float32:
+                return None, logits
+            score = torch.zeros((num_classes, *psize), dtype=torch.float32, device=vol.device)
+            cnt = torch.zeros(psize, dtype=torch.float32, device=vol.device)
+        for k in range(0, len(chunk), _WINDOW_MAX_BATCH):
+            ops.window_accumulate(logits[k:k + _WINDOW_MAX_BATCH], chunk[k:k + _WINDOW_MAX_BATCH], score, cnt, imp, softmax=True)
+    if want_score:
+        return ops.window_finalize(score, cnt, a, size, return_score=True), None
+    return (ops.window_finalize(score, cnt, a, size), None), None
+
+
 @torch.no_grad()
-def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_batch=4):
-    """``test_single_case_base`` up to the copy to the host: (label map int64 [W,H,D], score [C,W,H,D]) on the net's device."""
+def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_batch=4, mode="constant",
+                           want_score=True):
+    """``test_single_case_base`` up to the copy to the host: (label map int64 [W,H,D], score [C,W,H,D]) on the net's device.  On a HIP
+    device the windows are gathered, soft-maxed, accumulated, divided and arg-maxed by the window kernels (``ICL_VAL_WINDOWS``; the score
+    is None when ``want_score`` is false — the kernel then writes the label map alone); elsewhere, and when the network's output is not
+    fp32 [n, num_classes, *patch_size], by the ATen loop below.  Both walk the same window grid."""
     dev = next(net.parameters()).device
     w, h, d = image.shape
     pads = []
@@ -40,14 +126,11 @@ def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size
         pads.append((tot // 2, tot - tot // 2))
     add_pad = any(a + b > 0 for a, b in pads)
     vol = torch.as_tensor(np.ascontiguousarray(image), dtype=torch.float32, device=dev)
-    if add_pad:
-        vol = torch.nn.functional.pad(vol, (pads[2][0], pads[2][1], pads[1][0], pads[1][1], pads[0][0], pads[0][1]))
-    ww, hh, dd = vol.shape
+    imp = _importance_map(mode, patch_size, 0.125, dev)
+    ww, hh, dd = (n + a + b for n, (a, b) in zip((w, h, d), pads))      # the padded extents
     sx = math.ceil((ww - patch_size[0]) / stride_xy) + 1
     sy = math.ceil((hh - patch_size[1]) / stride_xy) + 1
     sz = math.ceil((dd - patch_size[2]) / stride_z) + 1
-    score = torch.zeros((num_classes, ww, hh, dd), dtype=torch.float32, device=dev)
-    cnt = torch.zeros((ww, hh, dd), dtype=torch.float32, device=dev)
     starts = []
     for x in range(sx):
         xs = min(stride_xy * x, ww - patch_size[0])
@@ -56,16 +139,33 @@ def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size
             for z in range(sz):
                 zs = min(stride_z * z, dd - patch_size[2])
                 starts.append((xs, ys, zs))
-    px, py, pz = patch_size
     icl = net_type in ("swinunetr_icl", "unet_3D_icl")
+    first_logits = None
+    if _window_kernels_apply(vol, num_classes):
+        done, first_logits = _single_case_kernels(net, icl, vol, pads, starts, tuple(int(v) for v in patch_size), num_classes,
+                                                  windows_per_batch, imp, want_score)
+        if done is not None:
+            return done
+    if add_pad:
+        vol = torch.nn.functional.pad(vol, (pads[2][0], pads[2][1], pads[1][0], pads[1][1], pads[0][0], pads[0][1]))
+    score = torch.zeros((num_classes, ww, hh, dd), dtype=torch.float32, device=dev)
+    cnt = torch.zeros((ww, hh, dd), dtype=torch.float32, device=dev)
+    px, py, pz = patch_size
     for i in range(0, len(starts), windows_per_batch):
         chunk = starts[i:i + windows_per_batch]
-        batch = torch.stack([vol[xs:xs + px, ys:ys + py, zs:zs + pz] for xs, ys, zs in chunk]).unsqueeze(1).contiguous()
-        logits = net(batch, inference=True) if icl else net(batch)
+        if i == 0 and first_logits is not None:      # handed over by the kernel loop: this batch has been through the network
+            logits = first_logits
+        else:
+            batch = torch.stack([vol[xs:xs + px, ys:ys + py, zs:zs + pz] for xs, ys, zs in chunk]).unsqueeze(1).contiguous()
+            logits = net(batch, inference=True) if icl else net(batch)
         prob = torch.softmax(logits, dim=1)
         for j, (xs, ys, zs) in enumerate(chunk):
-            score[:, xs:xs + px, ys:ys + py, zs:zs + pz] += prob[j]
-            cnt[xs:xs + px, ys:ys + py, zs:zs + pz] += 1
+            if imp is None:
+                score[:, xs:xs + px, ys:ys + py, zs:zs + pz] += prob[j]
+                cnt[xs:xs + px, ys:ys + py, zs:zs + pz] += 1
+            else:
+                score[:, xs:xs + px, ys:ys + py, zs:zs + pz] += prob[j] * imp
+                cnt[xs:xs + px, ys:ys + py, zs:zs + pz] += imp
     score = score / cnt.unsqueeze(0)
     label_map = torch.argmax(score, dim=0)
     if add_pad:
@@ -216,7 +316,7 @@ def test_all_case_base(net, net_type, base_dir, test_list="full_test.list", num_
     for image, label in cases:
         gt = _upload_label(label, dev) if on_device else None
         if gt is not None:      # the label map stays on the device; the ground truth goes up once per case
-            prediction, _ = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes)
+            prediction, _ = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes, want_score=False)
             for i, m in enumerate(cal_metric_multiclass(gt, prediction, num_classes)):
                 metric_cal[i].append(m)
             continue
@@ -242,37 +342,92 @@ def _scan_starts(size: int, roi: int, overlap: float):
     return [i * interval - max(i * interval + roi - size, 0) for i in range(num)]
 
 
+def _sliding_window_kernels(inputs, size, roi, pads, psize, starts, sw_batch_size, predictor, imp, kwargs):
+    """The window loop of ``sliding_window_inference`` on the window kernels: ``inputs`` fp32 [B, Cin, *size], unpadded (the gather
+    zero-fills), ``starts`` (batch index, origin in the padded frame ``psize``).  Returns (averaged outputs [B, C, *size], None) — or (None, the
+    first batch's prediction) when that prediction is not a tensor [n, C <= 256, *roi] on the device of ``inputs``: the caller's ATen loop
+    then takes over with that batch already computed, so the predictor sees every batch once."""
+    from . import ops
+    inputs = inputs.contiguous()
+    b, cin = inputs.shape[:2]
+    a = tuple(p[0] for p in pads)
+    out = cnt = None
+    for i in range(0, len(starts), sw_batch_size):
+        chunk = starts[i:i + sw_batch_size]
+        # runs of windows of one volume, at most 16 each: one launch per run
+        runs, k = [], 0
+        while k < len(chunk):
+            e = k + 1
+            while e < len(chunk) and e - k < _WINDOW_MAX_BATCH and chunk[e][0] == chunk[k][0]:
+                e += 1
+            runs.append((k, e))
+            k = e
+        win = torch.empty((len(chunk), cin, *roi), dtype=torch.float32, device=inputs.device)
+        for k, e in runs:
+            ops.window_gather(inputs[chunk[k][0]], [c[1:] for c in chunk[k:e]], roi, a, psize, out=win[k:e])
+        pred = predictor(win, **kwargs)
+        if out is None and (not torch.is_tensor(pred) or pred.dim() != 5 or pred.shape[0] != len(chunk) or list(pred.shape[2:]) != list(roi)
+                            or not 1 <= pred.shape[1] <= _WINDOW_MAX_CLASSES or pred.device != inputs.device):
+            return None, pred
+        pred = pred.float()
+        if out is None:
+            out = torch.zeros((b, pred.shape[1], *psize), dtype=torch.float32, device=inputs.device)
+            cnt = torch.zeros((b, *psize), dtype=torch.float32, device=inputs.device)
+        for k, e in runs:
+            bi = chunk[k][0]
+            ops.window_accumulate(pred[k:e], [c[1:] for c in chunk[k:e]], out[bi], cnt[bi], imp, softmax=False)
+    res = [ops.window_finalize(out[bi], cnt[bi], a, size, return_score=True, label=False) for bi in range(b)]
+    return (res[0].unsqueeze(0) if b == 1 else torch.stack(res)), None
+
+
 @torch.no_grad()
-def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap: float = 0.25, **kwargs):
+def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap: float = 0.25, mode="constant", sigma_scale=0.125,
+                             **kwargs):
     """Restatement of ``monai.inferers.sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.25,
-    mode="constant")`` as the reference calls it (val_3D.py:130-132): symmetric zero padding of volumes smaller than the window,
-    the window grid of ``_scan_starts``, ``sw_batch_size`` windows per forward, predictor OUTPUTS (logits) averaged with constant
-    weights over overlapping windows, padding cropped off again.  Everything stays on the device of ``inputs``.  MONAI is not
-    installed in the build image: parity unpinned."""
+    mode="constant", sigma_scale=0.125)`` as the reference calls it (val_3D.py:130-132): symmetric zero padding of volumes smaller than the
+    window, the window grid of ``_scan_starts``, ``sw_batch_size`` windows per forward, predictor OUTPUTS (logits) averaged over
+    overlapping windows, padding cropped off again.  ``mode="constant"`` weights every window voxel alike; ``mode="gaussian"`` weights it
+    with ``gaussian_importance_map(roi_size, sigma_scale)``, which follows MONAI's Gaussian mode (MONAI filters a delta with an
+    erf-integrated kernel; see there) — any other mode is a ValueError.  Everything stays on the device of ``inputs``; an fp32 tensor on a
+    HIP device goes through the window kernels (``ICL_VAL_WINDOWS``), anything else, and a predictor whose output extent differs from the
+    window's, through the ATen loop below.  MONAI is not installed in the build image: parity unpinned."""
     b = inputs.shape[0]
     size = list(inputs.shape[2:])
     roi = [int(r) for r in roi_size]
+    imp = _importance_map(mode, roi, sigma_scale, inputs.device)
     pads = []
     for s, r in zip(size, roi):
         diff = max(r - s, 0)
         pads.append((diff // 2, diff - diff // 2))
+    psize = [s + a + c for s, (a, c) in zip(size, pads)]
+    grids = [_scan_starts(s, r, overlap) for s, r in zip(psize, roi)]
+    starts = [(bi, z, y, x) for bi in range(b) for z in grids[0] for y in grids[1] for x in grids[2]]
+    first_pred = None
+    if _window_kernels_apply(inputs) and len(size) == 3:
+        done, first_pred = _sliding_window_kernels(inputs, size, roi, pads, psize, starts, sw_batch_size, predictor, imp, kwargs)
+        if done is not None:
+            return done
     if any(a + c for a, c in pads):
         flat = [v for a, c in reversed(pads) for v in (a, c)]
         inputs = torch.nn.functional.pad(inputs, flat)
-    psize = list(inputs.shape[2:])
-    grids = [_scan_starts(s, r, overlap) for s, r in zip(psize, roi)]
-    starts = [(bi, z, y, x) for bi in range(b) for z in grids[0] for y in grids[1] for x in grids[2]]
     out = cnt = None
     for i in range(0, len(starts), sw_batch_size):
         chunk = starts[i:i + sw_batch_size]
-        win = torch.stack([inputs[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] for bi, z, y, x in chunk]).contiguous()
-        pred = predictor(win, **kwargs)
+        if i == 0 and first_pred is not None:      # handed over by the kernel loop: this batch has been through the predictor
+            pred = first_pred
+        else:
+            win = torch.stack([inputs[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] for bi, z, y, x in chunk]).contiguous()
+            pred = predictor(win, **kwargs)
         if out is None:
             out = torch.zeros((b, pred.shape[1], *psize), dtype=torch.float32, device=inputs.device)
             cnt = torch.zeros((b, 1, *psize), dtype=torch.float32, device=inputs.device)
         for j, (bi, z, y, x) in enumerate(chunk):
-            out[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] += pred[j].float()
-            cnt[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] += 1
+            if imp is None:
+                out[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] += pred[j].float()
+                cnt[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] += 1
+            else:
+                out[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] += pred[j].float() * imp
+                cnt[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] += imp
     out = out / cnt
     sl = tuple(slice(a, a + s) for (a, _), s in zip(pads, size))
     return out[(slice(None), slice(None)) + sl]

@@ -504,6 +504,31 @@ int64_t icl_seg_metrics_ws_bytes(int n0, int n1, int n2, int num_classes);
 int icl_seg_metrics(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int n0, int n1, int n2, int num_classes, int all_border,
                     int64_t* out, void* ws, void* stream);
 
+/* ---- the 3-D sliding window of the validation loops on the device (csrc/kernels/window.h; val_3D.py:18-73: test_single_case_base's pad,
+ * window grid, soft-max, score / count maps, divide, arg-max and crop; val_3D.py:128-132: monai.inferers.sliding_window_inference as the
+ * AMOS loop calls it; both restated in icl_amd/val_3D.py).  Volumes are dense with the last axis fastest.  origins: HOST int32 [n][3], the
+ * windows' origins in the PADDED frame p0 x p1 x p2 (copied into the kernel arguments), n <= 16 windows of extent r0 x r1 x r2; the unpadded
+ * volume s0 x s1 x s2 starts at (a0, a1, a2) of the padded frame.  Each call returns -1 (nothing launched, icl_last_error() says why) for
+ * n outside 1..16, classes outside 1..256, or an origin that puts a window outside the padded extent.
+ * icl_window_gather (val_3D.py:18-41,57-62 and :128-132; replaces F.pad + one slice per window + stack + contiguous, bit-equal):
+ *   out [n][cin][r0][r1][r2] <- vol [cin][s0][s1][s2], voxels outside the unpadded volume read as 0. */
+int icl_window_gather(const float* vol, float* out, const int32_t* origins, int n, int cin, int s0, int s1, int s2, int a0, int a1, int a2,
+                      int p0, int p1, int p2, int r0, int r1, int r2, void* stream);
+/* icl_window_accumulate (val_3D.py:63-70 and :128-132): score [c][p0][p1][p2] and weight [p0][p1][p2] += the batch's windows, logits
+ *   [n][c][r0][r1][r2].  One thread owns a destination voxel and walks the windows in their given order: the adds are those of the loop
+ *   over windows, in its order, with no atomics; the launch covers the bounding box of the windows.  softmax != 0: the value added is the
+ *   soft-max over the class axis of the window's logits (the BraTS loop), else the logits (the AMOS loop).  importance == NULL:
+ *   score += value, weight += 1; else importance [r0][r1][r2]: score = score + importance * value (product and sum rounded one after the
+ *   other, never fused), weight += importance. */
+int icl_window_accumulate(const float* logits, const float* importance, float* score, float* weight, const int32_t* origins, int n, int c,
+                          int p0, int p1, int p2, int r0, int r1, int r2, int softmax, void* stream);
+/* icl_window_finalize (val_3D.py:71-73 and :128-132): label [s0][s1][s2] int64 = arg-max over the classes of score / weight (IEEE fp32
+ *   division; the lowest index wins among equals, NaN as torch.argmax treats it) on the unpadded extent; quotients (may be NULL): the
+ *   quotients themselves, cropped, [c][s0][s1][s2] — where nothing is cropped they may be `score` itself (division in place).  label may
+ *   be NULL when the quotients are all that is wanted. */
+int icl_window_finalize(const float* score, const float* weight, int64_t* label, float* quotients, int c, int p0, int p1, int p2, int a0,
+                        int a1, int a2, int s0, int s1, int s2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1716,9 +1716,18 @@ int icl_dropout(const float* x, float* y, int64_t n, uint32_t seed, float p, con
   return icl_drop_path(x, y, n, 1, seed, p, seed_dev, stream);
 }
 
+// Class groups of the loss kernels: 0 = registers, 4 classes; 1 = registers, 16 classes; 2 = the generic-class path (17 .. 256 classes, or any
+// count with the test-only override ICL_LOSS_GENERIC=1, read per call: the tests switch it)
+static bool loss_force_generic() {
+  const char* e = getenv("ICL_LOSS_GENERIC");
+  return e && atoi(e) == 1;
+}
+static int loss_class_group(int nc) { return nc <= 4 ? 0 : (nc <= 16 ? 1 : 2); }
+
 int icl_loss_fwd(const float* a, const float* b, const int64_t* labels, const float* weight, float* stats, float* out,
                  int batch, int nc, int64_t s, int mode, int a_is_prob, void* stream) {
-  if (!a || !stats || !out || batch < 1 || nc < 1 || nc > 16 || s < 1 || mode < 0 || mode > 3) return fail(-1, "loss_fwd: bad argument");
+  if (nc < 1 || nc > icl::kLossMaxNc) return fail(-1, "loss_fwd: %d classes (1 .. %d)", nc, icl::kLossMaxNc);
+  if (!a || !stats || !out || batch < 1 || s < 1 || mode < 0 || mode > 3) return fail(-1, "loss_fwd: bad argument");
   if ((mode <= 1) != (labels != nullptr) || (mode >= 2) != (b != nullptr)) return fail(-1, "loss_fwd: target does not match mode");
   hipStream_t st = (hipStream_t)stream;
   const long total = (long)batch * s;
@@ -1726,7 +1735,9 @@ int icl_loss_fwd(const float* a, const float* b, const int64_t* labels, const fl
   float* part = stats + (3 * nc + 1);   // per-block partial sums behind the reduced statistics
   const dim3 grid(nblk), block(256);
   const long long* lab = (const long long*)labels;
-  if (nc <= 4) {
+  if (nc > 16 || loss_force_generic()) {
+    ICL_LAUNCH(icl::loss_stats_generic_kernel, grid, block, 0, st, a, b, lab, part, batch, nc, (long)s, a_is_prob);
+  } else if (nc <= 4) {
     ICL_LAUNCH((icl::loss_stats_kernel<4>), grid, block, 0, st, a, b, lab, part, batch, nc, (long)s, a_is_prob);
   } else {
     ICL_LAUNCH((icl::loss_stats_kernel<16>), grid, block, 0, st, a, b, lab, part, batch, nc, (long)s, a_is_prob);
@@ -1738,14 +1749,15 @@ int icl_loss_fwd(const float* a, const float* b, const int64_t* labels, const fl
   return check_launch("loss_finalize");
 }
 
-static int loss_multi_fill(const IclLossJob* jobs, int count, bool bwd, icl::LossMulti& m, int& most, bool& small_nc) {
+static int loss_multi_fill(const IclLossJob* jobs, int count, bool bwd, icl::LossMulti& m, int& most, int& group) {
   if (!jobs || count < 1 || count > icl::kLossMulti) return fail(-1, "loss_multi: 1 .. %d jobs", icl::kLossMulti);
   most = 1;
-  small_nc = jobs[0].nc <= 4;
+  group = loss_class_group(jobs[0].nc);
   for (int j = 0; j < count; ++j) {
     const IclLossJob& q = jobs[j];
-    if (!q.a || !q.stats || q.batch < 1 || q.nc < 1 || q.nc > 16 || q.s < 1 || q.mode < 0 || q.mode > 3 || (q.nc <= 4) != small_nc)
-      return fail(-1, "loss_multi: bad job %d (all jobs need nc <= 4 or all nc > 4)", j);
+    if (q.nc < 1 || q.nc > icl::kLossMaxNc) return fail(-1, "loss_multi: job %d has %d classes (1 .. %d)", j, q.nc, icl::kLossMaxNc);
+    if (!q.a || !q.stats || q.batch < 1 || q.s < 1 || q.mode < 0 || q.mode > 3 || loss_class_group(q.nc) != group)
+      return fail(-1, "loss_multi: bad job %d (all jobs of a call need nc <= 4, or all 5 .. 16, or all 17 .. %d)", j, icl::kLossMaxNc);
     if ((q.mode <= 1) != (q.labels != nullptr) || (q.mode >= 2) != (q.b != nullptr)) return fail(-1, "loss_multi: target of job %d does not match its mode", j);
     if (bwd ? !q.ga : !q.out) return fail(-1, "loss_multi: job %d has no output", j);
     const long total = (long)q.batch * q.s;
@@ -1755,17 +1767,19 @@ static int loss_multi_fill(const IclLossJob* jobs, int count, bool bwd, icl::Los
     m.nblk[j] = bwd ? grid_for(total, 256, 4096) : grid_for(total, 256, ICL_LOSS_MAX_BLOCKS);      // as icl_loss_bwd / icl_loss_fwd
     if (m.nblk[j] > most) most = m.nblk[j];
   }
+  if (loss_force_generic()) group = 2;
   return 0;
 }
 
 int icl_loss_fwd_multi(const IclLossJob* jobs, int count, void* stream) {
   icl::LossMulti m{};
-  int most = 1;
-  bool small_nc = true;
-  int rc = loss_multi_fill(jobs, count, false, m, most, small_nc);
+  int most = 1, group = 0;
+  int rc = loss_multi_fill(jobs, count, false, m, most, group);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (small_nc) {
+  if (group == 2) {
+    ICL_LAUNCH(icl::loss_stats_generic_multi_kernel, dim3(most, count), dim3(256), 0, st, m);
+  } else if (group == 0) {
     ICL_LAUNCH((icl::loss_stats_multi_kernel<4>), dim3(most, count), dim3(256), 0, st, m);
   } else {
     ICL_LAUNCH((icl::loss_stats_multi_kernel<16>), dim3(most, count), dim3(256), 0, st, m);
@@ -1778,11 +1792,12 @@ int icl_loss_fwd_multi(const IclLossJob* jobs, int count, void* stream) {
 
 int icl_loss_bwd_multi(const IclLossJob* jobs, int count, void* stream) {
   icl::LossMulti m{};
-  int most = 1;
-  bool small_nc = true;
-  int rc = loss_multi_fill(jobs, count, true, m, most, small_nc);
+  int most = 1, group = 0;
+  int rc = loss_multi_fill(jobs, count, true, m, most, group);
   if (rc) return rc;
-  if (small_nc) {
+  if (group == 2) {
+    ICL_LAUNCH(icl::loss_grad_generic_multi_kernel, dim3(most, count), dim3(256), 0, (hipStream_t)stream, m);
+  } else if (group == 0) {
     ICL_LAUNCH((icl::loss_grad_multi_kernel<4>), dim3(most, count), dim3(256), 0, (hipStream_t)stream, m);
   } else {
     ICL_LAUNCH((icl::loss_grad_multi_kernel<16>), dim3(most, count), dim3(256), 0, (hipStream_t)stream, m);
@@ -1793,13 +1808,17 @@ int icl_loss_bwd_multi(const IclLossJob* jobs, int count, void* stream) {
 int icl_loss_bwd(const float* a, const float* b, const int64_t* labels, const float* weight, const float* stats,
                  const float* gout0, const float* gout1, float* ga, int batch, int nc, int64_t s, int mode, int a_is_prob,
                  void* stream) {
-  if (!a || !stats || !ga || batch < 1 || nc < 1 || nc > 16 || s < 1) return fail(-1, "loss_bwd: bad argument");
+  if (nc < 1 || nc > icl::kLossMaxNc) return fail(-1, "loss_bwd: %d classes (1 .. %d)", nc, icl::kLossMaxNc);
+  if (!a || !stats || !ga || batch < 1 || s < 1) return fail(-1, "loss_bwd: bad argument");
   hipStream_t st = (hipStream_t)stream;
   const long total = (long)batch * s;
   const float inv_vox = 1.0f / (float)total, inv_elems = 1.0f / ((float)total * (float)nc);
   const dim3 grid(grid_for(total, 256, 4096)), block(256);
   const long long* lab = (const long long*)labels;
-  if (nc <= 4) {
+  if (nc > 16 || loss_force_generic()) {
+    ICL_LAUNCH(icl::loss_grad_generic_kernel, grid, block, 0, st, a, b, lab, stats, weight, gout0, gout1, ga, batch, nc, (long)s, mode, inv_vox,
+               inv_elems, a_is_prob);
+  } else if (nc <= 4) {
     ICL_LAUNCH((icl::loss_grad_kernel<4>), grid, block, 0, st, a, b, lab, stats, weight, gout0, gout1, ga, batch, nc, (long)s, mode, inv_vox,
                inv_elems, a_is_prob);
   } else {
@@ -1908,17 +1927,28 @@ int icl_gelu_bwd(const float* gy, const float* x, float* gx, int64_t n, void* st
   return check_launch("gelu_bwd");
 }
 
+// more classes than the LDS arrays of the logits and dK / dV kernels hold: the class-tiled instantiations (test-only override ICL_ATTN_TILED=1:
+// for any class count, read per call)
+static bool attn_class_tiles(int nc) {
+  const char* e = getenv("ICL_ATTN_TILED");
+  return nc > icl::kAttnMaxNc || (e && atoi(e) == 1);
+}
+
 int icl_attn_fwd(const float* q, const float* kv, float* logits, float* out, float* stats, int b, int h, int nc, int n, int d,
                  float scale, void* stream) {
-  if (!q || !kv || !logits || !out || !stats || b < 1 || h < 1 || nc < 1 || nc > icl::kAttnMaxNc || n < 1 || (d != 8 && d != 16))
-    return fail(-1, "attn_fwd: bad argument (nc <= 16, head dim 8 or 16)");
+  if (nc < 1 || nc > icl::kAttnMaxClasses) return fail(-1, "attn_fwd: %d classes (1 .. %d)", nc, icl::kAttnMaxClasses);
+  if (!q || !kv || !logits || !out || !stats || b < 1 || h < 1 || n < 1 || (d != 8 && d != 16))
+    return fail(-1, "attn_fwd: bad argument (head dim 8 or 16)");
   hipStream_t st = (hipStream_t)stream;
   const dim3 g1((n + 255) / 256, b * h), g2(b * h * nc);
+  const bool tiled = attn_class_tiles(nc);
   if (d == 16) {
-    ICL_LAUNCH((icl::attn_logits_kernel<16>), g1, dim3(256), 0, st, q, kv, logits, b, h, nc, n, scale);
+    if (tiled) ICL_LAUNCH((icl::attn_logits_kernel<16, true>), g1, dim3(256), 0, st, q, kv, logits, b, h, nc, n, scale);
+    else ICL_LAUNCH((icl::attn_logits_kernel<16, false>), g1, dim3(256), 0, st, q, kv, logits, b, h, nc, n, scale);
     ICL_LAUNCH((icl::attn_softmax_pv_kernel<16, 256>), g2, dim3(256), 0, st, (const float*)logits, kv, out, stats, b, h, nc, n);
   } else {
-    ICL_LAUNCH((icl::attn_logits_kernel<8>), g1, dim3(256), 0, st, q, kv, logits, b, h, nc, n, scale);
+    if (tiled) ICL_LAUNCH((icl::attn_logits_kernel<8, true>), g1, dim3(256), 0, st, q, kv, logits, b, h, nc, n, scale);
+    else ICL_LAUNCH((icl::attn_logits_kernel<8, false>), g1, dim3(256), 0, st, q, kv, logits, b, h, nc, n, scale);
     ICL_LAUNCH((icl::attn_softmax_pv_kernel<8, 256>), g2, dim3(256), 0, st, (const float*)logits, kv, out, stats, b, h, nc, n);
   }
   return check_launch("attn_fwd");
@@ -1938,17 +1968,20 @@ int icl_attn_bwd(const float* q, const float* kv, const float* logits, const flo
 // NULL: the row-per-workgroup dQ kernel
 int icl_attn_bwd_ws(const float* q, const float* kv, const float* logits, const float* stats, const float* out, const float* gout,
                     const float* glog, float* gq, float* gkv, void* ws, int b, int h, int nc, int n, int d, float scale, void* stream) {
-  if (!q || !kv || !logits || !stats || !out || !gq || !gkv || b < 1 || h < 1 || nc < 1 || nc > icl::kAttnMaxNc || n < 1 ||
-      (d != 8 && d != 16))
+  if (nc < 1 || nc > icl::kAttnMaxClasses) return fail(-1, "attn_bwd: %d classes (1 .. %d)", nc, icl::kAttnMaxClasses);
+  if (!q || !kv || !logits || !stats || !out || !gq || !gkv || b < 1 || h < 1 || n < 1 || (d != 8 && d != 16))
     return fail(-1, "attn_bwd: bad argument");
   hipStream_t st = (hipStream_t)stream;
   const dim3 g1((n + 255) / 256, b * h), g2(b * h * nc);
   float* pq = (float*)ws;
+  const bool tiled = attn_class_tiles(nc);
   if (d == 16) {
-    ICL_LAUNCH((icl::attn_bwd_kv_kernel<16>), g1, dim3(256), 0, st, q, kv, logits, stats, out, gout, glog, gkv, b, h, nc, n, scale, pq);
+    if (tiled) ICL_LAUNCH((icl::attn_bwd_kv_kernel<16, true>), g1, dim3(256), 0, st, q, kv, logits, stats, out, gout, glog, gkv, b, h, nc, n, scale, pq);
+    else ICL_LAUNCH((icl::attn_bwd_kv_kernel<16, false>), g1, dim3(256), 0, st, q, kv, logits, stats, out, gout, glog, gkv, b, h, nc, n, scale, pq);
     if (!pq) ICL_LAUNCH((icl::attn_bwd_q_kernel<16, 256>), g2, dim3(256), 0, st, kv, logits, stats, out, gout, glog, gq, b, h, nc, n, scale);
   } else {
-    ICL_LAUNCH((icl::attn_bwd_kv_kernel<8>), g1, dim3(256), 0, st, q, kv, logits, stats, out, gout, glog, gkv, b, h, nc, n, scale, pq);
+    if (tiled) ICL_LAUNCH((icl::attn_bwd_kv_kernel<8, true>), g1, dim3(256), 0, st, q, kv, logits, stats, out, gout, glog, gkv, b, h, nc, n, scale, pq);
+    else ICL_LAUNCH((icl::attn_bwd_kv_kernel<8, false>), g1, dim3(256), 0, st, q, kv, logits, stats, out, gout, glog, gkv, b, h, nc, n, scale, pq);
     if (!pq) ICL_LAUNCH((icl::attn_bwd_q_kernel<8, 256>), g2, dim3(256), 0, st, kv, logits, stats, out, gout, glog, gq, b, h, nc, n, scale);
   }
   if (pq) {

@@ -233,6 +233,175 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
   loss_grad_body<NCMAX>(a, b, labels, stats, weight, gout0, gout1, ga, B, nc, S, mode, inv_vox, inv_elems, a_is_prob, blockIdx.x, gridDim.x);
 }
 
+// ---------------------------------------------------------------- generic-class path: 17 .. 256 classes
+// The kernels above keep every class of a voxel and every per-class sum in registers (NCMAX = 4 | 16).  Here NOTHING a thread holds grows
+// with nc: a thread owns one voxel of a 256-voxel tile and walks the class axis (loads coalesced along the voxel axis, class stride S) —
+//   walk 1  the stable soft-max normaliser, online: running max m and sum of exp(v - m), one exp per class;
+//   walk 2  p_c = exp(v_c - m) / sum and the three per-class terms of the voxel.
+// The repeated walks hit the cache (a tile is 1 KB x nc).  Each term is summed over the wave (wave_sum) and lane 0 adds it to the wave's own
+// row of LDS accumulators, tile after tile in a fixed order; at the end the four rows are added in wave order and written as the block's
+// partials in the layout of loss_stats_body, so loss_finalize_body reduces them unchanged: no float atomics, bit-reproducible.  The tile
+// loop is block-uniform (a dead lane computes on the last voxel and contributes zeros) because the wave sums sit inside it.
+constexpr int kLossMaxNc = 256;
+
+// max and sum of exp(v - max) over the nc values at p[0], p[S], ... (online: one exp per class)
+__device__ __forceinline__ void softmax_norm_strided(const float* __restrict__ p, int nc, long S, float& m, float& sum) {
+  m = p[0];
+  sum = 1.f;
+  for (int c = 1; c < nc; ++c) {
+    const float v = p[(long)c * S];
+    const float e = expf(-fabsf(v - m));
+    sum = v > m ? sum * e + 1.f : sum + e;
+    m = fmaxf(m, v);
+  }
+}
+
+__device__ __forceinline__ void loss_stats_generic_body(const float* __restrict__ a, const float* __restrict__ b,
+                                                        const long long* __restrict__ labels, float* __restrict__ part,
+                                                        int B, int nc, long S, int a_is_prob, int bx, int nbx) {
+  __shared__ float acc[4][3 * kLossMaxNc + 1];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int nslot = 3 * nc + 1;
+  float* my = acc[wid];
+  for (int i = lane; i < nslot; i += 64) my[i] = 0.f;
+  __syncthreads();
+  float sx = 0.f;
+  const long total = (long)B * S;
+  for (long e0 = (long)bx * 256; e0 < total; e0 += (long)nbx * 256) {
+    const long e = e0 + threadIdx.x;
+    const bool live = e < total;
+    const long ec = live ? e : total - 1;
+    const long bi = ec / S, s = ec - bi * S;
+    const float* ap = a + bi * nc * S + s;
+    float m = 0.f, inv = 1.f;
+    if (!a_is_prob) {
+      float sum;
+      softmax_norm_strided(ap, nc, S, m, sum);
+      inv = 1.0f / sum;
+      if (labels) {
+        const int y = (int)labels[ec];
+        const float ay = (y >= 0 && y < nc) ? ap[(long)y * S] : 0.f;
+        if (live) sx += (m + logf(sum)) - ay;
+      }
+    }
+    if (labels) {
+      const int y = (int)labels[ec];
+      for (int c = 0; c < nc; ++c) {
+        const float v = ap[(long)c * S];
+        const float p = a_is_prob ? v : expf(v - m) * inv;
+        const float t = (live && c == y) ? 1.f : 0.f;
+        const float r0 = wave_sum(p * t), r1 = wave_sum(live ? p * p : 0.f), r2 = wave_sum(t);
+        if (lane == 0) { my[c] += r0; my[nc + c] += r1; my[2 * nc + c] += r2; }
+      }
+    } else {
+      const float* bp = b + bi * nc * S + s;
+      float m2, sum2;
+      softmax_norm_strided(bp, nc, S, m2, sum2);
+      const float inv2 = 1.0f / sum2;
+      for (int c = 0; c < nc; ++c) {
+        const float v = ap[(long)c * S];
+        const float p = live ? (a_is_prob ? v : expf(v - m) * inv) : 0.f;
+        const float q = live ? expf(bp[(long)c * S] - m2) * inv2 : 0.f;
+        const float d = p - q;
+        sx += d * d;
+        const float r0 = wave_sum(p * q), r1 = wave_sum(p), r2 = wave_sum(q);
+        if (lane == 0) { my[c] += r0; my[nc + c] += r1; my[2 * nc + c] += r2; }
+      }
+    }
+  }
+  {
+    const float rx = wave_sum(sx);
+    if (lane == 0) my[3 * nc] = rx;
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < nslot; t += 256)
+    part[(long)bx * nslot + t] = ((acc[0][t] + acc[1][t]) + acc[2][t]) + acc[3][t];
+}
+__global__ __launch_bounds__(256) void loss_stats_generic_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                 const long long* __restrict__ labels, float* __restrict__ part,
+                                                                 int B, int nc, long S, int a_is_prob) {
+  loss_stats_generic_body(a, b, labels, part, B, nc, S, a_is_prob, blockIdx.x, gridDim.x);
+}
+
+// The gradient of loss_grad_body with the per-class coefficients in LDS (3 x 256 floats, computed once per block) and three walks over
+// the classes of a voxel: the normaliser(s), dot = sum_c d_c p_c (soft-max inputs only), the gradient itself.
+__device__ __forceinline__ void loss_grad_generic_body(const float* __restrict__ a, const float* __restrict__ b,
+                                                       const long long* __restrict__ labels, const float* __restrict__ stats,
+                                                       const float* __restrict__ weight, const float* __restrict__ gout0,
+                                                       const float* __restrict__ gout1, float* __restrict__ ga, int B, int nc,
+                                                       long S, int mode, float inv_vox, float inv_elems, int a_is_prob, int bx, int nbx) {
+  __shared__ float al[kLossMaxNc], be[kLossMaxNc], gm[kLossMaxNc];
+  const float g0 = gout0 ? gout0[0] : 0.f, g1 = gout1 ? gout1[0] : 0.f;
+  for (int c = threadIdx.x; c < nc; c += 256) {
+    const float num = 2.f * stats[c] + kDiceEps;
+    const float den = stats[nc + c] + stats[2 * nc + c] + kDiceEps;
+    const float w = (weight ? weight[c] : 1.f) * g1 / (float)nc;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (mode == 0 || mode == 1) { x = -2.f * w / den; y = 2.f * w * num / (den * den); }
+    else if (mode == 2) { x = -2.f * w / den; z = w * num / (den * den); }
+    else { x = -2.f * g0 * inv_elems; y = 2.f * g0 * inv_elems; }
+    al[c] = x; be[c] = y; gm[c] = z;
+  }
+  __syncthreads();
+  const float kappa = (mode == 1) ? g0 * inv_vox : 0.f;
+  const long total = (long)B * S;
+  for (long e = (long)bx * 256 + threadIdx.x; e < total; e += (long)nbx * 256) {
+    const long bi = e / S, s = e - bi * S;
+    const float* ap = a + bi * nc * S + s;
+    float* gp = ga + bi * nc * S + s;
+    float m = 0.f, inv = 1.f;
+    if (!a_is_prob) {
+      float sum;
+      softmax_norm_strided(ap, nc, S, m, sum);
+      inv = 1.0f / sum;
+    }
+    if (labels) {
+      const int y = (int)labels[e];
+      float dot = 0.f;
+      if (!a_is_prob) {
+        for (int c = 0; c < nc; ++c) {
+          const float p = expf(ap[(long)c * S] - m) * inv;
+          dot += ((c == y ? al[c] : 0.f) + be[c] * p + gm[c]) * p;
+        }
+      }
+      for (int c = 0; c < nc; ++c) {
+        const float v = ap[(long)c * S];
+        const float p = a_is_prob ? v : expf(v - m) * inv;
+        const float T = (c == y) ? 1.f : 0.f;
+        const float d = al[c] * T + be[c] * p + gm[c];
+        gp[(long)c * S] = (a_is_prob ? d : p * (d - dot)) + kappa * (p - T);
+      }
+    } else {
+      const float* bp = b + bi * nc * S + s;
+      float m2, sum2;
+      softmax_norm_strided(bp, nc, S, m2, sum2);
+      const float inv2 = 1.0f / sum2;
+      float dot = 0.f;
+      if (!a_is_prob) {
+        for (int c = 0; c < nc; ++c) {
+          const float p = expf(ap[(long)c * S] - m) * inv;
+          const float T = expf(bp[(long)c * S] - m2) * inv2;
+          dot += (al[c] * T + be[c] * p + gm[c]) * p;
+        }
+      }
+      for (int c = 0; c < nc; ++c) {
+        const float v = ap[(long)c * S];
+        const float p = a_is_prob ? v : expf(v - m) * inv;
+        const float T = expf(bp[(long)c * S] - m2) * inv2;
+        const float d = al[c] * T + be[c] * p + gm[c];
+        gp[(long)c * S] = a_is_prob ? d : p * (d - dot);
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void loss_grad_generic_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                const long long* __restrict__ labels, const float* __restrict__ stats,
+                                                                const float* __restrict__ weight, const float* __restrict__ gout0,
+                                                                const float* __restrict__ gout1, float* __restrict__ ga, int B, int nc,
+                                                                long S, int mode, float inv_vox, float inv_elems, int a_is_prob) {
+  loss_grad_generic_body(a, b, labels, stats, weight, gout0, gout1, ga, B, nc, S, mode, inv_vox, inv_elems, a_is_prob, blockIdx.x, gridDim.x);
+}
+
 // ---------------------------------------------------------------- all loss terms of a step in one launch per pass (round 6)
 // The five-part objective of the trainer (:105-112) is ten reductions — CE + Dice on the logits, three AuxLoss3D maps, three
 // PseudoSoftLoss3D maps, three softmax-MSE pairs — each a statistics launch and a one-block finalize, one behind the other on the step's
@@ -265,6 +434,19 @@ __global__ __launch_bounds__(256) void loss_grad_multi_kernel(LossMulti m) {
   const float total = (float)((long)m.B[j] * m.S[j]);
   loss_grad_body<NCMAX>(m.a[j], m.b[j], m.lab[j], m.stats[j], m.weight[j], m.g0[j], m.g1[j], m.ga[j], m.B[j], m.nc[j], m.S[j], m.mode[j],
                         1.0f / total, 1.0f / (total * (float)m.nc[j]), m.aip[j], blockIdx.x, m.nblk[j]);
+}
+
+__global__ __launch_bounds__(256) void loss_stats_generic_multi_kernel(LossMulti m) {
+  const int j = blockIdx.y;
+  if ((int)blockIdx.x >= m.nblk[j]) return;
+  loss_stats_generic_body(m.a[j], m.b[j], m.lab[j], m.stats[j] + (3 * m.nc[j] + 1), m.B[j], m.nc[j], m.S[j], m.aip[j], blockIdx.x, m.nblk[j]);
+}
+__global__ __launch_bounds__(256) void loss_grad_generic_multi_kernel(LossMulti m) {
+  const int j = blockIdx.y;
+  if ((int)blockIdx.x >= m.nblk[j]) return;
+  const float total = (float)((long)m.B[j] * m.S[j]);
+  loss_grad_generic_body(m.a[j], m.b[j], m.lab[j], m.stats[j], m.weight[j], m.g0[j], m.g1[j], m.ga[j], m.B[j], m.nc[j], m.S[j], m.mode[j],
+                         1.0f / total, 1.0f / (total * (float)m.nc[j]), m.aip[j], blockIdx.x, m.nblk[j]);
 }
 
 }  // namespace icl

@@ -304,27 +304,44 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* __restrict__
 // reference's `attn1.permute(0, 2, 1, 3)`, so the caller's permute is a no-op and the token-axis LayerNorm / MLP that follow read
 // contiguous rows (as [B,h,nc,N] every consumer started with a transposing copy, forward and backward)
 // out  [B,h,nc,D]   = softmax_N(logits) @ v;  stats[B,h,nc,2] = (row max, sum of exp) for the backward.
+// The kernels that stage the queries / output gradients of all classes in LDS (logits, dK / dV) come in two instantiations over the same
+// arrays: TILED = false is the launch of up to kAttnMaxNc classes as it always was (same code, same registers, same bits); TILED = true
+// walks the classes in tiles of kAttnMaxNc — up to kAttnMaxClasses classes, every sum in the same class order.
 constexpr int kAttnMaxNc = 16;
+constexpr int kAttnMaxClasses = 256;
 
-template <int D>
+template <int D, bool TILED>
 __global__ __launch_bounds__(256) void attn_logits_kernel(const float* __restrict__ q, const float* __restrict__ kv, float* __restrict__ logits,
                                                           int B, int H, int nc, int N, float scale) {
   __shared__ float qs[kAttnMaxNc * D];
   const int bh = blockIdx.y;  // b*H + h
   const int b = bh / H, h = bh % H;
-  for (int i = threadIdx.x; i < nc * D; i += 256) qs[i] = q[(long)bh * nc * D + i];
-  __syncthreads();
   const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
-  const float* kp = kv + (((long)b * N + n) * 2 + 0) * H * D + h * D;
+  const bool live = n < N;
+  const float* kp = kv + (((long)b * N + (live ? n : N - 1)) * 2 + 0) * H * D + h * D;
   float k[D];
+  if (TILED) {
 #pragma unroll
-  for (int d = 0; d < D; ++d) k[d] = kp[d];
-  for (int c = 0; c < nc; ++c) {
-    float s = 0.f;
+    for (int d = 0; d < D; ++d) k[d] = kp[d];
+  }
+  for (int c0 = 0; c0 < (TILED ? nc : 1); c0 += kAttnMaxNc) {
+    const int tc = !TILED ? nc : (nc - c0 < kAttnMaxNc ? nc - c0 : kAttnMaxNc);
+    if (TILED && c0) __syncthreads();      // the previous tile's readers are done with qs
+    for (int i = threadIdx.x; i < tc * D; i += 256) qs[i] = q[((long)bh * nc + c0) * D + i];
+    __syncthreads();
+    if (!TILED) {
+      if (!live) return;
 #pragma unroll
-    for (int d = 0; d < D; ++d) s += qs[c * D + d] * k[d];
-    logits[(((long)b * nc + c) * H + h) * N + n] = s * scale;
+      for (int d = 0; d < D; ++d) k[d] = kp[d];
+    } else if (!live) {
+      continue;
+    }
+    for (int c = 0; c < tc; ++c) {
+      float s = 0.f;
+#pragma unroll
+      for (int d = 0; d < D; ++d) s += qs[c * D + d] * k[d];
+      logits[(((long)b * nc + c0 + c) * H + h) * N + n] = s * scale;
+    }
   }
 }
 
@@ -387,7 +404,7 @@ __global__ __launch_bounds__(NT) void attn_softmax_pv_kernel(const float* __rest
 // sum over its tokens of g[c][n] k[n][d] (attn_dq_reduce_kernel adds the workgroups' shares in order and scales).  With the token axis of the
 // 24^3 level (13,824 tokens, 8-16 (sample, head, class) rows) the row-per-workgroup dQ kernel below is an 89 us latency chain on the query chain
 // of the backward pass; here the products ride on the pass that has g and the token's K / V row in registers already.
-template <int D>
+template <int D, bool TILED>
 __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float* __restrict__ q, const float* __restrict__ kv, const float* __restrict__ logits,
                                                           const float* __restrict__ stats, const float* __restrict__ out,
                                                           const float* __restrict__ gout, const float* __restrict__ glog,
@@ -397,51 +414,68 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float* __restric
   __shared__ float dqw[4][D];
   const int bh = blockIdx.y;
   const int b = bh / H, h = bh % H;
-  for (int i = threadIdx.x; i < nc * D; i += 256) {
-    qs[i] = q[(long)bh * nc * D + i];
-    gos[i] = gout ? gout[(long)bh * nc * D + i] : 0.f;
-  }
-  for (int i = threadIdx.x; i < nc * 2; i += 256) ms[i] = stats[(long)bh * nc * 2 + i];
-  __syncthreads();
-  if (threadIdx.x < nc) {
-    float s = 0.f;
-    for (int d = 0; d < D; ++d) s += out[((long)bh * nc + threadIdx.x) * D + d] * gos[threadIdx.x * D + d];
-    dl[threadIdx.x] = s;  // delta_c
-  }
-  __syncthreads();
   const int n = blockIdx.x * 256 + threadIdx.x;
   const bool live = n < N;
-  if (!live && pq == nullptr) return;
   const long base = ((long)b * N + (live ? n : N - 1)) * 2 * H * D + h * D;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   float v[D], k[D], dk[D], dv[D];
+  if (TILED) {
 #pragma unroll
-  for (int d = 0; d < D; ++d) {
-    v[d] = kv[base + (long)H * D + d];
-    k[d] = pq ? kv[base + d] : 0.f;
-    dk[d] = 0.f; dv[d] = 0.f;
+    for (int d = 0; d < D; ++d) {
+      v[d] = kv[base + (long)H * D + d];
+      k[d] = pq ? kv[base + d] : 0.f;
+      dk[d] = 0.f; dv[d] = 0.f;
+    }
   }
-  for (int c = 0; c < nc; ++c) {
-    const long li = (((long)b * nc + c) * H + h) * N + (live ? n : N - 1);
-    const float p = expf(logits[li] - ms[c * 2]) / ms[c * 2 + 1];
-    float dp = 0.f;
-#pragma unroll
-    for (int d = 0; d < D; ++d) dp += gos[c * D + d] * v[d];
-    const float g = live ? (glog ? glog[li] : 0.f) + p * (dp - dl[c]) : 0.f;
-#pragma unroll
-    for (int d = 0; d < D; ++d) { dk[d] += scale * g * qs[c * D + d]; dv[d] += p * gos[c * D + d]; }
-    if (pq) {
-      // the workgroup's sum of g k[d] for class c: wave sums, then the four waves in order
+  // TILED: class tiles of kAttnMaxNc through qs / gos / dl / ms; dk, dv run on over the tiles in class order
+  for (int c0 = 0; c0 < (TILED ? nc : 1); c0 += kAttnMaxNc) {
+    const int tc = !TILED ? nc : (nc - c0 < kAttnMaxNc ? nc - c0 : kAttnMaxNc);
+    if (TILED && c0) __syncthreads();
+    for (int i = threadIdx.x; i < tc * D; i += 256) {
+      qs[i] = q[((long)bh * nc + c0) * D + i];
+      gos[i] = gout ? gout[((long)bh * nc + c0) * D + i] : 0.f;
+    }
+    for (int i = threadIdx.x; i < tc * 2; i += 256) ms[i] = stats[((long)bh * nc + c0) * 2 + i];
+    __syncthreads();
+    if (threadIdx.x < tc) {
+      float s = 0.f;
+      for (int d = 0; d < D; ++d) s += out[((long)bh * nc + c0 + threadIdx.x) * D + d] * gos[threadIdx.x * D + d];
+      dl[threadIdx.x] = s;  // delta_c
+    }
+    __syncthreads();
+    if (!TILED) {
+      if (!live && pq == nullptr) return;
 #pragma unroll
       for (int d = 0; d < D; ++d) {
-        const float w = wave_sum(g * k[d]);
-        if (lane == 0) dqw[wid][d] = w;
+        v[d] = kv[base + (long)H * D + d];
+        k[d] = pq ? kv[base + d] : 0.f;
+        dk[d] = 0.f; dv[d] = 0.f;
       }
-      __syncthreads();
-      if (threadIdx.x < D)
-        pq[(((long)blockIdx.x * gridDim.y + bh) * nc + c) * D + threadIdx.x] =
-            ((dqw[0][threadIdx.x] + dqw[1][threadIdx.x]) + dqw[2][threadIdx.x]) + dqw[3][threadIdx.x];
-      __syncthreads();
+    } else if (!live && pq == nullptr) {
+      continue;      // a token past the end only takes part in the barriers (and in the wave sums of the dQ shares)
+    }
+    for (int c = 0; c < tc; ++c) {
+      const long li = (((long)b * nc + c0 + c) * H + h) * N + (live ? n : N - 1);
+      const float p = expf(logits[li] - ms[c * 2]) / ms[c * 2 + 1];
+      float dp = 0.f;
+#pragma unroll
+      for (int d = 0; d < D; ++d) dp += gos[c * D + d] * v[d];
+      const float g = live ? (glog ? glog[li] : 0.f) + p * (dp - dl[c]) : 0.f;
+#pragma unroll
+      for (int d = 0; d < D; ++d) { dk[d] += scale * g * qs[c * D + d]; dv[d] += p * gos[c * D + d]; }
+      if (pq) {
+        // the workgroup's sum of g k[d] for class c: wave sums, then the four waves in order
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+          const float w = wave_sum(g * k[d]);
+          if (lane == 0) dqw[wid][d] = w;
+        }
+        __syncthreads();
+        if (threadIdx.x < D)
+          pq[(((long)blockIdx.x * gridDim.y + bh) * nc + c0 + c) * D + threadIdx.x] =
+              ((dqw[0][threadIdx.x] + dqw[1][threadIdx.x]) + dqw[2][threadIdx.x]) + dqw[3][threadIdx.x];
+        __syncthreads();
+      }
     }
   }
   if (!live) return;

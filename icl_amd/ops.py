@@ -2109,6 +2109,15 @@ def window_attention_keep_probe(like: torch.Tensor, base: int, count: int, seed:
     return out != 0
 
 
+PROTO_ATTN_WS_MIN_TOKENS = 1024      # token axes from here on take icl_attn_bwd_ws with its dQ-share workspace (the tests move it)
+MAX_CLASSES = 256      # the loss kernels (csrc/kernels/loss.h, kLossMaxNc) and the prototype attention (token.h, kAttnMaxClasses)
+
+
+def _check_classes(nc: int, what: str) -> None:
+    if not 1 <= nc <= MAX_CLASSES:
+        raise ValueError(f"icl_amd {what}: {nc} classes; the training kernels take 1 .. {MAX_CLASSES} (ops.MAX_CLASSES)")
+
+
 class _ProtoAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qh, kv, heads, scale):
@@ -2119,6 +2128,7 @@ class _ProtoAttention(torch.autograd.Function):
         B, h, nc, d = qh.shape
         N = kv.shape[1]
         assert h == heads and kv.shape[2] == 2 * h * d
+        _check_classes(nc, "prototype attention")
         logits = torch.empty((B, nc, h, N), dtype=torch.float32, device=qh.device)       # class-major: the layout the reference returns
         out = torch.empty((B, h, nc, d), dtype=torch.float32, device=qh.device)
         stats = torch.empty((B, h, nc, 2), dtype=torch.float32, device=qh.device)
@@ -2139,7 +2149,7 @@ class _ProtoAttention(torch.autograd.Function):
         gkv = torch.empty_like(kv)
         # dQ from the shares the dK / dV pass writes per 256-token chunk (long token axes: the row-per-workgroup dQ kernel is a latency
         # chain on the backward's query chain); short axes keep the two-kernel form (one launch fewer than shares + sum... the same count)
-        ws = _ws(L.icl_attn_bwd_ws_bytes(B, h, nc, N, d), qh) if N >= 1024 else None
+        ws = _ws(L.icl_attn_bwd_ws_bytes(B, h, nc, N, d), qh) if N >= PROTO_ATTN_WS_MIN_TOKENS else None
         _lib.check(L.icl_attn_bwd_ws(_ptr(qh), _ptr(kv), _ptr(logits), _ptr(stats), _ptr(out), _ptr(gout), _ptr(glog), _ptr(gq), _ptr(gkv),
                                      _ptr(ws), B, h, nc, N, d, ctx.scale, _stream(qh)), "attn_bwd")
         return gq, gkv, None, None
@@ -2292,7 +2302,7 @@ class _QueryAttend(torch.autograd.Function):
                 grads[12:14] = [gqcw, gqcb]
         glog = glog.contiguous() if glog is not None else None
         gq, gkv = new(R, C), torch.empty_like(kv)
-        ws = _ws(L.icl_attn_bwd_ws_bytes(B, h, nc, N, d), kv) if N >= 1024 else None
+        ws = _ws(L.icl_attn_bwd_ws_bytes(B, h, nc, N, d), kv) if N >= PROTO_ATTN_WS_MIN_TOKENS else None
         _lib.check(L.icl_attn_bwd_ws(_ptr(qf), _ptr(kv), _ptr(logits), _ptr(stats), _ptr(a), _ptr(ga), _ptr(glog), _ptr(gq), _ptr(gkv),
                                      _ptr(ws), B, h, nc, N, d, scale, _stream(kv)), "attn_bwd")
         dn1 = new(R, C)
@@ -2345,6 +2355,7 @@ class _FusedLoss(torch.autograd.Function):
         a = a.contiguous()
         target = target.contiguous()
         B, nc = a.shape[0], a.shape[1]
+        _check_classes(nc, "loss")
         S = a.numel() // (B * nc)
         hard = mode <= 1
         if hard:
@@ -2401,6 +2412,7 @@ class _FusedLossMulti(torch.autograd.Function):
         _require(*a_s, *t_s)
         dev = a_s[0].device
         nc = a_s[0].shape[1]
+        _check_classes(nc, "loss")
         per = (3 * nc + 1) * (1 + LOSS_MAX_BLOCKS)
         stats = torch.empty((n, per), dtype=torch.float32, device=dev)
         out = torch.empty((n, 2), dtype=torch.float32, device=dev)
@@ -2462,7 +2474,8 @@ class _FusedLossMulti(torch.autograd.Function):
 def fused_losses(terms):
     """``terms``: list of (a, target, mode) with mode 1 = (cross-entropy, Dice(softmax)) on int64 labels, 2 = soft Dice against logits,
     3 = softmax MSE against logits (the targets of modes 2 / 3 are detached).  Returns the list of (term0, term1) pairs — one statistics
-    launch, one finalize launch, one gradient launch for all of them when there are at most 12 with one class count."""
+    launch, one finalize launch, one gradient launch for all of them when there are at most 12 with one class count (one class count is
+    one class group of icl_loss_fwd_multi: <= 4, 5 .. 16 or 17 .. 256 classes)."""
     if not terms:
         return []
     ncs = {t[0].shape[1] for t in terms}

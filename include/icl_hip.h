@@ -216,7 +216,9 @@ int icl_drop_path_add(const float* x, const float* res, float* y, int64_t n, int
  *   mode 2 soft Dice        out = {0, dice}          mode 3 softmax MSE      out = {mse, 0}
  * stats: ICL_LOSS_STATS_FLOATS(nc) floats — the 3*nc+1 reduced sums (kept for backward) followed by per-workgroup partials,
  * summed in a fixed order (no atomics: the loss is bit-reproducible and nothing needs zeroing); gout0 / gout1: upstream grads of out[0] / out[1], one float each, NULL when
- * that output does not reach the loss; ga: gradient w.r.t. a.  weight (per-class Dice weights) may be NULL.  nc <= 16. */
+ * that output does not reach the loss; ga: gradient w.r.t. a.  weight (per-class Dice weights) may be NULL.
+ * 1 <= nc <= 256: up to 16 classes stay in registers, 17 .. 256 take the generic-class kernels (same stats buffer, same fixed
+ * summation order); outside that range the calls return -1 and launch nothing. */
 #define ICL_LOSS_MAX_BLOCKS 1024
 #define ICL_LOSS_STATS_FLOATS(nc) ((3 * (nc) + 1) * (1 + ICL_LOSS_MAX_BLOCKS))
 int icl_loss_fwd(const float* a, const float* b, const int64_t* labels, const float* weight, float* stats, float* out,
@@ -227,7 +229,8 @@ int icl_loss_bwd(const float* a, const float* b, const int64_t* labels, const fl
 /* All loss terms of a step in one statistics launch + one finalize launch (icl_loss_fwd_multi) and one gradient launch
  * (icl_loss_bwd_multi): job j is call j of icl_loss_fwd / icl_loss_bwd — same blocks, same partial sums, same order (bit-identical).
  * The trainer's objective (train_inherent_consistent_unet_3D_BraTS.py:105-112) is ten such terms.  `jobs`: HOST array of <= 12;
- * per job the arguments of the single-term calls (stats: ICL_LOSS_STATS_FLOATS(nc) floats, out: 2 floats; gout0 / gout1 / ga: backward). */
+ * per job the arguments of the single-term calls (stats: ICL_LOSS_STATS_FLOATS(nc) floats, out: 2 floats; gout0 / gout1 / ga: backward).
+ * All jobs of one call belong to one class group: nc <= 4, 5 .. 16, or 17 .. 256. */
 typedef struct IclLossJob {
   const float* a; const float* b; const int64_t* labels; const float* weight;
   float* stats; float* out;
@@ -253,7 +256,7 @@ int icl_gelu_fwd(const float* x, float* y, int64_t n, void* stream);
 int icl_gelu_bwd(const float* gy, const float* x, float* gx, int64_t n, void* stream);
 /* Prototype cross-attention of Query_Attention.forward (:283-297): q [B,h,nc,d] (reshape-quirk layout of fc_q's output),
  * kv [B,N,2,h,d] (fc_kv output).  logits [B,nc,h,N] = scale*q.k (the pre-softmax map, in the class-major layout the reference returns it in: `attn1.permute(0, 2, 1, 3)`, :296),
- * out [B,h,nc,d] = softmax_N(logits) @ v, stats [B,h,nc,2] = (row max, sum exp).  d in {8,16}, nc <= 16.
+ * out [B,h,nc,d] = softmax_N(logits) @ v, stats [B,h,nc,2] = (row max, sum exp).  d in {8,16}, 1 <= nc <= 256 (more than 16: staged in LDS 16 at a time).
  * Backward: gout / glog (either may be NULL) are the upstream gradients of out / logits. */
 int icl_attn_fwd(const float* q, const float* kv, float* logits, float* out, float* stats, int b, int h, int nc, int n, int d,
                  float scale, void* stream);

@@ -2364,6 +2364,50 @@ int icl_crop_rotflip(const void* const* images, const void* const* labels, const
   return check_launch("crop_rotflip");
 }
 
+int icl_volume_feed(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params, int batch,
+                    float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream) {
+  if (!images || !labels || !int_params || !float_params || !image_out || !label_out) return fail(-1, "volume_feed: null pointer");
+  if (batch < 1 || batch > icl::kFeedMaxBatch) return fail(-1, "volume_feed: batch %d out of range (1 <= batch <= %d)", batch, icl::kFeedMaxBatch);
+  if (R0 < 1 || R1 < 1 || R2 < 1) return fail(-1, "volume_feed: output extents %d x %d x %d (each must be >= 1)", R0, R1, R2);
+  if ((long)R0 * R1 * R2 > 0x7fffffffL) return fail(-1, "volume_feed: output extents %d x %d x %d (more than 2^31 - 1 voxels a sample)", R0, R1, R2);
+  const int R[3] = {R0, R1, R2};
+  icl::VolumeFeedBatch fb{};
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* q = int_params + 14 * b;      // n[3], c[3], s[3], l[3], flip, k
+    icl::VolumeFeedSample& s = fb.s[b];
+    s.image = (const float*)images[b];
+    s.label = (const uint8_t*)labels[b];
+    if (!s.image || !s.label) return fail(-1, "volume_feed: sample %d: null volume pointer", b);
+    for (int a = 0; a < 3; ++a) {
+      const int n = q[a], c = q[3 + a], sz = q[6 + a], l = q[9 + a];
+      if (n < 1) return fail(-1, "volume_feed: sample %d: extent %d of axis %d (must be >= 1)", b, n, a);
+      if (c < 0 || sz < 1 || (long)c + sz > n)
+        return fail(-1, "volume_feed: sample %d: crop [%d, %d + %d) of axis %d outside the extent %d", b, c, c, sz, a, n);
+      if (l < 0 || (long)l + sz > R[a])
+        return fail(-1, "volume_feed: sample %d: left pad %d + crop size %d of axis %d outside the output extent %d", b, l, sz, a, R[a]);
+    }
+    s.n1 = q[1]; s.n2 = q[2];
+    s.c0 = q[3]; s.c1 = q[4]; s.c2 = q[5];
+    s.s0 = q[6]; s.s1 = q[7]; s.s2 = q[8];
+    s.l0 = q[9]; s.l1 = q[10]; s.l2 = q[11];
+    s.flip = q[12]; s.k = q[13];
+    s.mul = float_params[2 * b]; s.add = float_params[2 * b + 1];
+    if (s.flip < 0 || s.flip > 7) return fail(-1, "volume_feed: sample %d: flip mask %d outside 0..7", b, s.flip);
+    if (s.k < 0 || s.k > 3) return fail(-1, "volume_feed: sample %d: k = %d outside 0..3", b, s.k);
+    if ((s.k & 1) && R0 != R1)
+      return fail(-1, "volume_feed: sample %d: k = %d with output extents %d x %d (an odd rot90 needs R0 == R1)", b, s.k, R0, R1);
+  }
+  const long voxels = (long)R0 * R1 * R2;      // per sample; one grid row per sample
+  if ((R2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
+    ICL_LAUNCH(icl::volume_feed_kernel<4>, dim3(grid_for(voxels / 4, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb, image_out,
+               (long long*)label_out, R0, R1, R2);
+  } else {
+    ICL_LAUNCH(icl::volume_feed_kernel<1>, dim3(grid_for(voxels, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb, image_out,
+               (long long*)label_out, R0, R1, R2);
+  }
+  return check_launch("volume_feed");
+}
+
 int icl_slice_augment(const void* const* images, const void* const* labels, const int32_t* int_params, const double* double_params,
                       int batch, float* image_out, uint8_t* label_out, int o0, int o1, void* stream) {
   if (!images || !labels || !int_params || !double_params || !image_out || !label_out)

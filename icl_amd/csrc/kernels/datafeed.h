@@ -165,4 +165,88 @@ __global__ __launch_bounds__(256) void slice_resize_kernel(const T* __restrict__
   }
 }
 
+// ---- 3-D AMOS trainer: the random transforms of train_inherent_consistent_unet_3D_AMOS22.py:102-133 (RandSpatialCropd ->
+// SpatialPadd -> three RandFlipd -> RandRotate90d -> RandShiftIntensityd) as ONE gather over volumes resident in HBM.  The chain
+// differs from crop_rotflip_kernel's (symmetric padding AFTER the crop, three independent flips with the depth axis among them,
+// an intensity term that also lands on the padded voxels), so it has a kernel of its own.  Forward, per sample:
+//   x = src[c : c + s];  x = zero-pad to R with l_a on the left;  flip axis 0 / 1 / 2 for bits 0 / 1 / 2 of `flip`;
+//   x = np.rot90(x, k, axes=(0, 1));  image only: fp32(fp32(x * mul) + add) on EVERY voxel (two roundings: contraction off).
+// Every output voxel is mapped backwards through rot90 -> flips -> padding -> crop origin.  Odd k needs R0 == R1 (the launcher
+// checks), so the flipped patch always has the output's extents.
+struct VolumeFeedSample {
+  const float* image;        // [n0][n1][n2] fp32
+  const uint8_t* label;      // [n0][n1][n2] uint8
+  int n1, n2;                // source extents of axes 1 and 2 (the launcher has checked c + s <= n on every axis)
+  int c0, c1, c2;            // crop origin in the source
+  int s0, s1, s2;            // crop size, min(R, n) per axis
+  int l0, l1, l2;            // zero padding on the left of each axis (R - s - l on the right)
+  int flip;                  // bit a: np.flip on axis a
+  int k;                     // np.rot90(., k, axes=(0, 1)), k in 0..3
+  float mul, add;            // intensity: v * mul + add
+};
+
+struct VolumeFeedBatch {
+  VolumeFeedSample s[kFeedMaxBatch];     // 80 B a record: 1,280 B of the 4 KB kernel-argument block
+};
+
+// image_out [B][1][R0][R1][R2] fp32, label_out [B][R0][R1][R2] int64.  grid (x, B).  One thread per V consecutive depth voxels (V = 4: R2 % 4 == 0,
+// both outputs 16-byte aligned; one 16-byte image store and two 16-byte label stores; the source is walked forwards or, with flip
+// bit 2, backwards along depth).  No LDS, no atomics.
+template <int V>
+__global__ __launch_bounds__(256) void volume_feed_kernel(VolumeFeedBatch fb, float* __restrict__ image_out, long long* __restrict__ label_out,
+                                                          int R0, int R1, int R2) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  static_assert(V == 1 || V == 4, "one voxel or one quad per thread");
+  const int q2 = R2 / V;
+  const unsigned per = (unsigned)R0 * R1 * q2;                                // the launcher keeps R0 * R1 * R2 below 2^31
+  const int b = blockIdx.y;                                                   // one sample per grid row: its record is wave-uniform
+  const VolumeFeedSample& s = fb.s[b];
+  for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < per; r += gridDim.x * blockDim.x) {
+    const long e = (long)b * per + r;
+    const int l = (int)(r % q2) * V;
+    const unsigned rj = r / q2;
+    const int j = (int)(rj % R1), i = (int)(rj / R1);
+    // rot90 on axes (0, 1): out[i][j] = flipped[fa][fc] (the maps of crop_rotflip_kernel, with the patch extents R0, R1)
+    int fa, fc;
+    switch (s.k & 3) {
+      case 0: fa = i; fc = j; break;
+      case 1: fa = j; fc = R1 - 1 - i; break;
+      case 2: fa = R0 - 1 - i; fc = R1 - 1 - j; break;
+      default: fa = R0 - 1 - j; fc = i; break;
+    }
+    if (s.flip & 1) fa = R0 - 1 - fa;
+    if (s.flip & 2) fc = R1 - 1 - fc;
+    const int a = fa - s.l0, c = fc - s.l1;                                   // padded -> cropped coordinates
+    const bool rev = (s.flip & 4) != 0;
+    const int d0 = (rev ? R2 - 1 - l : l) - s.l2, step = rev ? -1 : 1;
+    const bool row = a >= 0 && a < s.s0 && c >= 0 && c < s.s1;
+    const long base = row ? ((long)(s.c0 + a) * s.n1 + (s.c1 + c)) * s.n2 + s.c2 : 0;
+    float v[V];
+    unsigned lab[V];
+#pragma unroll
+    for (int t = 0; t < V; ++t) {
+      const int d = d0 + t * step;
+      float x = 0.f;
+      lab[t] = 0u;
+      if (row && d >= 0 && d < s.s2) {
+        x = s.image[base + d];
+        lab[t] = s.label[base + d];
+      }
+      const float m = x * s.mul;
+      v[t] = m + s.add;
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(image_out + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
+      uint4* lp = reinterpret_cast<uint4*>(label_out + e * 4);                 // labels are 0..255: the high dwords are 0
+      lp[0] = make_uint4(lab[0], 0u, lab[1], 0u);
+      lp[1] = make_uint4(lab[2], 0u, lab[3], 0u);
+    } else {
+      image_out[e] = v[0];
+      label_out[e] = (long long)lab[0];
+    }
+  }
+}
+
 }  // namespace icl

@@ -417,6 +417,18 @@ int icl_relpos_bias_bwd_sum(float* dbias, int chunks, const int32_t* inv, const 
 int icl_crop_rotflip(const void* const* images, const void* const* labels, const int32_t* params, int batch, float* image_out,
                      int64_t* label_out, int o0, int o1, int o2, void* stream);
 
+/* ---- on-device random transforms of the 3-D AMOS trainer (train_inherent_consistent_unet_3D_AMOS22.py:102-133: RandSpatialCropd ->
+ * SpatialPadd -> RandFlipd on axis 0, 1, 2 -> RandRotate90d -> RandShiftIntensityd) as one gather over volumes resident in HBM.
+ * images[b] / labels[b]: HOST arrays of device pointers to the fp32 [n0,n1,n2] volume and its uint8 label; int_params: HOST int32
+ * [batch][14] = {n0, n1, n2, crop origin c0, c1, c2, crop size s0, s1, s2 (min(R, n)), left zero padding l0, l1, l2 (R - s - l on
+ * the right), flip mask (bit a: np.flip on axis a), k (np.rot90 count on axes 0,1, 0..3)}; float_params: HOST fp32 [batch][2] =
+ * {mul, add}: every image voxel, padded ones included, becomes fp32(fp32(v * mul) + add); padded labels are 0.  Drawn by the caller
+ * (icl_amd.dataloaders.amos.draw_amos_params).  image_out [batch,1,R0,R1,R2] fp32, label_out [batch,R0,R1,R2] int64.  batch <= 16.
+ * Returns -1, launching nothing, for a null pointer, a batch outside 1..16, c < 0, s < 1, c + s > n, l < 0, l + s > R, k outside
+ * 0..3, or an odd k with R0 != R1 (the rotated patch would not have the output's shape). */
+int icl_volume_feed(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params, int batch,
+                    float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream);
+
 /* ---- on-device RandomGenerator of the 2-D trainers (dataloaders/dataset.py:147-166; composed at
  * train_inherent_consistent_unet_2D.py:75 and ..._swinunet_2D.py): "maybe rot90 + flip, else maybe ndimage.rotate by an integer
  * angle, then ndimage.zoom to the patch", all order 0, as ONE gather over slices resident in HBM, bit for bit scipy's result.

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
 
 import torch  # noqa: F401  — must be loaded BEFORE libicl_hip.so: both link libamdhip64, and the process must end up with
 #                       torch's copy of the HIP runtime only (two runtimes: "no ROCm-capable device is detected" at launch)
@@ -21,6 +21,7 @@ _lib_path = None
 _host_pointers_ok = False  # True only for the test-only emulation library
 
 P, I, L, F = c_void_p, c_int, c_int64, c_float
+D = c_double
 
 _SIGNATURES = {
     "icl_abi_version": (c_int, []),
@@ -133,6 +134,8 @@ _SIGNATURES = {
     "icl_qchain_wgrad": (c_int, [P, P, P, P, P, P, P, P, I, P]),
     "icl_seg_metrics_ws_bytes": (c_int64, [I, I, I, I]),
     "icl_seg_metrics": (c_int, [P, I, P, I, I, I, I, I, I, P, P, P]),
+    "icl_seg_surface_ws_bytes": (c_int64, [I, I, I, I]),
+    "icl_seg_surface_metrics": (c_int, [P, I, P, I, I, I, I, I, D, D, D, D, P, P, P, P]),
     "icl_window_gather": (c_int, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "icl_window_accumulate": (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "icl_window_finalize": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),

@@ -24,6 +24,7 @@
 #include "kernels/datafeed.h"
 #include "kernels/qchain.h"
 #include "kernels/metrics.h"
+#include "kernels/metrics_surface.h"
 #include "kernels/window.h"
 
 #ifdef ICL_TWO_UNITS
@@ -2636,6 +2637,114 @@ int icl_seg_metrics(const void* pred, int pred_dtype, const void* gt, int gt_dty
     ICL_LAUNCH(icl::seg_select_kernel, dim3(1), dim3(icl::kSegSelectThreads), 0, st, (const unsigned*)w.cnt, (const int*)w.box, w.hist,
                (long long*)out, k);
     if (int e = check_launch("seg_edt / seg_select")) return e;
+  }
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- surface metrics with a voxel spacing: HD95 / HD / ASD / ASSD / NSD in the spacing's units (kernels/metrics_surface.h)
+namespace {
+
+struct SurfWs {
+  unsigned* cnt; unsigned* flags; unsigned* hist; int* box; icl::SurfSel* state; double* psum; double* pmax; unsigned* pcnt;
+  unsigned char* bp; unsigned char* bg; double* ta; double* tb; double* dense[2];
+  int64_t zero_bytes, total;
+};
+
+SurfWs surf_layout(char* base, int n0, int n1, int n2, int nc) {
+  SurfWs w{};
+  const int64_t v = (int64_t)n0 * n1 * n2;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += seg_align(bytes); return p; };
+  w.cnt = (unsigned*)take((int64_t)nc * icl::kSegCnt * 4);
+  w.flags = (unsigned*)take((int64_t)2 * nc * (n0 + n1 + n2) * 4);
+  w.hist = (unsigned*)take((int64_t)icl::kSurfPasses * 2 * icl::kSurfBins * 4);
+  w.zero_bytes = off;                       // counters, presence flags and histograms start at zero
+  w.box = (int*)take((int64_t)nc * 16 * 4);
+  w.state = (icl::SurfSel*)take((int64_t)icl::kSurfPasses * sizeof(icl::SurfSel));
+  w.psum = (double*)take((int64_t)2 * icl::kSurfMaxParts * 8);
+  w.pmax = (double*)take((int64_t)2 * icl::kSurfMaxParts * 8);
+  w.pcnt = (unsigned*)take((int64_t)2 * icl::kSurfMaxParts * 4);
+  w.bp = (unsigned char*)take(v);
+  w.bg = (unsigned char*)take(v);
+  w.ta = (double*)take(v * 8);              // axis-2 pass: F0 x F1 x Q2 <= V
+  w.tb = (double*)take(v * 8);              // axis-1 pass: F0 x Q1 x Q2 <= V
+  w.dense[0] = (double*)take(v * 8);        // squared distances of dP to dG over the box of dP
+  w.dense[1] = (double*)take(v * 8);        // ... of dG to dP over the box of dG
+  w.total = off;
+  return w;
+}
+
+bool surf_shape_ok(int n0, int n1, int n2, int nc) {
+  if (n0 < 1 || n1 < 1 || n2 < 1 || nc < 2 || nc > icl::kSegMaxClasses) return false;
+  return (int64_t)n0 * n1 * n2 <= 0x7fffffffLL;      // 32-bit counters
+}
+
+template <int PASS>
+void surf_radix_launch(const SurfWs& w, dim3 grid, int k, hipStream_t st) {
+  ICL_LAUNCH((icl::surf_radix_kernel<PASS>), grid, dim3(icl::kSurfThreads), 0, st, (const double*)w.dense[0], (const double*)w.dense[1],
+             (const unsigned*)w.cnt, (const int*)w.box, w.hist, w.state, k);
+}
+
+inline bool surf_positive_finite(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }      // false for NaN and infinity
+
+}  // namespace
+
+extern "C" {
+
+int64_t icl_seg_surface_ws_bytes(int n0, int n1, int n2, int num_classes) {
+  if (!surf_shape_ok(n0, n1, n2, num_classes)) return -1;
+  return surf_layout(nullptr, n0, n1, n2, num_classes).total;
+}
+
+int icl_seg_surface_metrics(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int n0, int n1, int n2, int num_classes, double s0,
+                            double s1, double s2, double tolerance, int64_t* counts, double* values, void* ws, void* stream) {
+  if (!pred || !gt || !counts || !values || !ws || !surf_shape_ok(n0, n1, n2, num_classes))
+    return fail(-1, "seg_surface_metrics: bad argument (2 <= num_classes <= %d, n0 n1 n2 <= 2^31 - 1 voxels, workspace of icl_seg_surface_ws_bytes)",
+                icl::kSegMaxClasses);
+  if (!surf_positive_finite(s0) || !surf_positive_finite(s1) || !surf_positive_finite(s2))
+    return fail(-1, "seg_surface_metrics: the spacing must be three finite positive numbers, got (%g, %g, %g)", s0, s1, s2);
+  if (!(tolerance >= 0.0) || !(tolerance <= 1.7976931348623157e308))
+    return fail(-1, "seg_surface_metrics: the tolerance must be finite and not negative, got %g", tolerance);
+  if (pred_dtype != 1 && pred_dtype != 8) return fail(-1, "seg_surface_metrics: label element size must be 1 (uint8) or 8 (int64)");
+  if (gt_dtype != 1 && gt_dtype != 8) return fail(-1, "seg_surface_metrics: label element size must be 1 (uint8) or 8 (int64)");
+  const int nc = num_classes;
+  hipStream_t st = (hipStream_t)stream;
+  const SurfWs w = surf_layout((char*)ws, n0, n1, n2, nc);
+  const double tau2 = tolerance * tolerance;
+  ICL_MEMSET_ASYNC(ws, 0, (size_t)w.zero_bytes, st);
+  SegWs first{};      // the first stage is the integer path's: same kernels, same instantiations
+  first.cnt = w.cnt; first.flags = w.flags; first.bp = w.bp; first.bg = w.bg;
+  if (pred_dtype == 1) seg_border_dispatch_gt<uint8_t>(pred, gt, gt_dtype, first, n0, n1, n2, nc, 0, st);
+  else seg_border_dispatch_gt<long long>(pred, gt, gt_dtype, first, n0, n1, n2, nc, 0, st);
+  if (int e = check_launch("seg_border")) return e;
+  ICL_LAUNCH(icl::seg_bbox_kernel, dim3(nc), dim3(256), 0, st, (const unsigned*)w.cnt, (const unsigned*)w.flags, w.box, n0, n1, n2, nc);
+  if (int e = check_launch("seg_bbox")) return e;
+  const long v = (long)n0 * n1 * n2;
+  const dim3 grid(grid_for(v, 256));      // enough for the largest region; workgroups past a class's region do nothing
+  const int parts = grid_for(v, icl::kSurfThreads, icl::kSurfMaxParts);
+  const dim3 rgrid(grid_for(2 * v, icl::kSurfThreads, 2048));      // the select reads both dense buffers
+  for (int k = 1; k < nc; ++k) {
+    for (int dir = 0; dir < 2; ++dir) {      // 0: distances from dP to dG (features dG, queries dP); 1: the other way round
+      const unsigned char* feat = dir ? w.bp : w.bg;
+      const unsigned char* query = dir ? w.bg : w.bp;
+      ICL_LAUNCH(icl::surf_edt_axis2_kernel, grid, dim3(256), 0, st, feat, (const int*)w.box, w.ta, k, dir, n1, n2, s2);
+      ICL_LAUNCH(icl::surf_edt_axis1_kernel, grid, dim3(256), 0, st, (const double*)w.ta, (const int*)w.box, w.tb, k, dir, s1);
+      ICL_LAUNCH(icl::surf_edt_axis0_kernel, grid, dim3(256), 0, st, (const double*)w.tb, query, (const int*)w.box, w.dense[dir], k, dir, n1, n2, s0);
+      ICL_LAUNCH(icl::surf_reduce_kernel, dim3(parts), dim3(icl::kSurfThreads), 0, st, (const double*)w.dense[dir], (const int*)w.box,
+                 w.psum + dir * icl::kSurfMaxParts, w.pmax + dir * icl::kSurfMaxParts, w.pcnt + dir * icl::kSurfMaxParts, k, dir, tau2);
+    }
+    surf_radix_launch<0>(w, rgrid, k, st);
+    surf_radix_launch<1>(w, rgrid, k, st);
+    surf_radix_launch<2>(w, rgrid, k, st);
+    surf_radix_launch<3>(w, rgrid, k, st);
+    surf_radix_launch<4>(w, rgrid, k, st);
+    surf_radix_launch<5>(w, rgrid, k, st);
+    ICL_LAUNCH(icl::surf_finish_kernel, dim3(1), dim3(icl::kSurfThreads), 0, st, (const unsigned*)w.cnt, (const int*)w.box, w.hist,
+               (const icl::SurfSel*)w.state, (const double*)w.psum, (const double*)w.pmax, (const unsigned*)w.pcnt, parts, (long long*)counts,
+               values, k);
+    if (int e = check_launch("surf_edt / surf_radix / surf_finish")) return e;
   }
   return 0;
 }

@@ -2605,6 +2605,47 @@ def seg_metrics(pred: torch.Tensor, gt: torch.Tensor, num_classes: int) -> torch
     return out
 
 
+def seg_surface_metrics(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, spacing, tolerance: float = 1.0):
+    """Per-class records of the surface metrics with a voxel spacing (include/icl_hip.h icl_seg_surface_metrics): ``(counts, values)`` on
+    the device of the maps.  ``counts`` int64 [num_classes - 1, 7], row c - 1 = (|P|, |G|, |P & G|, |dP|, |dG|, voxels of dP within
+    ``tolerance`` of dG, voxels of dG within ``tolerance`` of dP); ``values`` float64 [num_classes - 1, 6] = (sq[k0], sq[k0 + 1] of the union
+    of both directions' squared distances, max d^2 P -> G, max d^2 G -> P, sum d P -> G, sum d G -> P), -1 when P or G is empty.
+    ``spacing``: three finite positive numbers (the voxel size along the three axes).  Always the floating-point path, also for spacing
+    (1, 1, 1).  Asynchronous on the current stream.  The maps are exactly 3-D; label dtypes as ``seg_metrics``."""
+    if pred.shape != gt.shape:
+        raise ValueError(f"seg_surface_metrics: shapes differ {tuple(pred.shape)} vs {tuple(gt.shape)}")
+    if pred.dim() != 3:
+        raise ValueError(f"seg_surface_metrics: needs a 3-D label map, got {tuple(pred.shape)}")
+    for t in (pred, gt):
+        if t.dtype not in _SEG_DTYPES:
+            raise TypeError(f"seg_surface_metrics: unsupported label dtype {t.dtype}")
+        if not t.is_cuda and not _lib.host_pointers_ok():
+            raise RuntimeError("icl_amd: HIP kernels need device tensors (no CPU fallback)")
+    if pred.device != gt.device:
+        raise ValueError("seg_surface_metrics: pred and gt on different devices")
+    try:
+        sp = [float(v) for v in spacing]
+    except TypeError:
+        raise ValueError(f"seg_surface_metrics: spacing must be three numbers, got {spacing!r}") from None
+    if len(sp) != 3 or not all(math.isfinite(v) and v > 0 for v in sp):
+        raise ValueError(f"seg_surface_metrics: spacing must be three finite positive numbers, got {spacing!r}")
+    tol = float(tolerance)
+    if not (math.isfinite(tol) and tol >= 0):
+        raise ValueError(f"seg_surface_metrics: tolerance must be finite and not negative, got {tolerance!r}")
+    n0, n1, n2 = (int(v) for v in pred.shape)
+    pred, gt = pred.contiguous(), gt.contiguous()
+    L = _lib.lib()
+    nbytes = L.icl_seg_surface_ws_bytes(n0, n1, n2, int(num_classes))
+    if nbytes < 0:
+        raise ValueError(f"seg_surface_metrics: shape {(n0, n1, n2)} / num_classes {num_classes} not supported (2 <= num_classes <= 256)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    counts = torch.empty((int(num_classes) - 1, 7), dtype=torch.int64, device=pred.device)
+    values = torch.empty((int(num_classes) - 1, 6), dtype=torch.float64, device=pred.device)
+    _lib.check(L.icl_seg_surface_metrics(_ptr(pred), _SEG_DTYPES[pred.dtype], _ptr(gt), _SEG_DTYPES[gt.dtype], n0, n1, n2, int(num_classes),
+                                         sp[0], sp[1], sp[2], tol, _ptr(counts), _ptr(values), _ptr(ws), _stream(pred)), "seg_surface_metrics")
+    return counts, values
+
+
 # --------------------------------------------------------------------------------------
 # 3-D sliding window of the validation loops (val_3D.py:18-73, :128-132; csrc/kernels/window.h)
 # --------------------------------------------------------------------------------------

@@ -20,14 +20,18 @@ import torch
 from scipy.ndimage import zoom
 
 from .dataloaders.dataset import resize_slices
-from .val_3D import _upload_label, binary_dice, binary_hd95, cal_metric_multiclass, val_metrics_mode
+from .val_3D import _normalize_spacing, _upload_label, binary_dice, binary_hd95, cal_metric_multiclass, val_metrics_mode
 
 
-def calculate_metric_percase(pred, gt):
-    """val_2D.py:10-22 (binarises its arguments like the reference)."""
+def calculate_metric_percase(pred, gt, voxelspacing=None):
+    """val_2D.py:10-22 (binarises its arguments like the reference).  ``voxelspacing``: HD95 in its units (``val_3D.binary_hd95``)."""
     pred = np.asarray(pred) > 0
     gt = np.asarray(gt) > 0
+    if voxelspacing is not None:
+        voxelspacing = _normalize_spacing(voxelspacing)
     if pred.sum() > 0 and gt.sum() > 0:
+        if voxelspacing is not None:
+            return binary_dice(pred, gt), binary_hd95(pred, gt, voxelspacing)
         return binary_dice(pred, gt), binary_hd95(pred, gt)
     if pred.sum() > 0 and gt.sum() == 0:
         return 0, 373.128664
@@ -75,31 +79,37 @@ def _predict_volume(image, net, patch_size, inference_kw, slices_per_batch):
     return prediction
 
 
-def _score_volume(prediction, label, net, classes):
+def _score_volume(prediction, label, net, classes, voxelspacing=None):
     """``[calculate_metric_percase(prediction == i, label == i) for i in 1..classes-1]``; with the net on a HIP device both maps go up
     once (a device prediction stays where it is) and every class is scored by the metric kernels (the same values and types: Dice and
-    HD95 are symmetric in their arguments).  ``prediction``: a numpy array or a device tensor."""
+    HD95 are symmetric in their arguments).  ``prediction``: a numpy array or a device tensor.  ``voxelspacing``: a number, or three for
+    the [slices, H, W] volume — HD95 in its units (``cal_metric_multiclass``)."""
+    if voxelspacing is not None:
+        voxelspacing = _normalize_spacing(voxelspacing)
     dev = next(net.parameters()).device
     if dev.type == "cuda" and val_metrics_mode() == "device" and 2 <= classes <= 256:
         gt = _upload_label(label, dev)
         if gt is not None and gt.shape == prediction.shape:
-            return cal_metric_multiclass(gt, prediction if torch.is_tensor(prediction) else torch.from_numpy(prediction).to(dev), classes)
+            return cal_metric_multiclass(gt, prediction if torch.is_tensor(prediction) else torch.from_numpy(prediction).to(dev), classes,
+                                         voxelspacing)
     if torch.is_tensor(prediction):
         prediction = prediction.cpu().numpy()
-    return [calculate_metric_percase(prediction == i, label == i) for i in range(1, classes)]
+    return [calculate_metric_percase(prediction == i, label == i, voxelspacing) for i in range(1, classes)]
 
 
-def test_single_volume_ours(image, label, net, writer=None, iter_num=0, classes=4, patch_size=(224, 224), slices_per_batch=16):
-    """val_2D.py:35-54: ``image`` / ``label`` are [1, slices, H, W] tensors (one case of the validation loader)."""
+def test_single_volume_ours(image, label, net, writer=None, iter_num=0, classes=4, patch_size=(224, 224), slices_per_batch=16,
+                            voxelspacing=None):
+    """val_2D.py:35-54: ``image`` / ``label`` are [1, slices, H, W] tensors (one case of the validation loader).  ``voxelspacing``: a
+    number, or (slice thickness, pixel height, pixel width) — HD95 in its units; None: voxels, as the reference."""
     image = image.squeeze(0).cpu().detach().numpy()
     label = label.squeeze(0).cpu().detach().numpy()
     prediction = _predict_volume(image, net, patch_size, {"inference": True}, slices_per_batch)
-    return _score_volume(prediction, label, net, classes)
+    return _score_volume(prediction, label, net, classes, voxelspacing)
 
 
-def test_single_volume(image, label, net, classes, patch_size=(256, 256), slices_per_batch=16):
-    """val_2D.py:109-131: the plain networks (``net(input)``)."""
+def test_single_volume(image, label, net, classes, patch_size=(256, 256), slices_per_batch=16, voxelspacing=None):
+    """val_2D.py:109-131: the plain networks (``net(input)``).  ``voxelspacing`` as in ``test_single_volume_ours``."""
     image = image.squeeze(0).cpu().detach().numpy()
     label = label.squeeze(0).cpu().detach().numpy()
     prediction = _predict_volume(image, net, patch_size, {}, slices_per_batch)
-    return _score_volume(prediction, label, net, classes)
+    return _score_volume(prediction, label, net, classes, voxelspacing)

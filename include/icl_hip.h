@@ -519,6 +519,23 @@ int64_t icl_seg_metrics_ws_bytes(int n0, int n1, int n2, int num_classes);
 int icl_seg_metrics(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int n0, int n1, int n2, int num_classes, int all_border,
                     int64_t* out, void* ws, void* stream);
 
+/* ---- surface metrics with a voxel spacing, every foreground class (csrc/kernels/metrics_surface.h).  Replaces
+ * medpy.metric.binary.hd95 / hd / asd / assd called with `voxelspacing` (the reference's val_3D.py:85-97 / val_2D.py:10-22 call hd95 without
+ * it, so its HD95 is in voxel units), and the voxel-border NSD; restated in icl_amd/val_3D.py (binary_hd95, binary_hd, binary_asd,
+ * binary_assd, binary_nsd).  pred / gt, dtypes and class rule as icl_seg_metrics; the maps are exactly 3-D.  (s0, s1, s2): the voxel
+ * spacing along n0, n1, n2, finite and positive; tolerance: the NSD tolerance tau in the spacing's units, finite and >= 0.
+ * counts: DEVICE int64 [num_classes - 1][7], row c - 1 = {|P|, |G|, |P & G|, |dP|, |dG|, #{p in dP: d(p, dG)^2 <= tau^2},
+ * #{g in dG: d(g, dP)^2 <= tau^2}}.  values: DEVICE double [num_classes - 1][6], row c - 1 = {sq[k0], sq[k0 + 1], max d^2 (dP -> dG),
+ * max d^2 (dG -> dP), sum d (dP -> dG), sum d (dG -> dP)}: sq the sorted union of the squared distances sum_a ((double)delta_a s_a)^2 of
+ * both directions, k0 = floor(0.95 (n - 1)), n = |dP| + |dG|; every value is -1 when dP or dG is empty.  The squares are exact distance
+ * transform values (each product and sum rounded once, no contraction); the host takes the roots of the two order statistics and of the
+ * maxima.  The sums are added in a fixed order: two calls are bit-equal.  2 <= num_classes <= 256; ws: icl_seg_surface_ws_bytes bytes
+ * (-1: shape not supported), 34 bytes per voxel plus about 150 KiB.  15 (num_classes - 1) + 3 launches, no synchronisation.  A bad
+ * argument (also a non-finite or non-positive spacing, a negative or non-finite tolerance) returns -1 and launches nothing. */
+int64_t icl_seg_surface_ws_bytes(int n0, int n1, int n2, int num_classes);
+int icl_seg_surface_metrics(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int n0, int n1, int n2, int num_classes, double s0,
+                            double s1, double s2, double tolerance, int64_t* counts, double* values, void* ws, void* stream);
+
 /* ---- the 3-D sliding window of the validation loops on the device (csrc/kernels/window.h; val_3D.py:18-73: test_single_case_base's pad,
  * window grid, soft-max, score / count maps, divide, arg-max and crop; val_3D.py:128-132: monai.inferers.sliding_window_inference as the
  * AMOS loop calls it; both restated in icl_amd/val_3D.py).  Volumes are dense with the last axis fastest.  origins: HOST int32 [n][3], the

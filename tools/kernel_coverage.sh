@@ -1,6 +1,8 @@
 # usage (GPU box): bash tools/kernel_coverage.sh   -> gpurun_out/kernel_coverage.txt
 # Which kernels of libicl_hip.so does the GPU suite + the three bench configurations launch?  (rocprofv3 kernel trace, names only)
 # (volume_feed_kernel<1> and <4>, the AMOS data feed, are launched by tests/test_gpu_amos_feed.py: the (6, 6, 5) and (6, 6, 8) sweeps)
+# (the surface-metric kernels of metrics_surface.h — surf_edt_axis2/1/0, surf_reduce, surf_radix<0..5>, surf_finish — are launched by
+#  tests/test_gpu_surface_metrics.py)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/cov

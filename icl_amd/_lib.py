@@ -136,6 +136,9 @@ _SIGNATURES = {
     "icl_seg_metrics": (c_int, [P, I, P, I, I, I, I, I, I, P, P, P]),
     "icl_seg_surface_ws_bytes": (c_int64, [I, I, I, I]),
     "icl_seg_surface_metrics": (c_int, [P, I, P, I, I, I, I, I, D, D, D, D, P, P, P, P]),
+    "icl_seg_components_ws_bytes": (c_int64, [I, I, I, I]),
+    "icl_seg_components": (c_int, [P, I, I, I, I, I, I, P, P, P, P]),
+    "icl_seg_filter_components": (c_int, [P, I, I, I, I, I, I, I, c_int64, P, P, P, P]),
     "icl_window_gather": (c_int, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "icl_window_accumulate": (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "icl_window_finalize": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),

@@ -25,6 +25,7 @@
 #include "kernels/qchain.h"
 #include "kernels/metrics.h"
 #include "kernels/metrics_surface.h"
+#include "kernels/components.h"
 #include "kernels/window.h"
 
 #ifdef ICL_TWO_UNITS
@@ -2747,6 +2748,112 @@ int icl_seg_surface_metrics(const void* pred, int pred_dtype, const void* gt, in
     if (int e = check_launch("surf_edt / surf_radix / surf_finish")) return e;
   }
   return 0;
+}
+
+}  // extern "C"
+
+// ---- connected components of a label map and the keep-largest / minimum-size filter (kernels/components.h)
+namespace {
+
+struct CcWs {
+  int* parent; int* size; int* labels; unsigned long long* pkey; int* pcnt; long long* rec;
+  int64_t total;
+};
+
+CcWs cc_layout(char* base, int n0, int n1, int n2) {
+  CcWs w{};
+  const int64_t v = (int64_t)n0 * n1 * n2;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += seg_align(bytes); return p; };
+  w.parent = (int*)take(v * 4);
+  w.size = (int*)take(v * 4);
+  w.labels = (int*)take(v * 4);             // the filter's labels (icl_seg_components writes the caller's)
+  w.pkey = (unsigned long long*)take((int64_t)icl::kCcMaxParts * icl::kSegMaxClasses * 8);
+  w.pcnt = (int*)take((int64_t)icl::kCcMaxParts * icl::kSegMaxClasses * 4);
+  w.rec = (long long*)take((int64_t)icl::kSegMaxClasses * icl::kCcRec * 8);
+  w.total = off;
+  return w;
+}
+
+bool cc_shape_ok(int n0, int n1, int n2, int nc) {
+  return seg_shape_ok(n0, n1, n2, nc) && (int64_t)n0 * n1 * n2 + 1 <= 0x7fffffffLL;      // a label is 1 + a voxel index, in an int32
+}
+
+template <typename T, int CONN>
+void cc_label_launch(const void* map, const CcWs& w, int* labels, long long* counts, int n0, int n1, int n2, int nc, hipStream_t st) {
+  const long v = (long)n0 * n1 * n2;
+  const int nt0 = (n0 + icl::kCcT0 - 1) / icl::kCcT0, nt1 = (n1 + icl::kCcT1 - 1) / icl::kCcT1, nt2 = (n2 + icl::kCcT2 - 1) / icl::kCcT2;
+  const dim3 grid(grid_for(v, 256));
+  const int parts = grid_for(v, icl::kCcThreads, icl::kCcMaxParts);
+  ICL_LAUNCH((icl::cc_tile_kernel<T, CONN>), dim3((unsigned)((long)nt0 * nt1 * nt2)), dim3(icl::kCcThreads), 0, st, (const T*)map, w.parent,
+             w.size, n0, n1, n2, nc, nt1, nt2);
+  ICL_LAUNCH((icl::cc_merge_kernel<T, CONN>), grid, dim3(256), 0, st, (const T*)map, w.parent, n0, n1, n2, nc);
+  ICL_LAUNCH(icl::cc_flatten_kernel, grid, dim3(256), 0, st, (const int*)w.parent, labels, w.size, v);
+  ICL_LAUNCH((icl::cc_reduce_kernel<T>), dim3(parts), dim3(icl::kCcThreads), 0, st, (const T*)map, (const int*)labels, (const int*)w.size,
+             w.pkey, w.pcnt, v, nc);
+  ICL_LAUNCH(icl::cc_finish_kernel, dim3(1), dim3(icl::kCcThreads), 0, st, (const unsigned long long*)w.pkey, (const int*)w.pcnt, parts,
+             w.rec, counts, nc);
+}
+
+template <typename T>
+void cc_label_dispatch(const void* map, const CcWs& w, int* labels, long long* counts, int n0, int n1, int n2, int nc, int connectivity,
+                       hipStream_t st) {
+  switch (connectivity) {
+    case 1: cc_label_launch<T, 1>(map, w, labels, counts, n0, n1, n2, nc, st); break;
+    case 2: cc_label_launch<T, 2>(map, w, labels, counts, n0, n1, n2, nc, st); break;
+    default: cc_label_launch<T, 3>(map, w, labels, counts, n0, n1, n2, nc, st);
+  }
+}
+
+// the checks both entry points share; 0 when the arguments are fine
+int cc_check(const char* who, const void* map, int dtype, int n0, int n1, int n2, int nc, int connectivity, const void* ws) {
+  if (!map || !ws || !cc_shape_ok(n0, n1, n2, nc))
+    return fail(-1, "%s: bad argument (2 <= num_classes <= %d, n0 n1 n2 <= 2^31 - 2 voxels, workspace of icl_seg_components_ws_bytes)", who,
+                icl::kSegMaxClasses);
+  if (connectivity < 1 || connectivity > 3) return fail(-1, "%s: connectivity must be 1, 2 or 3, got %d", who, connectivity);
+  if (dtype != 1 && dtype != 8) return fail(-1, "%s: label element size must be 1 (uint8) or 8 (int64)", who);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t icl_seg_components_ws_bytes(int n0, int n1, int n2, int num_classes) {
+  if (!cc_shape_ok(n0, n1, n2, num_classes)) return -1;
+  return cc_layout(nullptr, n0, n1, n2).total;
+}
+
+int icl_seg_components(const void* map, int dtype, int n0, int n1, int n2, int num_classes, int connectivity, int32_t* labels, int64_t* counts,
+                       void* ws, void* stream) {
+  if (int e = cc_check("seg_components", map, dtype, n0, n1, n2, num_classes, connectivity, ws)) return e;
+  if (!labels || !counts) return fail(-1, "seg_components: labels and counts must not be null");
+  hipStream_t st = (hipStream_t)stream;
+  const CcWs w = cc_layout((char*)ws, n0, n1, n2);
+  if (dtype == 1) cc_label_dispatch<uint8_t>(map, w, labels, (long long*)counts, n0, n1, n2, num_classes, connectivity, st);
+  else cc_label_dispatch<long long>(map, w, labels, (long long*)counts, n0, n1, n2, num_classes, connectivity, st);
+  return check_launch("cc_tile / cc_merge / cc_flatten / cc_reduce / cc_finish");
+}
+
+int icl_seg_filter_components(const void* map, int dtype, int n0, int n1, int n2, int num_classes, int connectivity, int keep_largest,
+                              int64_t min_size, void* out, int64_t* counts, void* ws, void* stream) {
+  if (int e = cc_check("seg_filter_components", map, dtype, n0, n1, n2, num_classes, connectivity, ws)) return e;
+  if (!out) return fail(-1, "seg_filter_components: out must not be null");
+  if (min_size < 0) return fail(-1, "seg_filter_components: min_size must not be negative, got %lld", (long long)min_size);
+  hipStream_t st = (hipStream_t)stream;
+  const CcWs w = cc_layout((char*)ws, n0, n1, n2);
+  const long v = (long)n0 * n1 * n2;
+  const dim3 grid(grid_for(v, 256));
+  if (dtype == 1) {
+    cc_label_dispatch<uint8_t>(map, w, w.labels, (long long*)counts, n0, n1, n2, num_classes, connectivity, st);
+    ICL_LAUNCH((icl::cc_filter_kernel<uint8_t>), grid, dim3(256), 0, st, (const uint8_t*)map, (const int*)w.labels, (const int*)w.size,
+               (const long long*)w.rec, (uint8_t*)out, v, num_classes, keep_largest ? 1 : 0, (long long)min_size);
+  } else {
+    cc_label_dispatch<long long>(map, w, w.labels, (long long*)counts, n0, n1, n2, num_classes, connectivity, st);
+    ICL_LAUNCH((icl::cc_filter_kernel<long long>), grid, dim3(256), 0, st, (const long long*)map, (const int*)w.labels, (const int*)w.size,
+               (const long long*)w.rec, (long long*)out, v, num_classes, keep_largest ? 1 : 0, (long long)min_size);
+  }
+  return check_launch("cc_tile / cc_merge / cc_flatten / cc_reduce / cc_finish / cc_filter");
 }
 
 }  // extern "C"

@@ -2646,6 +2646,59 @@ def seg_surface_metrics(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, 
     return counts, values
 
 
+def _seg_components_args(who, label_map, num_classes, connectivity):
+    """The checks ``seg_components`` and ``seg_filter_components`` share: (contiguous 3-D view, n0, n1, n2, workspace)."""
+    geo = seg_metrics_shape(label_map)
+    if geo is None:
+        raise ValueError(f"{who}: needs a 3-D label map (leading axes of length 1 allowed), got {tuple(label_map.shape)}")
+    if label_map.dtype not in _SEG_DTYPES:
+        raise TypeError(f"{who}: unsupported label dtype {label_map.dtype}")
+    if not label_map.is_cuda and not _lib.host_pointers_ok():
+        raise RuntimeError("icl_amd: HIP kernels need device tensors (no CPU fallback)")
+    if isinstance(connectivity, bool) or not isinstance(connectivity, int) or connectivity not in (1, 2, 3):
+        raise ValueError(f"{who}: connectivity must be 1, 2 or 3, got {connectivity!r}")
+    n0, n1, n2 = geo[:3]
+    nbytes = _lib.lib().icl_seg_components_ws_bytes(n0, n1, n2, int(num_classes))
+    if nbytes < 0:
+        raise ValueError(f"{who}: shape {(n0, n1, n2)} / num_classes {num_classes} not supported (2 <= num_classes <= 256)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=label_map.device)
+    return label_map.contiguous(), n0, n1, n2, ws
+
+
+def seg_components(label_map: torch.Tensor, num_classes: int, connectivity: int = 1):
+    """Connected components of every foreground class in one labelling (include/icl_hip.h icl_seg_components): ``(labels, counts)`` on the
+    device of the map.  ``labels`` int32 of the map's shape: 0 on background, else 1 + the linear index of the component's first voxel
+    in raster order; ``counts`` int64 [num_classes - 1, 3], row c - 1 = (components of class c, voxels in the largest, its label — 0
+    when the class is absent; among equal sizes the component that starts first).  ``connectivity`` 1 / 2 / 3: 6 / 18 / 26 neighbours.
+    Asynchronous on the current stream.  Label dtypes and shapes as ``seg_metrics`` (a leading axis of length 1 adds no neighbour)."""
+    m, n0, n1, n2, ws = _seg_components_args("seg_components", label_map, num_classes, connectivity)
+    labels = torch.empty(label_map.shape, dtype=torch.int32, device=m.device)
+    counts = torch.empty((int(num_classes) - 1, 3), dtype=torch.int64, device=m.device)
+    _lib.check(_lib.lib().icl_seg_components(_ptr(m), _SEG_DTYPES[m.dtype], n0, n1, n2, int(num_classes), connectivity, _ptr(labels),
+                                             _ptr(counts), _ptr(ws), _stream(m)), "seg_components")
+    return labels, counts
+
+
+def seg_filter_components(label_map: torch.Tensor, num_classes: int, connectivity: int = 1, keep_largest: bool = True, min_size: int = 0,
+                          out: torch.Tensor = None) -> torch.Tensor:
+    """The label map with the voxels of every component that is not kept set to 0 (include/icl_hip.h icl_seg_filter_components), in the
+    map's dtype and shape: a component is kept iff (not ``keep_largest`` or it is its class's largest; ties go to the one that starts
+    first in raster order) and it has at least ``min_size`` voxels.  Labels outside 1..num_classes-1 are background and come out as 0.
+    ``out``: a contiguous tensor of the map's shape, dtype and device to write into — it may be the map itself.  Asynchronous on the
+    current stream."""
+    m, n0, n1, n2, ws = _seg_components_args("seg_filter_components", label_map, num_classes, connectivity)
+    if isinstance(min_size, bool) or not isinstance(min_size, int) or not 0 <= min_size < 2 ** 63:
+        raise ValueError(f"seg_filter_components: min_size must be an integer >= 0, got {min_size!r}")
+    if out is None:
+        out = torch.empty_like(m)
+    elif out.shape != label_map.shape or out.dtype != label_map.dtype or out.device != label_map.device or not out.is_contiguous():
+        raise ValueError("seg_filter_components: out must be contiguous with the map's shape, dtype and device")
+    _lib.check(_lib.lib().icl_seg_filter_components(_ptr(m), _SEG_DTYPES[m.dtype], n0, n1, n2, int(num_classes), connectivity,
+                                                    1 if keep_largest else 0, min_size, _ptr(out), None, _ptr(ws), _stream(m)),
+               "seg_filter_components")
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # 3-D sliding window of the validation loops (val_3D.py:18-73, :128-132; csrc/kernels/window.h)
 # --------------------------------------------------------------------------------------

@@ -20,7 +20,8 @@ import torch
 from scipy.ndimage import zoom
 
 from .dataloaders.dataset import resize_slices
-from .val_3D import _normalize_spacing, _upload_label, binary_dice, binary_hd95, cal_metric_multiclass, val_metrics_mode
+from .val_3D import (_normalize_spacing, _postprocess_args, _upload_label, binary_dice, binary_hd95, cal_metric_multiclass, keep_components,
+                     val_metrics_mode)
 
 
 def calculate_metric_percase(pred, gt, voxelspacing=None):
@@ -97,19 +98,30 @@ def _score_volume(prediction, label, net, classes, voxelspacing=None):
     return [calculate_metric_percase(prediction == i, label == i, voxelspacing) for i in range(1, classes)]
 
 
+def _postprocess_volume(prediction, classes, postprocess):
+    """``postprocess=`` of the two loops: the stacked [slices, H, W] prediction (numpy array or device tensor) through
+    ``val_3D.keep_components`` as one 3-D map; None leaves it as it is."""
+    post = _postprocess_args(postprocess)
+    return prediction if post is None else keep_components(prediction, classes, **post)
+
+
 def test_single_volume_ours(image, label, net, writer=None, iter_num=0, classes=4, patch_size=(224, 224), slices_per_batch=16,
-                            voxelspacing=None):
+                            voxelspacing=None, postprocess=None):
     """val_2D.py:35-54: ``image`` / ``label`` are [1, slices, H, W] tensors (one case of the validation loader).  ``voxelspacing``: a
-    number, or (slice thickness, pixel height, pixel width) — HD95 in its units; None: voxels, as the reference."""
+    number, or (slice thickness, pixel height, pixel width) — HD95 in its units; None: voxels, as the reference.  ``postprocess``: None (the
+    reference), ``"largest"`` or a dict of ``val_3D.keep_components``' keywords — connected-component filter of the stacked prediction
+    before it is scored."""
+    _postprocess_args(postprocess)
     image = image.squeeze(0).cpu().detach().numpy()
     label = label.squeeze(0).cpu().detach().numpy()
     prediction = _predict_volume(image, net, patch_size, {"inference": True}, slices_per_batch)
-    return _score_volume(prediction, label, net, classes, voxelspacing)
+    return _score_volume(_postprocess_volume(prediction, classes, postprocess), label, net, classes, voxelspacing)
 
 
-def test_single_volume(image, label, net, classes, patch_size=(256, 256), slices_per_batch=16, voxelspacing=None):
-    """val_2D.py:109-131: the plain networks (``net(input)``).  ``voxelspacing`` as in ``test_single_volume_ours``."""
+def test_single_volume(image, label, net, classes, patch_size=(256, 256), slices_per_batch=16, voxelspacing=None, postprocess=None):
+    """val_2D.py:109-131: the plain networks (``net(input)``).  ``voxelspacing`` and ``postprocess`` as in ``test_single_volume_ours``."""
+    _postprocess_args(postprocess)
     image = image.squeeze(0).cpu().detach().numpy()
     label = label.squeeze(0).cpu().detach().numpy()
     prediction = _predict_volume(image, net, patch_size, {}, slices_per_batch)
-    return _score_volume(prediction, label, net, classes, voxelspacing)
+    return _score_volume(_postprocess_volume(prediction, classes, postprocess), label, net, classes, voxelspacing)

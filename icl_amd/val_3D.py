@@ -446,6 +446,93 @@ def surface_metrics_multiclass(gt, pred, num_classes, voxelspacing=None, toleran
     return [_surface_metrics_host(pred == c, gt == c, sp, tol) for c in range(1, num_classes)]
 
 
+# --------------------------------------------------------------------------------------------------------------------
+# Connected-component post-processing between the arg-max and the scores (kernels/components.h, include/icl_hip.h icl_seg_components)
+# --------------------------------------------------------------------------------------------------------------------
+
+def components_mode() -> str:
+    """``ICL_VAL_COMPONENTS``: ``device`` (default) filters label maps that are on a HIP device with the component kernels, ``host`` forces
+    the scipy path (A/B runs).  Host data always take scipy."""
+    mode = os.environ.get("ICL_VAL_COMPONENTS", "device")
+    if mode not in ("device", "host"):
+        raise ValueError(f"ICL_VAL_COMPONENTS must be 'device' or 'host', got {mode!r}")
+    return mode
+
+
+def _components_args(num_classes, connectivity, keep_largest, min_size):
+    if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or num_classes < 2:
+        raise ValueError(f"num_classes must be an integer >= 2, got {num_classes!r}")
+    if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or connectivity not in (1, 2, 3):
+        raise ValueError(f"connectivity must be 1, 2 or 3, got {connectivity!r}")
+    if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)) or min_size < 0:
+        raise ValueError(f"min_size must be an integer >= 0, got {min_size!r}")
+    return int(num_classes), int(connectivity), bool(keep_largest), int(min_size)
+
+
+def _keep_components_host(m3, num_classes, connectivity, keep_largest, min_size):
+    """The filter on a 3-D numpy map, restated on ``scipy.ndimage.label`` (one labelling per class): int64 map of the kept voxels' classes.
+    scipy numbers the components in raster order of their first voxel, so ``np.argmax`` over their sizes is the largest, and among equal
+    sizes the one that starts first — the kernels' tie rule."""
+    from scipy.ndimage import generate_binary_structure, label
+    structure = generate_binary_structure(3, connectivity)
+    out = np.zeros(m3.shape, dtype=np.int64)
+    for c in range(1, num_classes):
+        lab, n = label(m3 == c, structure)
+        if n == 0:
+            continue
+        sizes = np.bincount(lab.ravel(), minlength=n + 1)
+        sizes[0] = 0
+        keep = sizes >= min_size
+        if keep_largest:
+            largest = np.zeros_like(keep)
+            largest[int(np.argmax(sizes))] = True
+            keep &= largest
+        keep[0] = False
+        out[keep[lab]] = c
+    return out
+
+
+def keep_components(label_map, num_classes, connectivity=1, keep_largest=True, min_size=0):
+    """Connected-component post-processing of a label map: per class c in 1..num_classes-1 the components of ``label_map == c``
+    (``connectivity`` 1 / 2 / 3: 6 / 18 / 26 neighbours) that are kept stay, every other voxel becomes 0.  A component is kept iff (not
+    ``keep_largest`` or it is its class's largest; among equal sizes the one whose first voxel comes first in raster order) and it has at
+    least ``min_size`` voxels.  Labels outside 1..num_classes-1 are background.  The map is 3-D, or 3-D behind leading axes of length 1 (they
+    are squeezed first: such an axis adds no neighbour).  Returns what it was given — a tensor on the same device or a numpy array, same
+    dtype and shape.  A uint8 / bool / int64 tensor on a HIP device is filtered by the component kernels and stays there
+    (``ICL_VAL_COMPONENTS=host`` forces scipy); anything else by scipy on the host."""
+    nc, k, largest, ms = _components_args(num_classes, connectivity, keep_largest, min_size)
+    shape = tuple(label_map.shape)
+    if len(shape) < 3 or any(s != 1 for s in shape[:-3]):
+        raise ValueError(f"keep_components needs a 3-D label map (leading axes of length 1 allowed), got shape {shape}")
+    if torch.is_tensor(label_map):
+        from . import ops
+        if (label_map.is_cuda and components_mode() == "device" and nc <= 256 and label_map.dtype in ops._SEG_DTYPES
+                and 0 < label_map.numel() < 2 ** 31 - 1):
+            return ops.seg_filter_components(label_map, nc, k, largest, ms)
+        host = label_map.cpu().numpy()
+        out = _keep_components_host(host.reshape(shape[-3:]), nc, k, largest, ms)
+        return torch.from_numpy(out.reshape(shape).astype(host.dtype)).to(label_map.device)
+    host = np.asarray(label_map)
+    return _keep_components_host(host.reshape(shape[-3:]), nc, k, largest, ms).reshape(shape).astype(host.dtype)
+
+
+def _postprocess_args(postprocess):
+    """``postprocess=`` of the validation loops -> keyword arguments of ``keep_components``, or None.  ``"largest"``: the largest
+    component of each class under connectivity 1; a dict: any of ``connectivity``, ``keep_largest``, ``min_size``."""
+    if postprocess is None:
+        return None
+    if isinstance(postprocess, str):
+        if postprocess != "largest":
+            raise ValueError(f"postprocess must be None, 'largest' or a dict of keep_components' keywords, got {postprocess!r}")
+        return {"connectivity": 1, "keep_largest": True, "min_size": 0}
+    if not isinstance(postprocess, dict) or set(postprocess) - {"connectivity", "keep_largest", "min_size"}:
+        raise ValueError(f"postprocess must be None, 'largest' or a dict of keep_components' keywords, got {postprocess!r}")
+    kw = {"connectivity": 1, "keep_largest": True, "min_size": 0}
+    kw.update(postprocess)
+    _components_args(2, kw["connectivity"], kw["keep_largest"], kw["min_size"])
+    return kw
+
+
 def _upload_label(label, device):
     """A host label map as a device tensor of a dtype the metric kernels read (uint8 / bool or int64), or None: the numpy path.
     Floating label maps (MONAI's ``LoadImaged`` yields float32 labels to the AMOS loop) are taken when every value is an integer, for
@@ -467,12 +554,15 @@ def _upload_label(label, device):
 
 
 def test_all_case_base(net, net_type, base_dir, test_list="full_test.list", num_classes=4, patch_size=(48, 160, 160),
-                       stride_xy=32, stride_z=24, cases=None, voxelspacing=None):
+                       stride_xy=32, stride_z=24, cases=None, voxelspacing=None, postprocess=None):
     """val_3D.py:100-118.  ``cases`` (iterable of (image, label) numpy pairs) replaces the h5 files when given; otherwise
     the reference's ``{base_dir}/data/{id}.h5`` layout is read with h5py (not installed in the build image).  ``voxelspacing`` (a number
-    or three, the voxel size along the label map's axes) gives HD95 in its units (``cal_metric_multiclass``); None: voxels, as the reference."""
+    or three, the voxel size along the label map's axes) gives HD95 in its units (``cal_metric_multiclass``); None: voxels, as the reference.
+    ``postprocess``: None (the reference), ``"largest"`` or a dict of ``keep_components``' keywords — the predicted label map goes through
+    ``keep_components`` before it is scored (on the device when it is there)."""
     if voxelspacing is not None:
         voxelspacing = _normalize_spacing(voxelspacing)
+    post = _postprocess_args(postprocess)
     if cases is None:
         import h5py  # noqa: F401 — same dependency as the reference
         with open(base_dir + "/{}".format(test_list), "r") as f:
@@ -490,10 +580,14 @@ def test_all_case_base(net, net_type, base_dir, test_list="full_test.list", num_
         gt = _upload_label(label, dev) if on_device else None
         if gt is not None:      # the label map stays on the device; the ground truth goes up once per case
             prediction, _ = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes, want_score=False)
+            if post is not None:
+                prediction = keep_components(prediction, num_classes, **post)
             for i, m in enumerate(cal_metric_multiclass(gt, prediction, num_classes, voxelspacing)):
                 metric_cal[i].append(m)
             continue
         prediction = test_single_case_base(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=num_classes)
+        if post is not None:
+            prediction = keep_components(prediction, num_classes, **post)
         for i in range(1, num_classes):
             metric_cal[i - 1].append(cal_metric(label == i, prediction == i, voxelspacing))
     return metric_cal
@@ -606,14 +700,16 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     return out[(slice(None), slice(None)) + sl]
 
 
-def test_all_case_amos(net, net_type, val_loader, num_classes=4, voxelspacing=None):
+def test_all_case_amos(net, net_type, val_loader, num_classes=4, voxelspacing=None, postprocess=None):
     """val_3D.py:120-137: every validation volume through ``sliding_window_inference(image, (96, 96, 96), 4, net[, inference=True])``,
     argmax over the averaged logits, ``cal_metric`` per foreground class.  The reference wraps the inference in fp16 autocast; the
     HIP kernels compute in fp32 (a strictly more accurate evaluation of the same network).  ``voxelspacing`` (a number or three: the voxel
     size along D, H, W) gives HD95 in its units; the loop scores [1, D, H, W] maps, on which every voxel of a class is a border voxel,
-    and those take the numpy path when a spacing is given (the surface kernels take 3-D maps)."""
+    and those take the numpy path when a spacing is given (the surface kernels take 3-D maps).  ``postprocess``: as in
+    ``test_all_case_base``; the [1, D, H, W] prediction is filtered as the 3-D map behind its leading axis."""
     if voxelspacing is not None:
         voxelspacing = _normalize_spacing(voxelspacing)
+    post = _postprocess_args(postprocess)
     metric_cal = [[] for _ in range(num_classes - 1)]
     net.eval()
     dev = next(net.parameters()).device
@@ -623,12 +719,16 @@ def test_all_case_amos(net, net_type, val_loader, num_classes=4, voxelspacing=No
         logits = sliding_window_inference(image, (96, 96, 96), 4, net, **kw)
         if dev.type == "cuda" and val_metrics_mode() == "device":
             prediction = torch.argmax(logits, dim=1)
+            if post is not None:
+                prediction = keep_components(prediction, num_classes, **post)
             gt = _upload_label(label, dev)
             if gt is not None and _device_metrics_apply(gt, prediction, num_classes):
                 for i, m in enumerate(cal_metric_multiclass(gt, prediction, num_classes, voxelspacing)):
                     metric_cal[i].append(m)
                 continue
         prediction = torch.argmax(logits, dim=1).cpu().numpy()
+        if post is not None:
+            prediction = keep_components(prediction, num_classes, **post)
         label = np.asarray(label.cpu() if torch.is_tensor(label) else label)
         for i in range(1, num_classes):
             metric_cal[i - 1].append(cal_metric(label == i, prediction == i, voxelspacing))

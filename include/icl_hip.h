@@ -536,6 +536,28 @@ int64_t icl_seg_surface_ws_bytes(int n0, int n1, int n2, int num_classes);
 int icl_seg_surface_metrics(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int n0, int n1, int n2, int num_classes, double s0,
                             double s1, double s2, double tolerance, int64_t* counts, double* values, void* ws, void* stream);
 
+/* ---- connected components of a label map, every foreground class in one labelling, and the keep-largest / minimum-size filter that
+ * validation pipelines apply between the arg-max and the scores (csrc/kernels/components.h; scipy.ndimage.label once per class on the host,
+ * restated in icl_amd/val_3D.py keep_components).  map: dense [n0][n1][n2] label map (axis 2 fastest), element size dtype: 1 = uint8,
+ * 8 = int64; class rule as icl_seg_metrics.  Two neighbouring voxels belong to one component when they carry the same class;
+ * connectivity 1 / 2 / 3: 6 / 18 / 26 neighbours (scipy.ndimage.generate_binary_structure(3, connectivity)).
+ * labels: DEVICE int32 [n0 n1 n2]: 0 on background, else 1 + the linear index of the component's first voxel in raster order — a function
+ * of the map alone; two calls are bit-equal.  counts: DEVICE int64 [num_classes - 1][3], row c - 1 = {components of class c, voxels in
+ * the largest, label of the largest (0 when the class is absent)}; among components of equal size the one whose first voxel comes first
+ * counts as the largest (np.argmax over scipy's sizes).
+ * icl_seg_filter_components: out[v] = the class of v when its component is kept, else 0 (labels outside 1..num_classes-1 are background
+ * and come out as 0); a component is kept iff (keep_largest == 0 or it is its class's largest) and its voxel count >= min_size.  out:
+ * DEVICE, the map's element size; it may be the map itself.  counts may be NULL there.
+ * 2 <= num_classes <= 256, n0 n1 n2 <= 2^31 - 2; ws: icl_seg_components_ws_bytes bytes (-1: shape not supported), 12 bytes per voxel plus
+ * about 780 KiB.  5 launches (6 with the filter) whatever the data and num_classes, no synchronisation, no workgroup waits for another.  A bad
+ * argument (also a connectivity outside 1..3, a negative min_size, an element size other than 1 / 8, a null pointer) returns -1 and
+ * launches nothing. */
+int64_t icl_seg_components_ws_bytes(int n0, int n1, int n2, int num_classes);
+int icl_seg_components(const void* map, int dtype, int n0, int n1, int n2, int num_classes, int connectivity, int32_t* labels, int64_t* counts,
+                       void* ws, void* stream);
+int icl_seg_filter_components(const void* map, int dtype, int n0, int n1, int n2, int num_classes, int connectivity, int keep_largest,
+                              int64_t min_size, void* out, int64_t* counts /* may be NULL */, void* ws, void* stream);
+
 /* ---- the 3-D sliding window of the validation loops on the device (csrc/kernels/window.h; val_3D.py:18-73: test_single_case_base's pad,
  * window grid, soft-max, score / count maps, divide, arg-max and crop; val_3D.py:128-132: monai.inferers.sliding_window_inference as the
  * AMOS loop calls it; both restated in icl_amd/val_3D.py).  Volumes are dense with the last axis fastest.  origins: HOST int32 [n][3], the

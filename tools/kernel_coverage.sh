@@ -3,6 +3,9 @@
 # (volume_feed_kernel<1> and <4>, the AMOS data feed, are launched by tests/test_gpu_amos_feed.py: the (6, 6, 5) and (6, 6, 8) sweeps)
 # (the surface-metric kernels of metrics_surface.h — surf_edt_axis2/1/0, surf_reduce, surf_radix<0..5>, surf_finish — are launched by
 #  tests/test_gpu_surface_metrics.py)
+# (the connected-component kernels of components.h — cc_tile_kernel<uint8 | int64, 1 | 2 | 3>, cc_merge_kernel<uint8 | int64, 1 | 2 | 3>,
+#  cc_flatten_kernel, cc_reduce_kernel<uint8 | int64>, cc_finish_kernel, cc_filter_kernel<uint8 | int64> — are launched by
+#  tests/test_gpu_components.py: test_case and test_scattered_prediction_64x80x72 run both element sizes under each connectivity)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/cov

@@ -2554,24 +2554,28 @@ struct SegWs {
   int64_t zero_bytes, total;
 };
 
-inline int64_t seg_align(int64_t b) { return (b + 255) / 256 * 256; }
+// carves a workspace into buffers that start at multiples of 256 bytes; a null base only adds the sizes up (the *_ws_bytes queries)
+struct WsCarver {
+  char* base; int64_t off;
+  template <typename T>
+  T* take(int64_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) / 256 * 256; return (T*)p; }
+};
 
 SegWs seg_layout(char* base, int n0, int n1, int n2, int nc) {
   SegWs w{};
   const int64_t v = (int64_t)n0 * n1 * n2;
   const int64_t nbins = (int64_t)(n0 - 1) * (n0 - 1) + (int64_t)(n1 - 1) * (n1 - 1) + (int64_t)(n2 - 1) * (n2 - 1) + 1;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += seg_align(bytes); return p; };
-  w.cnt = (unsigned*)take((int64_t)nc * icl::kSegCnt * 4);
-  w.flags = (unsigned*)take((int64_t)2 * nc * (n0 + n1 + n2) * 4);
-  w.hist = (unsigned*)take(nbins * 4);
-  w.zero_bytes = off;                       // counters, presence flags and histogram start at zero
-  w.box = (int*)take((int64_t)nc * 16 * 4);
-  w.bp = (unsigned char*)take(v);
-  w.bg = (unsigned char*)take(v);
-  w.da = (int*)take(v * 4);
-  w.db = (int*)take(v * 4);
-  w.total = off;
+  WsCarver c{base, 0};
+  w.cnt = c.take<unsigned>((int64_t)nc * icl::kSegCnt * 4);
+  w.flags = c.take<unsigned>((int64_t)2 * nc * (n0 + n1 + n2) * 4);
+  w.hist = c.take<unsigned>(nbins * 4);
+  w.zero_bytes = c.off;                     // counters, presence flags and histogram start at zero
+  w.box = c.take<int>((int64_t)nc * 16 * 4);
+  w.bp = c.take<unsigned char>(v);
+  w.bg = c.take<unsigned char>(v);
+  w.da = c.take<int>(v * 4);
+  w.db = c.take<int>(v * 4);
+  w.total = c.off;
   return w;
 }
 
@@ -2582,20 +2586,30 @@ bool seg_shape_ok(int n0, int n1, int n2, int nc) {
   return v <= 0x7fffffffLL && nbins < (int64_t)icl::kSegInf;      // 32-bit counters and squared distances
 }
 
-template <typename TP, typename TG>
-void seg_border_launch(const void* pred, const void* gt, const SegWs& w, int n0, int n1, int n2, int nc, int all_border, hipStream_t st) {
-  ICL_LAUNCH((icl::seg_border_kernel<TP, TG>), dim3(grid_for((long)n0 * n1 * n2, 256)), dim3(256), 0, st, (const TP*)pred, (const TG*)gt, w.bp,
-             w.bg, w.cnt, w.flags, n0, n1, n2, nc, all_border);
+// the ABI's label element size -> the element type: f(T()) with T = uint8_t (1: uint8 / bool) or long long (8: int64); false, and no
+// call, for any other size
+template <typename F>
+bool seg_label_dispatch(int elem_size, F&& f) {
+  switch (elem_size) {
+    case 1: f(uint8_t()); return true;
+    case 8: f((long long)0); return true;
+    default: return false;
+  }
 }
 
-template <typename TP>
-int seg_border_dispatch_gt(const void* pred, const void* gt, int gt_dtype, const SegWs& w, int n0, int n1, int n2, int nc, int all_border,
-                           hipStream_t st) {
-  switch (gt_dtype) {
-    case 1: seg_border_launch<TP, uint8_t>(pred, gt, w, n0, n1, n2, nc, all_border, st); return 0;
-    case 8: seg_border_launch<TP, long long>(pred, gt, w, n0, n1, n2, nc, all_border, st); return 0;
-    default: return -1;
-  }
+// the border stage both metric entry points start with; false (nothing launched) for a label element size that is not 1 or 8
+bool seg_border_launch(const void* pred, int pred_dtype, const void* gt, int gt_dtype, unsigned char* bp, unsigned char* bg, unsigned* cnt,
+                       unsigned* flags, int n0, int n1, int n2, int nc, int all_border, hipStream_t st) {
+  bool ok = false;
+  seg_label_dispatch(pred_dtype, [&](auto tp) {
+    ok = seg_label_dispatch(gt_dtype, [&](auto tg) {
+      using TP = decltype(tp);
+      using TG = decltype(tg);
+      ICL_LAUNCH((icl::seg_border_kernel<TP, TG>), dim3(grid_for((long)n0 * n1 * n2, 256)), dim3(256), 0, st, (const TP*)pred, (const TG*)gt,
+                 bp, bg, cnt, flags, n0, n1, n2, nc, all_border);
+    });
+  });
+  return ok;
 }
 
 }  // namespace
@@ -2616,13 +2630,8 @@ int icl_seg_metrics(const void* pred, int pred_dtype, const void* gt, int gt_dty
   hipStream_t st = (hipStream_t)stream;
   const SegWs w = seg_layout((char*)ws, n0, n1, n2, nc);
   ICL_MEMSET_ASYNC(ws, 0, (size_t)w.zero_bytes, st);
-  int rc;
-  switch (pred_dtype) {
-    case 1: rc = seg_border_dispatch_gt<uint8_t>(pred, gt, gt_dtype, w, n0, n1, n2, nc, all_border ? 1 : 0, st); break;
-    case 8: rc = seg_border_dispatch_gt<long long>(pred, gt, gt_dtype, w, n0, n1, n2, nc, all_border ? 1 : 0, st); break;
-    default: rc = -1;
-  }
-  if (rc) return fail(-1, "seg_metrics: label element size must be 1 (uint8) or 8 (int64)");
+  if (!seg_border_launch(pred, pred_dtype, gt, gt_dtype, w.bp, w.bg, w.cnt, w.flags, n0, n1, n2, nc, all_border ? 1 : 0, st))
+    return fail(-1, "seg_metrics: label element size must be 1 (uint8) or 8 (int64)");
   if (int e = check_launch("seg_border")) return e;
   ICL_LAUNCH(icl::seg_bbox_kernel, dim3(nc), dim3(256), 0, st, (const unsigned*)w.cnt, (const unsigned*)w.flags, w.box, n0, n1, n2, nc);
   if (int e = check_launch("seg_bbox")) return e;
@@ -2656,24 +2665,23 @@ struct SurfWs {
 SurfWs surf_layout(char* base, int n0, int n1, int n2, int nc) {
   SurfWs w{};
   const int64_t v = (int64_t)n0 * n1 * n2;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += seg_align(bytes); return p; };
-  w.cnt = (unsigned*)take((int64_t)nc * icl::kSegCnt * 4);
-  w.flags = (unsigned*)take((int64_t)2 * nc * (n0 + n1 + n2) * 4);
-  w.hist = (unsigned*)take((int64_t)icl::kSurfPasses * 2 * icl::kSurfBins * 4);
-  w.zero_bytes = off;                       // counters, presence flags and histograms start at zero
-  w.box = (int*)take((int64_t)nc * 16 * 4);
-  w.state = (icl::SurfSel*)take((int64_t)icl::kSurfPasses * sizeof(icl::SurfSel));
-  w.psum = (double*)take((int64_t)2 * icl::kSurfMaxParts * 8);
-  w.pmax = (double*)take((int64_t)2 * icl::kSurfMaxParts * 8);
-  w.pcnt = (unsigned*)take((int64_t)2 * icl::kSurfMaxParts * 4);
-  w.bp = (unsigned char*)take(v);
-  w.bg = (unsigned char*)take(v);
-  w.ta = (double*)take(v * 8);              // axis-2 pass: F0 x F1 x Q2 <= V
-  w.tb = (double*)take(v * 8);              // axis-1 pass: F0 x Q1 x Q2 <= V
-  w.dense[0] = (double*)take(v * 8);        // squared distances of dP to dG over the box of dP
-  w.dense[1] = (double*)take(v * 8);        // ... of dG to dP over the box of dG
-  w.total = off;
+  WsCarver c{base, 0};
+  w.cnt = c.take<unsigned>((int64_t)nc * icl::kSegCnt * 4);
+  w.flags = c.take<unsigned>((int64_t)2 * nc * (n0 + n1 + n2) * 4);
+  w.hist = c.take<unsigned>((int64_t)icl::kSurfPasses * 2 * icl::kSurfBins * 4);
+  w.zero_bytes = c.off;                     // counters, presence flags and histograms start at zero
+  w.box = c.take<int>((int64_t)nc * 16 * 4);
+  w.state = c.take<icl::SurfSel>((int64_t)icl::kSurfPasses * sizeof(icl::SurfSel));
+  w.psum = c.take<double>((int64_t)2 * icl::kSurfMaxParts * 8);
+  w.pmax = c.take<double>((int64_t)2 * icl::kSurfMaxParts * 8);
+  w.pcnt = c.take<unsigned>((int64_t)2 * icl::kSurfMaxParts * 4);
+  w.bp = c.take<unsigned char>(v);
+  w.bg = c.take<unsigned char>(v);
+  w.ta = c.take<double>(v * 8);             // axis-2 pass: F0 x F1 x Q2 <= V
+  w.tb = c.take<double>(v * 8);             // axis-1 pass: F0 x Q1 x Q2 <= V
+  w.dense[0] = c.take<double>(v * 8);       // squared distances of dP to dG over the box of dP
+  w.dense[1] = c.take<double>(v * 8);       // ... of dG to dP over the box of dG
+  w.total = c.off;
   return w;
 }
 
@@ -2715,10 +2723,8 @@ int icl_seg_surface_metrics(const void* pred, int pred_dtype, const void* gt, in
   const SurfWs w = surf_layout((char*)ws, n0, n1, n2, nc);
   const double tau2 = tolerance * tolerance;
   ICL_MEMSET_ASYNC(ws, 0, (size_t)w.zero_bytes, st);
-  SegWs first{};      // the first stage is the integer path's: same kernels, same instantiations
-  first.cnt = w.cnt; first.flags = w.flags; first.bp = w.bp; first.bg = w.bg;
-  if (pred_dtype == 1) seg_border_dispatch_gt<uint8_t>(pred, gt, gt_dtype, first, n0, n1, n2, nc, 0, st);
-  else seg_border_dispatch_gt<long long>(pred, gt, gt_dtype, first, n0, n1, n2, nc, 0, st);
+  // the first stage is the integer path's: same kernels, same instantiations
+  (void)seg_border_launch(pred, pred_dtype, gt, gt_dtype, w.bp, w.bg, w.cnt, w.flags, n0, n1, n2, nc, 0, st);      // sizes checked above
   if (int e = check_launch("seg_border")) return e;
   ICL_LAUNCH(icl::seg_bbox_kernel, dim3(nc), dim3(256), 0, st, (const unsigned*)w.cnt, (const unsigned*)w.flags, w.box, n0, n1, n2, nc);
   if (int e = check_launch("seg_bbox")) return e;
@@ -2763,15 +2769,14 @@ struct CcWs {
 CcWs cc_layout(char* base, int n0, int n1, int n2) {
   CcWs w{};
   const int64_t v = (int64_t)n0 * n1 * n2;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base ? base + off : nullptr; off += seg_align(bytes); return p; };
-  w.parent = (int*)take(v * 4);
-  w.size = (int*)take(v * 4);
-  w.labels = (int*)take(v * 4);             // the filter's labels (icl_seg_components writes the caller's)
-  w.pkey = (unsigned long long*)take((int64_t)icl::kCcMaxParts * icl::kSegMaxClasses * 8);
-  w.pcnt = (int*)take((int64_t)icl::kCcMaxParts * icl::kSegMaxClasses * 4);
-  w.rec = (long long*)take((int64_t)icl::kSegMaxClasses * icl::kCcRec * 8);
-  w.total = off;
+  WsCarver c{base, 0};
+  w.parent = c.take<int>(v * 4);
+  w.size = c.take<int>(v * 4);
+  w.labels = c.take<int>(v * 4);            // the filter's labels (icl_seg_components writes the caller's)
+  w.pkey = c.take<unsigned long long>((int64_t)icl::kCcMaxParts * icl::kSegMaxClasses * 8);
+  w.pcnt = c.take<int>((int64_t)icl::kCcMaxParts * icl::kSegMaxClasses * 4);
+  w.rec = c.take<long long>((int64_t)icl::kSegMaxClasses * icl::kCcRec * 8);
+  w.total = c.off;
   return w;
 }
 
@@ -2830,8 +2835,9 @@ int icl_seg_components(const void* map, int dtype, int n0, int n1, int n2, int n
   if (!labels || !counts) return fail(-1, "seg_components: labels and counts must not be null");
   hipStream_t st = (hipStream_t)stream;
   const CcWs w = cc_layout((char*)ws, n0, n1, n2);
-  if (dtype == 1) cc_label_dispatch<uint8_t>(map, w, labels, (long long*)counts, n0, n1, n2, num_classes, connectivity, st);
-  else cc_label_dispatch<long long>(map, w, labels, (long long*)counts, n0, n1, n2, num_classes, connectivity, st);
+  seg_label_dispatch(dtype, [&](auto t) {
+    cc_label_dispatch<decltype(t)>(map, w, labels, (long long*)counts, n0, n1, n2, num_classes, connectivity, st);
+  });
   return check_launch("cc_tile / cc_merge / cc_flatten / cc_reduce / cc_finish");
 }
 
@@ -2844,15 +2850,12 @@ int icl_seg_filter_components(const void* map, int dtype, int n0, int n1, int n2
   const CcWs w = cc_layout((char*)ws, n0, n1, n2);
   const long v = (long)n0 * n1 * n2;
   const dim3 grid(grid_for(v, 256));
-  if (dtype == 1) {
-    cc_label_dispatch<uint8_t>(map, w, w.labels, (long long*)counts, n0, n1, n2, num_classes, connectivity, st);
-    ICL_LAUNCH((icl::cc_filter_kernel<uint8_t>), grid, dim3(256), 0, st, (const uint8_t*)map, (const int*)w.labels, (const int*)w.size,
-               (const long long*)w.rec, (uint8_t*)out, v, num_classes, keep_largest ? 1 : 0, (long long)min_size);
-  } else {
-    cc_label_dispatch<long long>(map, w, w.labels, (long long*)counts, n0, n1, n2, num_classes, connectivity, st);
-    ICL_LAUNCH((icl::cc_filter_kernel<long long>), grid, dim3(256), 0, st, (const long long*)map, (const int*)w.labels, (const int*)w.size,
-               (const long long*)w.rec, (long long*)out, v, num_classes, keep_largest ? 1 : 0, (long long)min_size);
-  }
+  seg_label_dispatch(dtype, [&](auto t) {
+    using T = decltype(t);
+    cc_label_dispatch<T>(map, w, w.labels, (long long*)counts, n0, n1, n2, num_classes, connectivity, st);
+    ICL_LAUNCH((icl::cc_filter_kernel<T>), grid, dim3(256), 0, st, (const T*)map, (const int*)w.labels, (const int*)w.size,
+               (const long long*)w.rec, (T*)out, v, num_classes, keep_largest ? 1 : 0, (long long)min_size);
+  });
   return check_launch("cc_tile / cc_merge / cc_flatten / cc_reduce / cc_finish / cc_filter");
 }
 

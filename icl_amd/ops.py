@@ -2575,32 +2575,46 @@ def seg_metrics_shape(t: torch.Tensor):
     return shape[-3], shape[-2], shape[-1], int(len(shape) > 3)
 
 
+def _seg_label_maps(who, *maps, exactly_3d=False):
+    """What every ``seg_*`` entry does with its label maps (one, or pred and gt) first: the checks of shape, dtype and device, then
+    (contiguous maps, (n0, n1, n2, all_border)).  ``who`` starts every message.  The entry's own argument checks follow, then
+    ``_seg_workspace``."""
+    first = maps[0]
+    if len(maps) == 2 and first.shape != maps[1].shape:
+        raise ValueError(f"{who}: shapes differ {tuple(first.shape)} vs {tuple(maps[1].shape)}")
+    geo = seg_metrics_shape(first)
+    if exactly_3d and first.dim() != 3:
+        raise ValueError(f"{who}: needs a 3-D label map, got {tuple(first.shape)}")
+    if geo is None:
+        raise ValueError(f"{who}: needs a 3-D label map (leading axes of length 1 allowed), got {tuple(first.shape)}")
+    for t in maps:
+        if t.dtype not in _SEG_DTYPES:
+            raise TypeError(f"{who}: unsupported label dtype {t.dtype}")
+        if not t.is_cuda and not _lib.host_pointers_ok():
+            raise RuntimeError("icl_amd: HIP kernels need device tensors (no CPU fallback)")
+    if len(maps) == 2 and first.device != maps[1].device:
+        raise ValueError(f"{who}: pred and gt on different devices")
+    return [t.contiguous() for t in maps], geo
+
+
+def _seg_workspace(who, ws_bytes, geo, num_classes, device):
+    """The workspace of one ``seg_*`` call, sized by the entry's ``*_ws_bytes``, which also judges the shape and the class count."""
+    nbytes = ws_bytes(*geo[:3], int(num_classes))
+    if nbytes < 0:
+        raise ValueError(f"{who}: shape {geo[:3]} / num_classes {num_classes} not supported (2 <= num_classes <= 256)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def seg_metrics(pred: torch.Tensor, gt: torch.Tensor, num_classes: int) -> torch.Tensor:
     """Per-class integer records of Dice and HD95 (include/icl_hip.h icl_seg_metrics): int64 [num_classes - 1, 6] on the device of the
     maps, row c - 1 = (|P|, |G|, |P & G|, n, s0, s1) for P = pred == c, G = gt == c; n = number of surface voxels of both, s0 / s1 the
     squared surface distances at ranks floor(0.95 (n - 1)) and the next one (-1 when P or G is empty).  Asynchronous on the current
     stream; the maps stay where they are.  Label dtypes: uint8 / bool (h5 labels) and int64 (argmax); pred and gt may differ."""
-    if pred.shape != gt.shape:
-        raise ValueError(f"seg_metrics: shapes differ {tuple(pred.shape)} vs {tuple(gt.shape)}")
-    geo = seg_metrics_shape(pred)
-    if geo is None:
-        raise ValueError(f"seg_metrics: needs a 3-D label map (leading axes of length 1 allowed), got {tuple(pred.shape)}")
-    for t in (pred, gt):
-        if t.dtype not in _SEG_DTYPES:
-            raise TypeError(f"seg_metrics: unsupported label dtype {t.dtype}")
-        if not t.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("icl_amd: HIP kernels need device tensors (no CPU fallback)")
-    if pred.device != gt.device:
-        raise ValueError("seg_metrics: pred and gt on different devices")
-    n0, n1, n2, all_border = geo
-    pred, gt = pred.contiguous(), gt.contiguous()
     L = _lib.lib()
-    nbytes = L.icl_seg_metrics_ws_bytes(n0, n1, n2, int(num_classes))
-    if nbytes < 0:
-        raise ValueError(f"seg_metrics: shape {(n0, n1, n2)} / num_classes {num_classes} not supported (2 <= num_classes <= 256)")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    (pred, gt), geo = _seg_label_maps("seg_metrics", pred, gt)
+    ws = _seg_workspace("seg_metrics", L.icl_seg_metrics_ws_bytes, geo, num_classes, pred.device)
     out = torch.empty((int(num_classes) - 1, 6), dtype=torch.int64, device=pred.device)
-    _lib.check(L.icl_seg_metrics(_ptr(pred), _SEG_DTYPES[pred.dtype], _ptr(gt), _SEG_DTYPES[gt.dtype], n0, n1, n2, int(num_classes), all_border,
+    _lib.check(L.icl_seg_metrics(_ptr(pred), _SEG_DTYPES[pred.dtype], _ptr(gt), _SEG_DTYPES[gt.dtype], *geo[:3], int(num_classes), geo[3],
                                  _ptr(out), _ptr(ws), _stream(pred)), "seg_metrics")
     return out
 
@@ -2612,17 +2626,7 @@ def seg_surface_metrics(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, 
     of both directions' squared distances, max d^2 P -> G, max d^2 G -> P, sum d P -> G, sum d G -> P), -1 when P or G is empty.
     ``spacing``: three finite positive numbers (the voxel size along the three axes).  Always the floating-point path, also for spacing
     (1, 1, 1).  Asynchronous on the current stream.  The maps are exactly 3-D; label dtypes as ``seg_metrics``."""
-    if pred.shape != gt.shape:
-        raise ValueError(f"seg_surface_metrics: shapes differ {tuple(pred.shape)} vs {tuple(gt.shape)}")
-    if pred.dim() != 3:
-        raise ValueError(f"seg_surface_metrics: needs a 3-D label map, got {tuple(pred.shape)}")
-    for t in (pred, gt):
-        if t.dtype not in _SEG_DTYPES:
-            raise TypeError(f"seg_surface_metrics: unsupported label dtype {t.dtype}")
-        if not t.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("icl_amd: HIP kernels need device tensors (no CPU fallback)")
-    if pred.device != gt.device:
-        raise ValueError("seg_surface_metrics: pred and gt on different devices")
+    (pred, gt), (n0, n1, n2, _) = _seg_label_maps("seg_surface_metrics", pred, gt, exactly_3d=True)
     try:
         sp = [float(v) for v in spacing]
     except TypeError:
@@ -2632,13 +2636,8 @@ def seg_surface_metrics(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, 
     tol = float(tolerance)
     if not (math.isfinite(tol) and tol >= 0):
         raise ValueError(f"seg_surface_metrics: tolerance must be finite and not negative, got {tolerance!r}")
-    n0, n1, n2 = (int(v) for v in pred.shape)
-    pred, gt = pred.contiguous(), gt.contiguous()
     L = _lib.lib()
-    nbytes = L.icl_seg_surface_ws_bytes(n0, n1, n2, int(num_classes))
-    if nbytes < 0:
-        raise ValueError(f"seg_surface_metrics: shape {(n0, n1, n2)} / num_classes {num_classes} not supported (2 <= num_classes <= 256)")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    ws = _seg_workspace("seg_surface_metrics", L.icl_seg_surface_ws_bytes, (n0, n1, n2), num_classes, pred.device)
     counts = torch.empty((int(num_classes) - 1, 7), dtype=torch.int64, device=pred.device)
     values = torch.empty((int(num_classes) - 1, 6), dtype=torch.float64, device=pred.device)
     _lib.check(L.icl_seg_surface_metrics(_ptr(pred), _SEG_DTYPES[pred.dtype], _ptr(gt), _SEG_DTYPES[gt.dtype], n0, n1, n2, int(num_classes),
@@ -2648,21 +2647,10 @@ def seg_surface_metrics(pred: torch.Tensor, gt: torch.Tensor, num_classes: int, 
 
 def _seg_components_args(who, label_map, num_classes, connectivity):
     """The checks ``seg_components`` and ``seg_filter_components`` share: (contiguous 3-D view, n0, n1, n2, workspace)."""
-    geo = seg_metrics_shape(label_map)
-    if geo is None:
-        raise ValueError(f"{who}: needs a 3-D label map (leading axes of length 1 allowed), got {tuple(label_map.shape)}")
-    if label_map.dtype not in _SEG_DTYPES:
-        raise TypeError(f"{who}: unsupported label dtype {label_map.dtype}")
-    if not label_map.is_cuda and not _lib.host_pointers_ok():
-        raise RuntimeError("icl_amd: HIP kernels need device tensors (no CPU fallback)")
+    (m,), (n0, n1, n2, _) = _seg_label_maps(who, label_map)
     if isinstance(connectivity, bool) or not isinstance(connectivity, int) or connectivity not in (1, 2, 3):
         raise ValueError(f"{who}: connectivity must be 1, 2 or 3, got {connectivity!r}")
-    n0, n1, n2 = geo[:3]
-    nbytes = _lib.lib().icl_seg_components_ws_bytes(n0, n1, n2, int(num_classes))
-    if nbytes < 0:
-        raise ValueError(f"{who}: shape {(n0, n1, n2)} / num_classes {num_classes} not supported (2 <= num_classes <= 256)")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=label_map.device)
-    return label_map.contiguous(), n0, n1, n2, ws
+    return m, n0, n1, n2, _seg_workspace(who, _lib.lib().icl_seg_components_ws_bytes, (n0, n1, n2), num_classes, m.device)
 
 
 def seg_components(label_map: torch.Tensor, num_classes: int, connectivity: int = 1):

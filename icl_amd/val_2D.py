@@ -13,41 +13,25 @@ the metric kernels when the net is on a HIP device (``val_3D.cal_metric_multicla
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 from scipy.ndimage import zoom
 
 from .dataloaders.dataset import resize_slices
-from .val_3D import (_normalize_spacing, _postprocess_args, _upload_label, binary_dice, binary_hd95, cal_metric_multiclass, keep_components,
-                     val_metrics_mode)
+from .val_3D import _env_choice, _normalize_spacing, _postprocess_args, _score_prediction, cal_metric
+from .val_3D import keep_components  # noqa: F401 — the filter of ``postprocess=``: reachable from here as before
 
 
 def calculate_metric_percase(pred, gt, voxelspacing=None):
-    """val_2D.py:10-22 (binarises its arguments like the reference).  ``voxelspacing``: HD95 in its units (``val_3D.binary_hd95``)."""
-    pred = np.asarray(pred) > 0
-    gt = np.asarray(gt) > 0
-    if voxelspacing is not None:
-        voxelspacing = _normalize_spacing(voxelspacing)
-    if pred.sum() > 0 and gt.sum() > 0:
-        if voxelspacing is not None:
-            return binary_dice(pred, gt), binary_hd95(pred, gt, voxelspacing)
-        return binary_dice(pred, gt), binary_hd95(pred, gt)
-    if pred.sum() > 0 and gt.sum() == 0:
-        return 0, 373.128664
-    if pred.sum() == 0 and gt.sum() > 0:
-        return 0, 373.128664
-    return 1, 0
+    """val_2D.py:10-22 (binarises its arguments like the reference): ``val_3D.cal_metric``, which takes the ground truth first and holds
+    the empty-mask conventions.  ``voxelspacing``: HD95 in its units (``val_3D.binary_hd95``)."""
+    return cal_metric(gt, pred, voxelspacing)
 
 
 def val_resize_mode() -> str:
     """``ICL_VAL_RESIZE``: ``device`` (default) resizes the slices and the arg-max maps of a net on a HIP device with the slice-resize
     kernel, ``host`` forces scipy's ``zoom`` on the host (A/B runs).  CPU nets always take the host path."""
-    mode = os.environ.get("ICL_VAL_RESIZE", "device")
-    if mode not in ("device", "host"):
-        raise ValueError(f"ICL_VAL_RESIZE must be 'device' or 'host', got {mode!r}")
-    return mode
+    return _env_choice("ICL_VAL_RESIZE", ("device", "host"))
 
 
 def _zoom_gives(n_in, n_out):
@@ -80,29 +64,15 @@ def _predict_volume(image, net, patch_size, inference_kw, slices_per_batch):
     return prediction
 
 
-def _score_volume(prediction, label, net, classes, voxelspacing=None):
-    """``[calculate_metric_percase(prediction == i, label == i) for i in 1..classes-1]``; with the net on a HIP device both maps go up
-    once (a device prediction stays where it is) and every class is scored by the metric kernels (the same values and types: Dice and
-    HD95 are symmetric in their arguments).  ``prediction``: a numpy array or a device tensor.  ``voxelspacing``: a number, or three for
-    the [slices, H, W] volume — HD95 in its units (``cal_metric_multiclass``)."""
+def _score_volume(prediction, label, net, classes, voxelspacing=None, postprocess=None):
+    """``[calculate_metric_percase(prediction == i, label == i) for i in 1..classes-1]`` of the stacked [slices, H, W] prediction (a numpy
+    array or a device tensor), which goes through ``val_3D.keep_components`` as one 3-D map first when ``postprocess`` says so: the
+    scoring step of ``val_3D`` (``_score_prediction``) — on the metric kernels with the net on a HIP device and a label map of the
+    prediction's shape.  ``voxelspacing``: a number, or three for the [slices, H, W] volume — HD95 in its units."""
     if voxelspacing is not None:
         voxelspacing = _normalize_spacing(voxelspacing)
-    dev = next(net.parameters()).device
-    if dev.type == "cuda" and val_metrics_mode() == "device" and 2 <= classes <= 256:
-        gt = _upload_label(label, dev)
-        if gt is not None and gt.shape == prediction.shape:
-            return cal_metric_multiclass(gt, prediction if torch.is_tensor(prediction) else torch.from_numpy(prediction).to(dev), classes,
-                                         voxelspacing)
-    if torch.is_tensor(prediction):
-        prediction = prediction.cpu().numpy()
-    return [calculate_metric_percase(prediction == i, label == i, voxelspacing) for i in range(1, classes)]
-
-
-def _postprocess_volume(prediction, classes, postprocess):
-    """``postprocess=`` of the two loops: the stacked [slices, H, W] prediction (numpy array or device tensor) through
-    ``val_3D.keep_components`` as one 3-D map; None leaves it as it is."""
-    post = _postprocess_args(postprocess)
-    return prediction if post is None else keep_components(prediction, classes, **post)
+    return _score_prediction(prediction, label, classes, next(net.parameters()).device, voxelspacing, _postprocess_args(postprocess),
+                             also=lambda gt, pred, _: gt.shape == pred.shape)
 
 
 def test_single_volume_ours(image, label, net, writer=None, iter_num=0, classes=4, patch_size=(224, 224), slices_per_batch=16,
@@ -115,7 +85,7 @@ def test_single_volume_ours(image, label, net, writer=None, iter_num=0, classes=
     image = image.squeeze(0).cpu().detach().numpy()
     label = label.squeeze(0).cpu().detach().numpy()
     prediction = _predict_volume(image, net, patch_size, {"inference": True}, slices_per_batch)
-    return _score_volume(_postprocess_volume(prediction, classes, postprocess), label, net, classes, voxelspacing)
+    return _score_volume(prediction, label, net, classes, voxelspacing, postprocess)
 
 
 def test_single_volume(image, label, net, classes, patch_size=(256, 256), slices_per_batch=16, voxelspacing=None, postprocess=None):
@@ -124,4 +94,4 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), slices
     image = image.squeeze(0).cpu().detach().numpy()
     label = label.squeeze(0).cpu().detach().numpy()
     prediction = _predict_volume(image, net, patch_size, {}, slices_per_batch)
-    return _score_volume(_postprocess_volume(prediction, classes, postprocess), label, net, classes, voxelspacing)
+    return _score_volume(prediction, label, net, classes, voxelspacing, postprocess)

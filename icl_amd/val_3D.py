@@ -24,14 +24,19 @@ import numpy as np
 import torch
 
 
+def _env_choice(name, allowed):
+    """The environment variable ``name``: one of the two words ``allowed``, the first when it is not set; anything else is a ValueError."""
+    mode = os.environ.get(name, allowed[0])
+    if mode not in allowed:
+        raise ValueError(f"{name} must be {allowed[0]!r} or {allowed[1]!r}, got {mode!r}")
+    return mode
+
+
 def val_windows_mode() -> str:
     """``ICL_VAL_WINDOWS``: ``device`` (default) runs the sliding window of both 3-D validation loops — window gather, soft-max and
     accumulation, division, arg-max and crop — on the window kernels (csrc/kernels/window.h) when the volume is an fp32 tensor on a HIP
     device; ``aten`` forces the ATen loop (A/B runs).  Host tensors and other dtypes always take the ATen loop."""
-    mode = os.environ.get("ICL_VAL_WINDOWS", "device")
-    if mode not in ("device", "aten"):
-        raise ValueError(f"ICL_VAL_WINDOWS must be 'device' or 'aten', got {mode!r}")
-    return mode
+    return _env_choice("ICL_VAL_WINDOWS", ("device", "aten"))
 
 
 _WINDOW_MAX_CLASSES = 256      # icl_window_accumulate / icl_window_finalize
@@ -83,32 +88,96 @@ def test_single_case_base(net, net_type, image, stride_xy, stride_z, patch_size,
     return label_map.cpu().numpy()
 
 
-def _single_case_kernels(net, icl, vol, pads, starts, patch_size, num_classes, windows_per_batch, imp, want_score):
-    """The window loop of ``_single_case_on_device`` on the window kernels: vol fp32 [W,H,D] on a HIP device (unpadded; the gather
-    zero-fills), ``starts`` in the padded frame.  Returns ((label map, cropped score or None), None) — or (None, logits of the first
-    batch) when the network's output is not fp32 [n, num_classes, *patch_size]: the caller's ATen loop then takes over with that
-    batch already computed, so the network sees every batch once."""
+def _fits_brats(num_classes, roi):
+    """When the BraTS loop stays on the window kernels: fp32 logits of exactly [n, num_classes, *roi]."""
+    roi = tuple(int(r) for r in roi)
+    return lambda pred, n: tuple(pred.shape) == (n, num_classes, *roi) and pred.dtype == torch.float32
+
+
+def _fits_amos(roi, device):
+    """When the AMOS loop stays on the window kernels: a tensor [n, 1 <= C <= 256, *roi] of any dtype on ``device`` (the loop casts it)."""
+    return lambda pred, n: (torch.is_tensor(pred) and pred.dim() == 5 and pred.shape[0] == n and list(pred.shape[2:]) == list(roi)
+                            and 1 <= pred.shape[1] <= _WINDOW_MAX_CLASSES and pred.device == device)
+
+
+def _run_windows(vols, roi, pads, psize, starts, per_forward, forward, imp, softmax, want, kernels, fits, num_classes=None):
+    """The sliding window of both validation loops, and the only place that walks window origins.  ``vols`` fp32 [B, Cin, s0, s1, s2],
+    unpadded; ``pads`` the (before, after) zero padding per axis that brings it to the extent ``psize``; ``starts`` the windows as (batch
+    index, o0, o1, o2) in the padded frame, in loop order, ``per_forward`` of them per ``forward(win)`` (win [n, Cin, *roi]); ``imp`` the
+    importance map [*roi] or None.  A window adds ``softmax(pred, 1)`` (``softmax``) or ``pred.float()`` to the score map — times ``imp``
+    when there is one — and 1, or ``imp``, to the weight map; then come score / weight, the arg-max over the classes and the crop to the
+    volume.  ``want``: ``"label"``, ``"quotients"`` or ``"both"``.  Returns ((label maps int64 [B, *size] or None, quotients fp32
+    [B, C, *size] or None), handed).
+
+    ``kernels``: gather, accumulate and finalize on the window kernels (``ops.window_*``: a launch takes at most 16 windows, all of one
+    volume; the gather zero-fills, so the volume is not padded), else in ATen — the same adds in the same order.  The kernel form gives
+    up when ``fits(pred, n)``, the caller's rule, is false for the prediction of the FIRST batch: the loop goes on in ATen with that
+    prediction — ``handed``, None when there was no hand-over — so ``forward`` sees every batch once.  ``num_classes``: the channels of the score map; None takes them from the first prediction.  The kernel form
+    computes only what is wanted (quotients alone where nothing is cropped: divided in place); the ATen form has the quotients anyway
+    and returns them whatever ``want`` says."""
     from . import ops
-    size = tuple(vol.shape)
+    b, cin = vols.shape[:2]
+    size, roi, psize = tuple(vols.shape[2:]), tuple(int(r) for r in roi), tuple(psize)
     a = tuple(p[0] for p in pads)
-    psize = tuple(n + p[0] + p[1] for n, p in zip(size, pads))
-    score = cnt = None
-    for i in range(0, len(starts), windows_per_batch):
-        chunk = starts[i:i + windows_per_batch]
-        batch = torch.empty((len(chunk), 1, *patch_size), dtype=torch.float32, device=vol.device)
-        for k in range(0, len(chunk), _WINDOW_MAX_BATCH):
-            ops.window_gather(vol.unsqueeze(0), chunk[k:k + _WINDOW_MAX_BATCH], patch_size, a, psize, out=batch[k:k + _WINDOW_MAX_BATCH])
-        logits = net(batch, inference=True) if icl else net(batch)
+    r0, r1, r2 = roi
+
+    def padded(v):
+        return torch.nn.functional.pad(v, [n for p, q in reversed(pads) for n in (p, q)]) if any(p + q for p, q in pads) else v
+    vols = vols.contiguous() if kernels else padded(vols)
+    score = weight = handed = None
+    for i in range(0, len(starts), per_forward):
+        chunk = starts[i:i + per_forward]
+        if kernels:
+            runs, k = [], 0      # runs of windows of one volume, at most 16 each: one launch per run
+            while k < len(chunk):
+                e = k + 1
+                while e < len(chunk) and e - k < _WINDOW_MAX_BATCH and chunk[e][0] == chunk[k][0]:
+                    e += 1
+                runs.append((k, e))
+                k = e
+            win = torch.empty((len(chunk), cin, *roi), dtype=torch.float32, device=vols.device)
+            for k, e in runs:
+                ops.window_gather(vols[chunk[k][0]], [c[1:] for c in chunk[k:e]], roi, a, psize, out=win[k:e])
+        else:
+            win = torch.stack([vols[bi, :, z:z + r0, y:y + r1, x:x + r2] for bi, z, y, x in chunk]).contiguous()
+        pred = forward(win)
         if score is None:
-            if tuple(logits.shape) != (len(chunk), num_classes, *patch_size) or logits.dtype != torch.float32:
-                return None, logits
-            score = torch.zeros((num_classes, *psize), dtype=torch.float32, device=vol.device)
-            cnt = torch.zeros(psize, dtype=torch.float32, device=vol.device)
-        for k in range(0, len(chunk), _WINDOW_MAX_BATCH):
-            ops.window_accumulate(logits[k:k + _WINDOW_MAX_BATCH], chunk[k:k + _WINDOW_MAX_BATCH], score, cnt, imp, softmax=True)
-    if want_score:
-        return ops.window_finalize(score, cnt, a, size, return_score=True), None
-    return (ops.window_finalize(score, cnt, a, size), None), None
+            if kernels and not fits(pred, len(chunk)):      # hand-over: this batch has been through the network
+                kernels, handed, vols = False, pred, padded(vols)
+            nc = pred.shape[1] if num_classes is None else num_classes
+            score = torch.zeros((b, nc, *psize), dtype=torch.float32, device=vols.device)
+            weight = torch.zeros((b, *psize), dtype=torch.float32, device=vols.device)
+        if kernels:
+            pred = pred.float()
+            for k, e in runs:
+                bi = chunk[k][0]
+                ops.window_accumulate(pred[k:e], [c[1:] for c in chunk[k:e]], score[bi], weight[bi], imp, softmax=softmax)
+            continue
+        if softmax:
+            pred = torch.softmax(pred, dim=1)
+        for j, (bi, z, y, x) in enumerate(chunk):
+            value = pred[j] if softmax else pred[j].float()
+            if imp is None:
+                score[bi, :, z:z + r0, y:y + r1, x:x + r2] += value
+                weight[bi, z:z + r0, y:y + r1, x:x + r2] += 1
+            else:
+                score[bi, :, z:z + r0, y:y + r1, x:x + r2] += value * imp
+                weight[bi, z:z + r0, y:y + r1, x:x + r2] += imp
+    if kernels:
+        labels, quots = [], []
+        for bi in range(b):
+            res = ops.window_finalize(score[bi], weight[bi], a, size, return_score=want != "label", label=want != "quotients")
+            lab, quot = res if want == "both" else (res, None) if want == "label" else (None, res)
+            labels.append(lab)
+            quots.append(quot)
+
+        def join(ts):
+            return None if ts[0] is None else ts[0].unsqueeze(0) if b == 1 else torch.stack(ts)
+        return (join(labels), join(quots)), handed
+    score = score / weight.unsqueeze(1)
+    crop = tuple(slice(p, p + n) for p, n in zip(a, size))
+    label = torch.argmax(score, dim=1)[(slice(None),) + crop] if want != "quotients" else None
+    return (label, score[(slice(None), slice(None)) + crop]), handed
 
 
 @torch.no_grad()
@@ -117,17 +186,15 @@ def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size
     """``test_single_case_base`` up to the copy to the host: (label map int64 [W,H,D], score [C,W,H,D]) on the net's device.  On a HIP
     device the windows are gathered, soft-maxed, accumulated, divided and arg-maxed by the window kernels (``ICL_VAL_WINDOWS``; the score
     is None when ``want_score`` is false — the kernel then writes the label map alone); elsewhere, and when the network's output is not
-    fp32 [n, num_classes, *patch_size], by the ATen loop below.  Both walk the same window grid."""
+    fp32 [n, num_classes, *patch_size], in ATen (``_run_windows``).  Both walk the same window grid."""
     dev = next(net.parameters()).device
-    w, h, d = image.shape
     pads = []
-    for dim, p in zip((w, h, d), patch_size):
+    for dim, p in zip(image.shape, patch_size):
         tot = max(p - dim, 0)
         pads.append((tot // 2, tot - tot // 2))
-    add_pad = any(a + b > 0 for a, b in pads)
     vol = torch.as_tensor(np.ascontiguousarray(image), dtype=torch.float32, device=dev)
     imp = _importance_map(mode, patch_size, 0.125, dev)
-    ww, hh, dd = (n + a + b for n, (a, b) in zip((w, h, d), pads))      # the padded extents
+    ww, hh, dd = (n + a + b for n, (a, b) in zip(image.shape, pads))      # the padded extents
     sx = math.ceil((ww - patch_size[0]) / stride_xy) + 1
     sy = math.ceil((hh - patch_size[1]) / stride_xy) + 1
     sz = math.ceil((dd - patch_size[2]) / stride_z) + 1
@@ -138,41 +205,12 @@ def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size
             ys = min(stride_xy * y, hh - patch_size[1])
             for z in range(sz):
                 zs = min(stride_z * z, dd - patch_size[2])
-                starts.append((xs, ys, zs))
+                starts.append((0, xs, ys, zs))
     icl = net_type in ("swinunetr_icl", "unet_3D_icl")
-    first_logits = None
-    if _window_kernels_apply(vol, num_classes):
-        done, first_logits = _single_case_kernels(net, icl, vol, pads, starts, tuple(int(v) for v in patch_size), num_classes,
-                                                  windows_per_batch, imp, want_score)
-        if done is not None:
-            return done
-    if add_pad:
-        vol = torch.nn.functional.pad(vol, (pads[2][0], pads[2][1], pads[1][0], pads[1][1], pads[0][0], pads[0][1]))
-    score = torch.zeros((num_classes, ww, hh, dd), dtype=torch.float32, device=dev)
-    cnt = torch.zeros((ww, hh, dd), dtype=torch.float32, device=dev)
-    px, py, pz = patch_size
-    for i in range(0, len(starts), windows_per_batch):
-        chunk = starts[i:i + windows_per_batch]
-        if i == 0 and first_logits is not None:      # handed over by the kernel loop: this batch has been through the network
-            logits = first_logits
-        else:
-            batch = torch.stack([vol[xs:xs + px, ys:ys + py, zs:zs + pz] for xs, ys, zs in chunk]).unsqueeze(1).contiguous()
-            logits = net(batch, inference=True) if icl else net(batch)
-        prob = torch.softmax(logits, dim=1)
-        for j, (xs, ys, zs) in enumerate(chunk):
-            if imp is None:
-                score[:, xs:xs + px, ys:ys + py, zs:zs + pz] += prob[j]
-                cnt[xs:xs + px, ys:ys + py, zs:zs + pz] += 1
-            else:
-                score[:, xs:xs + px, ys:ys + py, zs:zs + pz] += prob[j] * imp
-                cnt[xs:xs + px, ys:ys + py, zs:zs + pz] += imp
-    score = score / cnt.unsqueeze(0)
-    label_map = torch.argmax(score, dim=0)
-    if add_pad:
-        sl = tuple(slice(a, a + n) for (a, _), n in zip(pads, (w, h, d)))
-        label_map = label_map[sl]
-        score = score[(slice(None),) + sl]
-    return label_map, score
+    (label_map, score), _ = _run_windows(
+        vol[None, None], patch_size, pads, (ww, hh, dd), starts, windows_per_batch, lambda win: net(win, inference=True) if icl else net(win),
+        imp, True, "both" if want_score else "label", _window_kernels_apply(vol, num_classes), _fits_brats(num_classes, patch_size), num_classes)
+    return label_map[0], None if score is None else score[0]
 
 
 def binary_dice(pred, gt) -> float:
@@ -294,10 +332,7 @@ def cal_metric(gt, pred, voxelspacing=None):
 def val_metrics_mode() -> str:
     """``ICL_VAL_METRICS``: ``device`` (default) scores label maps that are on a HIP device with the metric kernels, ``host`` forces the
     numpy path of ``cal_metric`` (A/B runs).  Host data always take the numpy path."""
-    mode = os.environ.get("ICL_VAL_METRICS", "device")
-    if mode not in ("device", "host"):
-        raise ValueError(f"ICL_VAL_METRICS must be 'device' or 'host', got {mode!r}")
-    return mode
+    return _env_choice("ICL_VAL_METRICS", ("device", "host"))
 
 
 def hd95_from_order_stats(n: int, sq0, sq1) -> float:
@@ -453,10 +488,7 @@ def surface_metrics_multiclass(gt, pred, num_classes, voxelspacing=None, toleran
 def components_mode() -> str:
     """``ICL_VAL_COMPONENTS``: ``device`` (default) filters label maps that are on a HIP device with the component kernels, ``host`` forces
     the scipy path (A/B runs).  Host data always take scipy."""
-    mode = os.environ.get("ICL_VAL_COMPONENTS", "device")
-    if mode not in ("device", "host"):
-        raise ValueError(f"ICL_VAL_COMPONENTS must be 'device' or 'host', got {mode!r}")
-    return mode
+    return _env_choice("ICL_VAL_COMPONENTS", ("device", "host"))
 
 
 def _components_args(num_classes, connectivity, keep_largest, min_size):
@@ -553,6 +585,28 @@ def _upload_label(label, device):
     return torch.as_tensor(np.ascontiguousarray(label), device=device)
 
 
+def _score_prediction(prediction, label, num_classes, dev, voxelspacing=None, post=None, also=None):
+    """The per-class list ``[cal_metric(label == c, prediction == c, voxelspacing) for c in 1..num_classes-1]`` of one case, behind the
+    optional ``keep_components(prediction, num_classes, **post)`` — the scoring step of the three validation loops (``test_all_case_base``,
+    ``test_all_case_amos``, ``val_2D``).  ``prediction``: a tensor on ``dev``, the net's device, or a numpy array; ``label``: a host array or
+    tensor.  With ``dev`` a HIP device, ``ICL_VAL_METRICS=device``, 2 <= num_classes <= 256, a label map that ``_upload_label`` takes and
+    ``also(gt, prediction, num_classes)`` (the caller's extra condition, if any; asked before a host prediction goes up) both maps are filtered and scored on the
+    device (``cal_metric_multiclass``); otherwise on the host, by numpy.  The filter runs once, where the scores are taken."""
+    if dev.type == "cuda" and val_metrics_mode() == "device" and 2 <= num_classes <= 256:
+        gt = _upload_label(label, dev)      # the ground truth goes up once per case
+        if gt is not None and (also is None or also(gt, prediction, num_classes)):
+            pred = prediction if torch.is_tensor(prediction) else torch.from_numpy(prediction).to(dev)
+            if post is not None:
+                pred = keep_components(pred, num_classes, **post)
+            return cal_metric_multiclass(gt, pred, num_classes, voxelspacing)
+    if torch.is_tensor(prediction):
+        prediction = prediction.cpu().numpy()
+    if post is not None:
+        prediction = keep_components(prediction, num_classes, **post)
+    label = np.asarray(label.cpu() if torch.is_tensor(label) else label)
+    return [cal_metric(label == c, prediction == c, voxelspacing) for c in range(1, num_classes)]
+
+
 def test_all_case_base(net, net_type, base_dir, test_list="full_test.list", num_classes=4, patch_size=(48, 160, 160),
                        stride_xy=32, stride_z=24, cases=None, voxelspacing=None, postprocess=None):
     """val_3D.py:100-118.  ``cases`` (iterable of (image, label) numpy pairs) replaces the h5 files when given; otherwise
@@ -575,21 +629,10 @@ def test_all_case_base(net, net_type, base_dir, test_list="full_test.list", num_
         cases = _gen()
     metric_cal = [[] for _ in range(num_classes - 1)]
     dev = next(net.parameters()).device
-    on_device = dev.type == "cuda" and val_metrics_mode() == "device" and 2 <= num_classes <= 256
-    for image, label in cases:
-        gt = _upload_label(label, dev) if on_device else None
-        if gt is not None:      # the label map stays on the device; the ground truth goes up once per case
-            prediction, _ = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes, want_score=False)
-            if post is not None:
-                prediction = keep_components(prediction, num_classes, **post)
-            for i, m in enumerate(cal_metric_multiclass(gt, prediction, num_classes, voxelspacing)):
-                metric_cal[i].append(m)
-            continue
-        prediction = test_single_case_base(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=num_classes)
-        if post is not None:
-            prediction = keep_components(prediction, num_classes, **post)
-        for i in range(1, num_classes):
-            metric_cal[i - 1].append(cal_metric(label == i, prediction == i, voxelspacing))
+    for image, label in cases:      # the label map stays on the net's device up to its scores
+        prediction, _ = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes, want_score=False)
+        for i, m in enumerate(_score_prediction(prediction, label, num_classes, dev, voxelspacing, post)):
+            metric_cal[i].append(m)
     return metric_cal
 
 
@@ -607,44 +650,6 @@ def _scan_starts(size: int, roi: int, overlap: float):
     interval = interval if interval > 0 else 1
     num = int(math.ceil(float(size - roi) / interval)) + 1
     return [i * interval - max(i * interval + roi - size, 0) for i in range(num)]
-
-
-def _sliding_window_kernels(inputs, size, roi, pads, psize, starts, sw_batch_size, predictor, imp, kwargs):
-    """The window loop of ``sliding_window_inference`` on the window kernels: ``inputs`` fp32 [B, Cin, *size], unpadded (the gather
-    zero-fills), ``starts`` (batch index, origin in the padded frame ``psize``).  Returns (averaged outputs [B, C, *size], None) — or (None, the
-    first batch's prediction) when that prediction is not a tensor [n, C <= 256, *roi] on the device of ``inputs``: the caller's ATen loop
-    then takes over with that batch already computed, so the predictor sees every batch once."""
-    from . import ops
-    inputs = inputs.contiguous()
-    b, cin = inputs.shape[:2]
-    a = tuple(p[0] for p in pads)
-    out = cnt = None
-    for i in range(0, len(starts), sw_batch_size):
-        chunk = starts[i:i + sw_batch_size]
-        # runs of windows of one volume, at most 16 each: one launch per run
-        runs, k = [], 0
-        while k < len(chunk):
-            e = k + 1
-            while e < len(chunk) and e - k < _WINDOW_MAX_BATCH and chunk[e][0] == chunk[k][0]:
-                e += 1
-            runs.append((k, e))
-            k = e
-        win = torch.empty((len(chunk), cin, *roi), dtype=torch.float32, device=inputs.device)
-        for k, e in runs:
-            ops.window_gather(inputs[chunk[k][0]], [c[1:] for c in chunk[k:e]], roi, a, psize, out=win[k:e])
-        pred = predictor(win, **kwargs)
-        if out is None and (not torch.is_tensor(pred) or pred.dim() != 5 or pred.shape[0] != len(chunk) or list(pred.shape[2:]) != list(roi)
-                            or not 1 <= pred.shape[1] <= _WINDOW_MAX_CLASSES or pred.device != inputs.device):
-            return None, pred
-        pred = pred.float()
-        if out is None:
-            out = torch.zeros((b, pred.shape[1], *psize), dtype=torch.float32, device=inputs.device)
-            cnt = torch.zeros((b, *psize), dtype=torch.float32, device=inputs.device)
-        for k, e in runs:
-            bi = chunk[k][0]
-            ops.window_accumulate(pred[k:e], [c[1:] for c in chunk[k:e]], out[bi], cnt[bi], imp, softmax=False)
-    res = [ops.window_finalize(out[bi], cnt[bi], a, size, return_score=True, label=False) for bi in range(b)]
-    return (res[0].unsqueeze(0) if b == 1 else torch.stack(res)), None
 
 
 @torch.no_grad()
@@ -669,35 +674,10 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     psize = [s + a + c for s, (a, c) in zip(size, pads)]
     grids = [_scan_starts(s, r, overlap) for s, r in zip(psize, roi)]
     starts = [(bi, z, y, x) for bi in range(b) for z in grids[0] for y in grids[1] for x in grids[2]]
-    first_pred = None
-    if _window_kernels_apply(inputs) and len(size) == 3:
-        done, first_pred = _sliding_window_kernels(inputs, size, roi, pads, psize, starts, sw_batch_size, predictor, imp, kwargs)
-        if done is not None:
-            return done
-    if any(a + c for a, c in pads):
-        flat = [v for a, c in reversed(pads) for v in (a, c)]
-        inputs = torch.nn.functional.pad(inputs, flat)
-    out = cnt = None
-    for i in range(0, len(starts), sw_batch_size):
-        chunk = starts[i:i + sw_batch_size]
-        if i == 0 and first_pred is not None:      # handed over by the kernel loop: this batch has been through the predictor
-            pred = first_pred
-        else:
-            win = torch.stack([inputs[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] for bi, z, y, x in chunk]).contiguous()
-            pred = predictor(win, **kwargs)
-        if out is None:
-            out = torch.zeros((b, pred.shape[1], *psize), dtype=torch.float32, device=inputs.device)
-            cnt = torch.zeros((b, 1, *psize), dtype=torch.float32, device=inputs.device)
-        for j, (bi, z, y, x) in enumerate(chunk):
-            if imp is None:
-                out[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] += pred[j].float()
-                cnt[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] += 1
-            else:
-                out[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] += pred[j].float() * imp
-                cnt[bi, :, z:z + roi[0], y:y + roi[1], x:x + roi[2]] += imp
-    out = out / cnt
-    sl = tuple(slice(a, a + s) for (a, _), s in zip(pads, size))
-    return out[(slice(None), slice(None)) + sl]
+    (_, out), _ = _run_windows(
+        inputs, roi, pads, psize, starts, sw_batch_size, lambda win: predictor(win, **kwargs), imp, False, "quotients",
+        _window_kernels_apply(inputs) and len(size) == 3, _fits_amos(roi, inputs.device))
+    return out
 
 
 def test_all_case_amos(net, net_type, val_loader, num_classes=4, voxelspacing=None, postprocess=None):
@@ -717,19 +697,7 @@ def test_all_case_amos(net, net_type, val_loader, num_classes=4, voxelspacing=No
         image, label = batch["image"].to(dev), batch["label"].squeeze(0)
         kw = {"inference": True} if net_type in ("unet_3D_icl", "swinunetr_icl") else {}
         logits = sliding_window_inference(image, (96, 96, 96), 4, net, **kw)
-        if dev.type == "cuda" and val_metrics_mode() == "device":
-            prediction = torch.argmax(logits, dim=1)
-            if post is not None:
-                prediction = keep_components(prediction, num_classes, **post)
-            gt = _upload_label(label, dev)
-            if gt is not None and _device_metrics_apply(gt, prediction, num_classes):
-                for i, m in enumerate(cal_metric_multiclass(gt, prediction, num_classes, voxelspacing)):
-                    metric_cal[i].append(m)
-                continue
-        prediction = torch.argmax(logits, dim=1).cpu().numpy()
-        if post is not None:
-            prediction = keep_components(prediction, num_classes, **post)
-        label = np.asarray(label.cpu() if torch.is_tensor(label) else label)
-        for i in range(1, num_classes):
-            metric_cal[i - 1].append(cal_metric(label == i, prediction == i, voxelspacing))
+        prediction = torch.argmax(logits, dim=1)
+        for i, m in enumerate(_score_prediction(prediction, label, num_classes, dev, voxelspacing, post, also=_device_metrics_apply)):
+            metric_cal[i].append(m)
     return metric_cal

@@ -160,3 +160,10 @@ def test_host_tensor_is_refused_by_the_product_library():
             ops.seg_filter_components(a, 2)
     finally:
         _lib._use_library_for_tests(build_emu(), host_pointers=True)
+
+
+# the sizes that the library of commit ca1119d2aa3a5921954c12ced9f9332573bd19a7 (the parent of the one that put the workspace carver into the
+# launchers) returns, recorded from its emulation build: the layout of the workspace has not moved
+@pytest.mark.parametrize("shape, nc, nbytes", [((1, 1, 1), 2, 793344), ((5, 7, 9), 3, 796416), ((3, 300, 2), 256, 814848), ((96, 96, 96), 16, 11409408)])
+def test_workspace_size_is_that_of_the_earlier_layout(shape, nc, nbytes):
+    assert _lib.lib().icl_seg_components_ws_bytes(*shape, nc) == nbytes

@@ -152,3 +152,36 @@ def test_fallback_sees_every_batch_once(dev, monkeypatch):
         calls[way] = net.calls
     assert calls["device"] == calls["aten"] == 1      # 2 x 1 x 2 windows, four per forward
     assert np.array_equal(out["device"][0], out["aten"][0]) and np.array_equal(out["device"][1], out["aten"][1])
+
+
+@pytest.mark.parametrize("mode", ["constant", "gaussian"])
+def test_brats_loop_seventeen_windows_in_one_forward(dev, monkeypatch, mode):
+    """Volume (20, 4, 8), window (4, 4, 8) at stride 1: the 17 windows of the grid go through ONE forward, which the kernel loop splits into
+    launches of 16 + 1.  Against ``ICL_VAL_WINDOWS=aten``: the score within 2e-6 (the band of the BraTS test above, for the same
+    reason), the labels equal wherever the ATen score's top-two gap exceeds 1e-5, which leaves out at most 1e-3 of the voxels."""
+    class ScaleNet(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.w = torch.nn.Parameter(torch.tensor([0.5, -1.0, 2.0], device=dev).view(1, 3, 1, 1, 1), requires_grad=False)
+            self.calls = 0
+
+        def forward(self, x):
+            self.calls += 1
+            return x * self.w
+    image = wr.volume((20, 4, 8)).numpy()
+    out = {}
+    for way in ("device", "aten"):
+        monkeypatch.setenv("ICL_VAL_WINDOWS", way)
+        net = ScaleNet()
+        out[way] = val_3D.test_single_case_base(net, "unet_3D", image, 1, 1, (4, 4, 8), num_classes=3, windows_per_batch=17, return_score=True,
+                                                mode=mode)
+        assert net.calls == 1
+    (lab_d, score_d), (lab_a, score_a) = out["device"], out["aten"]
+    assert lab_d.shape == lab_a.shape == (20, 4, 8) and lab_d.dtype == lab_a.dtype and score_d.shape == score_a.shape == (3, 20, 4, 8)
+    top = np.sort(score_a, axis=0)
+    clear = (top[-1] - top[-2]) > 1e-5
+    print(f"score: largest difference {np.abs(score_d - score_a).max():.3e}; labels that differ: {(lab_d != lab_a).mean():.3e}; "
+          f"voxels with a top-two gap <= 1e-5: {1.0 - clear.mean():.3e}")
+    assert 1.0 - clear.mean() <= 1e-3
+    assert np.abs(score_d - score_a).max() <= 2e-6
+    assert np.array_equal(lab_d[clear], lab_a[clear])

@@ -208,3 +208,10 @@ def test_label_upload_dtypes():
     assert _upload_label(f.astype(np.int16), "cpu").dtype == torch.int64
     assert _upload_label(f.astype(np.uint8), "cpu").dtype == torch.uint8
     assert _upload_label(np.array(["a"]), "cpu") is None
+
+
+# the sizes that the library of commit ca1119d2aa3a5921954c12ced9f9332573bd19a7 (the parent of the one that put the workspace carver into the
+# launchers) returns, recorded from its emulation build: the layout of the workspace has not moved
+@pytest.mark.parametrize("shape, nc, nbytes", [((1, 1, 1), 2, 2048), ((5, 7, 9), 3, 5120), ((3, 300, 2), 256, 1022720), ((96, 96, 96), 16, 8994304)])
+def test_workspace_size_is_that_of_the_earlier_layout(shape, nc, nbytes):
+    assert _lib.lib().icl_seg_metrics_ws_bytes(*shape, nc) == nbytes

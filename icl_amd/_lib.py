@@ -142,6 +142,24 @@ _SIGNATURES = {
     "icl_window_gather": (c_int, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "icl_window_accumulate": (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "icl_window_finalize": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
+    # live batch (DESIGN.md §4.4 "Live batch"): the entry point's signature with n_live behind n
+    "icl_last_live_fwd_kernel_name": (c_char_p, []),
+    "icl_last_wgrad_grid": (None, [P, P]),
+    "icl_conv3d_fwd_live_ok": (c_int, [I, I, I, I, I, I, I]),
+    "icl_conv3d_fwd_presplit_live": (c_int, [P, P, P, P, I, I, I, I, I, I, I, L, L, P]),
+    "icl_conv3d_fwd_presplit_ws_live": (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, L, L, P]),
+    "icl_conv3d_fwd_live": (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I, L, L, P]),
+    "icl_conv3d_wgrad_ws_bytes_live": (c_int64, [I, I, I, I, I]),
+    "icl_conv3d_wgrad_live": (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I, L, L, P]),
+    "icl_conv3d_wgrad_slabs_live": (c_int, [P, P, P, I, I, I, I, I, I, I, I, L, L, P, P]),
+    "icl_norm_bwd_live": (c_int, [P, P, P, P, P, P, P, P, P, I, I, I, L, I, I, I, P, P]),
+    "icl_maxpool2_bwd_add_live": (c_int, [P, P, P, P, I, I, I, I, I, I, I, L, P]),
+    "icl_trilinear_bwd_live": (c_int, [P, P, P, I, I, I, I, I, I, I, I, I, L, I, P]),
+    "icl_conv1x1_small_live": (c_int, [P, P, P, P, I, I, I, I, L, I, I, P]),
+    "icl_conv1x1_dropout_live": (c_int, [P, P, P, P, I, I, I, I, L, I, I, I, ctypes.c_uint32, F, P, P]),
+    "icl_conv1x1_wgrad_live": (c_int, [P, P, P, P, P, I, I, I, I, L, L, L, P]),
+    "icl_conv1x1_wgrad_dropout_live": (c_int, [P, P, P, P, P, I, I, I, I, L, L, ctypes.c_uint32, F, P, P]),
+    "icl_conv1x1_wgrad_dropout_norm_live": (c_int, [P, P, P, P, P, P, I, I, I, I, L, L, ctypes.c_uint32, F, P, P]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

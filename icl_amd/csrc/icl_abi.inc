@@ -255,6 +255,27 @@ inline int wgrad_max_split(int pairs, int n) {
 
 constexpr int kWgradWaveGroups = 2;   // 8-wave workgroups: two wave groups, each with its own slab
 
+// Live batch (icl_conv3d_wgrad_live): samples [n_live, n) of dY are exactly zero.  The tile-list kernels keep the plan of the batch of n
+// — tiles are numbered sample-outermost, so the workgroups that own live tiles are a prefix of the grid — launch that prefix only and
+// write the slabs of the rest as zeros (what those workgroups would have written): the reduction sums the same slabs in the same order,
+// the weight gradient is bit for bit the full call's.  0: no live batch.  Every other weight-gradient kernel runs the whole batch.
+thread_local int g_wgrad_n_live = 0;
+thread_local int g_wgrad_grid[2] = {0, 0};      // workgroups launched / planned by the last tile-list weight-gradient launch (tests)
+thread_local char g_kernel_live_fwd[160] = "";  // kernel of the last live input-gradient launch (icl_conv3d_fwd*_live), for the tests
+
+// workgroups of a tile-list launch that own a live tile; zeros to the slabs of the others
+inline int wgrad_live_prefix(float* gwp, int nsplit, int ntiles, int tiles_per_wg, int n, long slab_elems, hipStream_t stream) {
+  g_wgrad_grid[0] = g_wgrad_grid[1] = nsplit;
+  if (g_wgrad_n_live < 1 || g_wgrad_n_live >= n) return nsplit;
+  const long live_tiles = (long)g_wgrad_n_live * (ntiles / n);
+  int gx = (int)cdivl(live_tiles, tiles_per_wg);
+  if (gx >= nsplit) return nsplit;
+  if (gx < 1) gx = 1;
+  ICL_MEMSET_ASYNC(gwp + (size_t)gx * slab_elems, 0, (size_t)(nsplit - gx) * slab_elems * sizeof(float), stream);
+  g_wgrad_grid[0] = gx;
+  return gx;
+}
+
 template <class TC, int WV, int NCB, int TGN = 4>
 int conv_wgrad_static_go(const float* x, const float* gy, float* gwp, icl::ConvGeom g, int n, int* nslabs, hipStream_t stream) {
   g.TZ = TC::TZ; g.TY = TC::TY; g.TX = TC::TX; g.KC = 16; g.PS = TC::PS; g.PXL = TC::PXL; g.HX = TC::HX; g.CPP = TC::CPP; g.ksplit = 1;
@@ -297,7 +318,8 @@ int conv_wgrad_tr_go(const float* x, const float* gy, float* gwp, const icl::Con
   *nslabs = nsplit;
   { const char* e = getenv("ICL_WGRAD_TR_DBG"); w.dbg = e ? atoi(e) : 0; }
   ICL_SET_MAX_DYN_LDS((icl::conv3d_wgrad_tr_kernel<NCB>), 160 * 1024);
-  ICL_LAUNCH((icl::conv3d_wgrad_tr_kernel<NCB>), dim3(nsplit, pairs), dim3(512), C::LDS_BYTES, stream, x, gy, gwp, w);
+  const int gx = wgrad_live_prefix(gwp, nsplit, w.ntiles, w.tiles_per_wg, n, 27L * w.CinP * w.CoutP, stream);
+  ICL_LAUNCH((icl::conv3d_wgrad_tr_kernel<NCB>), dim3(gx, pairs), dim3(512), C::LDS_BYTES, stream, x, gy, gwp, w);
   snprintf(g_kernel, sizeof(g_kernel), "conv3d_wgrad_tr_kernel<%d>", NCB);
   return check_launch("conv3d_wgrad_tr");
 }
@@ -326,7 +348,8 @@ int conv_wgrad_zs_go(const float* x, const float* gy, float* gwp, const icl::Con
   *nslabs = nsplit;
   { const char* e = getenv("ICL_WGRAD_TR_DBG"); w.dbg = e ? atoi(e) : 0; }
   ICL_SET_MAX_DYN_LDS((icl::conv3d_wgrad_zs_kernel<NCB, NW>), 160 * 1024);
-  ICL_LAUNCH((icl::conv3d_wgrad_zs_kernel<NCB, NW>), dim3(nsplit, pairs), dim3(C::NT), C::LDS_BYTES, stream, x, gy, gwp, w);
+  const int gx = wgrad_live_prefix(gwp, nsplit, w.ntiles, w.tiles_per_wg, n, 27L * w.CinP * w.CoutP, stream);
+  ICL_LAUNCH((icl::conv3d_wgrad_zs_kernel<NCB, NW>), dim3(gx, pairs), dim3(C::NT), C::LDS_BYTES, stream, x, gy, gwp, w);
   snprintf(g_kernel, sizeof(g_kernel), "conv3d_wgrad_zs_kernel<%d, %d>", NCB, NW);
   return check_launch("conv3d_wgrad_zs");
 }
@@ -1418,19 +1441,25 @@ int icl_maxpool2_bwd(const float* gy, const uint8_t* idx, float* gx, int64_t nc,
 
 int icl_maxpool2_bwd_add(const float* gy, const uint8_t* idx, const float* add, float* gx, int n, int c, int dout, int hout, int wout,
                          int pool_depth, int64_t add_bstride, void* stream) {
+  return icl_maxpool2_bwd_add_live(gy, idx, add, gx, n, n, c, dout, hout, wout, pool_depth, add_bstride, stream);
+}
+
+int icl_maxpool2_bwd_add_live(const float* gy, const uint8_t* idx, const float* add, float* gx, int n, int skip_live, int c, int dout, int hout,
+                              int wout, int pool_depth, int64_t add_bstride, void* stream) {
   if (!gy || !gx || !idx || !add || n < 1 || c < 1 || dout < 1 || hout < 1 || wout < 1 || (pool_depth != 1 && pool_depth != 2) || (add_bstride & 1) ||
-      ((uintptr_t)add & 7))
+      ((uintptr_t)add & 7) || skip_live < 1 || skip_live > n)
     return fail(-1, "maxpool2_bwd_add: bad argument");
+  const long ncskip = (long)skip_live * c;
   const long total = (long)n * c * dout * hout * wout;
   // two x-neighbouring outputs per thread (16-byte accesses) where the rows allow it; ICL_MAXPOOL_BWD_X2=0: the 8-byte form (A/B)
   const char* e_x2 = getenv("ICL_MAXPOOL_BWD_X2");
   if ((wout & 1) == 0 && aligned16(add) && aligned16(gx) && ((uintptr_t)gy & 7) == 0 && (add_bstride & 3) == 0 && (e_x2 ? atoi(e_x2) : 1)) {
     ICL_LAUNCH(icl::maxpool2_bwd_add_x2_kernel, dim3(grid_for(total / 2, 256)), dim3(256), 0, (hipStream_t)stream, gy, idx, add, gx, (long)n * c, c,
-               dout, hout, wout, pool_depth, (long)add_bstride);
+               dout, hout, wout, pool_depth, (long)add_bstride, ncskip);
     return check_launch("maxpool2_bwd_add_x2");
   }
   ICL_LAUNCH(icl::maxpool2_bwd_add_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, gy, idx, add, gx, (long)n * c, c, dout,
-             hout, wout, pool_depth, (long)add_bstride);
+             hout, wout, pool_depth, (long)add_bstride, ncskip);
   return check_launch("maxpool2_bwd_add");
 }
 
@@ -1584,9 +1613,10 @@ icl::DropSpec drop_spec(int mode, uint32_t seed, float p, const uint32_t* seed_d
   return d;
 }
 
+// n_plan: the batch size the kernel is chosen for (a live batch runs the kernel of its full batch: the same bits per sample); 0: n
 int conv1x1_small_run(const float* x, const float* w, const float* bias, float* y, int n, int cin, int cout, int64_t s, int w_ostride,
-                      int w_istride, const icl::DropSpec& dr, hipStream_t st) {
-  if ((long)n * s >= 65536) {   // big volume: every input value loaded once per group of <= 16 outputs
+                      int w_istride, const icl::DropSpec& dr, hipStream_t st, int n_plan = 0) {
+  if ((long)(n_plan > n ? n_plan : n) * s >= 65536) {   // big volume: every input value loaded once per group of <= 16 outputs
     const long quads = (long)n * (s >> 2);
     const int ob = cout <= 1 ? 1 : cout <= 2 ? 2 : cout <= 4 ? 4 : cout <= 8 ? 8 : 16;
     const dim3 grid(grid_for(quads, 256, 1 << 16), (cout + ob - 1) / ob);
@@ -2973,6 +3003,167 @@ int icl_window_finalize(const float* score, const float* weight, int64_t* label,
     ICL_LAUNCH(icl::window_finalize_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, score, weight, (long long*)label, quotients, c, p, a, s);
   }
   return check_launch("window_finalize");
+}
+
+// ---- live batch (DESIGN.md §4.4 "Live batch"): a gradient whose samples [n_live, n) are exactly zero.  Every `_live` sibling computes samples
+// [0, n_live) exactly as its entry point does when called with n = n_live on the same pointers and batch strides (all of these operators
+// are per sample, and samples are the outermost index of every tensor, dropout-mask index and tile list), and writes zeros to samples
+// [n_live, n) of every output gradient in the same call on the same stream (a fill node under capture).  n_live == n: the entry point itself.
+
+namespace {
+inline int live_args(int n, int n_live, const char* who) {
+  if (n < 1 || n_live < 1 || n_live > n) return fail(-1, "%s: bad live batch (1 <= n_live <= n)", who);
+  return 0;
+}
+// zeros to samples [n_live, n) of a dense [n][elems] gradient
+inline int live_zero_tail(float* p, int n, int n_live, int64_t elems, hipStream_t st, const char* who) {
+  if (n_live >= n) return 0;
+  ICL_MEMSET_ASYNC(p + (size_t)n_live * elems, 0, (size_t)(n - n_live) * elems * sizeof(float), st);
+  return check_launch(who);
+}
+}  // namespace
+
+// 1: the 3^3 launcher plans a batch of n_live as it plans a batch of n — split-product kernels, nothing split over the channel chunks
+// (the deep levels' split count follows the batch size: their sums would re-associate) — so the live samples come out bit for bit.
+// The dry run of conv_fwd_split ends before the checks that hand a real call to the fp32 kernels, whose split does follow the batch size:
+// rows of 12 voxels and the 6^3 volume that turn out unsplit are refused here as well.  Not mirrored: operands that are not 16-byte
+// aligned (a real call then falls to the fp32 kernels; the samples stay correct, their last bits may differ from the full call's).
+int icl_conv3d_fwd_live_ok(int n, int n_live, int cin, int cout, int d, int h, int w) {
+  if (n < 1 || n_live < 1 || n_live > n || cin < 1 || cout < 1 || d < 1 || h < 1 || w < 1) return 0;
+  if (w == icl::Bf3F12::TX || (w == 6 && h == 6 && d == 6)) return 0;
+  const int64_t dense = (int64_t)d * h * w;
+  const int batch[2] = {n, n_live};
+  int ok = 1;
+  g_plan.dry = true;
+  for (int i = 0; i < 2; ++i) {
+    int64_t slab = 0;
+    if (conv_fwd_split(nullptr, nullptr, nullptr, nullptr, nullptr, batch[i], cin, cout, d, h, w, cin * dense, cout * dense, nullptr, nullptr,
+                       nullptr, false, nullptr, &slab) != 0 || slab != 0)
+      ok = 0;
+  }
+  g_plan.dry = false;
+  return ok;
+}
+
+const char* icl_last_live_fwd_kernel_name(void) { return g_kernel_live_fwd; }
+void icl_last_wgrad_grid(int32_t* launched, int32_t* planned) {
+  if (launched) *launched = g_wgrad_grid[0];
+  if (planned) *planned = g_wgrad_grid[1];
+}
+
+int icl_conv3d_fwd_presplit_live(const float* x, const void* wsplit, const float* bias, float* y, int n, int n_live, int cin, int cout, int d,
+                                 int h, int w, int64_t x_bstride, int64_t y_bstride, void* stream) {
+  if (int rc = live_args(n, n_live, "conv3d_fwd_presplit_live")) return rc;
+  if (n_live < n && y_bstride != (int64_t)cout * d * h * w) return fail(-1, "conv3d_fwd_presplit_live: y must be dense");
+  const int rc = icl_conv3d_fwd_presplit(x, wsplit, bias, y, n_live, cin, cout, d, h, w, x_bstride, y_bstride, stream);
+  if (rc) return rc;      // 1: nothing launched (the caller takes the fp32 pack), nothing zeroed
+  snprintf(g_kernel_live_fwd, sizeof(g_kernel_live_fwd), "%s", g_kernel);
+  return live_zero_tail(y, n, n_live, y_bstride, (hipStream_t)stream, "conv3d_fwd_presplit_live: tail");
+}
+
+int icl_conv3d_fwd_presplit_ws_live(const float* x, const void* wsplit, const float* bias, float* y, void* ws, int n, int n_live, int cin,
+                                    int cout, int d, int h, int w, int64_t x_bstride, int64_t y_bstride, void* stream) {
+  if (int rc = live_args(n, n_live, "conv3d_fwd_presplit_ws_live")) return rc;
+  if (n_live < n && y_bstride != (int64_t)cout * d * h * w) return fail(-1, "conv3d_fwd_presplit_ws_live: y must be dense");
+  const int rc = icl_conv3d_fwd_presplit_ws(x, wsplit, bias, y, ws, n_live, cin, cout, d, h, w, x_bstride, y_bstride, stream);
+  if (rc) return rc;
+  snprintf(g_kernel_live_fwd, sizeof(g_kernel_live_fwd), "%s", g_kernel);
+  return live_zero_tail(y, n, n_live, y_bstride, (hipStream_t)stream, "conv3d_fwd_presplit_ws_live: tail");
+}
+
+int icl_conv3d_fwd_live(const float* x, const float* wp, const float* bias, float* y, void* ws, int n, int n_live, int cin, int cout, int d,
+                        int h, int w, int ks, int64_t x_bstride, int64_t y_bstride, void* stream) {
+  if (int rc = live_args(n, n_live, "conv3d_fwd_live")) return rc;
+  if (n_live < n && y_bstride != (int64_t)cout * d * h * w) return fail(-1, "conv3d_fwd_live: y must be dense");
+  const int rc = icl_conv3d_fwd(x, wp, bias, y, ws, n_live, cin, cout, d, h, w, ks, x_bstride, y_bstride, stream);
+  if (rc) return rc;
+  snprintf(g_kernel_live_fwd, sizeof(g_kernel_live_fwd), "%s", g_kernel);
+  return live_zero_tail(y, n, n_live, y_bstride, (hipStream_t)stream, "conv3d_fwd_live: tail");
+}
+
+// The weight gradient has no per-sample output.  Its live form keeps the launch plan of the batch of n and skips the workgroups that own
+// no live tile (g_wgrad_n_live above): same slabs, same order, bit-identical sums.  Workspace as for n.
+int64_t icl_conv3d_wgrad_ws_bytes_live(int n, int n_live, int cin, int cout, int ks) {
+  if (n < 1 || n_live < 1 || n_live > n) return 0;
+  return icl_conv3d_wgrad_ws_bytes(n, cin, cout, ks);
+}
+
+int icl_conv3d_wgrad_live(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live, int cin, int cout, int d,
+                          int h, int w, int ks, int64_t x_bstride, int64_t gy_bstride, void* stream) {
+  if (int rc = live_args(n, n_live, "conv3d_wgrad_live")) return rc;
+  g_wgrad_n_live = n_live;
+  const int rc = icl_conv3d_wgrad(x, gy, gw, gbias, ws, n, cin, cout, d, h, w, ks, x_bstride, gy_bstride, stream);
+  g_wgrad_n_live = 0;
+  return rc;
+}
+
+int icl_conv3d_wgrad_slabs_live(const float* x, const float* gy, void* ws, int n, int n_live, int cin, int cout, int d, int h, int w, int ks,
+                                int64_t x_bstride, int64_t gy_bstride, int32_t* nslabs, void* stream) {
+  if (int rc = live_args(n, n_live, "conv3d_wgrad_slabs_live")) return rc;
+  g_wgrad_n_live = n_live;
+  const int rc = icl_conv3d_wgrad_slabs(x, gy, ws, n, cin, cout, d, h, w, ks, x_bstride, gy_bstride, nslabs, stream);
+  g_wgrad_n_live = 0;
+  return rc;
+}
+
+int icl_norm_bwd_live(const float* gy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* gx,
+                      float* dgamma, float* dbeta, int n, int n_live, int c, int64_t s, int mode, int use_batch_stats, int act, void* ws,
+                      void* stream) {
+  if (int rc = live_args(n, n_live, "norm_bwd_live")) return rc;
+  // instance statistics without an affine pair only: a batch group (mode 1) couples the samples, and dgamma / dbeta rows are per (n, c)
+  if (n_live < n && (mode != 0 || dgamma || dbeta)) return fail(-1, "norm_bwd_live: a live batch needs instance statistics, no affine pair");
+  const int rc = icl_norm_bwd(gy, x, mean, rstd, gamma, beta, gx, dgamma, dbeta, n_live, c, s, mode, use_batch_stats, act, ws, stream);
+  if (rc) return rc;
+  return live_zero_tail(gx, n, n_live, (int64_t)c * s, (hipStream_t)stream, "norm_bwd_live: tail");
+}
+
+int icl_trilinear_bwd_live(const float* gy, float* gx, void* ws, int n, int n_live, int c, int di, int hi, int wi, int dout, int hout, int wout,
+                           int64_t gy_bstride, int align_corners, void* stream) {
+  if (int rc = live_args(n, n_live, "trilinear_bwd_live")) return rc;
+  const int rc = icl_trilinear_bwd(gy, gx, ws, n_live, c, di, hi, wi, dout, hout, wout, gy_bstride, align_corners, stream);
+  if (rc) return rc;
+  return live_zero_tail(gx, n, n_live, (int64_t)c * di * hi * wi, (hipStream_t)stream, "trilinear_bwd_live: tail");
+}
+
+int icl_conv1x1_small_live(const float* x, const float* w, const float* bias, float* y, int n, int n_live, int cin, int cout, int64_t s,
+                           int w_ostride, int w_istride, void* stream) {
+  if (int rc = live_args(n, n_live, "conv1x1_small_live")) return rc;
+  if (!x || !w || !y || cin < 1 || cout < 1 || s < 4 || (s & 3)) return fail(-1, "conv1x1_small_live: bad argument (s %% 4 == 0)");
+  const int rc = conv1x1_small_run(x, w, bias, y, n_live, cin, cout, s, w_ostride, w_istride, icl::DropSpec{}, (hipStream_t)stream, n);
+  if (rc) return rc;
+  return live_zero_tail(y, n, n_live, (int64_t)cout * s, (hipStream_t)stream, "conv1x1_small_live: tail");
+}
+
+// (the mask is a hash of the element index (b * C + c) * S + v: the live samples are a prefix, their indices and masks are unchanged)
+int icl_conv1x1_dropout_live(const float* x, const float* w, const float* bias, float* y, int n, int n_live, int cin, int cout, int64_t s,
+                             int w_ostride, int w_istride, int mask_mode, uint32_t seed, float p, const uint32_t* seed_dev, void* stream) {
+  if (int rc = live_args(n, n_live, "conv1x1_dropout_live")) return rc;
+  if (!x || !w || !y || cin < 1 || cout < 1 || s < 4 || (s & 3) || (mask_mode != 1 && mask_mode != 2) || !(p >= 0.f && p < 1.f))
+    return fail(-1, "conv1x1_dropout_live: bad argument");
+  const int rc = conv1x1_small_run(x, w, bias, y, n_live, cin, cout, s, w_ostride, w_istride, drop_spec(mask_mode, seed, p, seed_dev),
+                                   (hipStream_t)stream, n);
+  if (rc) return rc;      // 1: n * s < 65536, nothing launched, nothing zeroed
+  return live_zero_tail(y, n, n_live, (int64_t)cout * s, (hipStream_t)stream, "conv1x1_dropout_live: tail");
+}
+
+int icl_conv1x1_wgrad_live(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live, int cin, int cout, int64_t s,
+                           int64_t x_bstride, int64_t gy_bstride, void* stream) {
+  if (int rc = live_args(n, n_live, "conv1x1_wgrad_live")) return rc;
+  // (the row split of this HBM-bound reduction follows n * s: the whole batch, whose dead rows add exact zeros — bit-identical sums)
+  return icl_conv1x1_wgrad(x, gy, gw, gbias, ws, n, cin, cout, s, x_bstride, gy_bstride, stream);
+}
+
+int icl_conv1x1_wgrad_dropout_live(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live, int cin, int cout,
+                                   int64_t s, int64_t gy_bstride, uint32_t seed, float p, const uint32_t* seed_dev, void* stream) {
+  if (int rc = live_args(n, n_live, "conv1x1_wgrad_dropout_live")) return rc;
+  return icl_conv1x1_wgrad_dropout(x, gy, gw, gbias, ws, n, cin, cout, s, gy_bstride, seed, p, seed_dev, stream);
+}
+
+int icl_conv1x1_wgrad_dropout_norm_live(const float* x, const float* ss, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live,
+                                        int cin, int cout, int64_t s, int64_t gy_bstride, uint32_t seed, float p, const uint32_t* seed_dev,
+                                        void* stream) {
+  if (int rc = live_args(n, n_live, "conv1x1_wgrad_dropout_norm_live")) return rc;
+  return icl_conv1x1_wgrad_dropout_norm(x, ss, gy, gw, gbias, ws, n, cin, cout, s, gy_bstride, seed, p, seed_dev, stream);
 }
 
 }  // extern "C"

@@ -104,10 +104,13 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restri
 // gx = add + scatter(gy): the gradient of a tensor that feeds BOTH a max-pool and a skip connection (conv1 .. conv4 of the 3D U-Net,
 // /root/reference/code/networks/unet_3D_icl.py:100-116: `maxpool(conv)` and `up_concat(conv, .)`) in one pass — autograd would run the
 // pooling backward (a full write of gx) and then add the skip gradient (two full reads, one write).  `add` is the skip gradient:
-// [N][C] planes of the pooled-from extent, batches add_bstride apart (a channel slice of the concat gradient).
+// [N][C] planes of the pooled-from extent, batches add_bstride apart (a channel slice of the concat gradient).  Planes nc >= NCskip
+// (the samples past the live batch of the skip gradient, whose addend is exactly zero) take the pooling gradient alone: no load of
+// `add` is issued for them, and 0 + g keeps the bits of the full form.  Outputs are numbered plane-outermost: the test is uniform in
+// every workgroup but the one whose outputs straddle plane NCskip.
 __global__ __launch_bounds__(256) void maxpool2_bwd_add_kernel(const float* __restrict__ gy, const unsigned char* __restrict__ idx,
                                                                const float* __restrict__ add, float* __restrict__ gx, long NC, int C, int Do,
-                                                               int Ho, int Wo, int pd, long add_bstride) {
+                                                               int Ho, int Wo, int pd, long add_bstride, long NCskip) {
   const long total = NC * Do * Ho * Wo;
   const int H = Ho * 2, W = Wo * 2;
   const long plane = (long)Do * pd * H * W;
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_add_kernel(const float* __re
     const int bi = idx[o];
     for (int k = 0; k < nk; k += 2) {
       const long off = ((k >> 2) * H + ((k >> 1) & 1)) * (long)W;
-      const float2 s = *reinterpret_cast<const float2*>(a + off);
+      const float2 s = nc < NCskip ? *reinterpret_cast<const float2*>(a + off) : make_float2(0.f, 0.f);
       *reinterpret_cast<float2*>(p + off) = make_float2(s.x + (bi == k ? g : 0.f), s.y + (bi == k + 1 ? g : 0.f));
     }
   }
@@ -137,7 +140,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_add_kernel(const float* __re
 // on the step's critical path (the first encoder block's backward has nothing beside it): 100 us with the 8-byte form.  Same values.
 __global__ __launch_bounds__(256) void maxpool2_bwd_add_x2_kernel(const float* __restrict__ gy, const unsigned char* __restrict__ idx,
                                                                   const float* __restrict__ add, float* __restrict__ gx, long NC, int C, int Do,
-                                                                  int Ho, int Wo, int pd, long add_bstride) {
+                                                                  int Ho, int Wo, int pd, long add_bstride, long NCskip) {
   const int Wo2 = Wo >> 1;
   const long total = NC * Do * Ho * Wo2;
   const int H = Ho * 2, W = Wo * 2;
@@ -158,7 +161,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_add_x2_kernel(const float* _
     const int b0 = idx[o], b1 = idx[o + 1];
     for (int k = 0; k < nk; k += 2) {
       const long off = ((k >> 2) * H + ((k >> 1) & 1)) * (long)W;
-      const float4 s = *reinterpret_cast<const float4*>(a + off);
+      const float4 s = nc < NCskip ? *reinterpret_cast<const float4*>(a + off) : make_float4(0.f, 0.f, 0.f, 0.f);
       *reinterpret_cast<float4*>(p + off) = make_float4(s.x + (b0 == k ? g.x : 0.f), s.y + (b0 == k + 1 ? g.x : 0.f),
                                                         s.z + (b1 == k ? g.y : 0.f), s.w + (b1 == k + 1 ? g.y : 0.f));
     }

@@ -341,12 +341,17 @@ class PackedWeights:
             e[7] = True
 
 
-def conv3d_forward_raw(x, wp, bias, n, cin, cout, d, h, w, ks, x_bstride, y, y_bstride, wsplit=None, want_stats=False):
+def conv3d_forward_raw(x, wp, bias, n, cin, cout, d, h, w, ks, x_bstride, y, y_bstride, wsplit=None, want_stats=False, n_live=None):
     """``wsplit``: the pack's bf16 planes when the step's PackedWeights.begin_step() has split them already.
+    ``n_live`` (input gradients only; y dense): samples [0, n_live) are computed, samples [n_live, n) of y written as zeros (the `_live`
+    entry points); the plan, the workspaces and the FLOP / byte figures are those of a batch of n_live.
     ``want_stats``: returns the InstanceNorm statistics of y — [n * cout, slots, 3] (count, mean, M2) summaries written by the
     convolution's epilogue (icl_conv3d_fwd_presplit_stats) — or None when this shape / path does not produce them."""
     L = _lib.lib()
     s = d * h * w
+    if n_live is not None:
+        assert not want_stats
+        return _conv3d_forward_raw_live(x, wp, bias, n, n_live, cin, cout, d, h, w, ks, x_bstride, y, y_bstride, wsplit)
     # algorithmic work of this launch (SURVEY.md Appendix B): 2*taps*Cin*Cout FLOP per voxel; 4*(I+O+W) bytes
     flops = 2.0 * ks ** 3 * cin * cout * s * n
     nbytes = 4.0 * (n * s * (cin + cout) + ks ** 3 * cin * cout)
@@ -377,6 +382,31 @@ def conv3d_forward_raw(x, wp, bias, n, cin, cout, d, h, w, ks, x_bstride, y, y_b
                 return
         _lib.check(L.icl_conv3d_fwd(_ptr(x), _ptr(wp), _ptr(bias), _ptr(y), _ptr(ws), n, cin, cout, d, h, w, ks,
                                     x_bstride, y_bstride, _stream(x)), "conv3d_fwd")
+
+
+def _conv3d_forward_raw_live(x, wp, bias, n, k, cin, cout, d, h, w, ks, x_bstride, y, y_bstride, wsplit):
+    """conv3d_forward_raw on the live samples [0, k) of a batch of n (the same choice of entry points), zeros to y[k:]."""
+    L = _lib.lib()
+    s = d * h * w
+    flops = 2.0 * ks ** 3 * cin * cout * s * k
+    nbytes = 4.0 * (k * s * (cin + cout) + ks ** 3 * cin * cout)
+    need = L.icl_conv3d_fwd_ws_bytes(k, cin, cout, d, h, w, ks)
+    ws = _ws(need, x) if need else None
+    with _timed("conv3d_mfma_fwd_kernel", flops, nbytes, x):
+        if wsplit is not None and ks == 3:
+            kneed = L.icl_conv3d_fwd_presplit_ws_bytes(k, cin, cout, d, h, w)
+            if kneed:
+                kws = _ws(kneed, x)
+                rc = L.icl_conv3d_fwd_presplit_ws_live(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), _ptr(kws), n, k, cin, cout, d, h, w,
+                                                       x_bstride, y_bstride, _stream(x))
+            else:
+                rc = L.icl_conv3d_fwd_presplit_live(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), n, k, cin, cout, d, h, w, x_bstride,
+                                                    y_bstride, _stream(x))
+            if rc != 1:
+                _lib.check(rc, "conv3d_fwd_presplit_live")
+                return
+        _lib.check(L.icl_conv3d_fwd_live(_ptr(x), _ptr(wp), _ptr(bias), _ptr(y), _ptr(ws), n, k, cin, cout, d, h, w, ks,
+                                         x_bstride, y_bstride, _stream(x)), "conv3d_fwd_live")
 
 
 _ZERO_CACHE = {}
@@ -473,6 +503,17 @@ class _Conv3d(torch.autograd.Function):
         cout, ks = weight.shape[0], weight.shape[2]
         s = d * h * w
         gx = gw = gb = None
+        # live batch: the 3^3 split-product / fp32 MFMA paths and the <= 16-channel 1x1x1 path run on samples [0, k); every other form
+        # (channel GEMM, first-layer planes, one-input-channel kernels, 6^3 flat tile) reads the whole gradient — its tail is real zeros
+        k = live_of(gy, n)
+        if k is not None and (ctx.pointwise_gemm or getattr(ctx, "cin1", False) or cin * 27 <= FIRST_CONV_PLANES_MAX_K
+                              or (ks == 3 and (d, h, w) == (6, 6, 6) and _f6_split_ok(x, weight))
+                              or (ks == 1 and not ctx.pointwise_small)
+                              or (ks == 3 and not L.icl_conv3d_fwd_live_ok(n, k, cout, cin, d, h, w))):
+            # (last line: the 3^3 launcher splits the deep levels over the channel chunks by the batch size: a live batch runs only where
+            # it gets the full batch's kernels — its samples come out bit for bit; icl_conv1x1_small_live keeps the full batch's kernel itself)
+            k = None
+        nl = n if k is None else k
         lane = (ks == 3 and WgradLane.wants(x, s) and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not getattr(ctx, "cin1", False)
                 and not (cin * 27 <= FIRST_CONV_PLANES_MAX_K))
         if lane:
@@ -484,12 +525,18 @@ class _Conv3d(torch.autograd.Function):
                 gemm(weight, gy, cin, s, cout, cin, s, False, False, out=gx, ldc=s, batch=n, b_bstride=cout * s, c_bstride=cin * s)
             elif ctx.pointwise_small:
                 gx = torch.empty_like(x)
-                _lib.check(L.icl_conv1x1_small(_ptr(gy), _ptr(weight), None, _ptr(gx), n, cout, cin, s, 1, cin, _stream(x)),
-                           "conv1x1_small dgrad")
+                if k is not None:
+                    _lib.check(L.icl_conv1x1_small_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, k, cout, cin, s, 1, cin, _stream(x)),
+                               "conv1x1_small_live dgrad")
+                else:
+                    _lib.check(L.icl_conv1x1_small(_ptr(gy), _ptr(weight), None, _ptr(gx), n, cout, cin, s, 1, cin, _stream(x)),
+                               "conv1x1_small dgrad")
+                mark_live(gx, k)
             else:
                 gx = torch.empty_like(x)
                 wpt = ctx.wpt if ctx.wpt is not None else pack_weights(weight, 1)
-                conv3d_forward_raw(gy, wpt, None, n, cout, cin, d, h, w, ks, cout * s, gx, cin * s, wsplit=getattr(ctx, "wsd", None))
+                conv3d_forward_raw(gy, wpt, None, n, cout, cin, d, h, w, ks, cout * s, gx, cin * s, wsplit=getattr(ctx, "wsd", None), n_live=k)
+                mark_live(gx, k)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             gw = torch.empty_like(weight)
             gb = torch.empty(cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
@@ -503,14 +550,18 @@ class _Conv3d(torch.autograd.Function):
                 # optimisers, user code writing into .grad) every bias gets its own zero tensor.
                 gb = _cached_zeros(cout, x.device).view(cout) if getattr(StepScope.current, "packed", None) is not None else x.new_zeros(cout)
                 gb_arg = None
-            flops = 2.0 * ks ** 3 * cin * cout * s * n
-            nbytes = 4.0 * (n * s * (cin + cout) + 2 * ks ** 3 * cin * cout)
+            flops = 2.0 * ks ** 3 * cin * cout * s * nl
+            nbytes = 4.0 * (nl * s * (cin + cout) + 2 * ks ** 3 * cin * cout)
             if ks == 1 and s % 4 == 0 and n * s >= CONV1X1_WGRAD_MIN_VOXELS:
                 # big-volume 1x1x1 convolution: HBM-bound channel-major reduction, rows split over many waves
                 ws = _ws(L.icl_conv1x1_wgrad_ws_bytes(n, s, cin, cout), x)
                 with _timed("conv1x1_wgrad_kernel", flops, nbytes, x):
-                    _lib.check(L.icl_conv1x1_wgrad(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, cin, cout, s, cin * s,
-                                                   cout * s, _stream(x)), "conv1x1_wgrad")
+                    if k is not None:
+                        _lib.check(L.icl_conv1x1_wgrad_live(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, k, cin, cout, s, cin * s,
+                                                            cout * s, _stream(x)), "conv1x1_wgrad_live")
+                    else:
+                        _lib.check(L.icl_conv1x1_wgrad(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, cin, cout, s, cin * s,
+                                                       cout * s, _stream(x)), "conv1x1_wgrad")
             elif getattr(ctx, "cin1", False) and w % 4 == 0 and gb_arg is None and gy.data_ptr() % 16 == 0:
                 ws = _ws(L.icl_conv3d_cin1_wgrad_ws_bytes(n, d, h), x)
                 with _timed("conv_cin1_wgrad_kernel", flops, nbytes, x):
@@ -546,26 +597,27 @@ class _Conv3d(torch.autograd.Function):
                         if gb_arg is not None:
                             gb_arg.copy_(gb2)
                         return
+                    # (the `_live` entry points with k == n ARE the plain ones: one call site for both)
                     if swap:
-                        ws = _ws(L.icl_conv3d_wgrad_ws_bytes(n, cout, cin, ks), x)
+                        ws = _ws(L.icl_conv3d_wgrad_ws_bytes_live(n, nl, cout, cin, ks), x)
                         gws = torch.empty((cin, cout, ks, ks, ks), dtype=torch.float32, device=x.device)
                         with _timed("conv3d_mfma_wgrad_kernel", flops, nbytes, x):
-                            _lib.check(L.icl_conv3d_wgrad(_ptr(gy), _ptr(x), _ptr(gws), None, _ptr(ws), n, cout, cin, d, h, w, ks,
-                                                          cout * s, cin * s, _stream(x)), "conv3d_wgrad (roles exchanged)")
+                            _lib.check(L.icl_conv3d_wgrad_live(_ptr(gy), _ptr(x), _ptr(gws), None, _ptr(ws), n, nl, cout, cin, d, h, w, ks,
+                                                               cout * s, cin * s, _stream(x)), "conv3d_wgrad (roles exchanged)")
                         gw.copy_(gws.flip(2, 3, 4).transpose(0, 1))
                         return
-                    ws = _ws(L.icl_conv3d_wgrad_ws_bytes(n, cin, cout, ks), x)
+                    ws = _ws(L.icl_conv3d_wgrad_ws_bytes_live(n, nl, cin, cout, ks), x)
                     if gb_arg is None and DeferredWgradReduce.wants(weight):
                         # the slab sum is a leaf of the pass: queued, one launch for all of them when backward has ended
                         ns = ctypes.c_int32(0)
                         with _timed("conv3d_mfma_wgrad_kernel", flops, nbytes, x):
-                            _lib.check(L.icl_conv3d_wgrad_slabs(_ptr(x), _ptr(gy), _ptr(ws), n, cin, cout, d, h, w, ks, cin * s, cout * s,
-                                                                ctypes.byref(ns), _stream(x)), "conv3d_wgrad_slabs")
+                            _lib.check(L.icl_conv3d_wgrad_slabs_live(_ptr(x), _ptr(gy), _ptr(ws), n, nl, cin, cout, d, h, w, ks, cin * s,
+                                                                     cout * s, ctypes.byref(ns), _stream(x)), "conv3d_wgrad_slabs")
                         DeferredWgradReduce.defer(ws, gw, cout, cin, ks, ns.value, weight)
                         return
                     with _timed("conv3d_mfma_wgrad_kernel", flops, nbytes, x):
-                        _lib.check(L.icl_conv3d_wgrad(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, cin, cout, d, h, w, ks,
-                                                      cin * s, cout * s, _stream(x)), "conv3d_wgrad")
+                        _lib.check(L.icl_conv3d_wgrad_live(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, nl, cin, cout, d, h, w, ks,
+                                                           cin * s, cout * s, _stream(x)), "conv3d_wgrad")
                 if lane:
                     # deep level: beside the input gradient instead of behind it (the lane was forked where dY was complete, before
                     # the input gradient above was queued on this stream)
@@ -699,6 +751,12 @@ class _NormAct(torch.autograd.Function):
         if gamma is not None:
             dg = torch.empty_like(gamma)
             db = torch.empty_like(beta)
+        k = live_of(gy, n) if (mode == 0 and gamma is None) else None      # instance statistics: per sample
+        if k is not None:
+            ws = _ws(L.icl_norm_ws_bytes(k, c, s), x)
+            _lib.check(L.icl_norm_bwd_live(_ptr(gy), _ptr(x), _ptr(mean), _ptr(rstd), None, None, _ptr(gx), None, None, n, k, c, s, mode, ubs,
+                                           act, _ptr(ws), _stream(x)), "norm_bwd_live")
+            return mark_live(gx, k), dg, db, None, None, None, None, None, None, None, None
         ws = _ws(L.icl_norm_ws_bytes(n, c, s), x)
         _lib.check(L.icl_norm_bwd(_ptr(gy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(gx), _ptr(dg),
                                   _ptr(db), n, c, s, mode, ubs, act, _ptr(ws), _stream(x)), "norm_bwd")
@@ -779,6 +837,12 @@ class _NormActLazy(torch.autograd.Function):
         n, c = y.shape[0], y.shape[1]
         s = y.numel() // (n * c)
         gy = torch.empty_like(y)
+        k = live_of(ga, n)
+        if k is not None:
+            ws = _ws(L.icl_norm_ws_bytes(k, c, s), y)
+            _lib.check(L.icl_norm_bwd_live(_ptr(ga), _ptr(y), _ptr(mean), _ptr(rstd), None, None, _ptr(gy), None, None, n, k, c, s, 0, 1, 1,
+                                           _ptr(ws), _stream(y)), "norm_bwd_live")
+            return mark_live(gy, k), None, None
         ws = _ws(L.icl_norm_ws_bytes(n, c, s), y)
         _lib.check(L.icl_norm_bwd(_ptr(ga), _ptr(y), _ptr(mean), _ptr(rstd), None, None, _ptr(gy), None, None, n, c, s, 0, 1, 1, _ptr(ws),
                                   _stream(y)), "norm_bwd")
@@ -968,8 +1032,15 @@ class _SkipAndPool(torch.autograd.Function):
         ok = (gskip is not None and gskip.dtype == torch.float32 and tuple(gskip.shape) == tuple(gx.shape)
               and gskip.stride()[1:] == (plane, 4 * h * w, 2 * w, 1) and gskip.stride(0) % 2 == 0 and gskip.data_ptr() % 8 == 0)
         if ok:
-            _lib.check(L.icl_maxpool2_bwd_add(_ptr(gy), _ptr(idx), _vp(gskip.data_ptr()), _ptr(gx), n, c, d, h, w, 2, gskip.stride(0),
-                                              _stream(gy)), "maxpool2_bwd_add")
+            # the mark stops here: a live-batch skip gradient meets the full pooling gradient.  Samples past the live batch take the
+            # pooling gradient alone (no load of the skip addend, whose bytes there are zeros)
+            k = live_of(gskip, n)
+            if k is not None:
+                _lib.check(L.icl_maxpool2_bwd_add_live(_ptr(gy), _ptr(idx), _vp(gskip.data_ptr()), _ptr(gx), n, k, c, d, h, w, 2,
+                                                       gskip.stride(0), _stream(gy)), "maxpool2_bwd_add_live")
+            else:
+                _lib.check(L.icl_maxpool2_bwd_add(_ptr(gy), _ptr(idx), _vp(gskip.data_ptr()), _ptr(gx), n, c, d, h, w, 2, gskip.stride(0),
+                                                  _stream(gy)), "maxpool2_bwd_add")
             return gx
         _lib.check(L.icl_maxpool2_bwd(_ptr(gy), _ptr(idx), _ptr(gx), n * c, d, h, w, 2, _stream(gy)), "maxpool2_bwd")
         return gx if gskip is None else gx + gskip
@@ -1085,16 +1156,24 @@ class _UpCat(torch.autograd.Function):
         n, cs, cd, d, h, w = ctx.dims
         s = d * h * w
         gskip = gdeep = None
+        k = live_of(g, n)
         if ctx.needs_input_grad[0]:
             # a VIEW of the concat gradient, not a copy: the skip tensor also feeds the max-pool, so autograd adds this to the pooling
-            # gradient right away (one strided read instead of a copy pass plus a read); a sole consumer makes it contiguous itself
-            gskip = g[:, :cs]
+            # gradient right away (one strided read instead of a copy pass plus a read); a sole consumer makes it contiguous itself.
+            # A view does not inherit the live-batch mark of its base: this one is marked explicitly (its tail is g's tail)
+            gskip = mark_live(g[:, :cs], k)
         if ctx.needs_input_grad[1]:
             gdeep = torch.empty((n, cd, d // 2, h // 2, w // 2), dtype=torch.float32, device=g.device)
             gv = g[:, cs:]
-            ws = _ws(L.icl_trilinear_bwd_ws_bytes(n, cd, d // 2, h // 2, w // 2, d, h, w), g)
-            _lib.check(L.icl_trilinear_bwd(_vp(gv.data_ptr()), _ptr(gdeep), _ptr(ws), n, cd, d // 2, h // 2, w // 2, d, h, w,
-                                           (cs + cd) * s, 0, _stream(g)), "trilinear_bwd")
+            if k is not None:
+                ws = _ws(L.icl_trilinear_bwd_ws_bytes(k, cd, d // 2, h // 2, w // 2, d, h, w), g)
+                _lib.check(L.icl_trilinear_bwd_live(_vp(gv.data_ptr()), _ptr(gdeep), _ptr(ws), n, k, cd, d // 2, h // 2, w // 2, d, h, w,
+                                                    (cs + cd) * s, 0, _stream(g)), "trilinear_bwd_live")
+                mark_live(gdeep, k)
+            else:
+                ws = _ws(L.icl_trilinear_bwd_ws_bytes(n, cd, d // 2, h // 2, w // 2, d, h, w), g)
+                _lib.check(L.icl_trilinear_bwd(_vp(gv.data_ptr()), _ptr(gdeep), _ptr(ws), n, cd, d // 2, h // 2, w // 2, d, h, w,
+                                               (cs + cd) * s, 0, _stream(g)), "trilinear_bwd")
         return gskip, gdeep
 
 
@@ -1386,17 +1465,21 @@ class _DropoutConv1x1(torch.autograd.Function):
         cout = weight.shape[0]
         s = x.numel() // (n * cin)
         gx = gw = gb = None
+        k = live_of(gy, n)
+        nl = n if k is None else k
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            _lib.check(L.icl_conv1x1_dropout(_ptr(gy), _ptr(weight), None, _ptr(gx), n, cout, cin, s, 1, cin, 2, seed, p, _ptr(ctx.seed_dev),
-                                             _stream(x)), "conv1x1_dropout dgrad")
+            # (the `_live` entry points with n_live == n ARE the plain ones)
+            _lib.check(L.icl_conv1x1_dropout_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, nl, cout, cin, s, 1, cin, 2, seed, p,
+                                                  _ptr(ctx.seed_dev), _stream(x)), "conv1x1_dropout dgrad")
+            mark_live(gx, k)
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             gw = torch.empty_like(weight)
             gb = torch.empty(cout, dtype=torch.float32, device=x.device) if has_bias else None
             ws = _ws(L.icl_conv1x1_wgrad_ws_bytes(n, s, cin, cout), x)
-            with _timed("conv1x1_wgrad_kernel", 2.0 * cin * cout * s * n, 4.0 * n * s * (cin + cout), x):
-                _lib.check(L.icl_conv1x1_wgrad_dropout(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), n, cin, cout, s, cout * s, seed, p,
-                                                       _ptr(ctx.seed_dev), _stream(x)), "conv1x1_wgrad_dropout")
+            with _timed("conv1x1_wgrad_kernel", 2.0 * cin * cout * s * nl, 4.0 * nl * s * (cin + cout), x):
+                _lib.check(L.icl_conv1x1_wgrad_dropout_live(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), n, nl, cin, cout, s, cout * s, seed,
+                                                            p, _ptr(ctx.seed_dev), _stream(x)), "conv1x1_wgrad_dropout")
         return gx, gw, gb, None, None, None
 
 
@@ -1428,20 +1511,26 @@ class _DropoutConv1x1Lazy(torch.autograd.Function):
         cout = weight.shape[0]
         s = t.numel() // (n * cin)
         gx = gw = gb = None
+        k = live_of(gy, n)
+        nl = n if k is None else k
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(t)      # the gradient of the NORMALISED activation (what `t` stands for in the autograd graph)
+            # (the `_live` entry points with n_live == n ARE the plain ones)
             if p > 0.0:
-                _lib.check(L.icl_conv1x1_dropout(_ptr(gy), _ptr(weight), None, _ptr(gx), n, cout, cin, s, 1, cin, 2, seed, p, _ptr(ctx.seed_dev),
-                                                 _stream(t)), "conv1x1_dropout dgrad")
+                _lib.check(L.icl_conv1x1_dropout_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, nl, cout, cin, s, 1, cin, 2, seed, p,
+                                                      _ptr(ctx.seed_dev), _stream(t)), "conv1x1_dropout dgrad")
             else:
-                _lib.check(L.icl_conv1x1_small(_ptr(gy), _ptr(weight), None, _ptr(gx), n, cout, cin, s, 1, cin, _stream(t)), "conv1x1_small dgrad")
+                _lib.check(L.icl_conv1x1_small_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, nl, cout, cin, s, 1, cin, _stream(t)),
+                           "conv1x1_small dgrad")
+            mark_live(gx, k)
         if ctx.needs_input_grad[2] or (has_bias and ctx.needs_input_grad[3]):
             gw = torch.empty_like(weight)
             gb = torch.empty(cout, dtype=torch.float32, device=t.device) if has_bias else None
             ws = _ws(L.icl_conv1x1_wgrad_ws_bytes(n, s, cin, cout), t)
-            with _timed("conv1x1_wgrad_kernel", 2.0 * cin * cout * s * n, 4.0 * n * s * (cin + cout), t):
-                _lib.check(L.icl_conv1x1_wgrad_dropout_norm(_ptr(t), _ptr(ss), _ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), n, cin, cout, s, cout * s,
-                                                            seed, p, _ptr(ctx.seed_dev), _stream(t)), "conv1x1_wgrad_dropout_norm")
+            with _timed("conv1x1_wgrad_kernel", 2.0 * cin * cout * s * nl, 4.0 * nl * s * (cin + cout), t):
+                _lib.check(L.icl_conv1x1_wgrad_dropout_norm_live(_ptr(t), _ptr(ss), _ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), n, nl, cin, cout, s,
+                                                                 cout * s, seed, p, _ptr(ctx.seed_dev), _stream(t)),
+                           "conv1x1_wgrad_dropout_norm")
         return gx, None, gw, gb, None, None, None
 
 
@@ -1901,8 +1990,45 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor, idx_back: torch.Tensor) ->
     return _GatherRows.apply(src, idx, idx_back)
 
 
+# --------------------------------------------------------------------------------------
+# Live batch (DESIGN.md §4.4 "Live batch"): "samples [0, k) of this gradient hold values, samples [k, n) are exactly zero" — in MEMORY too: the tail is
+# always written, so a consumer that does not know the mark reads a correct gradient.  The unlabeled stream's logits enter the loss only
+# as a detached target (utils/losses.py:294), so autograd hands _SplitBatch.backward no gradient for them; every Function of the upper
+# decoder's backward (all per sample) then runs its kernels on the live samples and passes the mark on with its input gradient.
+# --------------------------------------------------------------------------------------
+
+_LIVE_ATTR = "_icl_live_batch"
+
+
+def live_batch_enabled() -> bool:
+    """ICL_LIVE_BATCH=0 (read per call): no mark is ever created — every backward launches what it launched without this."""
+    return os.environ.get("ICL_LIVE_BATCH", "1") != "0"
+
+
+def mark_live(t: Optional[torch.Tensor], k: Optional[int]):
+    """Marks ``t`` (the caller has WRITTEN zeros to t[k:]) as live on samples [0, k); returns ``t``.  The mark is an attribute of this
+    tensor object — a view, slice or copy of it does not carry it — and holds the tensor's version: an in-place write (autograd
+    accumulating into the buffer) voids it.  k None / 0 / >= n: nothing to mark."""
+    if t is None or k is None or t.dim() == 0 or not (0 < int(k) < t.shape[0]) or not live_batch_enabled():
+        return t
+    setattr(t, _LIVE_ATTR, (int(k), t._version))
+    return t
+
+
+def live_of(t: Optional[torch.Tensor], n: int) -> Optional[int]:
+    """The live sample count of gradient ``t`` of a batch of ``n``, or None: full batch (no mark, a stale one, another leading dimension)."""
+    m = getattr(t, _LIVE_ATTR, None) if t is not None else None
+    if m is None or not live_batch_enabled():
+        return None
+    k, version = m
+    if version != t._version or t.dim() == 0 or t.shape[0] != n or not (0 < k < n):
+        return None
+    return k
+
+
 class _SplitBatch(torch.autograd.Function):
-    """(x[:k], x[k:]) whose gradient is ONE concatenation; two Python slices cost two zero fills, two copies and an add."""
+    """(x[:k], x[k:]) whose gradient is ONE concatenation; two Python slices cost two zero fills, two copies and an add.  A missing second
+    half is the one producer of a live-batch mark (``mark_live``)."""
 
     @staticmethod
     def forward(ctx, x, k):
@@ -1925,12 +2051,13 @@ class _SplitBatch(torch.autograd.Function):
             out = torch.empty((ctx.n,) + ctx.tail, dtype=torch.float32, device=ref.device)
             if all(t is None or t.data_ptr() % 16 == 0 for t in (ga, gb)):
                 _lib.check(_lib.lib().icl_concat2(_ptr(ga), na, _ptr(gb), nb, _ptr(out), _stream(ref)), "concat2")
-                return out, None
+                return mark_live(out, ctx.k if gb is None else None), None
+        live = ctx.k if (gb is None and ga is not None) else None
         if ga is None:
             ga = ref.new_zeros((ctx.k,) + ctx.tail)
         if gb is None:
             gb = ref.new_zeros((ctx.n - ctx.k,) + ctx.tail)
-        return torch.cat([ga, gb], 0), None
+        return mark_live(torch.cat([ga, gb], 0), live), None
 
 
 def cat_batch(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -99,6 +99,38 @@ int icl_conv3d_wgrad_slabs(const float* x, const float* gy, void* ws, int n, int
 int icl_conv3d_wgrad_reduce_multi(const void* const* ws, void* const* gw, const int32_t* cout, const int32_t* cin, const int32_t* ks,
                                   const int32_t* nslabs, int count, void* stream);
 
+/* ---- Live batch: the backward of the upper decoder on a gradient whose samples [n_live, n) are exactly zero.  The unlabeled stream's
+ * logits enter the loss only as a detached target (`de_predicts = predicts.clone().detach()`, /root/reference/code/utils/losses.py:294), so
+ * the gradient of the batch split has a zero second half and every operator from `final` down to the skip gradients of conv1 / conv2 and
+ * the decoder share of up3's gradient (unet_3D_icl.py:113-117, networks/utils.py:104-109,264,271-276) — all of them per sample — maps it
+ * to zeros.  A `_live` sibling takes n and n_live: samples [0, n_live) are computed exactly as the entry point computes them for
+ * n = n_live on the same pointers and batch strides; samples [n_live, n) of every output GRADIENT (dense [n][...] tensors) are written as
+ * zeros by the same call on the same stream (a fill node under graph capture) — nothing ever reads an unwritten tail.  Weight / bias
+ * gradients have no per-sample output: their live form keeps the launch plan of the batch of n — the tile-list kernels launch only the
+ * workgroups that own a live tile and write the other slabs as zeros, everything else runs the whole batch — so the sums are bit for bit
+ * those of the entry point called with n (workspaces as for n).  n_live == n is the entry point itself.
+ * 3x3x3 (and 1x1x1) input gradient = the forward entry points on the transposed pack (utils.py:104,107): */
+/* icl_conv3d_fwd_live_ok: 1 when the launcher plans the 3x3x3 product for a batch of n_live exactly as for a batch of n (split-product
+ * kernels, no split over the channel chunks), so that the live samples equal the full call's bit for bit; 0: run the full batch. */
+int icl_conv3d_fwd_live_ok(int n, int n_live, int cin, int cout, int d, int h, int w);
+/* For the tests (per thread, like icl_last_kernel_name): the kernel of the last live input-gradient launch, and the workgroups the last
+ * tile-list weight-gradient launch started / its plan holds (started < planned: a live batch skipped the workgroups without a live tile). */
+const char* icl_last_live_fwd_kernel_name(void);
+void icl_last_wgrad_grid(int32_t* launched, int32_t* planned);
+int icl_conv3d_fwd_presplit_live(const float* x, const void* wsplit, const float* bias, float* y, int n, int n_live, int cin, int cout, int d,
+                                 int h, int w, int64_t x_bstride, int64_t y_bstride, void* stream);
+int icl_conv3d_fwd_presplit_ws_live(const float* x, const void* wsplit, const float* bias, float* y, void* ws, int n, int n_live, int cin,
+                                    int cout, int d, int h, int w, int64_t x_bstride, int64_t y_bstride, void* stream);
+int icl_conv3d_fwd_live(const float* x, const float* wp, const float* bias, float* y, void* ws, int n, int n_live, int cin, int cout, int d,
+                        int h, int w, int ks, int64_t x_bstride, int64_t y_bstride, void* stream);
+/* weight gradient (utils.py:104,107; with x and gy exchanged: up_concat1.conv1, 48 -> 16).  The workspace queries of the forward forms
+ * (icl_conv3d_fwd_ws_bytes, icl_conv3d_fwd_presplit_ws_bytes) are asked with n = n_live. */
+int64_t icl_conv3d_wgrad_ws_bytes_live(int n, int n_live, int cin, int cout, int ks);
+int icl_conv3d_wgrad_live(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live, int cin, int cout, int d,
+                          int h, int w, int ks, int64_t x_bstride, int64_t gy_bstride, void* stream);
+int icl_conv3d_wgrad_slabs_live(const float* x, const float* gy, void* ws, int n, int n_live, int cin, int cout, int d, int h, int w, int ks,
+                                int64_t x_bstride, int64_t gy_bstride, int32_t* nslabs, void* stream);
+
 /* ---- InstanceNorm3d(+ReLU) (networks/utils.py:105-106,108-109) and BatchNorm3d(+ReLU)
  * (networks/unet_3D_icl.py:325-340).  mode 0 = instance (group = (n,c)), 1 = batch (group = c).
  * use_batch_stats 0 = normalise with the given mean/rstd... (eval-mode BatchNorm: mean=running_mean,
@@ -110,6 +142,11 @@ int icl_norm_fwd(const float* x, float* y, float* mean, float* rstd, const float
 int icl_norm_bwd(const float* gy, const float* x, const float* mean, const float* rstd, const float* gamma,
                  const float* beta, float* gx, float* dgamma, float* dbeta, int n, int c, int64_t s, int mode,
                  int use_batch_stats, int act, void* ws, void* stream);
+/* live batch (see icl_conv3d_fwd_presplit_live): InstanceNorm3d + ReLU backward of UnetConv3 (utils.py:105-106,108-109) on samples
+ * [0, n_live), zeros to the rest of gx.  mode 0 without an affine pair only (a batch group couples the samples). */
+int icl_norm_bwd_live(const float* gy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* gx,
+                      float* dgamma, float* dbeta, int n, int n_live, int c, int64_t s, int mode, int use_batch_stats, int act, void* ws,
+                      void* stream);
 /* Same, with a residual branch: y = act(norm(x) + res) and, backward, gres = act'(.) * gy next to gx.  This is the tail of
  * MONAI 1.0.1 UnetResBlock.forward ("out = norm2(conv2(.)); out += residual; out = lrelu(out)") used by every encoder/decoder
  * block of SwinUNETR (networks/swinunetr_icl.py:123-223).  res / gres may be NULL (then identical to icl_norm_fwd/_bwd). */
@@ -152,6 +189,11 @@ int icl_maxpool2_bwd(const float* gy, const uint8_t* idx, float* gx, int64_t nc,
  * elements apart (a channel slice of the concat gradient). */
 int icl_maxpool2_bwd_add(const float* gy, const uint8_t* idx, const float* add, float* gx, int n, int c, int dout, int hout, int wout,
                          int pool_depth, int64_t add_bstride, void* stream);
+/* the same where the skip gradient carries a live batch (unet_3D_icl.py:100-101,113-116: the skip gradients of conv1 / conv2 come from
+ * the upper decoder): samples >= skip_live take the pooling gradient alone and issue no load of `add` (its bytes there are zeros).  The
+ * pooling gradient gy is a full batch; so is gx.  Bit-identical to icl_maxpool2_bwd_add on an addend with a zero tail. */
+int icl_maxpool2_bwd_add_live(const float* gy, const uint8_t* idx, const float* add, float* gx, int n, int skip_live, int c, int dout, int hout,
+                              int wout, int pool_depth, int64_t add_bstride, void* stream);
 
 /* ---- trilinear / bilinear (D = 1) resize (networks/utils.py:264; networks/unet_icl.py:84-85; utils/losses.py:245,263,281,292).
  * align_corners=0: source scale in/out (what ATen uses for size= and for scale_factor=2); 1: (in-1)/(out-1). */
@@ -161,6 +203,10 @@ int icl_trilinear_fwd(const float* x, float* y, int n, int c, int di, int hi, in
 int64_t icl_trilinear_bwd_ws_bytes(int n, int c, int di, int hi, int wi, int dout, int hout, int wout);
 int icl_trilinear_bwd(const float* gy, float* gx, void* ws, int n, int c, int di, int hi, int wi, int dout, int hout, int wout,
                       int64_t gy_bstride, int align_corners, void* stream);
+/* live batch (see icl_conv3d_fwd_presplit_live): the backward of nn.Upsample(scale_factor=2) in UnetUp3_CT (utils.py:264,271-276) on
+ * samples [0, n_live) of gy, zeros to the rest of gx (dense); ws as for n = n_live. */
+int icl_trilinear_bwd_live(const float* gy, float* gx, void* ws, int n, int n_live, int c, int di, int hi, int wi, int dout, int hout, int wout,
+                           int64_t gy_bstride, int align_corners, void* stream);
 
 /* ---- strided row copy (torch.cat([skip, up], 1), networks/utils.py:276) */
 int icl_copy_rows(const float* src, float* dst, int64_t rows, int64_t row_elems, int64_t src_stride, int64_t dst_stride,
@@ -196,6 +242,20 @@ int icl_conv1x1_dropout_norm(const float* x, const float* ss, const float* w, co
                              int w_ostride, int w_istride, uint32_t seed, float p, const uint32_t* seed_dev, void* stream);
 int icl_conv1x1_wgrad_dropout_norm(const float* x, const float* ss, const float* gy, float* gw, float* gbias, void* ws, int n, int cin,
                                    int cout, int64_t s, int64_t gy_bstride, uint32_t seed, float p, const uint32_t* seed_dev, void* stream);
+/* live batch (see icl_conv3d_fwd_presplit_live) of the `final` layer's backward (unet_3D_icl.py:116-117): input gradients with a zeroed
+ * tail, weight / bias gradients over samples [0, n_live).  The dropout mask hashes the element index (b * C + c) * S + v; the live samples
+ * are a prefix, so their masks are those of the full batch.  The two input-gradient forms choose their kernel by the FULL batch (the
+ * big-volume kernel from n * s = 65536 on): the live samples are bit for bit those of the full call; icl_conv1x1_dropout_live returns 1
+ * (nothing launched, nothing zeroed) for n * s < 65536.  The weight / bias gradient forms run the whole batch (workspaces as for n). */
+int icl_conv1x1_small_live(const float* x, const float* w, const float* bias, float* y, int n, int n_live, int cin, int cout, int64_t s,
+                           int w_ostride, int w_istride, void* stream);
+int icl_conv1x1_dropout_live(const float* x, const float* w, const float* bias, float* y, int n, int n_live, int cin, int cout, int64_t s,
+                             int w_ostride, int w_istride, int mask_mode, uint32_t seed, float p, const uint32_t* seed_dev, void* stream);
+int icl_conv1x1_wgrad_dropout_live(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live, int cin, int cout,
+                                   int64_t s, int64_t gy_bstride, uint32_t seed, float p, const uint32_t* seed_dev, void* stream);
+int icl_conv1x1_wgrad_dropout_norm_live(const float* x, const float* ss, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live,
+                                        int cin, int cout, int64_t s, int64_t gy_bstride, uint32_t seed, float p, const uint32_t* seed_dev,
+                                        void* stream);
 
 /* ---- nn.Dropout(p) (networks/unet_3D_icl.py:67-68,110,116): y = keep ? x/(1-p) : 0 with a counter-based
  * mask keyed by (seed, element index); calling it again with the same seed on dY is the backward.  seed_dev (may be
@@ -362,6 +422,9 @@ int icl_linear_wgrad(const float* gy, const float* x, float* dw, float* db, void
 int64_t icl_conv1x1_wgrad_ws_bytes(int n, int64_t s, int cin, int cout);
 int icl_conv1x1_wgrad(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int cin, int cout, int64_t s,
                       int64_t x_bstride, int64_t gy_bstride, void* stream);
+/* live batch (see icl_conv3d_fwd_presplit_live; `final` without dropout, unet_3D_icl.py:117): the entry point on the whole batch */
+int icl_conv1x1_wgrad_live(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live, int cin, int cout, int64_t s,
+                           int64_t x_bstride, int64_t gy_bstride, void* stream);
 
 /* ---- Swin window attention: WindowAttention.forward core, networks/swinunetr_icl.py:728-747 —
  *   attn = softmax((q*scale) @ k^T + relative_position_bias [+ shift mask]);  out = attn @ v   per (window, head).

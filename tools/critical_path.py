@@ -40,8 +40,9 @@ def grad_mark(t, name):
 
 def run_backbone(self, x, heads=None):
     mark("forward start")
-    c1, p1 = ops.skip_and_pool(self.conv1(x))
-    c2, p2 = ops.skip_and_pool(self.conv2(grad_mark(p1, "B gradient of pool1 ready (conv2..4 backward done)")))
+    # (the model's own run_backbone, networks/unet_3D.py, with marks: deferred normalisation of the upper levels, fused `final`)
+    c1, p1 = ops.skip_and_pool(self.conv1(x, lazy=True))
+    c2, p2 = ops.skip_and_pool(self.conv2(grad_mark(p1, "B gradient of pool1 ready (conv2..4 backward done)"), lazy=True))
     c3, p3 = ops.skip_and_pool(self.conv3(p2))
     c3 = grad_mark(c3, "B skip gradient of c3 ready (up_concat3's convolutions and concat backward done)")
     c4, p4 = ops.skip_and_pool(self.conv4(p3))
@@ -59,9 +60,15 @@ def run_backbone(self, x, heads=None):
     if os.environ.get("CP_DETACH_HEADS", "0") != "0":      # what would the step take if the deep backward did not wait for the aligners?
         a_in = [t.detach() for t in a_in]
     extra = heads(a_in)
-    up2 = self.up_concat2(c2, grad_mark(up3, "B decoder gradient of up3 ready (up2/up1/final backward done)"))
-    up1 = self.dropout2(self.up_concat1(c1, up2))
-    out = self.final(up1)
+    up2 = self.up_concat2(c2, grad_mark(up3, "B decoder gradient of up3 ready (up2/up1/final backward done)"), lazy=True)
+    up1 = self.up_concat1(c1, up2, lazy=True)
+    drop = self.dropout2.p if (self.dropout2.training and self.dropout2.p > 0.0) else 0.0
+    if isinstance(up1, ops.LazyAct):
+        out = ops.conv1x1_lazy(up1, self.final.weight, self.final.bias, drop)
+    elif drop > 0.0:
+        out = ops.dropout_conv1x1(up1, self.final.weight, self.final.bias, drop)
+    else:
+        out = self.final(self.dropout2(up1))
     mark("F final conv done (main)")
     return out, [center, up4, up3], extra
 

@@ -6,6 +6,8 @@
 # (the connected-component kernels of components.h — cc_tile_kernel<uint8 | int64, 1 | 2 | 3>, cc_merge_kernel<uint8 | int64, 1 | 2 | 3>,
 #  cc_flatten_kernel, cc_reduce_kernel<uint8 | int64>, cc_finish_kernel, cc_filter_kernel<uint8 | int64> — are launched by
 #  tests/test_gpu_components.py: test_case and test_scattered_prediction_64x80x72 run both element sizes under each connectivity)
+# (the live batch of the upper decoder's backward, DESIGN.md §4.4, adds no kernel: its launches are the same kernels on fewer samples plus
+#  fill nodes; maxpool2_bwd_add_kernel / maxpool2_bwd_add_x2_kernel gained one argument — tests/test_gpu_live_batch.py runs both sides of it)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/cov

@@ -22,6 +22,7 @@
 #include "kernels/token.h"
 #include "kernels/gemm.h"
 #include "kernels/datafeed.h"
+#include "kernels/rankindex.h"
 #include "kernels/qchain.h"
 #include "kernels/metrics.h"
 #include "kernels/metrics_surface.h"
@@ -2396,48 +2397,134 @@ int icl_crop_rotflip(const void* const* images, const void* const* labels, const
   return check_launch("crop_rotflip");
 }
 
-int icl_volume_feed(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params, int batch,
-                    float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream) {
-  if (!images || !labels || !int_params || !float_params || !image_out || !label_out) return fail(-1, "volume_feed: null pointer");
-  if (batch < 1 || batch > icl::kFeedMaxBatch) return fail(-1, "volume_feed: batch %d out of range (1 <= batch <= %d)", batch, icl::kFeedMaxBatch);
-  if (R0 < 1 || R1 < 1 || R2 < 1) return fail(-1, "volume_feed: output extents %d x %d x %d (each must be >= 1)", R0, R1, R2);
-  if ((long)R0 * R1 * R2 > 0x7fffffffL) return fail(-1, "volume_feed: output extents %d x %d x %d (more than 2^31 - 1 voxels a sample)", R0, R1, R2);
+namespace {
+
+// The argument record of icl_volume_feed / icl_volume_feed_origins from the caller's rows, with every check of both.  device_origins:
+// the origin fields of the rows are not read; the record's c0, c1, c2 become the largest legal origin n - s (the kernel clamps).
+int volume_feed_records(const char* what, const void* const* images, const void* const* labels, const int32_t* int_params,
+                        const float* float_params, int batch, int R0, int R1, int R2, bool device_origins, icl::VolumeFeedBatch& fb) {
+  if (batch < 1 || batch > icl::kFeedMaxBatch) return fail(-1, "%s: batch %d out of range (1 <= batch <= %d)", what, batch, icl::kFeedMaxBatch);
+  if (R0 < 1 || R1 < 1 || R2 < 1) return fail(-1, "%s: output extents %d x %d x %d (each must be >= 1)", what, R0, R1, R2);
+  if ((long)R0 * R1 * R2 > 0x7fffffffL) return fail(-1, "%s: output extents %d x %d x %d (more than 2^31 - 1 voxels a sample)", what, R0, R1, R2);
   const int R[3] = {R0, R1, R2};
-  icl::VolumeFeedBatch fb{};
   for (int b = 0; b < batch; ++b) {
     const int32_t* q = int_params + 14 * b;      // n[3], c[3], s[3], l[3], flip, k
     icl::VolumeFeedSample& s = fb.s[b];
     s.image = (const float*)images[b];
     s.label = (const uint8_t*)labels[b];
-    if (!s.image || !s.label) return fail(-1, "volume_feed: sample %d: null volume pointer", b);
+    if (!s.image || !s.label) return fail(-1, "%s: sample %d: null volume pointer", what, b);
     for (int a = 0; a < 3; ++a) {
       const int n = q[a], c = q[3 + a], sz = q[6 + a], l = q[9 + a];
-      if (n < 1) return fail(-1, "volume_feed: sample %d: extent %d of axis %d (must be >= 1)", b, n, a);
-      if (c < 0 || sz < 1 || (long)c + sz > n)
-        return fail(-1, "volume_feed: sample %d: crop [%d, %d + %d) of axis %d outside the extent %d", b, c, c, sz, a, n);
+      if (n < 1) return fail(-1, "%s: sample %d: extent %d of axis %d (must be >= 1)", what, b, n, a);
+      if (device_origins) {
+        if (sz < 1 || sz > n) return fail(-1, "%s: sample %d: crop size %d of axis %d outside 1..%d", what, b, sz, a, n);
+      } else if (c < 0 || sz < 1 || (long)c + sz > n) {
+        return fail(-1, "%s: sample %d: crop [%d, %d + %d) of axis %d outside the extent %d", what, b, c, c, sz, a, n);
+      }
       if (l < 0 || (long)l + sz > R[a])
-        return fail(-1, "volume_feed: sample %d: left pad %d + crop size %d of axis %d outside the output extent %d", b, l, sz, a, R[a]);
+        return fail(-1, "%s: sample %d: left pad %d + crop size %d of axis %d outside the output extent %d", what, b, l, sz, a, R[a]);
     }
     s.n1 = q[1]; s.n2 = q[2];
     s.c0 = q[3]; s.c1 = q[4]; s.c2 = q[5];
     s.s0 = q[6]; s.s1 = q[7]; s.s2 = q[8];
+    if (device_origins) { s.c0 = q[0] - s.s0; s.c1 = q[1] - s.s1; s.c2 = q[2] - s.s2; }
     s.l0 = q[9]; s.l1 = q[10]; s.l2 = q[11];
     s.flip = q[12]; s.k = q[13];
     s.mul = float_params[2 * b]; s.add = float_params[2 * b + 1];
-    if (s.flip < 0 || s.flip > 7) return fail(-1, "volume_feed: sample %d: flip mask %d outside 0..7", b, s.flip);
-    if (s.k < 0 || s.k > 3) return fail(-1, "volume_feed: sample %d: k = %d outside 0..3", b, s.k);
+    if (s.flip < 0 || s.flip > 7) return fail(-1, "%s: sample %d: flip mask %d outside 0..7", what, b, s.flip);
+    if (s.k < 0 || s.k > 3) return fail(-1, "%s: sample %d: k = %d outside 0..3", what, b, s.k);
     if ((s.k & 1) && R0 != R1)
-      return fail(-1, "volume_feed: sample %d: k = %d with output extents %d x %d (an odd rot90 needs R0 == R1)", b, s.k, R0, R1);
+      return fail(-1, "%s: sample %d: k = %d with output extents %d x %d (an odd rot90 needs R0 == R1)", what, b, s.k, R0, R1);
   }
+  return 0;
+}
+
+// extents of a volume the rank index takes: MONAI casts crop centres to uint16, and the index counts in uint32
+int rank_extents_ok(const char* what, int b, int n0, int n1, int n2) {
+  if (n0 < 1 || n1 < 1 || n2 < 1 || n0 > 65535 || n1 > 65535 || n2 > 65535)
+    return fail(-1, "%s: sample %d: extents %d x %d x %d (each must be in 1..65535)", what, b, n0, n1, n2);
+  if ((long)n0 * n1 * n2 > 0x7fffffffL) return fail(-1, "%s: sample %d: extents %d x %d x %d (more than 2^31 - 1 voxels)", what, b, n0, n1, n2);
+  return 0;
+}
+
+inline bool rank_vec_ok(const void* image, const void* label) { return aligned16(image) && ((uintptr_t)label & 3) == 0; }
+
+}  // namespace
+
+int icl_volume_feed(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params, int batch,
+                    float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream) {
+  if (!images || !labels || !int_params || !float_params || !image_out || !label_out) return fail(-1, "volume_feed: null pointer");
+  icl::VolumeFeedBatch fb{};
+  if (const int rc = volume_feed_records("volume_feed", images, labels, int_params, float_params, batch, R0, R1, R2, false, fb)) return rc;
   const long voxels = (long)R0 * R1 * R2;      // per sample; one grid row per sample
   if ((R2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
-    ICL_LAUNCH(icl::volume_feed_kernel<4>, dim3(grid_for(voxels / 4, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb, image_out,
-               (long long*)label_out, R0, R1, R2);
+    ICL_LAUNCH((icl::volume_feed_kernel<4, false>), dim3(grid_for(voxels / 4, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb,
+               (const int*)nullptr, image_out, (long long*)label_out, R0, R1, R2);
   } else {
-    ICL_LAUNCH(icl::volume_feed_kernel<1>, dim3(grid_for(voxels, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb, image_out,
-               (long long*)label_out, R0, R1, R2);
+    ICL_LAUNCH((icl::volume_feed_kernel<1, false>), dim3(grid_for(voxels, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb,
+               (const int*)nullptr, image_out, (long long*)label_out, R0, R1, R2);
   }
   return check_launch("volume_feed");
+}
+
+int icl_volume_feed_origins(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params,
+                            int batch, const int32_t* origins, float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream) {
+  if (!images || !labels || !int_params || !float_params || !origins || !image_out || !label_out)
+    return fail(-1, "volume_feed_origins: null pointer");
+  icl::VolumeFeedBatch fb{};
+  if (const int rc = volume_feed_records("volume_feed_origins", images, labels, int_params, float_params, batch, R0, R1, R2, true, fb))
+    return rc;
+  const long voxels = (long)R0 * R1 * R2;
+  if ((R2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
+    ICL_LAUNCH((icl::volume_feed_kernel<4, true>), dim3(grid_for(voxels / 4, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb,
+               (const int*)origins, image_out, (long long*)label_out, R0, R1, R2);
+  } else {
+    ICL_LAUNCH((icl::volume_feed_kernel<1, true>), dim3(grid_for(voxels, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb,
+               (const int*)origins, image_out, (long long*)label_out, R0, R1, R2);
+  }
+  return check_launch("volume_feed_origins");
+}
+
+int icl_rank_tile(void) { return icl::kRankTile; }
+
+int icl_rank_index_build(const float* image, const uint8_t* label, int n0, int n1, int n2, float threshold, uint32_t* fg_index,
+                         uint32_t* bg_index, void* stream) {
+  if (!image || !label || !fg_index || !bg_index) return fail(-1, "rank_index_build: null pointer");
+  if (const int rc = rank_extents_ok("rank_index_build", 0, n0, n1, n2)) return rc;
+  const long total = (long)n0 * n1 * n2;
+  const int tiles = (int)cdivl(total, icl::kRankTile);
+  ICL_LAUNCH(icl::rank_count_kernel, dim3(tiles), dim3(icl::kRankThreads), 0, (hipStream_t)stream, image, label, (unsigned*)fg_index,
+             (unsigned*)bg_index, total, threshold, rank_vec_ok(image, label) ? 1 : 0);
+  if (const int rc = check_launch("rank_count")) return rc;
+  ICL_LAUNCH(icl::rank_scan_kernel, dim3(2), dim3(icl::kRankThreads), 0, (hipStream_t)stream, (unsigned*)fg_index, (unsigned*)bg_index, tiles);
+  return check_launch("rank_scan");
+}
+
+int icl_rank_select(const void* const* images, const void* const* labels, const void* const* fg_indices, const void* const* bg_indices,
+                    const int32_t* int_params, float threshold, int batch, int32_t* origins, void* stream) {
+  if (!images || !labels || !fg_indices || !bg_indices || !int_params || !origins) return fail(-1, "rank_select: null pointer");
+  if (batch < 1 || batch > icl::kFeedMaxBatch) return fail(-1, "rank_select: batch %d out of range (1 <= batch <= %d)", batch, icl::kFeedMaxBatch);
+  icl::RankSelectBatch sb{};
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* q = int_params + 8 * b;       // n[3], kind, rank, s[3]
+    icl::RankSelectSample& s = sb.s[b];
+    s.image = (const float*)images[b];
+    s.label = (const uint8_t*)labels[b];
+    if (!s.image || !s.label || !fg_indices[b] || !bg_indices[b]) return fail(-1, "rank_select: sample %d: null volume or index pointer", b);
+    if (const int rc = rank_extents_ok("rank_select", b, q[0], q[1], q[2])) return rc;
+    s.n0 = q[0]; s.n1 = q[1]; s.n2 = q[2];
+    s.kind = q[3]; s.rank = q[4];
+    s.s0 = q[5]; s.s1 = q[6]; s.s2 = q[7];
+    if (s.kind != icl::kRankFg && s.kind != icl::kRankBg) return fail(-1, "rank_select: sample %d: kind %d (0 foreground, 1 background)", b, s.kind);
+    if (s.rank < 0) return fail(-1, "rank_select: sample %d: rank %d (must be >= 0)", b, s.rank);
+    for (int a = 0; a < 3; ++a)
+      if (q[5 + a] < 1 || q[5 + a] > q[a]) return fail(-1, "rank_select: sample %d: crop size %d of axis %d outside 1..%d", b, q[5 + a], a, q[a]);
+    s.prefix = (const unsigned*)(s.kind == icl::kRankFg ? fg_indices[b] : bg_indices[b]);
+    s.tiles = (int)cdivl((long)s.n0 * s.n1 * s.n2, icl::kRankTile);
+    s.vec = rank_vec_ok(s.image, s.label) ? 1 : 0;
+  }
+  ICL_LAUNCH(icl::rank_select_kernel, dim3(batch), dim3(icl::kRankThreads), 0, (hipStream_t)stream, sb, threshold, (int*)origins);
+  return check_launch("rank_select");
 }
 
 int icl_slice_augment(const void* const* images, const void* const* labels, const int32_t* int_params, const double* double_params,

@@ -177,7 +177,7 @@ struct VolumeFeedSample {
   const float* image;        // [n0][n1][n2] fp32
   const uint8_t* label;      // [n0][n1][n2] uint8
   int n1, n2;                // source extents of axes 1 and 2 (the launcher has checked c + s <= n on every axis)
-  int c0, c1, c2;            // crop origin in the source
+  int c0, c1, c2;            // crop origin in the source (DEV: the largest legal origin, n - s)
   int s0, s1, s2;            // crop size, min(R, n) per axis
   int l0, l1, l2;            // zero padding on the left of each axis (R - s - l on the right)
   int flip;                  // bit a: np.flip on axis a
@@ -191,10 +191,14 @@ struct VolumeFeedBatch {
 
 // image_out [B][1][R0][R1][R2] fp32, label_out [B][R0][R1][R2] int64.  grid (x, B).  One thread per V consecutive depth voxels (V = 4: R2 % 4 == 0,
 // both outputs 16-byte aligned; one 16-byte image store and two 16-byte label stores; the source is walked forwards or, with flip
-// bit 2, backwards along depth).  No LDS, no atomics.
-template <int V>
-__global__ __launch_bounds__(256) void volume_feed_kernel(VolumeFeedBatch fb, float* __restrict__ image_out, long long* __restrict__ label_out,
-                                                          int R0, int R1, int R2) {
+// bit 2, backwards along depth).  No LDS, no atomics.  DEV = false (icl_volume_feed): the crop origin is the record's c0, c1, c2 and
+// `origins` is not read.  DEV = true (icl_volume_feed_origins): it comes from device memory, origins [B][3] int32, as
+// rank_select_kernel (rankindex.h) left it on the same stream: read once per workgroup at a wave-uniform address; the record's c0, c1,
+// c2 then hold the LARGEST legal origin n - s and an origin outside [0, n - s] is clamped into it, so no content of that buffer can
+// send a read outside the volume.
+template <int V, bool DEV>
+__global__ __launch_bounds__(256) void volume_feed_kernel(VolumeFeedBatch fb, const int* __restrict__ origins, float* __restrict__ image_out,
+                                                          long long* __restrict__ label_out, int R0, int R1, int R2) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -203,6 +207,13 @@ __global__ __launch_bounds__(256) void volume_feed_kernel(VolumeFeedBatch fb, fl
   const unsigned per = (unsigned)R0 * R1 * q2;                                // the launcher keeps R0 * R1 * R2 below 2^31
   const int b = blockIdx.y;                                                   // one sample per grid row: its record is wave-uniform
   const VolumeFeedSample& s = fb.s[b];
+  int o0 = 0, o1 = 0, o2 = 0;
+  if constexpr (DEV) {
+    const int* __restrict__ o = origins + 3 * b;
+    o0 = o[0] < 0 ? 0 : (o[0] > s.c0 ? s.c0 : o[0]);
+    o1 = o[1] < 0 ? 0 : (o[1] > s.c1 ? s.c1 : o[1]);
+    o2 = o[2] < 0 ? 0 : (o[2] > s.c2 ? s.c2 : o[2]);
+  }
   for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < per; r += gridDim.x * blockDim.x) {
     const long e = (long)b * per + r;
     const int l = (int)(r % q2) * V;
@@ -222,7 +233,7 @@ __global__ __launch_bounds__(256) void volume_feed_kernel(VolumeFeedBatch fb, fl
     const bool rev = (s.flip & 4) != 0;
     const int d0 = (rev ? R2 - 1 - l : l) - s.l2, step = rev ? -1 : 1;
     const bool row = a >= 0 && a < s.s0 && c >= 0 && c < s.s1;
-    const long base = row ? ((long)(s.c0 + a) * s.n1 + (s.c1 + c)) * s.n2 + s.c2 : 0;
+    const long base = row ? ((long)((DEV ? o0 : s.c0) + a) * s.n1 + ((DEV ? o1 : s.c1) + c)) * s.n2 + (DEV ? o2 : s.c2) : 0;
     float v[V];
     unsigned lab[V];
 #pragma unroll

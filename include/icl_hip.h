@@ -492,6 +492,32 @@ int icl_crop_rotflip(const void* const* images, const void* const* labels, const
 int icl_volume_feed(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params, int batch,
                     float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream);
 
+/* ---- foreground-balanced crops: the centre draws of MONAI's RandCropByPosNegLabeld (utils/data_utils.py:84-99, get_loader) on volumes
+ * resident in HBM, without an index list per voxel.  Members: fg = label != 0; bg = label == 0 && image > threshold (NaN is not > t).
+ * A RANK INDEX of a volume is, per list, a uint32 array of tiles + 1 entries, tiles = ceil(n0 n1 n2 / icl_rank_tile()): entry t = the
+ * number of members among the flat (C-order) voxels before tile t, the last entry = the length of the list.  Integer sums in a fixed
+ * order, no atomics: a function of the volume alone. */
+int icl_rank_tile(void);      /* consecutive flat voxels per index entry (1024) */
+/* Builds both indices of one volume (two launches).  image fp32 [n0,n1,n2], label uint8 [n0,n1,n2], fg_index / bg_index: DEVICE uint32
+ * [tiles + 1].  Returns -1, launching nothing, for a null pointer, an extent outside 1..65535 (MONAI casts crop centres to uint16) or
+ * more than 2^31 - 1 voxels. */
+int icl_rank_index_build(const float* image, const uint8_t* label, int n0, int n1, int n2, float threshold, uint32_t* fg_index,
+                         uint32_t* bg_index, void* stream);
+/* Crop origins of `batch` samples (<= 16) in one launch, one workgroup a sample: the voxel of rank `rank` in the chosen list is found
+ * through the index, unravelled to a centre, and origin_a = clamp(centre_a - s_a / 2, 0, n_a - s_a) (correct_crop_centers followed by
+ * SpatialCrop) is stored to origins [batch][3] int32 on the DEVICE.  images / labels / fg_indices / bg_indices: HOST arrays of device
+ * pointers; int_params: HOST int32 [batch][8] = {n0, n1, n2, kind (0 foreground, 1 background), rank, crop size s0, s1, s2}; threshold:
+ * the one the indices were built with.  rank < length of the list is the CALLER's check (only the host knows the totals); a larger
+ * rank still reads nothing outside the volume and yields the origin of voxel 0.  Returns -1, launching nothing, for a null pointer,
+ * a batch outside 1..16, extents as above, a kind outside {0, 1}, a negative rank or a crop size outside 1..n. */
+int icl_rank_select(const void* const* images, const void* const* labels, const void* const* fg_indices, const void* const* bg_indices,
+                    const int32_t* int_params, float threshold, int batch, int32_t* origins, void* stream);
+/* icl_volume_feed with the crop origins read from DEVICE memory (origins [batch][3] int32, as icl_rank_select left them on the same
+ * stream) instead of int_params, whose c0, c1, c2 are ignored.  Checks everything icl_volume_feed checks except the origin range
+ * (crop size: 1 <= s <= n); an origin outside [0, n - s] is clamped into it by the kernel. */
+int icl_volume_feed_origins(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params,
+                            int batch, const int32_t* origins, float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream);
+
 /* ---- on-device RandomGenerator of the 2-D trainers (dataloaders/dataset.py:147-166; composed at
  * train_inherent_consistent_unet_2D.py:75 and ..._swinunet_2D.py): "maybe rot90 + flip, else maybe ndimage.rotate by an integer
  * angle, then ndimage.zoom to the patch", all order 0, as ONE gather over slices resident in HBM, bit for bit scipy's result.

@@ -1,6 +1,8 @@
 # usage (GPU box): bash tools/kernel_coverage.sh   -> gpurun_out/kernel_coverage.txt
 # Which kernels of libicl_hip.so does the GPU suite + the three bench configurations launch?  (rocprofv3 kernel trace, names only)
-# (volume_feed_kernel<1> and <4>, the AMOS data feed, are launched by tests/test_gpu_amos_feed.py: the (6, 6, 5) and (6, 6, 8) sweeps)
+# (volume_feed_kernel<1, false> and <4, false>, the AMOS data feed, are launched by tests/test_gpu_amos_feed.py: the (6, 6, 5) and (6, 6, 8) sweeps)
+# (rank_count_kernel, rank_scan_kernel, rank_select_kernel of rankindex.h and volume_feed_kernel<1, true> and <4, true> of datafeed.h, the
+#  pos/neg feed, are launched by tests/test_gpu_posneg_feed.py: the index and select tests, and the (6, 6, 5) and (6, 6, 8) batches)
 # (the surface-metric kernels of metrics_surface.h — surf_edt_axis2/1/0, surf_reduce, surf_radix<0..5>, surf_finish — are launched by
 #  tests/test_gpu_surface_metrics.py)
 # (the connected-component kernels of components.h — cc_tile_kernel<uint8 | int64, 1 | 2 | 3>, cc_merge_kernel<uint8 | int64, 1 | 2 | 3>,

@@ -146,6 +146,8 @@ _SIGNATURES = {
     "icl_window_gather": (c_int, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "icl_window_accumulate": (c_int, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "icl_window_finalize": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
+    "icl_window_gather_flipped": (c_int, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "icl_window_accumulate_flipped": (c_int, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     # live batch (DESIGN.md §4.4 "Live batch"): the entry point's signature with n_live behind n
     "icl_last_live_fwd_kernel_name": (c_char_p, []),
     "icl_last_wgrad_grid": (None, [P, P]),

@@ -3005,6 +3005,19 @@ const char* win_batch(const int32_t* origins, int n, int p0, int p1, int p2, int
   return nullptr;
 }
 
+// flips [n] -> kernel arguments; nullptr + message when a mask is not a set of the three window axes
+const char* win_flips(const int32_t* flips, int n, icl::WinFlips& fl) {
+  static thread_local char msg[96];
+  for (int w = 0; w < n; ++w) {
+    if (flips[w] < 0 || flips[w] > 7) {
+      snprintf(msg, sizeof(msg), "window %d: mirror mask %d (0 <= mask <= 7)", w, flips[w]);
+      return msg;
+    }
+    fl.m |= (unsigned long long)flips[w] << (4 * w);
+  }
+  return nullptr;
+}
+
 inline bool win_pads_ok(int s0, int s1, int s2, int a0, int a1, int a2, int p0, int p1, int p2) {
   return s0 >= 1 && s1 >= 1 && s2 >= 1 && a0 >= 0 && a1 >= 0 && a2 >= 0 && (long)a0 + s0 <= p0 && (long)a1 + s1 <= p1 && (long)a2 + s2 <= p2;
 }
@@ -3013,43 +3026,59 @@ constexpr int kWinMaxWgs = 2048;
 
 template <int NCMAX>
 void win_accumulate_launch(bool quad, dim3 grid, hipStream_t st, const float* logits, const float* imp, float* score, float* weight,
-                           const icl::WinBatch& wb, int n, int c, icl::WinExt p, icl::WinExt r, icl::WinExt lo, icl::WinExt ext, int softmax) {
-  if (quad) {
+                           const icl::WinBatch& wb, const icl::WinFlips* fl, int n, int c, icl::WinExt p, icl::WinExt r, icl::WinExt lo,
+                           icl::WinExt ext, int softmax) {
+  if (fl) {
+    if (quad) {
+      ICL_LAUNCH((icl::window_accumulate_kernel<NCMAX, 4, icl::WinFlips>), grid, dim3(256), 0, st, logits, imp, score, weight, wb, n, c, p, r, lo, ext, softmax, *fl);
+    } else {
+      ICL_LAUNCH((icl::window_accumulate_kernel<NCMAX, 1, icl::WinFlips>), grid, dim3(256), 0, st, logits, imp, score, weight, wb, n, c, p, r, lo, ext, softmax, *fl);
+    }
+  } else if (quad) {
     ICL_LAUNCH((icl::window_accumulate_kernel<NCMAX, 4>), grid, dim3(256), 0, st, logits, imp, score, weight, wb, n, c, p, r, lo, ext, softmax);
   } else {
     ICL_LAUNCH((icl::window_accumulate_kernel<NCMAX, 1>), grid, dim3(256), 0, st, logits, imp, score, weight, wb, n, c, p, r, lo, ext, softmax);
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int icl_window_gather(const float* vol, float* out, const int32_t* origins, int n, int cin, int s0, int s1, int s2, int a0, int a1, int a2,
-                      int p0, int p1, int p2, int r0, int r1, int r2, void* stream) {
-  if (!vol || !out || !origins) return fail(-1, "window_gather: null pointer");
+// icl_window_gather (flips == nullptr) and icl_window_gather_flipped: one set of refusals, one grid, the kernel of the form asked for
+int win_gather(const char* who, const float* vol, float* out, const int32_t* origins, const int32_t* flips, bool flipped, int n, int cin,
+               int s0, int s1, int s2, int a0, int a1, int a2, int p0, int p1, int p2, int r0, int r1, int r2, void* stream) {
+  if (!vol || !out || !origins || (flipped && !flips)) return fail(-1, "%s: null pointer", who);
   if (cin < 1 || !win_pads_ok(s0, s1, s2, a0, a1, a2, p0, p1, p2))
-    return fail(-1, "window_gather: bad extents (Cin %d, volume %d x %d x %d at %d, %d, %d of %d x %d x %d)", cin, s0, s1, s2, a0, a1, a2, p0, p1, p2);
+    return fail(-1, "%s: bad extents (Cin %d, volume %d x %d x %d at %d, %d, %d of %d x %d x %d)", who, cin, s0, s1, s2, a0, a1, a2, p0, p1, p2);
   icl::WinBatch wb{};
-  if (const char* m = win_batch(origins, n, p0, p1, p2, r0, r1, r2, wb)) return fail(-1, "window_gather: %s", m);
+  icl::WinFlips fl{};
+  if (const char* m = win_batch(origins, n, p0, p1, p2, r0, r1, r2, wb)) return fail(-1, "%s: %s", who, m);
+  if (flipped)
+    if (const char* m = win_flips(flips, n, fl)) return fail(-1, "%s: %s", who, m);
   const icl::WinExt s{s0, s1, s2}, a{a0, a1, a2}, r{r0, r1, r2};
   const bool quad = (r2 & 3) == 0 && aligned16(vol) && aligned16(out);
   const long total = (long)cin * r0 * r1 * (quad ? r2 / 4 : r2);
   const dim3 grid(grid_for(total, 256, kWinMaxWgs / n > 0 ? kWinMaxWgs / n : 1), n);
-  if (quad) {
+  if (flipped) {
+    if (quad) {
+      ICL_LAUNCH((icl::window_gather_kernel<4, icl::WinFlips>), grid, dim3(256), 0, (hipStream_t)stream, vol, out, wb, cin, s, a, r, fl);
+    } else {
+      ICL_LAUNCH((icl::window_gather_kernel<1, icl::WinFlips>), grid, dim3(256), 0, (hipStream_t)stream, vol, out, wb, cin, s, a, r, fl);
+    }
+  } else if (quad) {
     ICL_LAUNCH(icl::window_gather_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, vol, out, wb, cin, s, a, r);
   } else {
     ICL_LAUNCH(icl::window_gather_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, vol, out, wb, cin, s, a, r);
   }
-  return check_launch("window_gather");
+  return check_launch(who);
 }
 
-int icl_window_accumulate(const float* logits, const float* importance, float* score, float* weight, const int32_t* origins, int n, int c,
-                          int p0, int p1, int p2, int r0, int r1, int r2, int softmax, void* stream) {
-  if (!logits || !score || !weight || !origins) return fail(-1, "window_accumulate: null pointer");
-  if (c < 1 || c > icl::kWinMaxClasses) return fail(-1, "window_accumulate: %d classes (1 <= C <= %d)", c, icl::kWinMaxClasses);
+int win_accumulate(const char* who, const float* logits, const float* importance, float* score, float* weight, const int32_t* origins,
+                   const int32_t* flips, bool flipped, int n, int c, int p0, int p1, int p2, int r0, int r1, int r2, int softmax, void* stream) {
+  if (!logits || !score || !weight || !origins || (flipped && !flips)) return fail(-1, "%s: null pointer", who);
+  if (c < 1 || c > icl::kWinMaxClasses) return fail(-1, "%s: %d classes (1 <= C <= %d)", who, c, icl::kWinMaxClasses);
   icl::WinBatch wb{};
-  if (const char* m = win_batch(origins, n, p0, p1, p2, r0, r1, r2, wb)) return fail(-1, "window_accumulate: %s", m);
+  icl::WinFlips fl{};
+  if (const char* m = win_batch(origins, n, p0, p1, p2, r0, r1, r2, wb)) return fail(-1, "%s: %s", who, m);
+  if (flipped)
+    if (const char* m = win_flips(flips, n, fl)) return fail(-1, "%s: %s", who, m);
   const icl::WinExt p{p0, p1, p2}, r{r0, r1, r2};
   int lo[3], hi[3];
   bool quad = (p2 & 3) == 0 && (r2 & 3) == 0 && aligned16(logits) && aligned16(score) && aligned16(weight) && (!importance || aligned16(importance));
@@ -3066,10 +3095,38 @@ int icl_window_accumulate(const float* logits, const float* importance, float* s
   const dim3 grid(grid_for(total, 256, kWinMaxWgs));
   hipStream_t st = (hipStream_t)stream;
   const int sm = softmax ? 1 : 0;
-  if (c <= 4) win_accumulate_launch<4>(quad, grid, st, logits, importance, score, weight, wb, n, c, p, r, l, ext, sm);
-  else if (c <= 16) win_accumulate_launch<16>(quad, grid, st, logits, importance, score, weight, wb, n, c, p, r, l, ext, sm);
-  else win_accumulate_launch<0>(quad, grid, st, logits, importance, score, weight, wb, n, c, p, r, l, ext, sm);
-  return check_launch("window_accumulate");
+  const icl::WinFlips* flp = flipped ? &fl : nullptr;
+  if (c <= 4) win_accumulate_launch<4>(quad, grid, st, logits, importance, score, weight, wb, flp, n, c, p, r, l, ext, sm);
+  else if (c <= 16) win_accumulate_launch<16>(quad, grid, st, logits, importance, score, weight, wb, flp, n, c, p, r, l, ext, sm);
+  else win_accumulate_launch<0>(quad, grid, st, logits, importance, score, weight, wb, flp, n, c, p, r, l, ext, sm);
+  return check_launch(who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int icl_window_gather(const float* vol, float* out, const int32_t* origins, int n, int cin, int s0, int s1, int s2, int a0, int a1, int a2,
+                      int p0, int p1, int p2, int r0, int r1, int r2, void* stream) {
+  return win_gather("window_gather", vol, out, origins, nullptr, false, n, cin, s0, s1, s2, a0, a1, a2, p0, p1, p2, r0, r1, r2, stream);
+}
+
+int icl_window_gather_flipped(const float* vol, float* out, const int32_t* origins, const int32_t* flips, int n, int cin, int s0, int s1,
+                              int s2, int a0, int a1, int a2, int p0, int p1, int p2, int r0, int r1, int r2, void* stream) {
+  return win_gather("window_gather_flipped", vol, out, origins, flips, true, n, cin, s0, s1, s2, a0, a1, a2, p0, p1, p2, r0, r1, r2, stream);
+}
+
+int icl_window_accumulate(const float* logits, const float* importance, float* score, float* weight, const int32_t* origins, int n, int c,
+                          int p0, int p1, int p2, int r0, int r1, int r2, int softmax, void* stream) {
+  return win_accumulate("window_accumulate", logits, importance, score, weight, origins, nullptr, false, n, c, p0, p1, p2, r0, r1, r2, softmax,
+                        stream);
+}
+
+int icl_window_accumulate_flipped(const float* logits, const float* importance, float* score, float* weight, const int32_t* origins,
+                                  const int32_t* flips, int n, int c, int p0, int p1, int p2, int r0, int r1, int r2, int softmax,
+                                  void* stream) {
+  return win_accumulate("window_accumulate_flipped", logits, importance, score, weight, origins, flips, true, n, c, p0, p1, p2, r0, r1, r2,
+                        softmax, stream);
 }
 
 int icl_window_finalize(const float* score, const float* weight, int64_t* label, float* quotients, int c, int p0, int p1, int p2, int a0,

@@ -8,6 +8,11 @@
 // (V = 1); grid-stride launches; no LDS, no atomics.  In the accumulation ONE thread owns a destination voxel (or a quad of them) and
 // walks the batch's windows in their given order, so overlapping windows of one batch neither race nor change the order of the adds:
 // every sum is the one the torch loop forms, window by window.
+// Mirror test-time augmentation: the instantiations window_gather_kernel<V, WinFlips> and window_accumulate_kernel<NCMAX, V, WinFlips>
+// take one mask per window of the batch behind their other arguments (a "pass": bit a set = axis a of the window mirrored).  The gather
+// writes flip(window, axes) — the same gather with a reversed source index; the accumulate adds flip(value, axes) — the same
+// read-modify-write with a reversed read of the logits, the importance map staying in the volume's frame.  Without the trailing
+// argument (FL empty) nothing of the masks is compiled in: the plain instantiations are the kernels they were.
 #pragma once
 
 namespace icl {
@@ -21,6 +26,13 @@ struct WinBatch {
 struct WinExt {
   int d0, d1, d2;
 };
+// one mirror mask per window of the batch, bit a set = axis a mirrored (0 .. 7): window w's mask in bits 4 w .. 4 w + 2.  One 64-bit
+// kernel argument on purpose: it arrives with one scalar load and a mask is a scalar shift (a byte array indexed by the pass was a
+// VECTOR byte load and a wait in front of every pass's loads — measured at 7 to 9 % of a launch).
+struct WinFlips {
+  unsigned long long m;
+};
+static_assert(kWinMaxBatch * 4 <= 64, "four bits per window in WinFlips::m");
 
 // product and sum of the weighted accumulation, each rounded on its own (the torch loop forms `w * value`, then adds).  hipcc contracts
 // a * b + c into an fma by default — also through __fmul_rn / __fadd_rn, which are plain operators in its headers — so both are
@@ -58,13 +70,37 @@ __device__ __forceinline__ void win_store(float* __restrict__ p, const float* v)
   }
 }
 
+__device__ __forceinline__ int win_mask(int) { return 0; }
+__device__ __forceinline__ int win_mask(int w, const WinFlips& fl) { return (int)(fl.m >> (4 * w)) & 7; }
+
+// a window's values along a mirrored last axis: the quad's lanes reversed when `rev` (a single value has no order); nothing without FLIP
+template <int V, bool FLIP>
+__device__ __forceinline__ void win_reverse(float* v, int rev) {
+  if constexpr (FLIP && V == 4) {
+    if (rev) {
+      const float t0 = v[0], t1 = v[1];
+      v[0] = v[3]; v[1] = v[2]; v[2] = t1; v[3] = t0;
+    }
+  }
+}
+template <int V, bool FLIP>
+__device__ __forceinline__ void win_load_pass(const float* __restrict__ p, float* v, int rev) {
+  win_load<V>(p, v);
+  win_reverse<V, FLIP>(v, rev);
+}
+
 // out [n][Cin][r0][r1][r2] <- vol [Cin][s0][s1][s2]; window w (= blockIdx.y) starts at wb.o[w] - a in the unpadded volume, voxels
 // outside it read as 0.  V = 4: r2 % 4 == 0 and 16-byte aligned pointers (the store is always a quad; the load is one where the quad
 // lies inside the row at a 16-byte aligned address, four guarded scalar loads otherwise).
-template <int V>
+// fl (FLIP): window w is written mirrored along the axes of its mask in fl — destination (i, j, l) reads the source of (r0 - 1 - i, j, l) for bit 0,
+// likewise bits 1 and 2; with V = 4 and bit 2 the destination quad l .. l + 3 is the source quad at r2 - 4 - l with its lanes reversed,
+// loaded under the same condition (the zero fill is the unflipped window's, mirrored with it).
+template <int V, typename... FL>
 __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ vol, float* __restrict__ out, WinBatch wb, int cin, WinExt s,
-                                                            WinExt a, WinExt r) {
+                                                            WinExt a, WinExt r, FL... fl) {
+  constexpr bool FLIP = sizeof...(FL) > 0;
   const int w = blockIdx.y;
+  const int f = win_mask(w, fl...);
   const int b0 = wb.o[w][0] - a.d0, b1 = wb.o[w][1] - a.d1, b2 = wb.o[w][2] - a.d2;
   const int r2v = r.d2 / V;
   const long total = (long)cin * r.d0 * r.d1 * r2v;
@@ -76,7 +112,12 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restr
     const int j = (int)(t % r.d1);
     t /= r.d1;
     const int i = (int)(t % r.d0), ci = (int)(t / r.d0);
-    const int x = b0 + i, y = b1 + j, z = b2 + l;
+    int x = b0 + i, y = b1 + j, z = b2 + l;
+    if constexpr (FLIP) {
+      if (f & 1) x = b0 + r.d0 - 1 - i;
+      if (f & 2) y = b1 + r.d1 - 1 - j;
+      if (f & 4) z = b2 + r.d2 - V - l;
+    }
     float v[V];
 #pragma unroll
     for (int u = 0; u < V; ++u) v[u] = 0.f;
@@ -90,6 +131,7 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restr
           if (z + u >= 0 && z + u < s.d2) v[u] = vol[row + z + u];
       }
     }
+    win_reverse<V, FLIP>(v, f & 4);
     win_store<V>(dst + e * V, v);
   }
 }
@@ -103,10 +145,14 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const float* __restr
 // the score map (the logits form takes that last walk only).
 // V = 4: p2, r2 and every origin's last coordinate are multiples of 4 and the pointers 16-byte aligned, so a quad lies inside or
 // outside a window as a whole.
-template <int NCMAX, int V>
+// fl (FLIP): window w's logits are those of the window mirrored along the axes of its mask in fl; the value added at (dx, dy, dz) of the window is
+// the one at the mirrored offset (r0 - 1 - dx for bit 0, likewise bits 1 and 2; V = 4 and bit 2: the quad at r2 - 4 - dz, aligned as r2
+// and dz are multiples of 4, lanes reversed).  The importance map is read at (dx, dy, dz): it lives in the volume's frame.
+template <int NCMAX, int V, typename... FL>
 __global__ __launch_bounds__(256) void window_accumulate_kernel(const float* __restrict__ logits, const float* __restrict__ imp,
                                                                 float* __restrict__ score, float* __restrict__ weight, WinBatch wb, int n, int C,
-                                                                WinExt p, WinExt r, WinExt lo, WinExt ext, int softmax) {
+                                                                WinExt p, WinExt r, WinExt lo, WinExt ext, int softmax, FL... fl) {
+  constexpr bool FLIP = sizeof...(FL) > 0;
   constexpr int NA = NCMAX > 0 ? NCMAX : 1;
   const int e2v = ext.d2 / V;
   const long total = (long)ext.d0 * ext.d1 * e2v;
@@ -136,7 +182,15 @@ __global__ __launch_bounds__(256) void window_accumulate_kernel(const float* __r
     for (int w = 0; w < n; ++w) {
       if (!((hit >> w) & 1u)) continue;
       const long off = ((long)(x - wb.o[w][0]) * r.d1 + (y - wb.o[w][1])) * r.d2 + (z - wb.o[w][2]);
-      const float* __restrict__ lp = logits + (long)w * C * P + off;
+      long offl = off;
+      int rev = 0;
+      if constexpr (FLIP) {
+        const int f = win_mask(w, fl...);
+        const int dx = x - wb.o[w][0], dy = y - wb.o[w][1], dz = z - wb.o[w][2];
+        rev = f & 4;
+        offl = ((long)((f & 1) ? r.d0 - 1 - dx : dx) * r.d1 + ((f & 2) ? r.d1 - 1 - dy : dy)) * r.d2 + (rev ? r.d2 - V - dz : dz);
+      }
+      const float* __restrict__ lp = logits + (long)w * C * P + offl;
       float wv[V];
 #pragma unroll
       for (int u = 0; u < V; ++u) wv[u] = 1.0f;
@@ -150,7 +204,7 @@ __global__ __launch_bounds__(256) void window_accumulate_kernel(const float* __r
           float q[V];
 #pragma unroll
           for (int u = 0; u < V; ++u) q[u] = 0.f;
-          if (c < C) win_load<V>(lp + (long)c * P, q);
+          if (c < C) win_load_pass<V, FLIP>(lp + (long)c * P, q, rev);
 #pragma unroll
           for (int u = 0; u < V; ++u) val[u][c] = q[u];
         }
@@ -175,10 +229,10 @@ __global__ __launch_bounds__(256) void window_accumulate_kernel(const float* __r
       } else {
         float m[V], inv[V];
         if (softmax) {
-          win_load<V>(lp, m);
+          win_load_pass<V, FLIP>(lp, m, rev);
           for (int c = 1; c < C; ++c) {
             float q[V];
-            win_load<V>(lp + (long)c * P, q);
+            win_load_pass<V, FLIP>(lp + (long)c * P, q, rev);
 #pragma unroll
             for (int u = 0; u < V; ++u) m[u] = fmaxf(m[u], q[u]);
           }
@@ -187,7 +241,7 @@ __global__ __launch_bounds__(256) void window_accumulate_kernel(const float* __r
           for (int u = 0; u < V; ++u) sum[u] = 0.f;
           for (int c = 0; c < C; ++c) {
             float q[V];
-            win_load<V>(lp + (long)c * P, q);
+            win_load_pass<V, FLIP>(lp + (long)c * P, q, rev);
 #pragma unroll
             for (int u = 0; u < V; ++u) sum[u] += expf(q[u] - m[u]);
           }
@@ -196,7 +250,7 @@ __global__ __launch_bounds__(256) void window_accumulate_kernel(const float* __r
         }
         for (int c = 0; c < C; ++c) {
           float q[V], a[V];
-          win_load<V>(lp + (long)c * P, q);
+          win_load_pass<V, FLIP>(lp + (long)c * P, q, rev);
           win_load<V>(score + (long)c * S + idx, a);
 #pragma unroll
           for (int u = 0; u < V; ++u) {

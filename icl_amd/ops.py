@@ -2825,11 +2825,24 @@ def _window_origins(origins):
     return (ctypes.c_int32 * max(len(flat), 1))(*flat), len(origins)
 
 
-def window_gather(vol: torch.Tensor, origins, roi, pads, padded, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def _window_flips(who, flips, n):
+    """``flips`` of ``window_gather`` / ``window_accumulate`` as a host int32 array: one mirror mask 0..7 per origin."""
+    masks = list(flips)
+    if len(masks) != n:
+        raise ValueError(f"{who}: {len(masks)} mirror masks for {n} windows")
+    for m in masks:
+        if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= 7:
+            raise ValueError(f"{who}: a mirror mask must be an integer 0..7 (bit a: axis a of the window), got {m!r}")
+    return (ctypes.c_int32 * max(n, 1))(*masks)
+
+
+def window_gather(vol: torch.Tensor, origins, roi, pads, padded, out: Optional[torch.Tensor] = None, flips=None) -> torch.Tensor:
     """``stack([pad(vol)[:, o0:o0 + r0, o1:o1 + r1, o2:o2 + r2] for o in origins]).contiguous()`` in one launch, bit-equal
     (include/icl_hip.h icl_window_gather): vol fp32 [Cin, s0, s1, s2]; origins: up to 16 triples in the padded frame ``padded``, in which the
     volume starts at ``pads`` = (a0, a1, a2); voxels outside the volume read as 0.  Returns [n, Cin, r0, r1, r2] (``out`` when given: a contiguous tensor of
-    that shape, e.g. a slice of a larger batch along its first axis).  Asynchronous on the current stream."""
+    that shape, e.g. a slice of a larger batch along its first axis).  ``flips``: one mirror mask 0..7 per origin (bit a set: the window is
+    mirrored along its spatial axis a) — window w comes out as ``torch.flip`` of the above along the axes of ``flips[w]``, from the same
+    launch (icl_window_gather_flipped); None: the plain kernel.  Asynchronous on the current stream."""
     _require(vol)
     if vol.dtype != torch.float32 or vol.dim() != 4:
         raise ValueError(f"window_gather: needs an fp32 [Cin, s0, s1, s2] volume, got {vol.dtype} {tuple(vol.shape)}")
@@ -2841,16 +2854,23 @@ def window_gather(vol: torch.Tensor, origins, roi, pads, padded, out: Optional[t
         out = torch.empty(shape, dtype=torch.float32, device=vol.device)
     elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != vol.device:
         raise ValueError(f"window_gather: out must be a contiguous fp32 {shape} tensor on the volume's device")
-    _lib.check(_lib.lib().icl_window_gather(_ptr(vol), _ptr(out), arr, n, vol.shape[0], *vol.shape[1:], *a, *p, *r, _stream(vol)), "window_gather")
+    if flips is None:
+        _lib.check(_lib.lib().icl_window_gather(_ptr(vol), _ptr(out), arr, n, vol.shape[0], *vol.shape[1:], *a, *p, *r, _stream(vol)), "window_gather")
+    else:
+        fl = _window_flips("window_gather", flips, n)
+        _lib.check(_lib.lib().icl_window_gather_flipped(_ptr(vol), _ptr(out), arr, fl, n, vol.shape[0], *vol.shape[1:], *a, *p, *r, _stream(vol)),
+                   "window_gather_flipped")
     return out
 
 
 def window_accumulate(logits: torch.Tensor, origins, score: torch.Tensor, weight: torch.Tensor, importance: Optional[torch.Tensor] = None,
-                      softmax: bool = False) -> None:
+                      softmax: bool = False, flips=None) -> None:
     """``score[:, window] += value`` and ``weight[window] += 1`` for every window of a batch, in the given order, in one launch
     (icl_window_accumulate): logits fp32 [n, C, r0, r1, r2] (n <= 16, C <= 256), score fp32 [C, p0, p1, p2] and weight fp32 [p0, p1, p2],
     updated in place.  ``softmax``: the value is softmax(logits, 1), else the logits.  ``importance`` fp32 [r0, r1, r2]: the value is
-    multiplied by it first (rounded, then added) and ``weight[window] += importance``."""
+    multiplied by it first (rounded, then added) and ``weight[window] += importance``.  ``flips``: one mirror mask 0..7 per origin — the
+    logits of window w were computed on the window mirrored along the axes of ``flips[w]`` and their value is mirrored back as it is read
+    (``score[:, window] += flip(value, axes)``, icl_window_accumulate_flipped); the importance map is not mirrored.  None: the plain kernel."""
     _require(logits, score, weight, importance)
     if logits.dim() != 5 or score.dim() != 4 or weight.dim() != 3 or score.shape[0] != logits.shape[1] or score.shape[1:] != weight.shape:
         raise ValueError(f"window_accumulate: shapes {tuple(logits.shape)}, {tuple(score.shape)}, {tuple(weight.shape)}")
@@ -2867,8 +2887,14 @@ def window_accumulate(logits: torch.Tensor, origins, score: torch.Tensor, weight
     arr, n = _window_origins(origins)
     if n != logits.shape[0]:
         raise ValueError(f"window_accumulate: {n} origins for {logits.shape[0]} windows")
-    _lib.check(_lib.lib().icl_window_accumulate(_ptr(logits), _ptr(importance), _ptr(score), _ptr(weight), arr, n, logits.shape[1],
-                                                *weight.shape, *logits.shape[2:], int(bool(softmax)), _stream(score)), "window_accumulate")
+    if flips is None:
+        _lib.check(_lib.lib().icl_window_accumulate(_ptr(logits), _ptr(importance), _ptr(score), _ptr(weight), arr, n, logits.shape[1],
+                                                    *weight.shape, *logits.shape[2:], int(bool(softmax)), _stream(score)), "window_accumulate")
+    else:
+        fl = _window_flips("window_accumulate", flips, n)
+        _lib.check(_lib.lib().icl_window_accumulate_flipped(_ptr(logits), _ptr(importance), _ptr(score), _ptr(weight), arr, fl, n,
+                                                            logits.shape[1], *weight.shape, *logits.shape[2:], int(bool(softmax)),
+                                                            _stream(score)), "window_accumulate_flipped")
 
 
 def window_finalize(score: torch.Tensor, weight: torch.Tensor, pads, size, return_score: bool = False, label: bool = True):

@@ -13,7 +13,9 @@ build image, so the HD95 half is "parity unpinned" (DESIGN.md §2).
 On a HIP device the stretch between the volume and the label map — window gather, soft-max, accumulation of the score and weight
 maps, division, arg-max, crop — runs on the window kernels (csrc/kernels/window.h, ``ops.window_*``; DESIGN.md §4.7) in both loops;
 ``ICL_VAL_WINDOWS=aten`` keeps the ATen loops, which also serve host tensors.  ``mode="gaussian"`` blends overlapping windows with a
-Gaussian importance map on either path.
+Gaussian importance map on either path.  ``mirror_axes=`` turns mirror test-time augmentation on in both loops: every window is predicted
+once per subset of those axes, mirrored, and each prediction is mirrored back into the average — in the indexing of the same kernels, at
+one forward per pass and no further tensor.
 """
 from __future__ import annotations
 
@@ -71,6 +73,31 @@ def _importance_map(mode, roi_size, sigma_scale, device):
     raise ValueError(f"sliding-window mode must be 'constant' or 'gaussian', got {mode!r}")
 
 
+def _mirror_masks(mirror_axes):
+    """``mirror_axes=`` of the validation loops -> the mirror masks of test-time augmentation, or None.  ``mirror_axes``: None (no
+    augmentation) or a sequence of distinct axes out of 0, 1, 2 — the window's three spatial axes — which may be empty; anything else is
+    a ValueError.  A mask is a subset of those axes as an integer, bit a set for axis a; all 2^len(mirror_axes) of them, in increasing
+    order, so mask 0 (the window as it is) comes first."""
+    if mirror_axes is None:
+        return None
+    try:
+        axes = None if isinstance(mirror_axes, (str, bytes)) else list(mirror_axes)
+    except TypeError:
+        axes = None
+    if (axes is None or any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) or a not in (0, 1, 2) for a in axes)
+            or len(set(axes)) != len(axes)):
+        raise ValueError(f"mirror_axes must be None or distinct axes out of 0, 1, 2, got {mirror_axes!r}")
+    masks = [0]
+    for a in sorted(int(a) for a in axes):
+        masks += [m | (1 << a) for m in masks]
+    return masks
+
+
+def _mask_dims(mask, first):
+    """The tensor axes of a mirror mask where the window's spatial axes start at ``first``."""
+    return [first + a for a in range(3) if (mask >> a) & 1]
+
+
 def _window_kernels_apply(t, num_classes=1) -> bool:
     return (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and 1 <= num_classes <= _WINDOW_MAX_CLASSES
             and val_windows_mode() == "device")
@@ -78,11 +105,13 @@ def _window_kernels_apply(t, num_classes=1) -> bool:
 
 @torch.no_grad()
 def test_single_case_base(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_batch=4,
-                          return_score=False, mode="constant"):
+                          return_score=False, mode="constant", mirror_axes=None):
     """image: numpy [W,H,D] (the reference's h5 layout).  Returns the label map (numpy int64 [W,H,D]).  ``mode``: ``constant`` (the
-    reference's plain average over overlapping windows) or ``gaussian`` (``gaussian_importance_map`` at sigma_scale 0.125)."""
+    reference's plain average over overlapping windows) or ``gaussian`` (``gaussian_importance_map`` at sigma_scale 0.125).
+    ``mirror_axes``: None, or the axes out of 0, 1, 2 (W, H, D) of mirror test-time augmentation (``_run_windows``); ``windows_per_batch``
+    then counts passes."""
     label_map, score = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes, windows_per_batch, mode,
-                                              return_score)
+                                              return_score, mirror_axes)
     if return_score:
         return label_map.cpu().numpy(), score.cpu().numpy()
     return label_map.cpu().numpy()
@@ -100,7 +129,7 @@ def _fits_amos(roi, device):
                             and 1 <= pred.shape[1] <= _WINDOW_MAX_CLASSES and pred.device == device)
 
 
-def _run_windows(vols, roi, pads, psize, starts, per_forward, forward, imp, softmax, want, kernels, fits, num_classes=None):
+def _run_windows(vols, roi, pads, psize, starts, per_forward, forward, imp, softmax, want, kernels, fits, num_classes=None, masks=None):
     """The sliding window of both validation loops, and the only place that walks window origins.  ``vols`` fp32 [B, Cin, s0, s1, s2],
     unpadded; ``pads`` the (before, after) zero padding per axis that brings it to the extent ``psize``; ``starts`` the windows as (batch
     index, o0, o1, o2) in the padded frame, in loop order, ``per_forward`` of them per ``forward(win)`` (win [n, Cin, *roi]); ``imp`` the
@@ -114,7 +143,14 @@ def _run_windows(vols, roi, pads, psize, starts, per_forward, forward, imp, soft
     up when ``fits(pred, n)``, the caller's rule, is false for the prediction of the FIRST batch: the loop goes on in ATen with that
     prediction — ``handed``, None when there was no hand-over — so ``forward`` sees every batch once.  ``num_classes``: the channels of the score map; None takes them from the first prediction.  The kernel form
     computes only what is wanted (quotients alone where nothing is cropped: divided in place); the ATen form has the quotients anyway
-    and returns them whatever ``want`` says."""
+    and returns them whatever ``want`` says.
+
+    ``masks`` (``_mirror_masks``; None: none of this) — mirror test-time augmentation.  The loop walks PASSES instead of windows: a pass is
+    a (window, mask) pair, window-major and mask-minor, and ``per_forward`` and the 16 of a launch count passes.  A pass with mask f
+    predicts ``flip(win, axes of f)`` and adds ``flip(value, the same axes)`` — times ``imp``, which is NOT flipped: it is indexed in the
+    volume's frame — so the quotient is the mean over all passes covering a voxel.  The kernel form does both flips in the indexing of
+    the gather and of the accumulate (``flips=``), the ATen form with ``torch.flip``; the hand-over works on passes as it does on
+    windows."""
     from . import ops
     b, cin = vols.shape[:2]
     size, roi, psize = tuple(vols.shape[2:]), tuple(int(r) for r in roi), tuple(psize)
@@ -125,6 +161,11 @@ def _run_windows(vols, roi, pads, psize, starts, per_forward, forward, imp, soft
         return torch.nn.functional.pad(v, [n for p, q in reversed(pads) for n in (p, q)]) if any(p + q for p, q in pads) else v
     vols = vols.contiguous() if kernels else padded(vols)
     score = weight = handed = None
+    if masks is not None:
+        starts = [s + (f,) for s in starts for f in masks]
+
+    def flips(run):
+        return None if masks is None else [c[4] for c in run]
     for i in range(0, len(starts), per_forward):
         chunk = starts[i:i + per_forward]
         if kernels:
@@ -137,9 +178,12 @@ def _run_windows(vols, roi, pads, psize, starts, per_forward, forward, imp, soft
                 k = e
             win = torch.empty((len(chunk), cin, *roi), dtype=torch.float32, device=vols.device)
             for k, e in runs:
-                ops.window_gather(vols[chunk[k][0]], [c[1:] for c in chunk[k:e]], roi, a, psize, out=win[k:e])
+                ops.window_gather(vols[chunk[k][0]], [c[1:4] for c in chunk[k:e]], roi, a, psize, out=win[k:e], flips=flips(chunk[k:e]))
         else:
-            win = torch.stack([vols[bi, :, z:z + r0, y:y + r1, x:x + r2] for bi, z, y, x in chunk]).contiguous()
+            wins = [vols[bi, :, z:z + r0, y:y + r1, x:x + r2] for bi, z, y, x, *_ in chunk]
+            if masks is not None:
+                wins = [w.flip(_mask_dims(c[4], 1)) if c[4] else w for w, c in zip(wins, chunk)]
+            win = torch.stack(wins).contiguous()
         pred = forward(win)
         if score is None:
             if kernels and not fits(pred, len(chunk)):      # hand-over: this batch has been through the network
@@ -151,12 +195,15 @@ def _run_windows(vols, roi, pads, psize, starts, per_forward, forward, imp, soft
             pred = pred.float()
             for k, e in runs:
                 bi = chunk[k][0]
-                ops.window_accumulate(pred[k:e], [c[1:] for c in chunk[k:e]], score[bi], weight[bi], imp, softmax=softmax)
+                ops.window_accumulate(pred[k:e], [c[1:4] for c in chunk[k:e]], score[bi], weight[bi], imp, softmax=softmax,
+                                      flips=flips(chunk[k:e]))
             continue
         if softmax:
             pred = torch.softmax(pred, dim=1)
-        for j, (bi, z, y, x) in enumerate(chunk):
+        for j, (bi, z, y, x, *f) in enumerate(chunk):
             value = pred[j] if softmax else pred[j].float()
+            if f and f[0]:
+                value = value.flip(_mask_dims(f[0], 1))
             if imp is None:
                 score[bi, :, z:z + r0, y:y + r1, x:x + r2] += value
                 weight[bi, z:z + r0, y:y + r1, x:x + r2] += 1
@@ -182,11 +229,12 @@ def _run_windows(vols, roi, pads, psize, starts, per_forward, forward, imp, soft
 
 @torch.no_grad()
 def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_batch=4, mode="constant",
-                           want_score=True):
+                           want_score=True, mirror_axes=None):
     """``test_single_case_base`` up to the copy to the host: (label map int64 [W,H,D], score [C,W,H,D]) on the net's device.  On a HIP
     device the windows are gathered, soft-maxed, accumulated, divided and arg-maxed by the window kernels (``ICL_VAL_WINDOWS``; the score
     is None when ``want_score`` is false — the kernel then writes the label map alone); elsewhere, and when the network's output is not
-    fp32 [n, num_classes, *patch_size], in ATen (``_run_windows``).  Both walk the same window grid."""
+    fp32 [n, num_classes, *patch_size], in ATen (``_run_windows``).  Both walk the same window grid — with ``mirror_axes``, the same passes of mirror test-time augmentation."""
+    masks = _mirror_masks(mirror_axes)
     dev = next(net.parameters()).device
     pads = []
     for dim, p in zip(image.shape, patch_size):
@@ -209,7 +257,7 @@ def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size
     icl = net_type in ("swinunetr_icl", "unet_3D_icl")
     (label_map, score), _ = _run_windows(
         vol[None, None], patch_size, pads, (ww, hh, dd), starts, windows_per_batch, lambda win: net(win, inference=True) if icl else net(win),
-        imp, True, "both" if want_score else "label", _window_kernels_apply(vol, num_classes), _fits_brats(num_classes, patch_size), num_classes)
+        imp, True, "both" if want_score else "label", _window_kernels_apply(vol, num_classes), _fits_brats(num_classes, patch_size), num_classes, masks)
     return label_map[0], None if score is None else score[0]
 
 
@@ -608,15 +656,18 @@ def _score_prediction(prediction, label, num_classes, dev, voxelspacing=None, po
 
 
 def test_all_case_base(net, net_type, base_dir, test_list="full_test.list", num_classes=4, patch_size=(48, 160, 160),
-                       stride_xy=32, stride_z=24, cases=None, voxelspacing=None, postprocess=None):
+                       stride_xy=32, stride_z=24, cases=None, voxelspacing=None, postprocess=None, mirror_axes=None):
     """val_3D.py:100-118.  ``cases`` (iterable of (image, label) numpy pairs) replaces the h5 files when given; otherwise
     the reference's ``{base_dir}/data/{id}.h5`` layout is read with h5py (not installed in the build image).  ``voxelspacing`` (a number
     or three, the voxel size along the label map's axes) gives HD95 in its units (``cal_metric_multiclass``); None: voxels, as the reference.
     ``postprocess``: None (the reference), ``"largest"`` or a dict of ``keep_components``' keywords — the predicted label map goes through
-    ``keep_components`` before it is scored (on the device when it is there)."""
+    ``keep_components`` before it is scored (on the device when it is there).  ``mirror_axes``: None (the reference) or the axes out of
+    0, 1, 2 of mirror test-time augmentation — every window is predicted once per subset of them, at one forward per pass
+    (``test_single_case_base``)."""
     if voxelspacing is not None:
         voxelspacing = _normalize_spacing(voxelspacing)
     post = _postprocess_args(postprocess)
+    _mirror_masks(mirror_axes)
     if cases is None:
         import h5py  # noqa: F401 — same dependency as the reference
         with open(base_dir + "/{}".format(test_list), "r") as f:
@@ -630,7 +681,8 @@ def test_all_case_base(net, net_type, base_dir, test_list="full_test.list", num_
     metric_cal = [[] for _ in range(num_classes - 1)]
     dev = next(net.parameters()).device
     for image, label in cases:      # the label map stays on the net's device up to its scores
-        prediction, _ = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes, want_score=False)
+        prediction, _ = _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size, num_classes, want_score=False,
+                                               mirror_axes=mirror_axes)
         for i, m in enumerate(_score_prediction(prediction, label, num_classes, dev, voxelspacing, post)):
             metric_cal[i].append(m)
     return metric_cal
@@ -654,7 +706,7 @@ def _scan_starts(size: int, roi: int, overlap: float):
 
 @torch.no_grad()
 def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap: float = 0.25, mode="constant", sigma_scale=0.125,
-                             **kwargs):
+                             mirror_axes=None, **kwargs):
     """Restatement of ``monai.inferers.sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.25,
     mode="constant", sigma_scale=0.125)`` as the reference calls it (val_3D.py:130-132): symmetric zero padding of volumes smaller than the
     window, the window grid of ``_scan_starts``, ``sw_batch_size`` windows per forward, predictor OUTPUTS (logits) averaged over
@@ -662,9 +714,14 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     with ``gaussian_importance_map(roi_size, sigma_scale)``, which follows MONAI's Gaussian mode (MONAI filters a delta with an
     erf-integrated kernel; see there) — any other mode is a ValueError.  Everything stays on the device of ``inputs``; an fp32 tensor on a
     HIP device goes through the window kernels (``ICL_VAL_WINDOWS``), anything else, and a predictor whose output extent differs from the
-    window's, through the ATen loop below.  MONAI is not installed in the build image: parity unpinned."""
+    window's, through the ATen loop below.  ``mirror_axes`` (not MONAI's): None, or the axes out of 0, 1, 2 (the three spatial axes of a
+    3-D input) of mirror test-time augmentation — ``sw_batch_size`` then counts passes (``_run_windows``); it is not handed to the
+    predictor.  MONAI is not installed in the build image: parity unpinned."""
+    masks = _mirror_masks(mirror_axes)
     b = inputs.shape[0]
     size = list(inputs.shape[2:])
+    if masks is not None and len(size) != 3:
+        raise ValueError(f"mirror_axes needs a 3-D input [B, C, D, H, W], got shape {tuple(inputs.shape)}")
     roi = [int(r) for r in roi_size]
     imp = _importance_map(mode, roi, sigma_scale, inputs.device)
     pads = []
@@ -676,27 +733,29 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     starts = [(bi, z, y, x) for bi in range(b) for z in grids[0] for y in grids[1] for x in grids[2]]
     (_, out), _ = _run_windows(
         inputs, roi, pads, psize, starts, sw_batch_size, lambda win: predictor(win, **kwargs), imp, False, "quotients",
-        _window_kernels_apply(inputs) and len(size) == 3, _fits_amos(roi, inputs.device))
+        _window_kernels_apply(inputs) and len(size) == 3, _fits_amos(roi, inputs.device), masks=masks)
     return out
 
 
-def test_all_case_amos(net, net_type, val_loader, num_classes=4, voxelspacing=None, postprocess=None):
+def test_all_case_amos(net, net_type, val_loader, num_classes=4, voxelspacing=None, postprocess=None, mirror_axes=None):
     """val_3D.py:120-137: every validation volume through ``sliding_window_inference(image, (96, 96, 96), 4, net[, inference=True])``,
     argmax over the averaged logits, ``cal_metric`` per foreground class.  The reference wraps the inference in fp16 autocast; the
     HIP kernels compute in fp32 (a strictly more accurate evaluation of the same network).  ``voxelspacing`` (a number or three: the voxel
     size along D, H, W) gives HD95 in its units; the loop scores [1, D, H, W] maps, on which every voxel of a class is a border voxel,
     and those take the numpy path when a spacing is given (the surface kernels take 3-D maps).  ``postprocess``: as in
-    ``test_all_case_base``; the [1, D, H, W] prediction is filtered as the 3-D map behind its leading axis."""
+    ``test_all_case_base``; the [1, D, H, W] prediction is filtered as the 3-D map behind its leading axis.  ``mirror_axes``: None, or the
+    axes out of 0, 1, 2 (D, H, W) of mirror test-time augmentation (``sliding_window_inference``)."""
     if voxelspacing is not None:
         voxelspacing = _normalize_spacing(voxelspacing)
     post = _postprocess_args(postprocess)
+    _mirror_masks(mirror_axes)
     metric_cal = [[] for _ in range(num_classes - 1)]
     net.eval()
     dev = next(net.parameters()).device
     for batch in val_loader:
         image, label = batch["image"].to(dev), batch["label"].squeeze(0)
         kw = {"inference": True} if net_type in ("unet_3D_icl", "swinunetr_icl") else {}
-        logits = sliding_window_inference(image, (96, 96, 96), 4, net, **kw)
+        logits = sliding_window_inference(image, (96, 96, 96), 4, net, mirror_axes=mirror_axes, **kw)
         prediction = torch.argmax(logits, dim=1)
         for i, m in enumerate(_score_prediction(prediction, label, num_classes, dev, voxelspacing, post, also=_device_metrics_apply)):
             metric_cal[i].append(m)

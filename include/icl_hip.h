@@ -657,6 +657,12 @@ int icl_seg_filter_components(const void* map, int dtype, int n0, int n1, int n2
  *   out [n][cin][r0][r1][r2] <- vol [cin][s0][s1][s2], voxels outside the unpadded volume read as 0. */
 int icl_window_gather(const float* vol, float* out, const int32_t* origins, int n, int cin, int s0, int s1, int s2, int a0, int a1, int a2,
                       int p0, int p1, int p2, int r0, int r1, int r2, void* stream);
+/* icl_window_gather_flipped (mirror test-time augmentation): icl_window_gather with one mirror mask per window, flips: HOST int32 [n], bit a
+ *   set = axis a of the window mirrored (0 .. 7; copied into the kernel arguments).  out[w] = flip(window w, the axes of flips[w]), bit-equal
+ *   to torch.flip of icl_window_gather's window, zero fill included: the same gather with a reversed source index, no second tensor.  A
+ *   mask outside 0..7 returns -1 (nothing launched), as does everything icl_window_gather refuses. */
+int icl_window_gather_flipped(const float* vol, float* out, const int32_t* origins, const int32_t* flips, int n, int cin, int s0, int s1,
+                              int s2, int a0, int a1, int a2, int p0, int p1, int p2, int r0, int r1, int r2, void* stream);
 /* icl_window_accumulate (val_3D.py:63-70 and :128-132): score [c][p0][p1][p2] and weight [p0][p1][p2] += the batch's windows, logits
  *   [n][c][r0][r1][r2].  One thread owns a destination voxel and walks the windows in their given order: the adds are those of the loop
  *   over windows, in its order, with no atomics; the launch covers the bounding box of the windows.  softmax != 0: the value added is the
@@ -665,6 +671,13 @@ int icl_window_gather(const float* vol, float* out, const int32_t* origins, int 
  *   other, never fused), weight += importance. */
 int icl_window_accumulate(const float* logits, const float* importance, float* score, float* weight, const int32_t* origins, int n, int c,
                           int p0, int p1, int p2, int r0, int r1, int r2, int softmax, void* stream);
+/* icl_window_accumulate_flipped (mirror test-time augmentation): icl_window_accumulate for logits computed on mirrored windows, flips as in
+ *   icl_window_gather_flipped.  The value of window w is mirrored back along the axes of flips[w] as it is read — score[:, window] +=
+ *   flip(value, axes) — in the same order and with the same roundings; the importance map is NOT mirrored: it is indexed in the volume's
+ *   frame.  A mask outside 0..7 returns -1 (nothing launched), as does everything icl_window_accumulate refuses. */
+int icl_window_accumulate_flipped(const float* logits, const float* importance, float* score, float* weight, const int32_t* origins,
+                                  const int32_t* flips, int n, int c, int p0, int p1, int p2, int r0, int r1, int r2, int softmax,
+                                  void* stream);
 /* icl_window_finalize (val_3D.py:71-73 and :128-132): label [s0][s1][s2] int64 = arg-max over the classes of score / weight (IEEE fp32
  *   division; the lowest index wins among equals, NaN as torch.argmax treats it) on the unpadded extent; quotients (may be NULL): the
  *   quotients themselves, cropped, [c][s0][s1][s2] — where nothing is cropped they may be `score` itself (division in place).  label may

@@ -104,20 +104,43 @@ void finish_tile(icl::ConvGeom& g, int ks, int ps_mod, int ps_of) {
   g.PS = ps;
 }
 
-template <int KS, int NBT, bool VEC>
-int conv_fwd_dispatch(const float* x, const float* wp, const float* bias, float* y, const icl::ConvGeom& g, dim3 grid, size_t lds,
-                      hipStream_t stream) {
-  if (lds > (size_t)kMaxDynLds) ICL_SET_MAX_DYN_LDS((icl::conv3d_mfma_fwd_kernel<KS, NBT, 8, kConvWaves, VEC>), kMaxDynLdsBig);
-  ICL_LAUNCH((icl::conv3d_mfma_fwd_kernel<KS, NBT, 8, kConvWaves, VEC>), grid, dim3(kConvWaves * 64), lds, stream, x, wp, bias, y, g);
-  snprintf(g_kernel, sizeof(g_kernel), "conv3d_mfma_fwd_kernel<%d, %d, 8, 4, %s>", KS, NBT, VEC ? "true" : "false");
-  return check_launch("conv3d_fwd");
+// ---- 3x3x3 / 1x1x1 forward and input gradient: plan first, then launch ------------------------------------------------------------
+// A plan is a value made from the shape and the environment switches alone — no tensor pointer, no stream.  The queries
+// (icl_conv3d_fwd_ws_bytes, _presplit_ws_bytes, _stats_slots, _live_ok) read plans; the launch functions take a plan and the pointers
+// and decide only what depends on the pointers.
+
+struct ConvShape { int n, cin, cout, d, h, w; };
+struct ConvArgs { const float* x; const float* wp; const float* bias; float* y; int64_t xbs, ybs; hipStream_t stream; };
+
+// the planner's switches, read per call: the tests switch them
+struct ConvEnv {
+  int split;               // ICL_CONV_SPLIT (1); 0: exact-fp32 MFMA everywhere
+  const char* min_vox;     // ICL_CONV_SPLIT_MIN: smallest volume of the split-product kernels (unset: 24^3; 12^3 / 6^3 on their flat tiles)
+  int flat24, flat12, flat6;   // ICL_CONV_SPLIT_FLAT / _FLAT12 / _FLAT6 (1): the flat tiles of rows of 24 / 12 voxels and of the 6^3 volume (A/B)
+  int ksplit;              // ICL_CONV_SPLIT_KSPLIT: 0: never split (A/B); n > 0: that many slices wherever the shape allows; unset (-1): cost model
+  int cus;                 // ICL_CONV_SPLIT_KSPLIT_CUS (256): the CUs a launch is planned for (the deep backward shares the chip with the narrow
+                           // update streams: optim.h sgd_factored_narrow_kernel)
+  const char* force_tile;  // ICL_CONV_FORCE_TILE, tests only: "48" forces the 4x8x16 fp32 tile on small volumes, "28" the 2x8x16 one
+};
+inline int env_int(const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; }
+ConvEnv conv_env() {
+  const int cus = env_int("ICL_CONV_SPLIT_KSPLIT_CUS", 0);
+  return {env_int("ICL_CONV_SPLIT", 1), getenv("ICL_CONV_SPLIT_MIN"), env_int("ICL_CONV_SPLIT_FLAT", 1), env_int("ICL_CONV_SPLIT_FLAT12", 1),
+          env_int("ICL_CONV_SPLIT_FLAT6", 1), env_int("ICL_CONV_SPLIT_KSPLIT", -1), cus > 0 ? cus : 256, getenv("ICL_CONV_FORCE_TILE")};
 }
 
-// dry-run state: icl_conv3d_fwd_ws_bytes() runs the launcher's own planning code without launching anything
-thread_local struct { bool dry; int64_t need; bool no_split; } g_plan = {false, 0, false};
+inline icl::ConvGeom conv_geom(int cin, int cout, int d, int h, int w, int64_t xbs, int64_t ybs) {
+  icl::ConvGeom g{};
+  g.Cin = cin; g.Cout = cout;
+  g.CinP = round_up(cin, 4); g.CoutP = round_up(cout, 16);
+  g.D = d; g.H = h; g.W = w;
+  g.x_bstride = xbs; g.y_bstride = ybs;
+  return g;
+}
 
 // sum the split-K partial slabs (+bias) into y; no-op when the launch was not split
-int splitk_reduce(const icl::ConvGeom& g, const float* bias, float* y, int n, int64_t ybs, hipStream_t stream) {
+template <class Geom>
+int splitk_reduce(const Geom& g, const float* bias, float* y, int n, int64_t ybs, hipStream_t stream) {
   if (g.ksplit <= 1) return 0;
   const long dhw = (long)g.D * g.H * g.W, per = (long)g.Cout * dhw;
   ICL_LAUNCH(icl::splitk_reduce_kernel, dim3(grid_for((long)n * per, 256)), dim3(256), 0, stream, (const float*)g.slab, bias, y, g.ksplit, n, per,
@@ -126,10 +149,7 @@ int splitk_reduce(const icl::ConvGeom& g, const float* bias, float* y, int n, in
 }
 
 // XCD-aware workgroup order (kernels/conv_mfma.h xcd_chunked): needs gridDim.x % 8 == 0.
-inline int xcd_remap_for(long grid_x) {
-  constexpr int on = 1;
-  return (on && grid_x % 8 == 0 && grid_x >= 64) ? 1 : 0;
-}
+inline int xcd_remap_for(long grid_x) { return (grid_x % 8 == 0 && grid_x >= 64) ? 1 : 0; }
 
 // Cin-chunk split for launches with too few workgroups to fill 256 CUs
 inline int choose_ksplit(long base, int nchunks) {
@@ -143,109 +163,166 @@ inline int choose_ksplit(long base, int nchunks) {
   return ksplit;
 }
 
-// ---- compile-time-tile 3x3x3 kernels (conv_mfma_static.h) -------------------------------------------------
-template <int NBT, class TC>
-int conv_fwd_static_go(const float* x, const float* wp, const float* bias, float* y, icl::ConvGeom g, int n, int64_t ybs,
-                       hipStream_t stream) {
-  constexpr int nb = NBT * 16;
+// ---- the fp32 MFMA kernels: flat full-row tiles, compile-time tiles, the generic kernel ------------------------------------------
+struct Fp32Plan {
+  int rc;                        // -1: no tiling covers the shape (g_err has the text)
+  ConvShape s;
+  icl::ConvGeom g;               // the tile and its LDS layout; strides, slab, the split taken and the workgroup order come with the pointers
+  int nbt, ntiles, ctiles;       // cout blocks per workgroup; grid = (ntiles * ksplit, ctiles, n)
+  size_t lds;
+  int ksplit;                    // the split over the Cin chunks this grid wants: taken when the call brings a workspace
+  int64_t slab_bytes;            // ... of this size
+  int (*go)(const Fp32Plan&, const ConvArgs&, float* slab);     // the instantiation that runs the plan
+};
+
+// what the tile choice leaves to do: the grid, the wanted k-split, the LDS bytes
+void fp32_plan_grid(Fp32Plan& p, int taps) {
+  const icl::ConvGeom& g = p.g;
+  const int nb = p.nbt * 16;
+  p.ntiles = g.ntx * g.nty * g.ntz;
+  p.ctiles = (g.CoutP + nb - 1) / nb;
+  p.ksplit = choose_ksplit((long)p.ntiles * p.ctiles * p.s.n, g.CinP / g.KC);
+  p.slab_bytes = p.ksplit > 1 ? (int64_t)p.ksplit * p.s.n * g.Cout * g.D * g.H * g.W * 4 : 0;
+  p.lds = (size_t)g.KC * (g.PS + taps * nb) * 4;
+}
+
+// the plan's geometry with the pointers of a call; no workspace supplied: run unsplit
+inline icl::ConvGeom fp32_launch_geom(const Fp32Plan& p, const ConvArgs& a, float* slab) {
+  icl::ConvGeom g = p.g;
+  g.x_bstride = a.xbs; g.y_bstride = a.ybs; g.slab = slab;
+  g.ksplit = slab ? p.ksplit : 1;
+  return g;
+}
+
+// compile-time tiles: FwdTile (conv_mfma_static.h, XCD-aware workgroup order) and the full-row FlatTile (conv_mfma_flat.h)
+template <int NBT, class TC, bool FLAT>
+int conv_fwd_tile_go(const Fp32Plan& p, const ConvArgs& a, float* slab) {
+  icl::ConvGeom g = fp32_launch_geom(p, a, slab);
+  const dim3 grid(p.ntiles * g.ksplit, p.ctiles, p.s.n);
+  if constexpr (FLAT) {
+    if (p.lds > (size_t)kMaxDynLds) ICL_SET_MAX_DYN_LDS((icl::conv3d_mfma_fwd_flat_kernel<NBT, TC>), kMaxDynLdsBig);
+    ICL_LAUNCH((icl::conv3d_mfma_fwd_flat_kernel<NBT, TC>), grid, dim3(256), p.lds, a.stream, a.x, a.wp, a.bias, a.y, g);
+    snprintf(g_kernel, sizeof(g_kernel), "conv3d_mfma_fwd_flat_kernel<%d, icl::FlatTile<%d, %d, %d, %d, %s> >", NBT, TC::TZ, TC::TY, TC::TX, TC::KC, TC::VEC ? "true" : "false");
+  } else {
+    if (p.lds > (size_t)kMaxDynLds) ICL_SET_MAX_DYN_LDS((icl::conv3d_mfma_fwd_static_kernel<NBT, TC>), kMaxDynLdsBig);
+    g.remap = xcd_remap_for((long)p.ntiles * g.ksplit);
+    ICL_LAUNCH((icl::conv3d_mfma_fwd_static_kernel<NBT, TC>), grid, dim3(256), p.lds, a.stream, a.x, a.wp, a.bias, a.y, g);
+    snprintf(g_kernel, sizeof(g_kernel), "conv3d_mfma_fwd_static_kernel<%d, icl::FwdTile<%d, %d, %d> >", NBT, TC::TZ, TC::TY, TC::KC);
+  }
+  const int rc = check_launch(FLAT ? "conv3d_fwd_flat" : "conv3d_fwd_static");
+  return rc ? rc : splitk_reduce(g, a.bias, a.y, p.s.n, a.ybs, a.stream);
+}
+
+template <int NBT, class TC, bool FLAT>
+Fp32Plan plan_tile(const ConvShape& s) {
+  Fp32Plan p{};
+  p.s = s; p.nbt = NBT;
+  icl::ConvGeom& g = p.g = conv_geom(s.cin, s.cout, s.d, s.h, s.w, 0, 0);
   g.TZ = TC::TZ; g.TY = TC::TY; g.TX = TC::TX; g.KC = TC::KC; g.PS = TC::PS; g.PXL = TC::PXL; g.HX = TC::HX; g.CPP = TC::CPP;
   g.ntx = (g.W + TC::TX - 1) / TC::TX;
   g.nty = (g.H + TC::TY - 1) / TC::TY;
   g.ntz = (g.D + TC::TZ - 1) / TC::TZ;
-  const int ntiles = g.ntx * g.nty * g.ntz;
-  const int ctiles = (g.CoutP + nb - 1) / nb;
-  const int nchunks = g.CinP / TC::KC;
-  const long base = (long)ntiles * ctiles * n;
-  int ksplit = choose_ksplit(base, nchunks);
-  if (ksplit > 1 && !g.slab && !g_plan.dry) ksplit = 1;   // no workspace supplied: run unsplit
-  g.ksplit = ksplit;
-  if (g_plan.dry) {
-    g_plan.need = ksplit > 1 ? (int64_t)ksplit * n * g.Cout * g.D * g.H * g.W * 4 : 0;
-    return 0;
-  }
-  const size_t lds = (size_t)(TC::KC * TC::PS + TC::T * TC::KC * nb) * 4;
-  if (lds > (size_t)kMaxDynLds) ICL_SET_MAX_DYN_LDS((icl::conv3d_mfma_fwd_static_kernel<NBT, TC>), kMaxDynLdsBig);
-  g.remap = xcd_remap_for((long)ntiles * ksplit);
-  ICL_LAUNCH((icl::conv3d_mfma_fwd_static_kernel<NBT, TC>), dim3(ntiles * ksplit, ctiles, n), dim3(256), lds, stream, x, wp, bias, y, g);
-  snprintf(g_kernel, sizeof(g_kernel), "conv3d_mfma_fwd_static_kernel<%d, icl::FwdTile<%d, %d, %d> >", NBT, TC::TZ, TC::TY, TC::KC);
-  const int rc = check_launch("conv3d_fwd_static");
-  return rc ? rc : splitk_reduce(g, bias, y, n, ybs, stream);
+  fp32_plan_grid(p, TC::T);
+  p.go = conv_fwd_tile_go<NBT, TC, FLAT>;
+  return p;
 }
 
-template <int NBT, class TC>
-int conv_fwd_flat_go(const float* x, const float* wp, const float* bias, float* y, icl::ConvGeom g, int n, int64_t ybs,
-                     hipStream_t stream) {
-  constexpr int nb = NBT * 16;
-  g.TZ = TC::TZ; g.TY = TC::TY; g.TX = TC::TX; g.KC = TC::KC; g.PS = TC::PS; g.PXL = TC::PXL; g.HX = TC::HX; g.CPP = TC::CPP;
-  g.ntx = (g.W + TC::TX - 1) / TC::TX;
-  g.nty = (g.H + TC::TY - 1) / TC::TY;
-  g.ntz = (g.D + TC::TZ - 1) / TC::TZ;
-  const int ntiles = g.ntx * g.nty * g.ntz;
-  const int ctiles = (g.CoutP + nb - 1) / nb;
-  const int nchunks = g.CinP / TC::KC;
-  const long base = (long)ntiles * ctiles * n;
-  int ksplit = choose_ksplit(base, nchunks);
-  if (ksplit > 1 && !g.slab && !g_plan.dry) ksplit = 1;   // no workspace supplied: run unsplit
-  g.ksplit = ksplit;
-  if (g_plan.dry) {
-    g_plan.need = ksplit > 1 ? (int64_t)ksplit * n * g.Cout * g.D * g.H * g.W * 4 : 0;
-    return 0;
-  }
-  const size_t lds = (size_t)(TC::KC * TC::PS + TC::T * TC::KC * nb) * 4;
-  if (lds > (size_t)kMaxDynLds) ICL_SET_MAX_DYN_LDS((icl::conv3d_mfma_fwd_flat_kernel<NBT, TC>), kMaxDynLdsBig);
-  ICL_LAUNCH((icl::conv3d_mfma_fwd_flat_kernel<NBT, TC>), dim3(ntiles * ksplit, ctiles, n), dim3(256), lds, stream, x, wp, bias, y, g);
-  snprintf(g_kernel, sizeof(g_kernel), "conv3d_mfma_fwd_flat_kernel<%d, icl::FlatTile<%d, %d, %d, %d, %s> >", NBT, TC::TZ, TC::TY, TC::TX, TC::KC, TC::VEC ? "true" : "false");
-  const int rc = check_launch("conv3d_fwd_flat");
-  return rc ? rc : splitk_reduce(g, bias, y, n, ybs, stream);
-}
-
-// narrow volumes (the deep U-Net levels): full-row tiles; returns 1 when not applicable
-int conv_fwd_flat(const float* x, const float* wp, const float* bias, float* y, const icl::ConvGeom& g, int n, int64_t ybs,
-                  hipStream_t stream) {
-  if ((g.CinP % 8) != 0 || g.Cout <= 16) return 1;
-  const bool nb48 = (g.CoutP % 48) == 0;
-  constexpr bool kc4 = false;
-  if (g.W == 24 && (g.H % 8) == 0) {
-    if (nb48) return conv_fwd_flat_go<3, icl::FlatTile<2, 8, 24, 4, true>>(x, wp, bias, y, g, n, ybs, stream);
-    return kc4 ? conv_fwd_flat_go<2, icl::FlatTile<2, 8, 24, 4, true>>(x, wp, bias, y, g, n, ybs, stream)
-               : conv_fwd_flat_go<2, icl::FlatTile<2, 8, 24, 8, true>>(x, wp, bias, y, g, n, ybs, stream);
-  }
-  if (g.W == 12 && (g.H % 4) == 0) {
-    if (nb48) return conv_fwd_flat_go<3, icl::FlatTile<4, 4, 12, 4, true>>(x, wp, bias, y, g, n, ybs, stream);
-    return kc4 ? conv_fwd_flat_go<2, icl::FlatTile<4, 4, 12, 4, true>>(x, wp, bias, y, g, n, ybs, stream)
-               : conv_fwd_flat_go<2, icl::FlatTile<4, 4, 12, 8, true>>(x, wp, bias, y, g, n, ybs, stream);
-  }
-  if (g.W == 6 && g.H == 6 && !nb48) return conv_fwd_flat_go<2, icl::FlatTile<6, 6, 6, 8, false>>(x, wp, bias, y, g, n, ybs, stream);
-  return 1;
+// narrow volumes (the deep U-Net levels): full-row tiles; false when not applicable
+bool plan_flat(const ConvShape& s, Fp32Plan& p) {
+  if ((round_up(s.cin, 4) % 8) != 0 || s.cout <= 16) return false;
+  const bool nb48 = (round_up(s.cout, 16) % 48) == 0;
+  if (s.w == 24 && (s.h % 8) == 0) p = nb48 ? plan_tile<3, icl::FlatTile<2, 8, 24, 4, true>, true>(s) : plan_tile<2, icl::FlatTile<2, 8, 24, 8, true>, true>(s);
+  else if (s.w == 12 && (s.h % 4) == 0) p = nb48 ? plan_tile<3, icl::FlatTile<4, 4, 12, 4, true>, true>(s) : plan_tile<2, icl::FlatTile<4, 4, 12, 8, true>, true>(s);
+  else if (s.w == 6 && s.h == 6 && !nb48) p = plan_tile<2, icl::FlatTile<6, 6, 6, 8, false>, true>(s);
+  else return false;
+  return true;
 }
 
 template <int TZ, int TY>
-int conv_fwd_static_tile(const float* x, const float* wp, const float* bias, float* y, const icl::ConvGeom& g, int n, int64_t ybs,
-                         int nbt, hipStream_t stream) {
+Fp32Plan plan_static_tile(const ConvShape& s, int nbt) {
   // KC = 4 channels per chunk: 6-14 % faster than 8 on every 96^3 / 48^3 shape (half the staging registers and LDS -> more waves per
   // SIMD; DESIGN.md section 4).  The 8-channel instantiations are gone (round 5: six kernels nothing launched).
-  if (nbt == 1) return conv_fwd_static_go<1, icl::FwdTile<TZ, TY, 4>>(x, wp, bias, y, g, n, ybs, stream);
-  if (nbt == 2) return conv_fwd_static_go<2, icl::FwdTile<TZ, TY, 4>>(x, wp, bias, y, g, n, ybs, stream);
-  return conv_fwd_static_go<3, icl::FwdTile<TZ, TY, 4>>(x, wp, bias, y, g, n, ybs, stream);
+  if (nbt == 1) return plan_tile<1, icl::FwdTile<TZ, TY, 4>, false>(s);
+  if (nbt == 2) return plan_tile<2, icl::FwdTile<TZ, TY, 4>, false>(s);
+  return plan_tile<3, icl::FwdTile<TZ, TY, 4>, false>(s);
 }
 
-// returns 1 when the shape is not covered by a static tile (caller falls back to the generic kernel)
-int conv_fwd_static(const float* x, const float* wp, const float* bias, float* y, const icl::ConvGeom& g, int n, int64_t ybs,
-                    hipStream_t stream) {
-  if ((g.W % 4) != 0 || g.W < 12 || (g.H % 4) != 0) return 1;
-  const int nbt = g.Cout <= 16 ? 1 : (g.CoutP % 48 == 0 ? 3 : 2);
-  const int ctiles = (g.CoutP + nbt * 16 - 1) / (nbt * 16);
-  if ((g.H % 8) == 0) {
-    const long big = (long)((g.D + 3) / 4) * (g.H / 8) * ((g.W + 15) / 16) * ctiles * n;
-    const char* force = getenv("ICL_CONV_FORCE_TILE");  // tests only: "48" forces the 4x8x16 tile on small volumes
+// false when the shape is not covered by a static tile (the generic kernel takes it)
+bool plan_static(const ConvShape& s, const ConvEnv& e, Fp32Plan& p) {
+  if ((s.w % 4) != 0 || s.w < 12 || (s.h % 4) != 0) return false;
+  const int coutP = round_up(s.cout, 16);
+  const int nbt = s.cout <= 16 ? 1 : (coutP % 48 == 0 ? 3 : 2);
+  if ((s.h % 8) == 0) {
+    const int ctiles = (coutP + nbt * 16 - 1) / (nbt * 16);
+    const long big = (long)((s.d + 3) / 4) * (s.h / 8) * ((s.w + 15) / 16) * ctiles * s.n;
+    const char* force = e.force_tile;
     // 32/48-cout blocks: the 2x8x16 tile (4 accumulator row groups per wave, <= 36 KB LDS -> 4 workgroups per CU) measures
     // 122-136 TFLOP/s on the 96^3 layers against 118-129 for 4x8x16; 16-cout blocks are 2 % faster on 4x8x16 (tools/conv_one.py)
-    if (nbt >= 2 && !(force && force[0] == '4')) return conv_fwd_static_tile<2, 8>(x, wp, bias, y, g, n, ybs, nbt, stream);
-    if (force && force[0] == '2' && force[1] == '8') return conv_fwd_static_tile<2, 8>(x, wp, bias, y, g, n, ybs, nbt, stream);
-    if (big >= 512 || (force && force[0] == '4' && force[1] == '8')) return conv_fwd_static_tile<4, 8>(x, wp, bias, y, g, n, ybs, nbt, stream);
-    return conv_fwd_static_tile<2, 8>(x, wp, bias, y, g, n, ybs, nbt, stream);
+    if (nbt >= 2 && !(force && force[0] == '4')) p = plan_static_tile<2, 8>(s, nbt);
+    else if (force && force[0] == '2' && force[1] == '8') p = plan_static_tile<2, 8>(s, nbt);
+    else if (big >= 512 || (force && force[0] == '4' && force[1] == '8')) p = plan_static_tile<4, 8>(s, nbt);
+    else p = plan_static_tile<2, 8>(s, nbt);
+  } else {
+    p = plan_static_tile<4, 4>(s, nbt);
   }
-  return conv_fwd_static_tile<4, 4>(x, wp, bias, y, g, n, ybs, nbt, stream);
+  return true;
+}
+
+template <int KS, int NBT, bool VEC>
+int conv_fwd_generic_go(const Fp32Plan& p, const ConvArgs& a, float* slab) {
+  const icl::ConvGeom g = fp32_launch_geom(p, a, slab);
+  if (p.lds > (size_t)kMaxDynLds) ICL_SET_MAX_DYN_LDS((icl::conv3d_mfma_fwd_kernel<KS, NBT, 8, kConvWaves, VEC>), kMaxDynLdsBig);
+  ICL_LAUNCH((icl::conv3d_mfma_fwd_kernel<KS, NBT, 8, kConvWaves, VEC>), dim3(p.ntiles * g.ksplit, p.ctiles, p.s.n), dim3(kConvWaves * 64), p.lds,
+             a.stream, a.x, a.wp, a.bias, a.y, g);
+  snprintf(g_kernel, sizeof(g_kernel), "conv3d_mfma_fwd_kernel<%d, %d, 8, 4, %s>", KS, NBT, VEC ? "true" : "false");
+  const int rc = check_launch("conv3d_fwd");
+  return rc ? rc : splitk_reduce(g, a.bias, a.y, p.s.n, a.ybs, a.stream);
+}
+
+// any extent, any channel count: run-time tiles (kernels/conv_mfma.h)
+template <int KS>
+Fp32Plan plan_generic(const ConvShape& s) {
+  Fp32Plan p{};
+  p.s = s;
+  icl::ConvGeom& g = p.g = conv_geom(s.cin, s.cout, s.d, s.h, s.w, 0, 0);
+  const bool vec = KS == 1 && (s.w % 4) == 0;      // 16-byte loads: instantiated for 1x1x1 only (see below)
+  choose_tile(g, KS, 512, vec);
+  finish_tile(g, KS, 16, 32);
+  constexpr int T = KS * KS * KS;
+  p.nbt = s.cout <= 16 ? 1 : (g.CoutP % 48 == 0 ? 3 : 2);
+  const int nb = p.nbt * 16;
+  const int per_ch = (g.TZ + KS - 1) * (g.TY + KS - 1) * (g.PXL / (vec ? 4 : 1));
+  for (int cand = 16; cand >= 4 && !g.KC; cand >>= 1) {
+    if (g.CinP % cand) continue;
+    if ((size_t)cand * (g.PS + T * nb) * 4 > (size_t)kMaxDynLdsFwd) continue;
+    if (T * cand * (nb / 4) > icl::kWX * kConvWaves * 64) continue;
+    const int cpp = cand / 4 > 1 ? cand / 4 : 1;
+    if (cpp * per_ch > icl::kJX * kConvWaves * 64) continue;
+    g.KC = cand;
+    g.CPP = cpp;
+  }
+  const int mt = g.TZ * g.TY * g.TX;
+  if (!g.KC) p.rc = fail(-1, "conv3d_fwd: no LDS tiling for %dx%dx%d cin %d cout %d", s.d, s.h, s.w, s.cin, s.cout);
+  else if (mt > kConvWaves * 8 * 16) p.rc = fail(-1, "conv3d_fwd: tile of %d voxels too large", mt);
+  if (p.rc) return p;
+  fp32_plan_grid(p, T);
+  // (the 16-byte-load instantiations of this generic kernel exist for 1x1x1 only: every 3x3x3 shape of the models runs on the split-product,
+  // flat or compile-time-tile kernels above, and what falls through to here — odd extents, channel counts that are no multiple of 4 — is
+  // not worth 135 KB of code object)
+#define ICL_FWD_CASE(NBT_) (vec ? conv_fwd_generic_go<KS, NBT_, KS == 1> : conv_fwd_generic_go<KS, NBT_, false>)
+  if (p.nbt == 1) p.go = ICL_FWD_CASE(1);
+  else if (p.nbt == 2) p.go = ICL_FWD_CASE(2);
+  else p.go = ICL_FWD_CASE(3);
+#undef ICL_FWD_CASE
+  return p;
+}
+
+// the fp32 plan of a shape: what runs where the split-product kernels do not
+template <int KS>
+Fp32Plan plan_conv_fp32(const ConvShape& s, const ConvEnv& e) {
+  Fp32Plan p{};
+  if (KS == 3 && (plan_flat(s, p) || plan_static(s, e, p))) return p;
+  return plan_generic<KS>(s);
 }
 
 // workgroups = pairs * n * split ~ two per CU; each (split, batch) pair owns one partial-sum slab
@@ -256,19 +333,18 @@ inline int wgrad_max_split(int pairs, int n) {
 
 constexpr int kWgradWaveGroups = 2;   // 8-wave workgroups: two wave groups, each with its own slab
 
-// Live batch (icl_conv3d_wgrad_live): samples [n_live, n) of dY are exactly zero.  The tile-list kernels keep the plan of the batch of n
+// Live batch (icl_conv3d_wgrad_live): samples [n_live, n) of dY are exactly zero (n_live == n: no live batch).  The tile-list kernels keep the plan of the batch of n
 // — tiles are numbered sample-outermost, so the workgroups that own live tiles are a prefix of the grid — launch that prefix only and
 // write the slabs of the rest as zeros (what those workgroups would have written): the reduction sums the same slabs in the same order,
-// the weight gradient is bit for bit the full call's.  0: no live batch.  Every other weight-gradient kernel runs the whole batch.
-thread_local int g_wgrad_n_live = 0;
+// the weight gradient is bit for bit the full call's.  Every other weight-gradient kernel runs the whole batch.
 thread_local int g_wgrad_grid[2] = {0, 0};      // workgroups launched / planned by the last tile-list weight-gradient launch (tests)
 thread_local char g_kernel_live_fwd[160] = "";  // kernel of the last live input-gradient launch (icl_conv3d_fwd*_live), for the tests
 
 // workgroups of a tile-list launch that own a live tile; zeros to the slabs of the others
-inline int wgrad_live_prefix(float* gwp, int nsplit, int ntiles, int tiles_per_wg, int n, long slab_elems, hipStream_t stream) {
+inline int wgrad_live_prefix(float* gwp, int nsplit, int ntiles, int tiles_per_wg, int n, int n_live, long slab_elems, hipStream_t stream) {
   g_wgrad_grid[0] = g_wgrad_grid[1] = nsplit;
-  if (g_wgrad_n_live < 1 || g_wgrad_n_live >= n) return nsplit;
-  const long live_tiles = (long)g_wgrad_n_live * (ntiles / n);
+  if (n_live >= n) return nsplit;
+  const long live_tiles = (long)n_live * (ntiles / n);
   int gx = (int)cdivl(live_tiles, tiles_per_wg);
   if (gx >= nsplit) return nsplit;
   if (gx < 1) gx = 1;
@@ -301,7 +377,7 @@ int conv_wgrad_static_go(const float* x, const float* gy, float* gwp, icl::ConvG
 // Split-product weight gradient (kernels/conv_wgrad_tr.h): 2 x 4 x 16 tiles in two LDS buffers, transposing LDS
 // reads, eight waves (k-step x tap half).  NCB = 2 when the padded Cout is a multiple of 32, else one cout block per workgroup column.
 template <int NCB>
-int conv_wgrad_tr_go(const float* x, const float* gy, float* gwp, const icl::ConvGeom& g, int n, int* nslabs, hipStream_t stream) {
+int conv_wgrad_tr_go(const float* x, const float* gy, float* gwp, const icl::ConvGeom& g, int n, int n_live, int* nslabs, hipStream_t stream) {
   typedef icl::WgTrT<NCB> C;
   icl::Bf3WGeom w{};
   w.Cin = g.Cin; w.Cout = g.Cout; w.CinP = g.CinP; w.CoutP = g.CoutP; w.D = g.D; w.H = g.H; w.W = g.W;
@@ -319,7 +395,7 @@ int conv_wgrad_tr_go(const float* x, const float* gy, float* gwp, const icl::Con
   *nslabs = nsplit;
   { const char* e = getenv("ICL_WGRAD_TR_DBG"); w.dbg = e ? atoi(e) : 0; }
   ICL_SET_MAX_DYN_LDS((icl::conv3d_wgrad_tr_kernel<NCB>), 160 * 1024);
-  const int gx = wgrad_live_prefix(gwp, nsplit, w.ntiles, w.tiles_per_wg, n, 27L * w.CinP * w.CoutP, stream);
+  const int gx = wgrad_live_prefix(gwp, nsplit, w.ntiles, w.tiles_per_wg, n, n_live, 27L * w.CinP * w.CoutP, stream);
   ICL_LAUNCH((icl::conv3d_wgrad_tr_kernel<NCB>), dim3(gx, pairs), dim3(512), C::LDS_BYTES, stream, x, gy, gwp, w);
   snprintf(g_kernel, sizeof(g_kernel), "conv3d_wgrad_tr_kernel<%d>", NCB);
   return check_launch("conv3d_wgrad_tr");
@@ -328,7 +404,7 @@ int conv_wgrad_tr_go(const float* x, const float* gy, float* gwp, const icl::Con
 // Split-product weight gradient walking z-columns of 1 x 8 x 16 tiles with a ring of halo planes in LDS (kernels/conv_wgrad_zs.h):
 // a phase stages 180 + 128 NCB positions instead of 432 + 128 NCB.  Same workspace bound and slab format as conv_wgrad_tr_go.
 template <int NCB>
-int conv_wgrad_zs_go(const float* x, const float* gy, float* gwp, const icl::ConvGeom& g, int n, int* nslabs, hipStream_t stream) {
+int conv_wgrad_zs_go(const float* x, const float* gy, float* gwp, const icl::ConvGeom& g, int n, int n_live, int* nslabs, hipStream_t stream) {
   // one cout block: ten waves — the 360 + 256 staging items of a phase are exactly one round of 640 threads (waves 8 and 9 only stage)
   constexpr int NW = NCB == 1 ? 10 : 8;
   typedef icl::WgZsT<NCB, NW> C;
@@ -349,7 +425,7 @@ int conv_wgrad_zs_go(const float* x, const float* gy, float* gwp, const icl::Con
   *nslabs = nsplit;
   { const char* e = getenv("ICL_WGRAD_TR_DBG"); w.dbg = e ? atoi(e) : 0; }
   ICL_SET_MAX_DYN_LDS((icl::conv3d_wgrad_zs_kernel<NCB, NW>), 160 * 1024);
-  const int gx = wgrad_live_prefix(gwp, nsplit, w.ntiles, w.tiles_per_wg, n, 27L * w.CinP * w.CoutP, stream);
+  const int gx = wgrad_live_prefix(gwp, nsplit, w.ntiles, w.tiles_per_wg, n, n_live, 27L * w.CinP * w.CoutP, stream);
   ICL_LAUNCH((icl::conv3d_wgrad_zs_kernel<NCB, NW>), dim3(gx, pairs), dim3(C::NT), C::LDS_BYTES, stream, x, gy, gwp, w);
   snprintf(g_kernel, sizeof(g_kernel), "conv3d_wgrad_zs_kernel<%d, %d>", NCB, NW);
   return check_launch("conv3d_wgrad_zs");
@@ -357,7 +433,7 @@ int conv_wgrad_zs_go(const float* x, const float* gy, float* gwp, const icl::Con
 
 // Weight gradient on split products (kernels/conv_wgrad_tr.h, conv_wgrad_zs.h).  Returns 1 when the shape is left to the fp32 kernels.
 // ICL_CONV_SPLIT=0 / ICL_WGRAD_SPLIT=0: exact-fp32 MFMA weight gradients.
-int conv_wgrad_split(const float* x, const float* gy, float* gwp, const icl::ConvGeom& g, int n, int* nslabs, hipStream_t stream) {
+int conv_wgrad_split(const float* x, const float* gy, float* gwp, const icl::ConvGeom& g, int n, int n_live, int* nslabs, hipStream_t stream) {
   const char* e_on = getenv("ICL_CONV_SPLIT");
   const char* e_min = getenv("ICL_CONV_SPLIT_MIN");
   const char* e_w = getenv("ICL_WGRAD_SPLIT");
@@ -373,15 +449,15 @@ int conv_wgrad_split(const float* x, const float* gy, float* gwp, const icl::Con
   // 96^3: x is staged once per 48 couts instead of once per 16).  ICL_WGRAD_ZS=0: the 2 x 4 x 16-tile kernel everywhere (A/B).
   const char* e_zs = getenv("ICL_WGRAD_ZS");
   if ((e_zs ? atoi(e_zs) : 1) && g.H % 8 == 0 && g.D >= 8) {
-    if (!two && g.CoutP % 48 == 0) return conv_wgrad_zs_go<3>(x, gy, gwp, g, n, nslabs, stream);
-    return two ? conv_wgrad_zs_go<2>(x, gy, gwp, g, n, nslabs, stream) : conv_wgrad_zs_go<1>(x, gy, gwp, g, n, nslabs, stream);
+    if (!two && g.CoutP % 48 == 0) return conv_wgrad_zs_go<3>(x, gy, gwp, g, n, n_live, nslabs, stream);
+    return two ? conv_wgrad_zs_go<2>(x, gy, gwp, g, n, n_live, nslabs, stream) : conv_wgrad_zs_go<1>(x, gy, gwp, g, n, n_live, nslabs, stream);
   }
-  return two ? conv_wgrad_tr_go<2>(x, gy, gwp, g, n, nslabs, stream) : conv_wgrad_tr_go<1>(x, gy, gwp, g, n, nslabs, stream);
+  return two ? conv_wgrad_tr_go<2>(x, gy, gwp, g, n, n_live, nslabs, stream) : conv_wgrad_tr_go<1>(x, gy, gwp, g, n, n_live, nslabs, stream);
 }
 
-int conv_wgrad_static(const float* x, const float* gy, float* gwp, const icl::ConvGeom& g, int n, int* nslabs, hipStream_t stream) {
+int conv_wgrad_static(const float* x, const float* gy, float* gwp, const icl::ConvGeom& g, int n, int n_live, int* nslabs, hipStream_t stream) {
   {   // the split-product kernels check their own shape conditions (the round-3 kernel takes any extent)
-    const int rc = conv_wgrad_split(x, gy, gwp, g, n, nslabs, stream);
+    const int rc = conv_wgrad_split(x, gy, gwp, g, n, n_live, nslabs, stream);
     if (rc != 1) return rc;
   }
   if ((g.W % 4) != 0 || g.W < 12 || (g.H % 4) != 0) return 1;
@@ -391,19 +467,6 @@ int conv_wgrad_static(const float* x, const float* gy, float* gwp, const icl::Co
   // one cout block: 8 waves x 8 tap groups (124 registers, no spills, four waves per SIMD): 79 vs 74 TFLOP/s on 16->16 @96^3,
   // 92 vs 86 on 48->16; with two / three cout blocks the same split spills (10 / 69 registers) and is equal / slower
   return conv_wgrad_static_go<icl::WgradTileT<4, 4>, 8, 1, 8>(x, gy, gwp, g, n, nslabs, stream);
-}
-
-// 3x3x3 forward / input gradient on the bf16 matrix pipe with every fp32 operand split exactly into three bf16 terms (six MFMA terms
-// per product, fp32 accumulation: fp32 accuracy at 2.67x the fp32 matrix rate, kernels/conv_bf16x3.h).  Takes the same packed fp32
-// weights as the fp32 kernels.  Returns 1 when the shape is left to them: Cin not a multiple of 16, rows not 16-byte granular, or a
-// volume too small for 4 x 8 x 16 tiles to fill the chip.  ICL_CONV_SPLIT=0 turns it off (exact-fp32-MFMA everywhere).
-// sum the split-K slices of a split-product launch (+ bias) into y
-int splitk_reduce_bf3(const icl::Bf3Geom& g, const float* bias, float* y, int n, int64_t ybs, hipStream_t stream) {
-  if (g.ksplit <= 1) return 0;
-  const long dhw = (long)g.D * g.H * g.W, per = (long)g.Cout * dhw;
-  ICL_LAUNCH(icl::splitk_reduce_kernel, dim3(grid_for((long)n * per, 256)), dim3(256), 0, stream, (const float*)g.slab, bias, y, g.ksplit, n, per,
-             dhw, (long)ybs);
-  return check_launch("splitk_reduce");
 }
 
 // Split over the channel chunks for the split-product launches of the deep levels (round 6).  `base` workgroups of `nchunks` chunk
@@ -432,7 +495,7 @@ int conv_fwd_split_go(const float* x, const float* wp, const float* bias, float*
   const size_t lds = flat == 12 ? icl::Bf3F12::lds_bytes(NBT, NBT == 1 ? 3 : 1)
                      : flat == 6 ? icl::Bf3F6::lds_bytes(NBT, NBT == 1 ? 3 : 1)
                      : flat   ? icl::Bf3F24::lds_bytes(NBT, NBT == 1 ? 3 : 1) : icl::Bf3T<8>::lds_bytes(NBT, NBT == 1 ? 3 : 1);
-  // g.wgs: a multiple of 8 (one tile list per XCD), from conv_fwd_split; split launches: one tile per workgroup, grid.z slices
+  // g.wgs: a multiple of 8 (one tile list per XCD), from split_geom; split launches: one tile per workgroup, grid.z slices
   const dim3 grid(g.wgs, (g.CoutP + 16 * NBT - 1) / (16 * NBT), g.ksplit > 1 ? g.ksplit : 1);
   // One cout block on 4 x 8 x 16 tiles (round 4): eight consumer waves + four loader waves (kernels/conv_bf16x3_ws.h), 1.10-1.18x the
   // single-role kernel on the 16-cout layers at 96^3 (16->16 130 vs 147-154 us, 48->16 370 vs 408, 32->16 256 vs 286; bit-identical
@@ -467,179 +530,125 @@ int conv_fwd_split_go(const float* x, const float* wp, const float* bias, float*
     snprintf(g_kernel, sizeof(g_kernel), "conv3d_bf16x3_fwd_kernel<%d, 8, 60>", NBT);
   }
   const int rc = check_launch("conv3d_fwd_split");
-  return rc ? rc : splitk_reduce_bf3(g, bias, y, g.nbatch, g.y_bstride, stream);
+  return rc ? rc : splitk_reduce(g, bias, y, g.nbatch, g.y_bstride, stream);
 }
 
-// stats != nullptr: InstanceNorm statistics of the output from the epilogue (kernels/conv_bf16x3.h bf3_stats_*), one summary per
-// (sample, channel, workgroup); *stats_slots receives the workgroup count (the normalisation's `nchunks`).  slots_only: no launch, just
-// the count (0 when the statistics cannot be produced: shape not on this kernel, or a workgroup's tile list would span two samples).
-// slab / slab_bytes_out: the workspace of the split-K launches of the deep levels (rows of 12 and 24 voxels, round 6).  With wp != nullptr
-// it lies behind the split weights in ws; the pre-split entry points pass their own (icl_conv3d_fwd_presplit_ws).  No slab, no split.
-int conv_fwd_split(const float* x, const float* wp, const float* bias, float* y, float* ws, int n, int cin, int cout, int d, int h, int w,
-                   int64_t xbs, int64_t ybs, hipStream_t stream, float* stats = nullptr, int* stats_slots = nullptr, bool slots_only = false,
-                   float* slab = nullptr, int64_t* slab_bytes_out = nullptr) {
-  const char* e_on = getenv("ICL_CONV_SPLIT");                // read per call: the tests switch it
-  const char* e_min = getenv("ICL_CONV_SPLIT_MIN");
-  const int on = e_on ? atoi(e_on) : 1;
-  // from 24^3 on (round 3, with schedule variant 60; batch 2, fp32 flat-tile kernel in brackets): 64->64 @24^3 62 us (78), 128->64 111
-  // (125), 64->128 117 (137), 32->64 35 (50); at 12^3 the 4 x 8 x 16 tiles leave most of the chip idle: 128->128 108 us (44)
-  // Round 6: rows of 12 voxels (the 12^3 level) on flat 4 x 4 x 12 tiles, split over the channel chunks so that the 18 tiles of a batch
-  // of two fill the chip (kernels/conv_bf16x3.h Bf3F12); needs two cout blocks per workgroup (CoutP % 32 == 0) and the slab workspace.
-  const char* e_f12 = getenv("ICL_CONV_SPLIT_FLAT12");
-  const bool f12_shape = w == icl::Bf3F12::TX && h % icl::Bf3F12::TY == 0 && d % icl::Bf3F12::TZ == 0 && round_up(cout, 16) % 32 == 0 &&
-                         (e_f12 ? atoi(e_f12) : 1);
-  // ... and a whole 6^3 volume (the centre block) as ONE flat tile (Bf3F6), likewise for split launches only
-  const char* e_f6 = getenv("ICL_CONV_SPLIT_FLAT6");
-  const bool f6_shape = w == 6 && h == 6 && d == 6 && round_up(cout, 16) % 32 == 0 && (e_f6 ? atoi(e_f6) : 1);
-  const long min_vox = e_min ? atol(e_min) : (f6_shape ? 216L : f12_shape ? 12L * 12 * 12 : 24L * 24 * 24);
-  if (!on || g_plan.no_split || (cin & 15) || ((w & 3) && !f6_shape) || (long)d * h * w < min_vox || (ybs & 3) || (long)d * h * w * 64 > (1L << 31)) return 1;
-  // workspace: the split weights, (Cin / 16) x 3 dz planes x 60 CoutP slots of 16 bytes
-  const int64_t need = (int64_t)(cin / 16) * 3 * 6 * icl::Bf3::SLOTS * round_up(cout, 16) * 16;
-  // split over the channel chunks (flat tiles only): slices x dense output
-  const char* e_flat = getenv("ICL_CONV_SPLIT_FLAT");
-  const bool f24_shape = w == icl::Bf3F24::TX && (e_flat ? atoi(e_flat) : 1);
-  const bool f12 = f12_shape && !f24_shape, f6 = f6_shape;
-  int ksplit = 1;
-  {
-    const char* e_ks = getenv("ICL_CONV_SPLIT_KSPLIT");      // 0: never split (A/B); n > 1: that many slices wherever the shape allows
-    const char* e_cus = getenv("ICL_CONV_SPLIT_KSPLIT_CUS"); // the CUs a launch is planned for (the deep backward shares the chip with the
-                                                            // narrow update streams: optim.h sgd_factored_narrow_kernel)
-    const int nchunks = cin / 16, cus = e_cus && atoi(e_cus) > 0 ? atoi(e_cus) : 256;
-    const int coutP = round_up(cout, 16);
-    if (f6) {
-      ksplit = choose_ksplit_bf3((long)n * (coutP / 32), nchunks, cus, 8.0, 4.0 * n * cout * d * h * w);      // one 8-wave workgroup per CU
-    } else if (f12) {
-      const long base = (long)n * (d / icl::Bf3F12::TZ) * (h / icl::Bf3F12::TY) * (coutP / 32);
-      ksplit = choose_ksplit_bf3(base, nchunks, 2 * cus, 6.0, 4.0 * n * cout * d * h * w);      // two workgroups per CU
-    } else if (f24_shape) {
-      const int nbt = coutP % 48 == 0 ? 3 : (cout > 16 ? 2 : 1);
-      const long base = (long)n * cdivl(d, icl::Bf3F24::TZ) * cdivl(h, icl::Bf3F24::TY) * cdivl(coutP, 16 * nbt);
-      ksplit = choose_ksplit_bf3(base, nchunks, cus, 6.0 * nbt, 4.0 * n * cout * d * h * w);
-    }
-    if (e_ks && atoi(e_ks) >= 0) ksplit = atoi(e_ks) == 0 ? 1 : (atoi(e_ks) < nchunks ? atoi(e_ks) : nchunks);
-    if (ksplit < 1) ksplit = 1;
-  }
-  const int64_t slab_need = ksplit > 1 ? (int64_t)ksplit * n * cout * d * h * w * 4 : 0;
-  if (slab_bytes_out) *slab_bytes_out = slab_need;
-  if (g_plan.dry) { g_plan.need = need + slab_need; return 0; }
-  if (!slots_only && (!ws || !aligned16(ws) || !aligned16(y))) return 1;      // (wp == nullptr: ws holds the split weights already)
-  if (wp && ksplit > 1) slab = ws + need / 4;                                  // behind the split weights (icl_conv3d_fwd_ws_bytes)
-  if (ksplit > 1 && !slab && !slots_only) {      // (slots_only: the plan itself — the caller is about to size the workspace from it)
-    if (f12 || f6) return 1;      // these tiles exist for split launches only: without a workspace the fp32 kernels take the call
-    ksplit = 1;
-  }
+// ---- the split-product plan and its launch ---------------------------------------------------------------------------------------
+struct SplitPlan {
+  bool ok;                       // the shape runs on the split-product kernels; a call is handed back only for what its pointers say
+  ConvShape s;
+  int flat;                      // tiles: 0: 4 x 8 x 16; 24 / 12: flat rows of that many voxels; 6: the whole 6^3 volume
+  int nbt;                       // cout blocks per workgroup
+  int ksplit;                    // slices over the channel chunks the cost model wants (1: none); taken when the call brings a slab
+  int64_t w_bytes, slab_bytes;   // the split weights, (Cin / 16) x 3 dz planes x 60 CoutP slots of 16 bytes; the slabs of the slices
+  int slots;                     // statistics slots per (sample, channel); 0 where the epilogue cannot give them
+  icl::Bf3Geom g;                // of the launch with `ksplit` slices; strides, slab and statistics come with the pointers
+};
+
+// The geometry of a split-product launch with `ksplit` slices, all but the pointers and strides.
+icl::Bf3Geom split_geom(const ConvShape& s, int flat, int ksplit) {
   icl::Bf3Geom g{};
-  g.Cin = cin; g.Cout = cout; g.CinP = round_up(cin, 4); g.CoutP = round_up(cout, 16);
-  g.D = d; g.H = h; g.W = w;
-  // rows of 24 voxels: flat 2 x 8 x 24 tiles (kernels/conv_bf16x3.h Bf3F24) instead of 4 x 8 x 16 ones whose second x tile is half
-  // empty; ICL_CONV_SPLIT_FLAT=0 switches it off (A/B)
-  const int flat = f6 ? 6 : f12 ? 12 : (f24_shape ? 24 : 0);
-  if ((f12 || f6) && ksplit <= 1 && !slots_only) return 1;      // (a 12^3 / 6^3 layer of one chunk: nothing to split, left to the fp32 kernels)
+  g.Cin = s.cin; g.Cout = s.cout; g.CinP = round_up(s.cin, 4); g.CoutP = round_up(s.cout, 16);
+  g.D = s.d; g.H = s.h; g.W = s.w;
   if (flat == 6) { g.ntz = g.nty = g.ntx = 1; }
-  else if (flat == 12) { g.ntz = d / icl::Bf3F12::TZ; g.nty = h / icl::Bf3F12::TY; g.ntx = 1; }
-  else if (flat) { g.ntz = (d + icl::Bf3F24::TZ - 1) / icl::Bf3F24::TZ; g.nty = (h + icl::Bf3F24::TY - 1) / icl::Bf3F24::TY; g.ntx = 1; }
-  else { g.ntz = (d + 3) / 4; g.nty = (h + 7) / 8; g.ntx = (w + 15) / 16; }
-  g.ntiles = n * g.ntz * g.nty * g.ntx;
-  g.nchunks = cin / 16;
-  g.x_bstride = xbs; g.y_bstride = ybs;
+  else if (flat == 12) { g.ntz = s.d / icl::Bf3F12::TZ; g.nty = s.h / icl::Bf3F12::TY; g.ntx = 1; }
+  else if (flat) { g.ntz = (s.d + icl::Bf3F24::TZ - 1) / icl::Bf3F24::TZ; g.nty = (s.h + icl::Bf3F24::TY - 1) / icl::Bf3F24::TY; g.ntx = 1; }
+  else { g.ntz = (s.d + 3) / 4; g.nty = (s.h + 7) / 8; g.ntx = (s.w + 15) / 16; }
+  g.ntiles = s.n * g.ntz * g.nty * g.ntx;
+  g.nchunks = s.cin / 16;
+  g.nbatch = s.n;
   g.flags = g.CoutP % 48 == 0 ? 2 : 0;      // non-temporal output stores for three cout blocks (kernels/conv_bf16x3.h)
   // the workgroup count along x, computed here and nowhere else: the launch grid AND the statistics slots per (sample, channel) that the
   // caller sized its buffer for (ADVICE round 4: the two must not be separate formulas)
   g.wgs = g.ntiles < 256 ? (g.ntiles + 7) / 8 * 8 : 256;
-  g.nbatch = n;
   if (ksplit > 1) {      // one tile per workgroup, grid.z slices, raw partial sums into the slab; no statistics from the epilogue
-    g.ksplit = ksplit; g.slab = slab; g.slab_stride = (long)n * cout * d * h * w;
+    g.ksplit = ksplit; g.slab_stride = (long)s.n * s.cout * s.d * s.h * s.w;
     g.flags = 4;           // (plain stores: the slab is read back at once)
     g.wgs = g.ntiles;
-    if (stats_slots) *stats_slots = 0;
-    if (slots_only) return 0;
-    if (stats) return 1;
-  } else if (stats || slots_only) {
-    // a workgroup walks tiles of ONE XCD's contiguous eighth of the tile list: its summary belongs to one sample iff no eighth spans two
-    const int tiles_per = g.ntz * g.nty * g.ntx, per_xcd = (g.ntiles + 7) / 8;
-    const bool one_sample = n == 1 || tiles_per % per_xcd == 0;
-    if (stats_slots) *stats_slots = one_sample ? g.wgs : 0;
-    if (slots_only) return 0;
-    if (!one_sample) return 1;
-    g.stats = stats; g.nbatch = n;
   }
-  if (flat == 12 || flat == 6) return conv_fwd_split_go<2>(x, wp, bias, y, (uint4*)ws, g, stream, flat);
-  if (g.CoutP % 48 == 0) return conv_fwd_split_go<3>(x, wp, bias, y, (uint4*)ws, g, stream, flat);
-  if (cout > 16) return conv_fwd_split_go<2>(x, wp, bias, y, (uint4*)ws, g, stream, flat);
-  return conv_fwd_split_go<1>(x, wp, bias, y, (uint4*)ws, g, stream, flat);
+  return g;
+}
+
+// InstanceNorm statistics from the epilogue (kernels/conv_bf16x3.h bf3_stats_*): one summary per (sample, channel, workgroup), g.wgs slots
+// (the normalisation's `nchunks`).  0: a split launch, or a workgroup's tile list would span two samples — a workgroup walks tiles of
+// ONE XCD's contiguous eighth of the tile list: its summary belongs to one sample iff no eighth spans two.
+inline int split_stats_slots(const icl::Bf3Geom& g) {
+  if (g.ksplit > 1) return 0;
+  const int tiles_per = g.ntz * g.nty * g.ntx, per_xcd = (g.ntiles + 7) / 8;
+  return g.nbatch == 1 || tiles_per % per_xcd == 0 ? g.wgs : 0;
+}
+
+// 3x3x3 forward / input gradient on the bf16 matrix pipe with every fp32 operand split exactly into three bf16 terms (six MFMA terms
+// per product, fp32 accumulation: fp32 accuracy at 2.67x the fp32 matrix rate, kernels/conv_bf16x3.h).  Takes the same packed fp32
+// weights as the fp32 kernels.  Not ok — left to them: Cin not a multiple of 16, rows not 16-byte granular, or a volume too small for
+// its tiles to fill the chip.
+SplitPlan plan_conv_split(const ConvShape& s, const ConvEnv& e) {
+  SplitPlan p{};
+  p.s = s;
+  const int coutP = round_up(s.cout, 16), nchunks = s.cin / 16;
+  const long vox = (long)s.d * s.h * s.w;
+  // from 24^3 on (round 3, with schedule variant 60; batch 2, fp32 flat-tile kernel in brackets): 64->64 @24^3 62 us (78), 128->64 111
+  // (125), 64->128 117 (137), 32->64 35 (50); at 12^3 the 4 x 8 x 16 tiles leave most of the chip idle: 128->128 108 us (44)
+  // Round 6: rows of 12 voxels (the 12^3 level) on flat 4 x 4 x 12 tiles, split over the channel chunks so that the 18 tiles of a batch
+  // of two fill the chip (kernels/conv_bf16x3.h Bf3F12); needs two cout blocks per workgroup (CoutP % 32 == 0) and the slab workspace.
+  const bool f12_shape = s.w == icl::Bf3F12::TX && s.h % icl::Bf3F12::TY == 0 && s.d % icl::Bf3F12::TZ == 0 && coutP % 32 == 0 && e.flat12;
+  // ... and a whole 6^3 volume (the centre block) as ONE flat tile (Bf3F6), likewise for split launches only
+  const bool f6 = s.w == 6 && s.h == 6 && s.d == 6 && coutP % 32 == 0 && e.flat6;
+  const long min_vox = e.min_vox ? atol(e.min_vox) : (f6 ? 216L : f12_shape ? 12L * 12 * 12 : 24L * 24 * 24);
+  if (!e.split || (s.cin & 15) || ((s.w & 3) && !f6) || vox < min_vox || vox * 64 > (1L << 31)) return p;
+  p.ok = true;
+  p.w_bytes = (int64_t)nchunks * 3 * 6 * icl::Bf3::SLOTS * coutP * 16;
+  // rows of 24 voxels: flat 2 x 8 x 24 tiles (kernels/conv_bf16x3.h Bf3F24) instead of 4 x 8 x 16 ones whose second x tile is half empty
+  const bool f24 = s.w == icl::Bf3F24::TX && e.flat24, f12 = f12_shape && !f24;
+  p.flat = f6 ? 6 : f12 ? 12 : (f24 ? 24 : 0);
+  p.nbt = (f12 || f6) ? 2 : coutP % 48 == 0 ? 3 : (s.cout > 16 ? 2 : 1);
+  // split over the channel chunks (flat tiles only): slices x dense output
+  const double out_bytes = 4.0 * s.n * s.cout * vox;
+  p.ksplit = 1;
+  if (f6) p.ksplit = choose_ksplit_bf3((long)s.n * (coutP / 32), nchunks, e.cus, 8.0, out_bytes);      // one 8-wave workgroup per CU
+  else if (f12) p.ksplit = choose_ksplit_bf3((long)s.n * (s.d / icl::Bf3F12::TZ) * (s.h / icl::Bf3F12::TY) * (coutP / 32), nchunks, 2 * e.cus, 6.0,
+                                             out_bytes);      // two workgroups per CU
+  else if (f24) p.ksplit = choose_ksplit_bf3((long)s.n * cdivl(s.d, icl::Bf3F24::TZ) * cdivl(s.h, icl::Bf3F24::TY) * cdivl(coutP, 16 * p.nbt), nchunks,
+                                             e.cus, 6.0 * p.nbt, out_bytes);
+  if (e.ksplit >= 0) p.ksplit = e.ksplit == 0 ? 1 : (e.ksplit < nchunks ? e.ksplit : nchunks);
+  if (p.ksplit < 1) p.ksplit = 1;
+  p.slab_bytes = p.ksplit > 1 ? (int64_t)p.ksplit * s.n * s.cout * vox * 4 : 0;
+  p.g = split_geom(s, p.flat, p.ksplit);
+  p.slots = split_stats_slots(p.g);
+  return p;
+}
+
+// Runs a split-product plan; 1: not this kernel, the fp32 kernels take the call.  a.wp == nullptr: ws holds the split weights already
+// (the pre-split entry points); else they are split into ws, and the slab of a split launch lies behind them (icl_conv3d_fwd_ws_bytes).
+// slab: the workspace of the split launches of the pre-split entry points (icl_conv3d_fwd_presplit_ws).  No slab, no split.
+// stats != nullptr: the epilogue writes the InstanceNorm statistics of the output there.
+int conv_fwd_split_launch(const SplitPlan& p, const ConvArgs& a, float* ws, float* stats = nullptr, float* slab = nullptr) {
+  if (!p.ok || (a.ybs & 3) || !ws || !aligned16(ws) || !aligned16(a.y)) return 1;
+  if (a.wp && p.ksplit > 1) slab = ws + p.w_bytes / 4;
+  const int ksplit = slab ? p.ksplit : 1;
+  // the 12-voxel rows and the 6^3 tile exist for split launches only: without a workspace, or with one chunk, the fp32 kernels take the call
+  if ((p.flat == 12 || p.flat == 6) && ksplit <= 1) return 1;
+  icl::Bf3Geom g = ksplit == p.ksplit ? p.g : split_geom(p.s, p.flat, 1);      // (rows of 24 without a slab: the unsplit launch)
+  g.x_bstride = a.xbs; g.y_bstride = a.ybs;
+  if (ksplit > 1) g.slab = slab;
+  if (stats) {
+    if (!split_stats_slots(g)) return 1;
+    g.stats = stats;
+  }
+  if (p.nbt == 2) return conv_fwd_split_go<2>(a.x, a.wp, a.bias, a.y, (uint4*)ws, g, a.stream, p.flat);
+  if (p.nbt == 3) return conv_fwd_split_go<3>(a.x, a.wp, a.bias, a.y, (uint4*)ws, g, a.stream, p.flat);
+  return conv_fwd_split_go<1>(a.x, a.wp, a.bias, a.y, (uint4*)ws, g, a.stream, p.flat);
 }
 
 template <int KS>
-int conv_fwd_launch(const float* x, const float* wp, const float* bias, float* y, float* ws, int n, int cin, int cout, int d, int h,
-                    int w, int64_t xbs, int64_t ybs, hipStream_t stream) {
+int conv_fwd_launch(const ConvShape& s, const ConvArgs& a, float* ws) {
+  const ConvEnv e = conv_env();
   if (KS == 3) {
-    icl::ConvGeom gs{};
-    gs.slab = ws;
-    gs.Cin = cin; gs.Cout = cout;
-    gs.CinP = round_up(cin, 4); gs.CoutP = round_up(cout, 16);
-    gs.D = d; gs.H = h; gs.W = w;
-    gs.x_bstride = xbs; gs.y_bstride = ybs;
-    int rc = conv_fwd_split(x, wp, bias, y, ws, n, cin, cout, d, h, w, xbs, ybs, stream);
-    if (rc != 1) return rc;
-    rc = conv_fwd_flat(x, wp, bias, y, gs, n, ybs, stream);
-    if (rc != 1) return rc;
-    rc = conv_fwd_static(x, wp, bias, y, gs, n, ybs, stream);
+    const int rc = conv_fwd_split_launch(plan_conv_split(s, e), a, ws);
     if (rc != 1) return rc;
   }
-  icl::ConvGeom g{};
-  g.slab = ws;
-  g.Cin = cin; g.Cout = cout;
-  g.CinP = round_up(cin, 4); g.CoutP = round_up(cout, 16);
-  g.D = d; g.H = h; g.W = w;
-  g.x_bstride = xbs; g.y_bstride = ybs;
-  const bool vec = KS == 1 && (w % 4) == 0;      // 16-byte loads: instantiated for 1x1x1 only (see below)
-  choose_tile(g, KS, 512, vec);
-  finish_tile(g, KS, 16, 32);
-  constexpr int T = KS * KS * KS;
-  const int nbt = cout <= 16 ? 1 : (g.CoutP % 48 == 0 ? 3 : 2);
-  const int nb = nbt * 16, nbp = nb;
-  const int pz = g.TZ + KS - 1, py = g.TY + KS - 1;
-  const int per_ch = pz * py * (g.PXL / (vec ? 4 : 1));
-  int kc = 0;
-  for (int cand = 16; cand >= 4; cand >>= 1) {
-    if (g.CinP % cand) continue;
-    if ((size_t)cand * (g.PS + T * nbp) * 4 > (size_t)kMaxDynLdsFwd) continue;
-    if (T * cand * (nb / 4) > icl::kWX * kConvWaves * 64) continue;
-    const int cpp = cand / 4 > 1 ? cand / 4 : 1;
-    if (cpp * per_ch > icl::kJX * kConvWaves * 64) continue;
-    kc = cand;
-    break;
-  }
-  if (!kc) return fail(-1, "conv3d_fwd: no LDS tiling for %dx%dx%d cin %d cout %d", d, h, w, cin, cout);
-  g.KC = kc;
-  g.CPP = kc / 4 > 1 ? kc / 4 : 1;
-  const size_t lds = (size_t)kc * (g.PS + T * nbp) * 4;
-  const int mt = g.TZ * g.TY * g.TX;
-  if (mt > kConvWaves * 8 * 16) return fail(-1, "conv3d_fwd: tile of %d voxels too large", mt);
-  const int ntiles = g.ntx * g.nty * g.ntz;
-  const int ctiles = (g.CoutP + nb - 1) / nb;
-  const int nchunks = g.CinP / kc;
-  const long base = (long)ntiles * ctiles * n;
-  int ksplit = choose_ksplit(base, nchunks);
-  if (ksplit > 1 && !g.slab && !g_plan.dry) ksplit = 1;   // no workspace supplied: run unsplit
-  g.ksplit = ksplit;
-  if (g_plan.dry) {
-    g_plan.need = ksplit > 1 ? (int64_t)ksplit * n * cout * d * h * w * 4 : 0;
-    return 0;
-  }
-  dim3 grid(ntiles * ksplit, ctiles, n);
-  // (the 16-byte-load instantiations of this generic kernel exist for 1x1x1 only: every 3x3x3 shape of the models runs on the split-product,
-  // flat or compile-time-tile kernels above, and what falls through to here — odd extents, channel counts that are no multiple of 4 — is
-  // not worth 135 KB of code object)
-#define ICL_FWD_CASE(NBT_)                                                                                     \
-  ((vec && KS == 1) ? conv_fwd_dispatch<KS, NBT_, KS == 1>(x, wp, bias, y, g, grid, lds, stream)                \
-                    : conv_fwd_dispatch<KS, NBT_, false>(x, wp, bias, y, g, grid, lds, stream))
-  int rc;
-  if (nbt == 1) rc = ICL_FWD_CASE(1);
-  else if (nbt == 2) rc = ICL_FWD_CASE(2);
-  else rc = ICL_FWD_CASE(3);
-#undef ICL_FWD_CASE
-  return rc ? rc : splitk_reduce(g, bias, y, n, ybs, stream);
+  const Fp32Plan p = plan_conv_fp32<KS>(s, e);
+  return p.rc ? p.rc : p.go(p, a, ws);
 }
 
 template <int KS, bool VEC>
@@ -654,15 +663,11 @@ int conv_wgrad_dispatch(const float* x, const float* gy, float* gwp, const icl::
 }
 
 template <int KS>
-int conv_wgrad_launch(const float* x, const float* gy, float* gwp, int n, int cin, int cout, int d, int h, int w,
+int conv_wgrad_launch(const float* x, const float* gy, float* gwp, int n, int n_live, int cin, int cout, int d, int h, int w,
                       int64_t xbs, int64_t gbs, int* nslabs, hipStream_t stream) {
-  icl::ConvGeom g{};
-  g.Cin = cin; g.Cout = cout;
-  g.CinP = round_up(cin, 4); g.CoutP = round_up(cout, 16);
-  g.D = d; g.H = h; g.W = w;
-  g.x_bstride = xbs; g.y_bstride = gbs;
+  icl::ConvGeom g = conv_geom(cin, cout, d, h, w, xbs, gbs);
   if (KS == 3) {
-    const int rc = conv_wgrad_static(x, gy, gwp, g, n, nslabs, stream);
+    const int rc = conv_wgrad_static(x, gy, gwp, g, n, n_live, nslabs, stream);
     if (rc != 1) return rc;
   }
   const bool vec = (w % 4) == 0;
@@ -1099,44 +1104,41 @@ int icl_conv3d_split_weights_multi(const void* const* wp, void* const* wsplit, c
   return 0;
 }
 
+// the pre-split entry points: wsplit holds the split weights already
+static int presplit_launch(const float* x, const void* wsplit, const float* bias, float* y, float* stats, float* slab, int n, int cin, int cout,
+                           int d, int h, int w, int64_t xbs, int64_t ybs, void* stream) {
+  return conv_fwd_split_launch(plan_conv_split({n, cin, cout, d, h, w}, conv_env()), {x, nullptr, bias, y, xbs, ybs, (hipStream_t)stream},
+                               (float*)const_cast<void*>(wsplit), stats, slab);
+}
+
 int icl_conv3d_fwd_presplit(const float* x, const void* wsplit, const float* bias, float* y, int n, int cin, int cout, int d, int h, int w,
                             int64_t x_bstride, int64_t y_bstride, void* stream) {
   if (!x || !wsplit || !y || n < 1 || cin < 1 || cout < 1 || d < 1 || h < 1 || w < 1) return fail(-1, "conv3d_fwd_presplit: bad argument");
-  return conv_fwd_split(x, nullptr, bias, y, (float*)const_cast<void*>(wsplit), n, cin, cout, d, h, w, x_bstride, y_bstride, (hipStream_t)stream);
+  return presplit_launch(x, wsplit, bias, y, nullptr, nullptr, n, cin, cout, d, h, w, x_bstride, y_bstride, stream);
 }
 
 int64_t icl_conv3d_fwd_presplit_ws_bytes(int n, int cin, int cout, int d, int h, int w) {
   if (n < 1 || cin < 1 || cout < 1 || d < 1 || h < 1 || w < 1) return 0;
-  int64_t slab = 0;
-  int slots = 0;
-  if (conv_fwd_split(nullptr, nullptr, nullptr, nullptr, nullptr, n, cin, cout, d, h, w, (int64_t)cin * d * h * w, (int64_t)cout * d * h * w,
-                     nullptr, nullptr, &slots, true, nullptr, &slab) != 0)
-    return 0;
-  return slab;
+  const SplitPlan p = plan_conv_split({n, cin, cout, d, h, w}, conv_env());
+  return p.ok ? p.slab_bytes : 0;
 }
 
 int icl_conv3d_fwd_presplit_ws(const float* x, const void* wsplit, const float* bias, float* y, void* ws, int n, int cin, int cout, int d,
                                int h, int w, int64_t x_bstride, int64_t y_bstride, void* stream) {
   if (!x || !wsplit || !y || n < 1 || cin < 1 || cout < 1 || d < 1 || h < 1 || w < 1) return fail(-1, "conv3d_fwd_presplit_ws: bad argument");
   if (ws && !aligned16(ws)) return fail(-1, "conv3d_fwd_presplit_ws: workspace not 16-byte aligned");
-  return conv_fwd_split(x, nullptr, bias, y, (float*)const_cast<void*>(wsplit), n, cin, cout, d, h, w, x_bstride, y_bstride, (hipStream_t)stream,
-                        nullptr, nullptr, false, (float*)ws);
+  return presplit_launch(x, wsplit, bias, y, nullptr, (float*)ws, n, cin, cout, d, h, w, x_bstride, y_bstride, stream);
 }
 
 int icl_conv3d_fwd_stats_slots(int n, int cin, int cout, int d, int h, int w) {
-  int slots = 0;
-  if (conv_fwd_split(nullptr, nullptr, nullptr, nullptr, nullptr, n, cin, cout, d, h, w, (int64_t)cin * d * h * w, (int64_t)cout * d * h * w,
-                     nullptr, nullptr, &slots, true) != 0)
-    return 0;
-  return slots;
+  const SplitPlan p = plan_conv_split({n, cin, cout, d, h, w}, conv_env());
+  return p.ok ? p.slots : 0;
 }
 
 int icl_conv3d_fwd_presplit_stats(const float* x, const void* wsplit, const float* bias, float* y, float* stats, int n, int cin, int cout,
                                   int d, int h, int w, int64_t x_bstride, int64_t y_bstride, void* stream) {
   if (!x || !wsplit || !y || !stats || n < 1 || cin < 1 || cout < 1) return fail(-1, "conv3d_fwd_presplit_stats: bad argument");
-  int slots = 0;
-  return conv_fwd_split(x, nullptr, bias, y, (float*)const_cast<void*>(wsplit), n, cin, cout, d, h, w, x_bstride, y_bstride, (hipStream_t)stream,
-                        stats, &slots, false);
+  return presplit_launch(x, wsplit, bias, y, stats, nullptr, n, cin, cout, d, h, w, x_bstride, y_bstride, stream);
 }
 
 int icl_conv3d_pack_weights_multi(const void* const* w, void* const* wp_fwd, void* const* wp_dgrad, const int32_t* cout, const int32_t* cin,
@@ -1165,28 +1167,22 @@ int icl_conv3d_pack_weights_multi(const void* const* w, void* const* wp_fwd, voi
 int icl_conv3d_fwd(const float* x, const float* wp, const float* bias, float* y, void* ws, int n, int cin, int cout, int d, int h,
                    int w, int ks, int64_t x_bstride, int64_t y_bstride, void* stream) {
   if (!x || !wp || !y || n < 1 || cin < 1 || cout < 1 || d < 1 || h < 1 || w < 1) return fail(-1, "conv3d_fwd: bad argument");
-  if (ks == 3) return conv_fwd_launch<3>(x, wp, bias, y, (float*)ws, n, cin, cout, d, h, w, x_bstride, y_bstride, (hipStream_t)stream);
-  if (ks == 1) return conv_fwd_launch<1>(x, wp, bias, y, (float*)ws, n, cin, cout, d, h, w, x_bstride, y_bstride, (hipStream_t)stream);
+  const ConvArgs a{x, wp, bias, y, x_bstride, y_bstride, (hipStream_t)stream};
+  if (ks == 3) return conv_fwd_launch<3>({n, cin, cout, d, h, w}, a, (float*)ws);
+  if (ks == 1) return conv_fwd_launch<1>({n, cin, cout, d, h, w}, a, (float*)ws);
   return fail(-1, "conv3d_fwd: kernel size %d unsupported", ks);
 }
 
 int64_t icl_conv3d_fwd_ws_bytes(int n, int cin, int cout, int d, int h, int w, int ks) {
   if (n < 1 || cin < 1 || cout < 1 || d < 1 || h < 1 || w < 1 || (ks != 1 && ks != 3)) return 0;
-  g_plan.dry = true;
-  g_plan.need = 0;
-  const int64_t dense = (int64_t)d * h * w;
-  if (ks == 3) conv_fwd_launch<3>(nullptr, nullptr, nullptr, nullptr, nullptr, n, cin, cout, d, h, w, cin * dense, cout * dense, nullptr);
-  else conv_fwd_launch<1>(nullptr, nullptr, nullptr, nullptr, nullptr, n, cin, cout, d, h, w, cin * dense, cout * dense, nullptr);
-  int64_t need = g_plan.need;
+  const ConvShape s{n, cin, cout, d, h, w};
+  const ConvEnv e = conv_env();
   if (ks == 3) {      // the split-product path may hand a call back to the fp32 kernels (alignment of the actual pointers): cover both plans
-    g_plan.no_split = true;
-    g_plan.need = 0;
-    conv_fwd_launch<3>(nullptr, nullptr, nullptr, nullptr, nullptr, n, cin, cout, d, h, w, cin * dense, cout * dense, nullptr);
-    g_plan.no_split = false;
-    if (g_plan.need > need) need = g_plan.need;
+    const SplitPlan p = plan_conv_split(s, e);
+    const int64_t split = p.ok ? p.w_bytes + p.slab_bytes : 0, fp32 = plan_conv_fp32<3>(s, e).slab_bytes;
+    return split > fp32 ? split : fp32;
   }
-  g_plan.dry = false;
-  return need;
+  return plan_conv_fp32<1>(s, e).slab_bytes;
 }
 
 int64_t icl_conv3d_wgrad_ws_bytes(int n, int cin, int cout, int ks) {
@@ -1201,14 +1197,20 @@ static bool wgrad_reduce_tall(int nslabs, long pe_all) {
   return nslabs >= tall_min && pe_all <= (1L << 18);   // many slabs of few elements: 16 slab lanes per element instead of 4
 }
 
-int icl_conv3d_wgrad_slabs(const float* x, const float* gy, void* ws, int n, int cin, int cout, int d, int h, int w, int ks,
+// the slabs of a weight gradient; n_live < n: samples [n_live, n) of gy are exactly zero (wgrad_live_prefix)
+static int wgrad_slabs_run(const float* x, const float* gy, void* ws, int n, int n_live, int cin, int cout, int d, int h, int w, int ks,
                            int64_t x_bstride, int64_t gy_bstride, int32_t* nslabs, void* stream) {
   if (!x || !gy || !ws || !nslabs || n < 1 || cin < 1 || cout < 1 || (ks != 1 && ks != 3)) return fail(-1, "conv3d_wgrad_slabs: bad argument");
   int ns = 0;
-  const int rc = ks == 3 ? conv_wgrad_launch<3>(x, gy, (float*)ws, n, cin, cout, d, h, w, x_bstride, gy_bstride, &ns, (hipStream_t)stream)
-                         : conv_wgrad_launch<1>(x, gy, (float*)ws, n, cin, cout, d, h, w, x_bstride, gy_bstride, &ns, (hipStream_t)stream);
+  const int rc = ks == 3 ? conv_wgrad_launch<3>(x, gy, (float*)ws, n, n_live, cin, cout, d, h, w, x_bstride, gy_bstride, &ns, (hipStream_t)stream)
+                         : conv_wgrad_launch<1>(x, gy, (float*)ws, n, n_live, cin, cout, d, h, w, x_bstride, gy_bstride, &ns, (hipStream_t)stream);
   *nslabs = ns;
   return rc;
+}
+
+int icl_conv3d_wgrad_slabs(const float* x, const float* gy, void* ws, int n, int cin, int cout, int d, int h, int w, int ks,
+                           int64_t x_bstride, int64_t gy_bstride, int32_t* nslabs, void* stream) {
+  return wgrad_slabs_run(x, gy, ws, n, n, cin, cout, d, h, w, ks, x_bstride, gy_bstride, nslabs, stream);
 }
 
 int icl_conv3d_wgrad_reduce_multi(const void* const* ws, void* const* gw, const int32_t* cout, const int32_t* cin, const int32_t* ks,
@@ -1236,18 +1238,16 @@ int icl_conv3d_wgrad_reduce_multi(const void* const* ws, void* const* gw, const 
   return 0;
 }
 
-int icl_conv3d_wgrad(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int cin, int cout, int d,
+static int wgrad_run(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live, int cin, int cout, int d,
                      int h, int w, int ks, int64_t x_bstride, int64_t gy_bstride, void* stream) {
   if (!x || !gy || !gw || !ws || n < 1 || cin < 1 || cout < 1 || (ks != 1 && ks != 3)) return fail(-1, "conv3d_wgrad: bad argument");
   hipStream_t s = (hipStream_t)stream;
   float* gwp = (float*)ws;
   int nslabs = 0;
-  int rc = ks == 3 ? conv_wgrad_launch<3>(x, gy, gwp, n, cin, cout, d, h, w, x_bstride, gy_bstride, &nslabs, s)
-                   : conv_wgrad_launch<1>(x, gy, gwp, n, cin, cout, d, h, w, x_bstride, gy_bstride, &nslabs, s);
+  int rc = ks == 3 ? conv_wgrad_launch<3>(x, gy, gwp, n, n_live, cin, cout, d, h, w, x_bstride, gy_bstride, &nslabs, s)
+                   : conv_wgrad_launch<1>(x, gy, gwp, n, n_live, cin, cout, d, h, w, x_bstride, gy_bstride, &nslabs, s);
   if (rc) return rc;
   const int T = ks * ks * ks;
-  const long total = (long)cout * cin * T;
-  (void)total;
   const long pe_all = icl_conv3d_packed_elems(cout, cin, ks, 0);
   if (wgrad_reduce_tall(nslabs, pe_all))
     ICL_LAUNCH(icl::reduce_unpack_wgrad_tall_kernel, dim3((unsigned)cdivl(pe_all, 16)), dim3(256), 0, s, (const float*)gwp, gw, cout, cin, T,
@@ -1278,17 +1278,15 @@ int icl_conv3d_wgrad(const float* x, const float* gy, float* gw, float* gbias, v
   return rc;
 }
 
+int icl_conv3d_wgrad(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int cin, int cout, int d,
+                     int h, int w, int ks, int64_t x_bstride, int64_t gy_bstride, void* stream) {
+  return wgrad_run(x, gy, gw, gbias, ws, n, n, cin, cout, d, h, w, ks, x_bstride, gy_bstride, stream);
+}
+
 int64_t icl_norm_ws_bytes(int n, int c, int64_t s) {
   const int64_t nch = (s + icl::kNormChunk - 1) / icl::kNormChunk;
   return ((int64_t)n * c * nch * 3 + (int64_t)n * c * 2 + 64) * 4;
 }
-
-namespace {
-inline bool norm_one_launch() {
-  constexpr int on = 1;
-  return on != 0;
-}
-}  // namespace
 
 int icl_norm_fwd(const float* x, float* y, float* mean, float* rstd, const float* gamma, const float* beta,
                  float* running_mean, float* running_var, int n, int c, int64_t s, int mode, int use_batch_stats,
@@ -1306,7 +1304,7 @@ int icl_norm_res_fwd(const float* x, const float* res, float* y, float* mean, fl
   const int nch = (int)((s + icl::kNormChunk - 1) / icl::kNormChunk);
   const float* part = nullptr;
   // instance statistics of rows that are one chunk (the 12^3 / 6^3 levels): summarised inside the normalisation launch
-  const int inline_stats = (use_batch_stats && mode == 0 && nch == 1 && !running_mean && norm_one_launch()) ? 1 : 0;
+  const int inline_stats = (use_batch_stats && mode == 0 && nch == 1 && !running_mean) ? 1 : 0;
   if (use_batch_stats && !inline_stats) {
     if (!ws) return fail(-1, "norm_fwd: workspace required");
     ICL_LAUNCH(icl::rowstats_partial_kernel, dim3(nch, R), dim3(icl::kNormThreads), 0, st, x, (float*)ws, (long)s, nch);
@@ -1344,7 +1342,7 @@ int icl_norm_res_bwd(const float* gy, const float* x, const float* res, const fl
   const int R = n * c;
   const int nch = (int)((s + icl::kNormChunk - 1) / icl::kNormChunk);
   float* part = (float*)ws;
-  if (mode == 0 && nch == 1 && norm_one_launch()) {
+  if (mode == 0 && nch == 1) {
     part = nullptr;      // instance statistics, one chunk per row: the apply launch computes the row's two sums itself
   } else {
     ICL_LAUNCH(icl::norm_act_bwd_partial_kernel, dim3(nch, R), dim3(icl::kNormThreads), 0, st, gy, x, mean, rstd, gamma, beta, part,
@@ -3163,30 +3161,37 @@ inline int live_args(int n, int n_live, const char* who) {
 inline int live_zero_tail(float* p, int n, int n_live, int64_t elems, hipStream_t st, const char* who) {
   if (n_live >= n) return 0;
   ICL_MEMSET_ASYNC(p + (size_t)n_live * elems, 0, (size_t)(n - n_live) * elems * sizeof(float), st);
-  return check_launch(who);
+  char what[96];
+  snprintf(what, sizeof(what), "%s: tail", who);
+  return check_launch(what);
+}
+// the live forms of the forward entry points: `call(n_live)` is the entry point on the live samples; then the record of its kernel and
+// the zero tail.  1 from the call: nothing launched (the caller takes the fp32 pack), nothing zeroed.
+extern "C++" template <class Call>
+int live_fwd(const char* who, float* y, int n, int n_live, int64_t dense, int64_t y_bstride, void* stream, Call call) {
+  if (int rc = live_args(n, n_live, who)) return rc;
+  if (n_live < n && y_bstride != dense) return fail(-1, "%s: y must be dense", who);
+  if (int rc = call(n_live)) return rc;
+  snprintf(g_kernel_live_fwd, sizeof(g_kernel_live_fwd), "%s", g_kernel);
+  return live_zero_tail(y, n, n_live, y_bstride, (hipStream_t)stream, who);
 }
 }  // namespace
 
-// 1: the 3^3 launcher plans a batch of n_live as it plans a batch of n — split-product kernels, nothing split over the channel chunks
+// 1: the 3^3 planner plans a batch of n_live as it plans a batch of n — split-product kernels, nothing split over the channel chunks
 // (the deep levels' split count follows the batch size: their sums would re-associate) — so the live samples come out bit for bit.
-// The dry run of conv_fwd_split ends before the checks that hand a real call to the fp32 kernels, whose split does follow the batch size:
-// rows of 12 voxels and the 6^3 volume that turn out unsplit are refused here as well.  Not mirrored: operands that are not 16-byte
-// aligned (a real call then falls to the fp32 kernels; the samples stay correct, their last bits may differ from the full call's).
+// Rows of 12 voxels and the 6^3 volume run on the split-product kernels only when split, else on the fp32 kernels, whose split does
+// follow the batch size: refused.  Not mirrored: operands that are not 16-byte aligned (a real call then falls to the fp32 kernels; the
+// samples stay correct, their last bits may differ from the full call's).
 int icl_conv3d_fwd_live_ok(int n, int n_live, int cin, int cout, int d, int h, int w) {
   if (n < 1 || n_live < 1 || n_live > n || cin < 1 || cout < 1 || d < 1 || h < 1 || w < 1) return 0;
   if (w == icl::Bf3F12::TX || (w == 6 && h == 6 && d == 6)) return 0;
-  const int64_t dense = (int64_t)d * h * w;
-  const int batch[2] = {n, n_live};
-  int ok = 1;
-  g_plan.dry = true;
-  for (int i = 0; i < 2; ++i) {
-    int64_t slab = 0;
-    if (conv_fwd_split(nullptr, nullptr, nullptr, nullptr, nullptr, batch[i], cin, cout, d, h, w, cin * dense, cout * dense, nullptr, nullptr,
-                       nullptr, false, nullptr, &slab) != 0 || slab != 0)
-      ok = 0;
+  const ConvEnv e = conv_env();
+  const int batches[2] = {n, n_live};
+  for (const int batch : batches) {
+    const SplitPlan p = plan_conv_split({batch, cin, cout, d, h, w}, e);
+    if (!p.ok || p.ksplit > 1) return 0;
   }
-  g_plan.dry = false;
-  return ok;
+  return 1;
 }
 
 const char* icl_last_live_fwd_kernel_name(void) { return g_kernel_live_fwd; }
@@ -3197,36 +3202,24 @@ void icl_last_wgrad_grid(int32_t* launched, int32_t* planned) {
 
 int icl_conv3d_fwd_presplit_live(const float* x, const void* wsplit, const float* bias, float* y, int n, int n_live, int cin, int cout, int d,
                                  int h, int w, int64_t x_bstride, int64_t y_bstride, void* stream) {
-  if (int rc = live_args(n, n_live, "conv3d_fwd_presplit_live")) return rc;
-  if (n_live < n && y_bstride != (int64_t)cout * d * h * w) return fail(-1, "conv3d_fwd_presplit_live: y must be dense");
-  const int rc = icl_conv3d_fwd_presplit(x, wsplit, bias, y, n_live, cin, cout, d, h, w, x_bstride, y_bstride, stream);
-  if (rc) return rc;      // 1: nothing launched (the caller takes the fp32 pack), nothing zeroed
-  snprintf(g_kernel_live_fwd, sizeof(g_kernel_live_fwd), "%s", g_kernel);
-  return live_zero_tail(y, n, n_live, y_bstride, (hipStream_t)stream, "conv3d_fwd_presplit_live: tail");
+  return live_fwd("conv3d_fwd_presplit_live", y, n, n_live, (int64_t)cout * d * h * w, y_bstride, stream, [&](int nl) {
+    return icl_conv3d_fwd_presplit(x, wsplit, bias, y, nl, cin, cout, d, h, w, x_bstride, y_bstride, stream); });
 }
 
 int icl_conv3d_fwd_presplit_ws_live(const float* x, const void* wsplit, const float* bias, float* y, void* ws, int n, int n_live, int cin,
                                     int cout, int d, int h, int w, int64_t x_bstride, int64_t y_bstride, void* stream) {
-  if (int rc = live_args(n, n_live, "conv3d_fwd_presplit_ws_live")) return rc;
-  if (n_live < n && y_bstride != (int64_t)cout * d * h * w) return fail(-1, "conv3d_fwd_presplit_ws_live: y must be dense");
-  const int rc = icl_conv3d_fwd_presplit_ws(x, wsplit, bias, y, ws, n_live, cin, cout, d, h, w, x_bstride, y_bstride, stream);
-  if (rc) return rc;
-  snprintf(g_kernel_live_fwd, sizeof(g_kernel_live_fwd), "%s", g_kernel);
-  return live_zero_tail(y, n, n_live, y_bstride, (hipStream_t)stream, "conv3d_fwd_presplit_ws_live: tail");
+  return live_fwd("conv3d_fwd_presplit_ws_live", y, n, n_live, (int64_t)cout * d * h * w, y_bstride, stream, [&](int nl) {
+    return icl_conv3d_fwd_presplit_ws(x, wsplit, bias, y, ws, nl, cin, cout, d, h, w, x_bstride, y_bstride, stream); });
 }
 
 int icl_conv3d_fwd_live(const float* x, const float* wp, const float* bias, float* y, void* ws, int n, int n_live, int cin, int cout, int d,
                         int h, int w, int ks, int64_t x_bstride, int64_t y_bstride, void* stream) {
-  if (int rc = live_args(n, n_live, "conv3d_fwd_live")) return rc;
-  if (n_live < n && y_bstride != (int64_t)cout * d * h * w) return fail(-1, "conv3d_fwd_live: y must be dense");
-  const int rc = icl_conv3d_fwd(x, wp, bias, y, ws, n_live, cin, cout, d, h, w, ks, x_bstride, y_bstride, stream);
-  if (rc) return rc;
-  snprintf(g_kernel_live_fwd, sizeof(g_kernel_live_fwd), "%s", g_kernel);
-  return live_zero_tail(y, n, n_live, y_bstride, (hipStream_t)stream, "conv3d_fwd_live: tail");
+  return live_fwd("conv3d_fwd_live", y, n, n_live, (int64_t)cout * d * h * w, y_bstride, stream, [&](int nl) {
+    return icl_conv3d_fwd(x, wp, bias, y, ws, nl, cin, cout, d, h, w, ks, x_bstride, y_bstride, stream); });
 }
 
 // The weight gradient has no per-sample output.  Its live form keeps the launch plan of the batch of n and skips the workgroups that own
-// no live tile (g_wgrad_n_live above): same slabs, same order, bit-identical sums.  Workspace as for n.
+// no live tile (wgrad_live_prefix): same slabs, same order, bit-identical sums.  Workspace as for n.
 int64_t icl_conv3d_wgrad_ws_bytes_live(int n, int n_live, int cin, int cout, int ks) {
   if (n < 1 || n_live < 1 || n_live > n) return 0;
   return icl_conv3d_wgrad_ws_bytes(n, cin, cout, ks);
@@ -3235,19 +3228,13 @@ int64_t icl_conv3d_wgrad_ws_bytes_live(int n, int n_live, int cin, int cout, int
 int icl_conv3d_wgrad_live(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live, int cin, int cout, int d,
                           int h, int w, int ks, int64_t x_bstride, int64_t gy_bstride, void* stream) {
   if (int rc = live_args(n, n_live, "conv3d_wgrad_live")) return rc;
-  g_wgrad_n_live = n_live;
-  const int rc = icl_conv3d_wgrad(x, gy, gw, gbias, ws, n, cin, cout, d, h, w, ks, x_bstride, gy_bstride, stream);
-  g_wgrad_n_live = 0;
-  return rc;
+  return wgrad_run(x, gy, gw, gbias, ws, n, n_live, cin, cout, d, h, w, ks, x_bstride, gy_bstride, stream);
 }
 
 int icl_conv3d_wgrad_slabs_live(const float* x, const float* gy, void* ws, int n, int n_live, int cin, int cout, int d, int h, int w, int ks,
                                 int64_t x_bstride, int64_t gy_bstride, int32_t* nslabs, void* stream) {
   if (int rc = live_args(n, n_live, "conv3d_wgrad_slabs_live")) return rc;
-  g_wgrad_n_live = n_live;
-  const int rc = icl_conv3d_wgrad_slabs(x, gy, ws, n, cin, cout, d, h, w, ks, x_bstride, gy_bstride, nslabs, stream);
-  g_wgrad_n_live = 0;
-  return rc;
+  return wgrad_slabs_run(x, gy, ws, n, n_live, cin, cout, d, h, w, ks, x_bstride, gy_bstride, nslabs, stream);
 }
 
 int icl_norm_bwd_live(const float* gy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* gx,
@@ -3258,7 +3245,7 @@ int icl_norm_bwd_live(const float* gy, const float* x, const float* mean, const 
   if (n_live < n && (mode != 0 || dgamma || dbeta)) return fail(-1, "norm_bwd_live: a live batch needs instance statistics, no affine pair");
   const int rc = icl_norm_bwd(gy, x, mean, rstd, gamma, beta, gx, dgamma, dbeta, n_live, c, s, mode, use_batch_stats, act, ws, stream);
   if (rc) return rc;
-  return live_zero_tail(gx, n, n_live, (int64_t)c * s, (hipStream_t)stream, "norm_bwd_live: tail");
+  return live_zero_tail(gx, n, n_live, (int64_t)c * s, (hipStream_t)stream, "norm_bwd_live");
 }
 
 int icl_trilinear_bwd_live(const float* gy, float* gx, void* ws, int n, int n_live, int c, int di, int hi, int wi, int dout, int hout, int wout,
@@ -3266,7 +3253,7 @@ int icl_trilinear_bwd_live(const float* gy, float* gx, void* ws, int n, int n_li
   if (int rc = live_args(n, n_live, "trilinear_bwd_live")) return rc;
   const int rc = icl_trilinear_bwd(gy, gx, ws, n_live, c, di, hi, wi, dout, hout, wout, gy_bstride, align_corners, stream);
   if (rc) return rc;
-  return live_zero_tail(gx, n, n_live, (int64_t)c * di * hi * wi, (hipStream_t)stream, "trilinear_bwd_live: tail");
+  return live_zero_tail(gx, n, n_live, (int64_t)c * di * hi * wi, (hipStream_t)stream, "trilinear_bwd_live");
 }
 
 int icl_conv1x1_small_live(const float* x, const float* w, const float* bias, float* y, int n, int n_live, int cin, int cout, int64_t s,
@@ -3275,7 +3262,7 @@ int icl_conv1x1_small_live(const float* x, const float* w, const float* bias, fl
   if (!x || !w || !y || cin < 1 || cout < 1 || s < 4 || (s & 3)) return fail(-1, "conv1x1_small_live: bad argument (s %% 4 == 0)");
   const int rc = conv1x1_small_run(x, w, bias, y, n_live, cin, cout, s, w_ostride, w_istride, icl::DropSpec{}, (hipStream_t)stream, n);
   if (rc) return rc;
-  return live_zero_tail(y, n, n_live, (int64_t)cout * s, (hipStream_t)stream, "conv1x1_small_live: tail");
+  return live_zero_tail(y, n, n_live, (int64_t)cout * s, (hipStream_t)stream, "conv1x1_small_live");
 }
 
 // (the mask is a hash of the element index (b * C + c) * S + v: the live samples are a prefix, their indices and masks are unchanged)
@@ -3287,7 +3274,7 @@ int icl_conv1x1_dropout_live(const float* x, const float* w, const float* bias, 
   const int rc = conv1x1_small_run(x, w, bias, y, n_live, cin, cout, s, w_ostride, w_istride, drop_spec(mask_mode, seed, p, seed_dev),
                                    (hipStream_t)stream, n);
   if (rc) return rc;      // 1: n * s < 65536, nothing launched, nothing zeroed
-  return live_zero_tail(y, n, n_live, (int64_t)cout * s, (hipStream_t)stream, "conv1x1_dropout_live: tail");
+  return live_zero_tail(y, n, n_live, (int64_t)cout * s, (hipStream_t)stream, "conv1x1_dropout_live");
 }
 
 int icl_conv1x1_wgrad_live(const float* x, const float* gy, float* gw, float* gbias, void* ws, int n, int n_live, int cin, int cout, int64_t s,

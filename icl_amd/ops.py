@@ -349,13 +349,15 @@ def conv3d_forward_raw(x, wp, bias, n, cin, cout, d, h, w, ks, x_bstride, y, y_b
     convolution's epilogue (icl_conv3d_fwd_presplit_stats) — or None when this shape / path does not produce them."""
     L = _lib.lib()
     s = d * h * w
-    if n_live is not None:
-        assert not want_stats
-        return _conv3d_forward_raw_live(x, wp, bias, n, n_live, cin, cout, d, h, w, ks, x_bstride, y, y_bstride, wsplit)
+    assert n_live is None or not want_stats
+    nl = n if n_live is None else n_live
+    live = () if n_live is None else (n_live,)      # the `_live` entry points take n_live behind n
+    presplit_ws, presplit, fwd = ((L.icl_conv3d_fwd_presplit_ws, L.icl_conv3d_fwd_presplit, L.icl_conv3d_fwd) if n_live is None else
+                                  (L.icl_conv3d_fwd_presplit_ws_live, L.icl_conv3d_fwd_presplit_live, L.icl_conv3d_fwd_live))
     # algorithmic work of this launch (SURVEY.md Appendix B): 2*taps*Cin*Cout FLOP per voxel; 4*(I+O+W) bytes
-    flops = 2.0 * ks ** 3 * cin * cout * s * n
-    nbytes = 4.0 * (n * s * (cin + cout) + ks ** 3 * cin * cout)
-    need = L.icl_conv3d_fwd_ws_bytes(n, cin, cout, d, h, w, ks)
+    flops = 2.0 * ks ** 3 * cin * cout * s * nl
+    nbytes = 4.0 * (nl * s * (cin + cout) + ks ** 3 * cin * cout)
+    need = L.icl_conv3d_fwd_ws_bytes(nl, cin, cout, d, h, w, ks)
     ws = _ws(need, x) if need else None
     with _timed("conv3d_mfma_fwd_kernel", flops, nbytes, x):
         if want_stats and wsplit is not None and ks == 3 and os.environ.get("ICL_CONV_STATS", "1") != "0":
@@ -369,44 +371,18 @@ def conv3d_forward_raw(x, wp, bias, n, cin, cout, d, h, w, ks, x_bstride, y, y_b
                     return stats
         if wsplit is not None and ks == 3:
             # deep levels (rows of 12 / 24 voxels): the launcher may split the channel chunks over workgroups and needs a slab workspace
-            kneed = L.icl_conv3d_fwd_presplit_ws_bytes(n, cin, cout, d, h, w)
+            kneed = L.icl_conv3d_fwd_presplit_ws_bytes(nl, cin, cout, d, h, w)
             if kneed:
                 kws = _ws(kneed, x)
-                rc = L.icl_conv3d_fwd_presplit_ws(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), _ptr(kws), n, cin, cout, d, h, w,
-                                                  x_bstride, y_bstride, _stream(x))
+                rc = presplit_ws(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), _ptr(kws), n, *live, cin, cout, d, h, w, x_bstride, y_bstride,
+                                 _stream(x))
             else:
-                rc = L.icl_conv3d_fwd_presplit(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), n, cin, cout, d, h, w, x_bstride, y_bstride,
-                                               _stream(x))
+                rc = presplit(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), n, *live, cin, cout, d, h, w, x_bstride, y_bstride, _stream(x))
             if rc != 1:         # 1: this shape does not run on the split-product kernel -> the fp32 pack below
-                _lib.check(rc, "conv3d_fwd_presplit")
+                _lib.check(rc, "conv3d_fwd_presplit" if n_live is None else "conv3d_fwd_presplit_live")
                 return
-        _lib.check(L.icl_conv3d_fwd(_ptr(x), _ptr(wp), _ptr(bias), _ptr(y), _ptr(ws), n, cin, cout, d, h, w, ks,
-                                    x_bstride, y_bstride, _stream(x)), "conv3d_fwd")
-
-
-def _conv3d_forward_raw_live(x, wp, bias, n, k, cin, cout, d, h, w, ks, x_bstride, y, y_bstride, wsplit):
-    """conv3d_forward_raw on the live samples [0, k) of a batch of n (the same choice of entry points), zeros to y[k:]."""
-    L = _lib.lib()
-    s = d * h * w
-    flops = 2.0 * ks ** 3 * cin * cout * s * k
-    nbytes = 4.0 * (k * s * (cin + cout) + ks ** 3 * cin * cout)
-    need = L.icl_conv3d_fwd_ws_bytes(k, cin, cout, d, h, w, ks)
-    ws = _ws(need, x) if need else None
-    with _timed("conv3d_mfma_fwd_kernel", flops, nbytes, x):
-        if wsplit is not None and ks == 3:
-            kneed = L.icl_conv3d_fwd_presplit_ws_bytes(k, cin, cout, d, h, w)
-            if kneed:
-                kws = _ws(kneed, x)
-                rc = L.icl_conv3d_fwd_presplit_ws_live(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), _ptr(kws), n, k, cin, cout, d, h, w,
-                                                       x_bstride, y_bstride, _stream(x))
-            else:
-                rc = L.icl_conv3d_fwd_presplit_live(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), n, k, cin, cout, d, h, w, x_bstride,
-                                                    y_bstride, _stream(x))
-            if rc != 1:
-                _lib.check(rc, "conv3d_fwd_presplit_live")
-                return
-        _lib.check(L.icl_conv3d_fwd_live(_ptr(x), _ptr(wp), _ptr(bias), _ptr(y), _ptr(ws), n, k, cin, cout, d, h, w, ks,
-                                         x_bstride, y_bstride, _stream(x)), "conv3d_fwd_live")
+        _lib.check(fwd(_ptr(x), _ptr(wp), _ptr(bias), _ptr(y), _ptr(ws), n, *live, cin, cout, d, h, w, ks, x_bstride, y_bstride, _stream(x)),
+                   "conv3d_fwd" if n_live is None else "conv3d_fwd_live")
 
 
 _ZERO_CACHE = {}
@@ -525,12 +501,9 @@ class _Conv3d(torch.autograd.Function):
                 gemm(weight, gy, cin, s, cout, cin, s, False, False, out=gx, ldc=s, batch=n, b_bstride=cout * s, c_bstride=cin * s)
             elif ctx.pointwise_small:
                 gx = torch.empty_like(x)
-                if k is not None:
-                    _lib.check(L.icl_conv1x1_small_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, k, cout, cin, s, 1, cin, _stream(x)),
-                               "conv1x1_small_live dgrad")
-                else:
-                    _lib.check(L.icl_conv1x1_small(_ptr(gy), _ptr(weight), None, _ptr(gx), n, cout, cin, s, 1, cin, _stream(x)),
-                               "conv1x1_small dgrad")
+                # (the `_live` entry points with nl == n ARE the plain ones: one call site for both)
+                _lib.check(L.icl_conv1x1_small_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, nl, cout, cin, s, 1, cin, _stream(x)),
+                           "conv1x1_small_live dgrad")
                 mark_live(gx, k)
             else:
                 gx = torch.empty_like(x)
@@ -556,12 +529,8 @@ class _Conv3d(torch.autograd.Function):
                 # big-volume 1x1x1 convolution: HBM-bound channel-major reduction, rows split over many waves
                 ws = _ws(L.icl_conv1x1_wgrad_ws_bytes(n, s, cin, cout), x)
                 with _timed("conv1x1_wgrad_kernel", flops, nbytes, x):
-                    if k is not None:
-                        _lib.check(L.icl_conv1x1_wgrad_live(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, k, cin, cout, s, cin * s,
-                                                            cout * s, _stream(x)), "conv1x1_wgrad_live")
-                    else:
-                        _lib.check(L.icl_conv1x1_wgrad(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, cin, cout, s, cin * s,
-                                                       cout * s, _stream(x)), "conv1x1_wgrad")
+                    _lib.check(L.icl_conv1x1_wgrad_live(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, nl, cin, cout, s, cin * s,
+                                                        cout * s, _stream(x)), "conv1x1_wgrad_live")
             elif getattr(ctx, "cin1", False) and w % 4 == 0 and gb_arg is None and gy.data_ptr() % 16 == 0:
                 ws = _ws(L.icl_conv3d_cin1_wgrad_ws_bytes(n, d, h), x)
                 with _timed("conv_cin1_wgrad_kernel", flops, nbytes, x):
@@ -597,7 +566,6 @@ class _Conv3d(torch.autograd.Function):
                         if gb_arg is not None:
                             gb_arg.copy_(gb2)
                         return
-                    # (the `_live` entry points with k == n ARE the plain ones: one call site for both)
                     if swap:
                         ws = _ws(L.icl_conv3d_wgrad_ws_bytes_live(n, nl, cout, cin, ks), x)
                         gws = torch.empty((cin, cout, ks, ks, ks), dtype=torch.float32, device=x.device)
@@ -752,15 +720,11 @@ class _NormAct(torch.autograd.Function):
             dg = torch.empty_like(gamma)
             db = torch.empty_like(beta)
         k = live_of(gy, n) if (mode == 0 and gamma is None) else None      # instance statistics: per sample
-        if k is not None:
-            ws = _ws(L.icl_norm_ws_bytes(k, c, s), x)
-            _lib.check(L.icl_norm_bwd_live(_ptr(gy), _ptr(x), _ptr(mean), _ptr(rstd), None, None, _ptr(gx), None, None, n, k, c, s, mode, ubs,
-                                           act, _ptr(ws), _stream(x)), "norm_bwd_live")
-            return mark_live(gx, k), dg, db, None, None, None, None, None, None, None, None
-        ws = _ws(L.icl_norm_ws_bytes(n, c, s), x)
-        _lib.check(L.icl_norm_bwd(_ptr(gy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(gx), _ptr(dg),
-                                  _ptr(db), n, c, s, mode, ubs, act, _ptr(ws), _stream(x)), "norm_bwd")
-        return gx, dg, db, None, None, None, None, None, None, None, None
+        nl = n if k is None else k
+        ws = _ws(L.icl_norm_ws_bytes(nl, c, s), x)
+        _lib.check(L.icl_norm_bwd_live(_ptr(gy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(gx), _ptr(dg), _ptr(db), n, nl, c,
+                                       s, mode, ubs, act, _ptr(ws), _stream(x)), "norm_bwd_live")
+        return mark_live(gx, k), dg, db, None, None, None, None, None, None, None, None
 
 
 def instance_norm_relu(x: torch.Tensor, relu: bool = True, eps: float = 1e-5) -> torch.Tensor:
@@ -838,15 +802,11 @@ class _NormActLazy(torch.autograd.Function):
         s = y.numel() // (n * c)
         gy = torch.empty_like(y)
         k = live_of(ga, n)
-        if k is not None:
-            ws = _ws(L.icl_norm_ws_bytes(k, c, s), y)
-            _lib.check(L.icl_norm_bwd_live(_ptr(ga), _ptr(y), _ptr(mean), _ptr(rstd), None, None, _ptr(gy), None, None, n, k, c, s, 0, 1, 1,
-                                           _ptr(ws), _stream(y)), "norm_bwd_live")
-            return mark_live(gy, k), None, None
-        ws = _ws(L.icl_norm_ws_bytes(n, c, s), y)
-        _lib.check(L.icl_norm_bwd(_ptr(ga), _ptr(y), _ptr(mean), _ptr(rstd), None, None, _ptr(gy), None, None, n, c, s, 0, 1, 1, _ptr(ws),
-                                  _stream(y)), "norm_bwd")
-        return gy, None, None
+        nl = n if k is None else k
+        ws = _ws(L.icl_norm_ws_bytes(nl, c, s), y)
+        _lib.check(L.icl_norm_bwd_live(_ptr(ga), _ptr(y), _ptr(mean), _ptr(rstd), None, None, _ptr(gy), None, None, n, nl, c, s, 0, 1, 1,
+                                       _ptr(ws), _stream(y)), "norm_bwd_live")
+        return mark_live(gy, k), None, None
 
 
 class _LazyMaterialize(torch.autograd.Function):

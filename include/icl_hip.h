@@ -50,7 +50,8 @@ int icl_conv3d_pack_weights_multi(const void* const* w, void* const* wp_fwd, voi
  * step (the sampled 13,824^2 mlp2 gradient) the two paths differ by 1.2e-3 while the quantity itself is only defined to 1.6e-2 (an input
  * perturbation of 1e-7 moves it that far on the fp32 kernels; round 4, profiles/r4_mlp2_grad_sensitivity.txt).  The split weights live in
  * ws (counted by icl_conv3d_fwd_ws_bytes; without ws the fp32 MFMA kernels run).  Environment: ICL_CONV_SPLIT=0 selects the fp32
- * MFMA kernels for every shape. */
+ * MFMA kernels for every shape.  icl_conv3d_fwd_ws_bytes and the other shape queries below (_presplit_ws_bytes, _stats_slots, _live_ok)
+ * read the launcher's plan — a function of the shape and the environment switches alone — and launch nothing. */
 int64_t icl_conv3d_fwd_ws_bytes(int n, int cin, int cout, int d, int h, int w, int ks);
 /* Split-product convolution with the weight split hoisted out of the call (the weights only change in the optimiser step):
  * icl_conv3d_split_weights_multi turns up to `count` packed weights wp[i] (icl_conv3d_pack_weights, mode 0 or 1; Cin % 16 == 0) into
@@ -110,7 +111,7 @@ int icl_conv3d_wgrad_reduce_multi(const void* const* ws, void* const* gw, const 
  * workgroups that own a live tile and write the other slabs as zeros, everything else runs the whole batch — so the sums are bit for bit
  * those of the entry point called with n (workspaces as for n).  n_live == n is the entry point itself.
  * 3x3x3 (and 1x1x1) input gradient = the forward entry points on the transposed pack (utils.py:104,107): */
-/* icl_conv3d_fwd_live_ok: 1 when the launcher plans the 3x3x3 product for a batch of n_live exactly as for a batch of n (split-product
+/* icl_conv3d_fwd_live_ok: 1 when the planner plans the 3x3x3 product for a batch of n_live exactly as for a batch of n (split-product
  * kernels, no split over the channel chunks), so that the live samples equal the full call's bit for bit; 0: run the full batch. */
 int icl_conv3d_fwd_live_ok(int n, int n_live, int cin, int cout, int d, int h, int w);
 /* For the tests (per thread, like icl_last_kernel_name): the kernel of the last live input-gradient launch, and the workgroups the last

@@ -1307,3 +1307,10 @@ def test_all_loss_terms_in_one_launch_are_bit_identical_to_the_single_term_calls
     total(multi).backward()
     for a, b in zip(g_single, (x.grad for x in leaves2)):
         assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("d,h,w", [(2, 8, 24), (4, 4, 12), (6, 6, 6)])
+def test_conv3d_split_launch_decides_on_its_pointers(monkeypatch, d, h, w):
+    """The pointer-dependent decisions of a split-product launch (icl_abi.inc conv_fwd_split_launch): tests/conv_plan_checks.py."""
+    from conv_plan_checks import check_pointer_fallbacks
+    check_pointer_fallbacks(monkeypatch, "cpu", d, h, w)

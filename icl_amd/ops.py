@@ -7,9 +7,10 @@ Each function cites the reference operator it replaces (paths relative to /root/
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 import os
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -244,6 +245,16 @@ def pack_weights(w: torch.Tensor, mode: int) -> torch.Tensor:
     return wp
 
 
+class _PackedEntry:
+    """What a PackedWeights cache keeps per Parameter."""
+    __slots__ = ("weight", "wp", "wpt", "valid", "split_fwd", "split_dgrad", "planes_valid", "wants_planes")
+
+    def __init__(self, weight, wp, wpt):
+        self.weight, self.wp, self.wpt, self.valid = weight, wp, wpt, False      # the Parameter, its two packs; valid: packed in this step
+        self.split_fwd = self.split_dgrad = None                                 # the bf16 planes of wp / wpt,
+        self.planes_valid = self.wants_planes = False      # ... split in this step; the weight has met a volume of the split-product kernels
+
+
 class PackedWeights:
     """Step-level cache of the packed convolution weights (forward + dgrad layout).  The weights only change in the optimiser
     step, so a step scope brackets the iteration with ``begin_step()`` / ``end_step()`` of its owner's cache (``StepScope.open(packed)``):
@@ -252,7 +263,7 @@ class PackedWeights:
     current = ScopeField("packed")      # the cache of the open step
 
     def __init__(self):
-        self.entries = {}     # id(parameter) -> [parameter, wp, wpt, valid, wsplit_fwd, wsplit_dgrad, planes valid, wants planes]
+        self.entries = {}     # id(parameter) -> _PackedEntry
 
     def begin_step(self):
         live = list(self.entries.values())
@@ -260,112 +271,101 @@ class PackedWeights:
             return
         L = _lib.lib()
         n = len(live)
-        arr = ctypes.c_void_p * n
-        iarr = ctypes.c_int32 * n
-        _lib.check(L.icl_conv3d_pack_weights_multi(arr(*[e[0].data_ptr() for e in live]), arr(*[e[1].data_ptr() for e in live]),
-                                                   arr(*[e[2].data_ptr() for e in live]), iarr(*[e[0].shape[0] for e in live]),
-                                                   iarr(*[e[0].shape[1] for e in live]), iarr(*[e[0].shape[2] for e in live]), n,
-                                                   _stream(live[0][0])), "pack_weights_multi")
+        arr, iarr = ctypes.c_void_p * n, ctypes.c_int32 * n
+        _lib.check(L.icl_conv3d_pack_weights_multi(arr(*[e.weight.data_ptr() for e in live]), arr(*[e.wp.data_ptr() for e in live]),
+                                                   arr(*[e.wpt.data_ptr() for e in live]), iarr(*[e.weight.shape[0] for e in live]),
+                                                   iarr(*[e.weight.shape[1] for e in live]), iarr(*[e.weight.shape[2] for e in live]), n,
+                                                   _stream(live[0].weight)), "pack_weights_multi")
         for e in live:
-            e[3] = True
+            e.valid = True
         # the three bf16 planes of every pack that can run on the split-product kernels (csrc/kernels/conv_bf16x3.h), again in one
         # launch: a convolution call then starts its kernel directly instead of a small split launch in front of it
         jobs = []
         for e in live:
-            cout, cin = e[0].shape[0], e[0].shape[1]
-            if e[0].shape[2] != 3 or not e[7]:      # only weights that have met a volume the split-product kernels take
+            cout, cin = e.weight.shape[0], e.weight.shape[1]
+            if e.weight.shape[2] != 3 or not e.wants_planes:      # only weights that have met a volume the split-product kernels take
                 continue
-            if e[4] is None and e[5] is None:
-                for slot, (ci, co) in ((4, (cin, cout)), (5, (cout, cin))):
-                    nb = L.icl_conv3d_split_ws_bytes(ci, co)
-                    if nb:
-                        e[slot] = torch.empty(nb // 4, dtype=torch.float32, device=e[0].device)
-            if e[4] is not None:
-                jobs.append((e[1], e[4], cin, cout))
-            if e[5] is not None:
-                jobs.append((e[2], e[5], cout, cin))
+            if e.split_fwd is None and e.split_dgrad is None:
+                e.split_fwd, e.split_dgrad = (torch.empty(nb // 4, dtype=torch.float32, device=e.weight.device) if nb else None
+                                              for nb in (L.icl_conv3d_split_ws_bytes(cin, cout), L.icl_conv3d_split_ws_bytes(cout, cin)))
+            if e.split_fwd is not None:
+                jobs.append((e.wp, e.split_fwd, cin, cout))
+            if e.split_dgrad is not None:
+                jobs.append((e.wpt, e.split_dgrad, cout, cin))
         if jobs:
             m = len(jobs)
             arr, iarr = ctypes.c_void_p * m, ctypes.c_int32 * m
             _lib.check(L.icl_conv3d_split_weights_multi(arr(*[j[0].data_ptr() for j in jobs]), arr(*[j[1].data_ptr() for j in jobs]),
-                                                        iarr(*[j[2] for j in jobs]), iarr(*[j[3] for j in jobs]), m, _stream(live[0][0])),
+                                                        iarr(*[j[2] for j in jobs]), iarr(*[j[3] for j in jobs]), m, _stream(live[0].weight)),
                        "split_weights_multi")
         for e in live:
-            e[6] = True
+            e.planes_valid = True
+
+    def end_step(self):
+        for e in self.entries.values():
+            e.valid = e.planes_valid = False
+
+    @staticmethod
+    def _entry(weight):
+        """(the cache of the open step, its entry for this very Parameter object); None for what does not exist."""
+        cache = getattr(StepScope.current, "packed", None) if isinstance(weight, torch.nn.Parameter) else None
+        e = cache.entries.get(id(weight)) if cache is not None else None
+        return cache, (e if e is not None and e.weight is weight else None)
 
     @staticmethod
     def split_of(weight):
         """(fwd planes, dgrad planes) of a weight whose packs were split by this step's ``begin_step()``; (None, None) otherwise."""
-        cache = getattr(StepScope.current, "packed", None) if isinstance(weight, torch.nn.Parameter) else None
-        e = cache.entries.get(id(weight)) if cache is not None else None
-        if e is None or e[0] is not weight or not e[3] or not e[6]:
-            return None, None
-        return e[4], e[5]
-
-    def end_step(self):
-        for e in self.entries.values():
-            e[3] = e[6] = False
+        _, e = PackedWeights._entry(weight)
+        return (e.split_fwd, e.split_dgrad) if e is not None and e.valid and e.planes_valid else (None, None)
 
     @staticmethod
     def get(weight):
         """(wp, wpt) of ``weight`` (contiguous [Cout, Cin, k, k, k]), packed now unless this step's begin_step() already did."""
         L = _lib.lib()
         cout, cin, ks = weight.shape[0], weight.shape[1], weight.shape[2]
-        cache = getattr(StepScope.current, "packed", None) if isinstance(weight, torch.nn.Parameter) else None
-        e = cache.entries.get(id(weight)) if cache is not None else None
-        if e is not None and e[0] is not weight:
-            e = None
-        if e is not None and e[3]:
-            return e[1], e[2]
-        if e is not None:
-            wp, wpt = e[1], e[2]
-        else:
-            wp = torch.empty(L.icl_conv3d_packed_elems(cout, cin, ks, 0), dtype=torch.float32, device=weight.device)
-            wpt = torch.empty(L.icl_conv3d_packed_elems(cout, cin, ks, 1), dtype=torch.float32, device=weight.device)
-        _lib.check(L.icl_conv3d_pack_weights_both(_ptr(weight), _ptr(wp), _ptr(wpt), cout, cin, ks, _stream(weight)), "pack_weights_both")
-        if cache is not None:
-            if e is not None:
-                e[1], e[2], e[3], e[6] = wp, wpt, True, False       # packed by this call: the split planes are stale
-            else:
-                cache.entries[id(weight)] = [weight, wp, wpt, True, None, None, False, False]
-        return wp, wpt
+        cache, e = PackedWeights._entry(weight)
+        if e is None:
+            e = _PackedEntry(weight, *(torch.empty(L.icl_conv3d_packed_elems(cout, cin, ks, mode), dtype=torch.float32, device=weight.device)
+                                       for mode in (0, 1)))
+            if cache is not None:
+                cache.entries[id(weight)] = e
+        if not e.valid:
+            _lib.check(L.icl_conv3d_pack_weights_both(_ptr(weight), _ptr(e.wp), _ptr(e.wpt), cout, cin, ks, _stream(weight)), "pack_weights_both")
+            e.valid, e.planes_valid = True, False       # packed by this call: the split planes are stale
+        return e.wp, e.wpt
 
     @staticmethod
     def note_volume(weight, voxels: int):
         """Called by the convolution with the size of the volume it runs on: weights that meet a volume of the split-product
         kernels (>= 6^3 voxels — the launcher decides per shape — unless ICL_CONV_SPLIT_MIN says otherwise) get their bf16 planes from
         the next begin_step() on."""
-        cache = getattr(StepScope.current, "packed", None) if isinstance(weight, torch.nn.Parameter) else None
-        e = cache.entries.get(id(weight)) if cache is not None else None
-        if e is not None and e[0] is weight and voxels >= int(os.environ.get("ICL_CONV_SPLIT_MIN", 6 ** 3)):
-            e[7] = True
+        _, e = PackedWeights._entry(weight)
+        if e is not None and voxels >= int(os.environ.get("ICL_CONV_SPLIT_MIN", 6 ** 3)):
+            e.wants_planes = True
 
 
 def conv3d_forward_raw(x, wp, bias, n, cin, cout, d, h, w, ks, x_bstride, y, y_bstride, wsplit=None, want_stats=False, n_live=None):
     """``wsplit``: the pack's bf16 planes when the step's PackedWeights.begin_step() has split them already.
-    ``n_live`` (input gradients only; y dense): samples [0, n_live) are computed, samples [n_live, n) of y written as zeros (the `_live`
-    entry points); the plan, the workspaces and the FLOP / byte figures are those of a batch of n_live.
+    ``n_live`` (input gradients only; y dense): samples [0, n_live) are computed, samples [n_live, n) of y written as zeros; the plan,
+    the workspaces and the FLOP / byte figures are those of a batch of n_live (the `_live` entry points: with n_live == n the plain ones).
     ``want_stats``: returns the InstanceNorm statistics of y — [n * cout, slots, 3] (count, mean, M2) summaries written by the
     convolution's epilogue (icl_conv3d_fwd_presplit_stats) — or None when this shape / path does not produce them."""
     L = _lib.lib()
     s = d * h * w
     assert n_live is None or not want_stats
     nl = n if n_live is None else n_live
-    live = () if n_live is None else (n_live,)      # the `_live` entry points take n_live behind n
-    presplit_ws, presplit, fwd = ((L.icl_conv3d_fwd_presplit_ws, L.icl_conv3d_fwd_presplit, L.icl_conv3d_fwd) if n_live is None else
-                                  (L.icl_conv3d_fwd_presplit_ws_live, L.icl_conv3d_fwd_presplit_live, L.icl_conv3d_fwd_live))
     # algorithmic work of this launch (SURVEY.md Appendix B): 2*taps*Cin*Cout FLOP per voxel; 4*(I+O+W) bytes
     flops = 2.0 * ks ** 3 * cin * cout * s * nl
     nbytes = 4.0 * (nl * s * (cin + cout) + ks ** 3 * cin * cout)
     need = L.icl_conv3d_fwd_ws_bytes(nl, cin, cout, d, h, w, ks)
     ws = _ws(need, x) if need else None
+    ptrs, dims = (_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y)), (cin, cout, d, h, w, x_bstride, y_bstride, _stream(x))
     with _timed("conv3d_mfma_fwd_kernel", flops, nbytes, x):
         if want_stats and wsplit is not None and ks == 3 and os.environ.get("ICL_CONV_STATS", "1") != "0":
             slots = L.icl_conv3d_fwd_stats_slots(n, cin, cout, d, h, w)
             if slots > 0:
                 stats = torch.empty((n * cout, slots, 3), dtype=torch.float32, device=x.device)
-                rc = L.icl_conv3d_fwd_presplit_stats(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), _ptr(stats), n, cin, cout, d, h, w,
-                                                     x_bstride, y_bstride, _stream(x))
+                rc = L.icl_conv3d_fwd_presplit_stats(*ptrs, _ptr(stats), n, *dims)
                 if rc != 1:
                     _lib.check(rc, "conv3d_fwd_presplit_stats")
                     return stats
@@ -374,265 +374,300 @@ def conv3d_forward_raw(x, wp, bias, n, cin, cout, d, h, w, ks, x_bstride, y, y_b
             kneed = L.icl_conv3d_fwd_presplit_ws_bytes(nl, cin, cout, d, h, w)
             if kneed:
                 kws = _ws(kneed, x)
-                rc = presplit_ws(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), _ptr(kws), n, *live, cin, cout, d, h, w, x_bstride, y_bstride,
-                                 _stream(x))
+                rc = L.icl_conv3d_fwd_presplit_ws_live(*ptrs, _ptr(kws), n, nl, *dims)
             else:
-                rc = presplit(_ptr(x), _ptr(wsplit), _ptr(bias), _ptr(y), n, *live, cin, cout, d, h, w, x_bstride, y_bstride, _stream(x))
+                rc = L.icl_conv3d_fwd_presplit_live(*ptrs, n, nl, *dims)
             if rc != 1:         # 1: this shape does not run on the split-product kernel -> the fp32 pack below
-                _lib.check(rc, "conv3d_fwd_presplit" if n_live is None else "conv3d_fwd_presplit_live")
+                _lib.check(rc, "conv3d_fwd_presplit_live")
                 return
-        _lib.check(fwd(_ptr(x), _ptr(wp), _ptr(bias), _ptr(y), _ptr(ws), n, *live, cin, cout, d, h, w, ks, x_bstride, y_bstride, _stream(x)),
-                   "conv3d_fwd" if n_live is None else "conv3d_fwd_live")
+        _lib.check(L.icl_conv3d_fwd_live(_ptr(x), _ptr(wp), _ptr(bias), _ptr(y), _ptr(ws), n, nl, cin, cout, d, h, w, ks, x_bstride, y_bstride,
+                                         _stream(x)), "conv3d_fwd_live")
 
 
-_ZERO_CACHE = {}
+@functools.lru_cache(maxsize=None)
+def _cached_zeros(n: int, device: str) -> torch.Tensor:
+    return torch.zeros(n, dtype=torch.float32, device=device)
 
 
-def _cached_zeros(n: int, device) -> torch.Tensor:
-    key = (n, str(device))
-    z = _ZERO_CACHE.get(key)
-    if z is None:
-        z = _ZERO_CACHE[key] = torch.zeros(n, dtype=torch.float32, device=device)
-    return z
-
+# The route of a convolution call: everything that follows from shapes, flags, environment switches and the thresholds below is decided
+# ONCE, by plan_conv3d, and carried from forward to backward as ctx.route.  What depends on pointers or on the state of
+# the backward pass is decided where the call is made, as the C launcher does with its plans: the 16-byte alignment of dY for the
+# one-input-channel weight gradient, a pre-split launch handing the call back (rc 1), icl_conv3d_fwd_stats_slots,
+# DeferredWgradReduce.wants, WgradLane.wants / adoptable, the live mark of dY (live_of) and icl_conv3d_fwd_live_ok.
 
 CONV1X1_WGRAD_MIN_VOXELS = 4096
 FIRST_CONV_PLANES_MAX_K = 32      # Cin * 27 <= 32, i.e. one input channel
 CONV1X1_GEMM_MIN_VOXELS = 65536
 CONV1X1_SMALL_MAX_CHANNELS = 16       # 1x1x1 convolutions with <= 16 -> <= 16 channels below the GEMM threshold: icl_conv1x1_small
+SMALL_CONV_MAX_VOXELS = 216      # 6^3
+WGRAD_SWAP_MIN_VOXELS = 24 ** 3    # exchanged-roles weight gradient (_wgrad_exchanged): only where the split-product kernels run
+SMALL_CONV_MIN_WEIGHTS = 128 * 128 * 27
+
+
+class ConvRoute(NamedTuple):
+    tiny: bool              # conv3d() and its fused forms run _conv3d_tiny_volume instead of _Conv3d (which takes `fwd` when called anyway)
+    fwd: str                # "gemm" (channel GEMM) | "small" (<= 16-channel 1x1x1) | "cin1" | "mfma" (MFMA / split product)
+    dgrad: Optional[str]    # "gemm" | "small" | "mfma"; None: the cin1 forward exists only where no input gradient is asked for
+    wgrad: str              # "rows" | "planes" | "product6" | "exchanged" | "mfma" (deferred slabs or direct: decided at launch)
+    wgrad_cin1: bool        # ... the one-input-channel kernel instead, where dY is 16-byte aligned
+    dgrad_live: bool        # the form runs on the live samples of a marked dY; a form that does not reads the whole gradient
+    wgrad_live: bool
+    lane_ok: bool           # the weight gradient may run on the WgradLane beside the input gradient
+    has_bias: bool
+    zero_bias_grad: bool
+
+
+def plan_conv3d(x_shape, w_shape, *, x_needs_grad: bool, has_bias: bool, zero_bias_grad: bool) -> ConvRoute:
+    """The route of Conv3d of x [n, cin, d, h, w] with weight [cout, cin, k, k, k], k 3 (pad 1) or 1; thresholds and switches as they are now."""
+    (n, cin, d, h, w), cout, ks = x_shape, w_shape[0], w_shape[2]
+    s = d * h * w
+    no_bias_grad = not has_bias or zero_bias_grad
+    first = cin * 27 <= FIRST_CONV_PLANES_MAX_K
+    # a whole 6^3 volume that the split-product kernel takes as ONE flat tile, split over the channel chunks (conv_bf16x3.h Bf3F6): the centre
+    # block of the 3-D U-Net.  Forward and input gradient are one launch + a slab sum each; the weight gradient keeps the product form.
+    flat6 = (ks == 3 and (d, h, w) == (6, 6, 6) and cin % 16 == 0 and cin >= 32 and ((cout + 15) // 16 * 16) % 32 == 0
+             and os.environ.get("ICL_CONV_SPLIT", "1") != "0" and os.environ.get("ICL_CONV_SPLIT_FLAT6", "1") != "0"
+             and os.environ.get("ICL_CONV_SPLIT_KSPLIT", "-1") != "0" and int(os.environ.get("ICL_CONV_SPLIT_MIN", 216)) <= 216)
+    # <= 6^3 voxels with >= 128x128 channels: a skinny GEMM that streams the weights once, unless the flat 6^3 tile takes the volume
+    tiny = ks == 3 and s <= SMALL_CONV_MAX_VOXELS and math.prod(w_shape) >= SMALL_CONV_MIN_WEIGHTS and not flat6
+    small_ch = cin <= CONV1X1_SMALL_MAX_CHANNELS and cout <= CONV1X1_SMALL_MAX_CHANNELS and s % 4 == 0
+    if ks == 1 and n * s >= CONV1X1_GEMM_MIN_VOXELS and not small_ch:
+        fwd = dgrad = "gemm"
+    elif ks == 1 and small_ch:
+        fwd = dgrad = "small"
+    elif (ks == 3 and cin == 1 and cout <= 16 and not x_needs_grad and 120 * (w + 2) <= 65536
+          and os.environ.get("ICL_CONV_CIN1", "1") != "0"):
+        fwd, dgrad = "cin1", None
+    else:
+        fwd = dgrad = "mfma"
+    if ks == 1 and s % 4 == 0 and n * s >= CONV1X1_WGRAD_MIN_VOXELS:
+        wgrad = "rows"
+    elif ks == 3 and first and w % 4 == 0 and n * s >= CONV1X1_WGRAD_MIN_VOXELS * 64:
+        wgrad = "planes"
+    elif flat6:
+        wgrad = "product6"
+    elif (ks == 3 and no_bias_grad and cout == 16 and cin % 48 == 0 and h % 8 == 0 and d >= 8 and w % 4 == 0
+          and s >= WGRAD_SWAP_MIN_VOXELS and os.environ.get("ICL_WGRAD_SWAP", "1") != "0"):
+        wgrad = "exchanged"
+    else:
+        wgrad = "mfma"
+    wgrad_cin1 = fwd == "cin1" and w % 4 == 0 and no_bias_grad
+    # live batch: the 3^3 split-product / fp32 MFMA paths, the <= 16-channel 1x1x1 path and the rows reduction run on samples [0, k); the
+    # channel GEMM, an MFMA 1x1x1 input gradient, the 6^3 product and a first-layer convolution in any form read the whole gradient
+    return ConvRoute(tiny=tiny, fwd=fwd, dgrad=dgrad, wgrad=wgrad, wgrad_cin1=wgrad_cin1,
+                     dgrad_live=dgrad == "small" or (dgrad == "mfma" and ks == 3),
+                     wgrad_live=wgrad in ("rows", "exchanged", "mfma") and not first and not wgrad_cin1,
+                     lane_ok=ks == 3 and x_needs_grad and not first, has_bias=has_bias, zero_bias_grad=zero_bias_grad)
 
 
 class _Conv3d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, zero_bias_grad=False, want_stats=False):
+    def forward(ctx, x, weight, bias, route, want_stats=False):
         """want_stats: returns (y, stats) — stats = the InstanceNorm summaries of y from the convolution's epilogue, or an empty
         tensor when this call did not produce them (the normalisation then runs its own statistics pass)."""
-        y = _Conv3d._forward(ctx, x, weight, bias, zero_bias_grad, want_stats)
-        if not want_stats:
-            return y
-        ctx.set_materialize_grads(False)      # (no zero tensor — a fill launch per call — for the non-differentiable statistics output)
-        stats = ctx.stats if getattr(ctx, "stats", None) is not None else torch.empty(0, dtype=torch.float32, device=x.device)
-        ctx.stats = None
-        ctx.mark_non_differentiable(stats)
-        return y, stats
-
-    @staticmethod
-    def _forward(ctx, x, weight, bias, zero_bias_grad, want_stats):
         _require(x, weight, bias)
-        x = x.contiguous()
-        weight = weight.contiguous()
-        ctx.zero_bias_grad = zero_bias_grad
-        n, cin, d, h, w = x.shape
-        cout, ks = weight.shape[0], weight.shape[2]
+        x, weight = x.contiguous(), weight.contiguous()
+        (n, cin, d, h, w), cout, ks = x.shape, weight.shape[0], weight.shape[2]
         assert weight.shape[1] == cin and weight.shape[2] == weight.shape[3] == weight.shape[4]
         s = d * h * w
         ctx.save_for_backward(x, weight)
         if ks == 3:
             WgradLane.note_use(weight)
-        ctx.has_bias = bias is not None
-        small_ch = cin <= CONV1X1_SMALL_MAX_CHANNELS and cout <= CONV1X1_SMALL_MAX_CHANNELS and s % 4 == 0
-        ctx.pointwise_gemm = ks == 1 and n * s >= CONV1X1_GEMM_MIN_VOXELS and not small_ch
-        if ctx.pointwise_gemm:
+        ctx.route, ctx.wpt, ctx.wsd = route, None, None
+        y = torch.empty((n, cout, d, h, w), dtype=torch.float32, device=x.device)
+        stats = wsf = None
+        if route.fwd == "gemm":
             # 1x1x1 convolution with many channels on a big volume = one batched product  W [Cout,Cin] x x[b] [Cin,S]  on the
             # tiled fp32-MFMA kernel (csrc/kernels/gemm.h), reading the channel-major volume in place (k-strided B operand)
-            y = torch.empty((n, cout, d, h, w), dtype=torch.float32, device=x.device)
             gemm(weight, x, cout, s, cin, cin, s, True, False, out=y, ldc=s, bias=bias, act=16, batch=n, b_bstride=cin * s,
                  c_bstride=cout * s)       # act 16: the bias is indexed by the output row (= channel)
-            return y
-        y = torch.empty((n, cout, d, h, w), dtype=torch.float32, device=x.device)
-        ctx.wpt = None
-        ctx.pointwise_small = ks == 1 and small_ch
-        if ctx.pointwise_small:
+        elif route.fwd == "small":
             # <= 16 channels (the aligner's h -> h / h -> 1 maps, the `final` 16 -> num_classes convolution on 96^3 voxels): VALU
             # kernels on the natural weight layout, HBM-bound on big volumes
             _lib.check(_lib.lib().icl_conv1x1_small(_ptr(x), _ptr(weight), _ptr(bias), _ptr(y), n, cin, cout, s, cin, 1, _stream(x)),
                        "conv1x1_small")
-            return y
-        ctx.cin1 = (ks == 3 and cin == 1 and cout <= 16 and not ctx.needs_input_grad[0] and 120 * (w + 2) <= 65536
-                    and os.environ.get("ICL_CONV_CIN1", "1") != "0")
-        if ctx.cin1:
+        elif route.fwd == "cin1":
             # the first convolution of the backbones (one input channel): K = 27, an HBM stream of the output (csrc/kernels/conv_cin1.h)
             with _timed("conv_cin1_fwd_kernel", 2.0 * 27 * cout * s * n, 4.0 * n * s * (1 + cout), x):
                 _lib.check(_lib.lib().icl_conv3d_cin1_fwd(_ptr(x), _ptr(weight), _ptr(bias), _ptr(y), n, cout, d, h, w, cin * s, cout * s,
                                                           _stream(x)), "conv3d_cin1_fwd")
-            return y
-        wsf = ctx.wsd = None
-        if ctx.needs_input_grad[0]:
-            # the input gradient will need the flipped/transposed packing too: one launch for both, kept for backward
-            wp, ctx.wpt = PackedWeights.get(weight)
-            wsf, ctx.wsd = PackedWeights.split_of(weight)
-            if ks == 3:
-                PackedWeights.note_volume(weight, s)
         else:
-            wp = pack_weights(weight, 0)
-        ctx.stats = conv3d_forward_raw(x, wp, bias, n, cin, cout, d, h, w, ks, cin * s, y, cout * s, wsplit=wsf, want_stats=want_stats)
-        return y
+            if ctx.needs_input_grad[0]:
+                # the input gradient will need the flipped/transposed packing too: one launch for both, kept for backward
+                wp, ctx.wpt = PackedWeights.get(weight)
+                wsf, ctx.wsd = PackedWeights.split_of(weight)
+                if ks == 3:
+                    PackedWeights.note_volume(weight, s)
+            else:
+                wp = pack_weights(weight, 0)
+            stats = conv3d_forward_raw(x, wp, bias, n, cin, cout, d, h, w, ks, cin * s, y, cout * s, wsplit=wsf, want_stats=want_stats)
+        if not want_stats:
+            return y
+        ctx.set_materialize_grads(False)      # (no zero tensor — a fill launch per call — for the non-differentiable statistics output)
+        if stats is None:
+            stats = torch.empty(0, dtype=torch.float32, device=x.device)
+        ctx.mark_non_differentiable(stats)
+        return y, stats
 
     @staticmethod
     def backward(ctx, gy, gstats=None):
         if gy is None:
             return None, None, None, None, None
         x, weight = ctx.saved_tensors
-        L = _lib.lib()
-        gy = gy.contiguous()
-        n, cin, d, h, w = x.shape
-        cout, ks = weight.shape[0], weight.shape[2]
-        s = d * h * w
-        gx = gw = gb = None
-        # live batch: the 3^3 split-product / fp32 MFMA paths and the <= 16-channel 1x1x1 path run on samples [0, k); every other form
-        # (channel GEMM, first-layer planes, one-input-channel kernels, 6^3 flat tile) reads the whole gradient — its tail is real zeros
+        route, gy = ctx.route, gy.contiguous()
+        (n, cin, d, h, w), cout, ks = x.shape, weight.shape[0], weight.shape[2]
+        # live batch: kept where both gradient forms of the route take one, and (3^3: the launcher splits the deep levels over the channel
+        # chunks by the batch size) only where the live batch gets the full batch's kernels — its samples come out bit for bit
         k = live_of(gy, n)
-        if k is not None and (ctx.pointwise_gemm or getattr(ctx, "cin1", False) or cin * 27 <= FIRST_CONV_PLANES_MAX_K
-                              or (ks == 3 and (d, h, w) == (6, 6, 6) and _f6_split_ok(x, weight))
-                              or (ks == 1 and not ctx.pointwise_small)
-                              or (ks == 3 and not L.icl_conv3d_fwd_live_ok(n, k, cout, cin, d, h, w))):
-            # (last line: the 3^3 launcher splits the deep levels over the channel chunks by the batch size: a live batch runs only where
-            # it gets the full batch's kernels — its samples come out bit for bit; icl_conv1x1_small_live keeps the full batch's kernel itself)
+        if k is not None and not (route.dgrad_live and route.wgrad_live
+                                  and (ks != 3 or _lib.lib().icl_conv3d_fwd_live_ok(n, k, cout, cin, d, h, w))):
             k = None
-        nl = n if k is None else k
-        lane = (ks == 3 and WgradLane.wants(x, s) and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not getattr(ctx, "cin1", False)
-                and not (cin * 27 <= FIRST_CONV_PLANES_MAX_K))
+        lane = route.lane_ok and WgradLane.wants(x, d * h * w) and ctx.needs_input_grad[1]
         if lane:
-            WgradLane.fork_point(gy)
+            WgradLane.fork_point(gy)      # where dY is complete, before the input gradient is queued on this stream
+        gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            if ctx.pointwise_gemm:
-                # gx[b] [Cin,S] = W^T gy[b]: A = W read transposed (k-strided), B = gy[b] [Cout,S] (k-strided)
-                gx = torch.empty_like(x)
-                gemm(weight, gy, cin, s, cout, cin, s, False, False, out=gx, ldc=s, batch=n, b_bstride=cout * s, c_bstride=cin * s)
-            elif ctx.pointwise_small:
-                gx = torch.empty_like(x)
-                # (the `_live` entry points with nl == n ARE the plain ones: one call site for both)
-                _lib.check(L.icl_conv1x1_small_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, nl, cout, cin, s, 1, cin, _stream(x)),
-                           "conv1x1_small_live dgrad")
-                mark_live(gx, k)
-            else:
-                gx = torch.empty_like(x)
-                wpt = ctx.wpt if ctx.wpt is not None else pack_weights(weight, 1)
-                conv3d_forward_raw(gy, wpt, None, n, cout, cin, d, h, w, ks, cout * s, gx, cin * s, wsplit=getattr(ctx, "wsd", None), n_live=k)
-                mark_live(gx, k)
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gw = torch.empty_like(weight)
-            gb = torch.empty(cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-            gb_arg = gb
-            if ctx.has_bias and ctx.zero_bias_grad:
-                # the conv feeds an InstanceNorm: its output is invariant to the bias, so dL/dbias == 0 exactly
-                # (the reference holds ~1e-8 rounding noise there); skip the reduction pass over dY.  The zero vector is a
-                # cached constant (nothing ever writes a non-zero into it), not a fill kernel per layer and step; returned as a
-                # fresh view so that AccumulateGrad adopts it instead of cloning a tensor it sees other references to.
-                # Only inside ICLTrainer's step bracket, where FusedSGD is the sole consumer of the gradient; anywhere else (stock
-                # optimisers, user code writing into .grad) every bias gets its own zero tensor.
-                gb = _cached_zeros(cout, x.device).view(cout) if getattr(StepScope.current, "packed", None) is not None else x.new_zeros(cout)
-                gb_arg = None
-            flops = 2.0 * ks ** 3 * cin * cout * s * nl
-            nbytes = 4.0 * (nl * s * (cin + cout) + 2 * ks ** 3 * cin * cout)
-            if ks == 1 and s % 4 == 0 and n * s >= CONV1X1_WGRAD_MIN_VOXELS:
-                # big-volume 1x1x1 convolution: HBM-bound channel-major reduction, rows split over many waves
-                ws = _ws(L.icl_conv1x1_wgrad_ws_bytes(n, s, cin, cout), x)
-                with _timed("conv1x1_wgrad_kernel", flops, nbytes, x):
-                    _lib.check(L.icl_conv1x1_wgrad_live(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, nl, cin, cout, s, cin * s,
-                                                        cout * s, _stream(x)), "conv1x1_wgrad_live")
-            elif getattr(ctx, "cin1", False) and w % 4 == 0 and gb_arg is None and gy.data_ptr() % 16 == 0:
-                ws = _ws(L.icl_conv3d_cin1_wgrad_ws_bytes(n, d, h), x)
-                with _timed("conv_cin1_wgrad_kernel", flops, nbytes, x):
-                    _lib.check(L.icl_conv3d_cin1_wgrad(_ptr(x), _ptr(gy), _ptr(gw), _ptr(ws), n, cout, d, h, w, cin * s, cout * s,
-                                                       _stream(x)), "conv3d_cin1_wgrad")
-            elif ks == 3 and cin * 27 <= FIRST_CONV_PLANES_MAX_K and w % 4 == 0 and n * s >= CONV1X1_WGRAD_MIN_VOXELS * 64:
-                # first convolution (one input channel, big volume): 27 shifted planes + the same HBM-bound reduction; the implicit
-                # GEMM pads Cin to 16 and takes 300 us for 0.8 GFLOP (batch 2, 96^3), this takes ~130
-                planes = torch.empty((n, cin * 27, s), dtype=torch.float32, device=x.device)
-                _lib.check(L.icl_im2col3_planes(_ptr(x), _ptr(planes), n, cin, d, h, w, _stream(x)), "im2col3_planes")
-                ws = _ws(L.icl_conv1x1_wgrad_ws_bytes(n, s, cin * 27, cout), x)
-                with _timed("conv1x1_wgrad_kernel", flops, nbytes, x):
-                    _lib.check(L.icl_conv1x1_wgrad(_ptr(planes), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, cin * 27, cout, s,
-                                                   cin * 27 * s, cout * s, _stream(x)), "conv1x1_wgrad")
-            else:
-                # One cout block but three (or six, nine ...) cin blocks — up_concat1.conv1, 48 -> 16 @96^3, the U-Net's largest weight
-                # gradient: with the roles of x and dY exchanged, dW[co][ci][t] = sum_q dY[co][q - t] x[ci][q], the z-column kernel stages
-                # ONE halo'd dY block for three x blocks instead of one halo'd x block per dY block (matrix pipe 52 -> 68 %,
-                # profiles/r5_pmc_conv.md); the result comes out as [cin][cout] with mirrored taps and is written back by two tiny copies.
-                tiny6 = ks == 3 and (d, h, w) == (6, 6, 6) and _f6_split_ok(x, weight)
-                swap = (ks == 3 and gb_arg is None and cout == 16 and cin % 48 == 0 and h % 8 == 0 and d >= 8 and w % 4 == 0
-                        and s >= WGRAD_SWAP_MIN_VOXELS and os.environ.get("ICL_WGRAD_SWAP", "1") != "0")
-
-                def wgrad():
-                    if tiny6:
-                        # dW[cout][cin * 27] = dY^T [cout, n S] x im2col(x) [n S, cin * 27]: the tall / skinny product of ops.linear's
-                        # weight gradient (the form _conv3d_tiny_volume gives it), here beside the split-product input gradient
-                        cols = torch.empty((n * s, cin * 27), dtype=torch.float32, device=x.device)
-                        _lib.check(L.icl_im2col3(_ptr(x), _ptr(cols), n, cin, d, h, w, _stream(x)), "im2col3")
-                        g2 = gy.reshape(n, cout, s).transpose(1, 2).reshape(n * s, cout).contiguous()
-                        gw2, gb2 = _tall_atb(g2, cols, gb_arg is not None)
-                        gw.copy_(gw2.view_as(gw))
-                        if gb_arg is not None:
-                            gb_arg.copy_(gb2)
-                        return
-                    if swap:
-                        ws = _ws(L.icl_conv3d_wgrad_ws_bytes_live(n, nl, cout, cin, ks), x)
-                        gws = torch.empty((cin, cout, ks, ks, ks), dtype=torch.float32, device=x.device)
-                        with _timed("conv3d_mfma_wgrad_kernel", flops, nbytes, x):
-                            _lib.check(L.icl_conv3d_wgrad_live(_ptr(gy), _ptr(x), _ptr(gws), None, _ptr(ws), n, nl, cout, cin, d, h, w, ks,
-                                                               cout * s, cin * s, _stream(x)), "conv3d_wgrad (roles exchanged)")
-                        gw.copy_(gws.flip(2, 3, 4).transpose(0, 1))
-                        return
-                    ws = _ws(L.icl_conv3d_wgrad_ws_bytes_live(n, nl, cin, cout, ks), x)
-                    if gb_arg is None and DeferredWgradReduce.wants(weight):
-                        # the slab sum is a leaf of the pass: queued, one launch for all of them when backward has ended
-                        ns = ctypes.c_int32(0)
-                        with _timed("conv3d_mfma_wgrad_kernel", flops, nbytes, x):
-                            _lib.check(L.icl_conv3d_wgrad_slabs_live(_ptr(x), _ptr(gy), _ptr(ws), n, nl, cin, cout, d, h, w, ks, cin * s,
-                                                                     cout * s, ctypes.byref(ns), _stream(x)), "conv3d_wgrad_slabs")
-                        DeferredWgradReduce.defer(ws, gw, cout, cin, ks, ns.value, weight)
-                        return
-                    with _timed("conv3d_mfma_wgrad_kernel", flops, nbytes, x):
-                        _lib.check(L.icl_conv3d_wgrad_live(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb_arg), _ptr(ws), n, nl, cin, cout, d, h, w, ks,
-                                                           cin * s, cout * s, _stream(x)), "conv3d_wgrad")
-                if lane:
-                    # deep level: beside the input gradient instead of behind it (the lane was forked where dY was complete, before
-                    # the input gradient above was queued on this stream)
-                    with WgradLane.on_lane(x, gy, gw, gb_arg):
-                        wgrad()
-                    if not WgradLane.adoptable(weight):
-                        WgradLane.sync_to_current(gw)      # accumulated / hooked gradient: no race with the lane (ADVICE round 4)
-                else:
-                    wgrad()
+            gx = _conv_dgrad(route, x, weight, gy, k, ctx.wpt, ctx.wsd)
+        if ctx.needs_input_grad[1] or (route.has_bias and ctx.needs_input_grad[2]):
+            gw, gb = _conv_wgrad(route, x, weight, gy, k, lane)
         return gx, gw, gb, None, None
+
+
+def _conv_dgrad(route, x, weight, gy, k, wpt, wsd):
+    (n, cin, d, h, w), cout, ks = x.shape, weight.shape[0], weight.shape[2]
+    s = d * h * w
+    gx = torch.empty_like(x)
+    if route.dgrad == "gemm":      # (never under a live mark: k is None)
+        # gx[b] [Cin,S] = W^T gy[b]: A = W read transposed (k-strided), B = gy[b] [Cout,S] (k-strided)
+        gemm(weight, gy, cin, s, cout, cin, s, False, False, out=gx, ldc=s, batch=n, b_bstride=cout * s, c_bstride=cin * s)
+    elif route.dgrad == "small":
+        _lib.check(_lib.lib().icl_conv1x1_small_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, n if k is None else k, cout, cin, s, 1, cin,
+                                                     _stream(x)), "conv1x1_small_live dgrad")
+    else:
+        conv3d_forward_raw(gy, wpt if wpt is not None else pack_weights(weight, 1), None, n, cout, cin, d, h, w, ks, cout * s, gx, cin * s,
+                           wsplit=wsd, n_live=k)
+    return mark_live(gx, k)
+
+
+# The weight-gradient forms: f(L, x, weight, gy, gw, gb, dims, cost) writes gw (and gb where it is not None) from samples [0, nl) of x
+# and dY; dims = (n, nl, cin, cout, d, h, w, ks, s), cost = (flops, bytes) of the launch for the KernelTimer.
+
+def _wgrad_rows(L, x, weight, gy, gw, gb, dims, cost):
+    """big-volume 1x1x1 convolution: HBM-bound channel-major reduction, rows split over many waves"""
+    n, nl, cin, cout, d, h, w, ks, s = dims
+    ws = _ws(L.icl_conv1x1_wgrad_ws_bytes(n, s, cin, cout), x)
+    with _timed("conv1x1_wgrad_kernel", *cost, x):
+        _lib.check(L.icl_conv1x1_wgrad_live(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), n, nl, cin, cout, s, cin * s, cout * s,
+                                            _stream(x)), "conv1x1_wgrad_live")
+
+
+def _wgrad_cin1(L, x, weight, gy, gw, gb, dims, cost):
+    n, nl, cin, cout, d, h, w, ks, s = dims
+    ws = _ws(L.icl_conv3d_cin1_wgrad_ws_bytes(n, d, h), x)
+    with _timed("conv_cin1_wgrad_kernel", *cost, x):
+        _lib.check(L.icl_conv3d_cin1_wgrad(_ptr(x), _ptr(gy), _ptr(gw), _ptr(ws), n, cout, d, h, w, cin * s, cout * s, _stream(x)),
+                   "conv3d_cin1_wgrad")
+
+
+def _wgrad_planes(L, x, weight, gy, gw, gb, dims, cost):
+    """first convolution (one input channel, big volume): 27 shifted planes + the reduction of _wgrad_rows over them; the implicit GEMM
+    pads Cin to 16 and takes 300 us for 0.8 GFLOP (batch 2, 96^3), this takes ~130"""
+    n, nl, cin, cout, d, h, w, ks, s = dims
+    planes = torch.empty((n, cin * 27, s), dtype=torch.float32, device=x.device)
+    _lib.check(L.icl_im2col3_planes(_ptr(x), _ptr(planes), n, cin, d, h, w, _stream(x)), "im2col3_planes")
+    _wgrad_rows(L, planes, weight, gy, gw, gb, (n, n, cin * 27, cout, d, h, w, 1, s), cost)
+
+
+def _wgrad_product6(L, x, weight, gy, gw, gb, dims, cost):
+    """dW[cout][cin * 27] = dY^T [cout, n S] x im2col(x) [n S, cin * 27]: the tall / skinny product of ops.linear's weight gradient (the
+    form _conv3d_tiny_volume gives it), here beside the split-product input gradient of the flat 6^3 tile"""
+    n, nl, cin, cout, d, h, w, ks, s = dims
+    cols = torch.empty((n * s, cin * 27), dtype=torch.float32, device=x.device)
+    _lib.check(L.icl_im2col3(_ptr(x), _ptr(cols), n, cin, d, h, w, _stream(x)), "im2col3")
+    g2 = gy.reshape(n, cout, s).transpose(1, 2).reshape(n * s, cout).contiguous()
+    gw2, gb2 = _tall_atb(g2, cols, gb is not None)
+    gw.copy_(gw2.view_as(gw))
+    if gb is not None:
+        gb.copy_(gb2)
+
+
+def _wgrad_exchanged(L, x, weight, gy, gw, gb, dims, cost):
+    """One cout block but three (or six, nine ...) cin blocks — up_concat1.conv1, 48 -> 16 @96^3, the U-Net's largest weight gradient:
+    with the roles of x and dY exchanged, dW[co][ci][t] = sum_q dY[co][q - t] x[ci][q], the z-column kernel stages ONE halo'd dY block for
+    three x blocks instead of one halo'd x block per dY block (matrix pipe 52 -> 68 %, profiles/r5_pmc_conv.md); the result comes out as
+    [cin][cout] with mirrored taps and is written back by two tiny copies.  (Never with a bias gradient: plan_conv3d.)"""
+    n, nl, cin, cout, d, h, w, ks, s = dims
+    ws = _ws(L.icl_conv3d_wgrad_ws_bytes_live(n, nl, cout, cin, ks), x)
+    gws = torch.empty((cin, cout, ks, ks, ks), dtype=torch.float32, device=x.device)
+    with _timed("conv3d_mfma_wgrad_kernel", *cost, x):
+        _lib.check(L.icl_conv3d_wgrad_live(_ptr(gy), _ptr(x), _ptr(gws), None, _ptr(ws), n, nl, cout, cin, d, h, w, ks, cout * s, cin * s,
+                                           _stream(x)), "conv3d_wgrad (roles exchanged)")
+    gw.copy_(gws.flip(2, 3, 4).transpose(0, 1))
+
+
+def _wgrad_mfma(L, x, weight, gy, gw, gb, dims, cost):
+    n, nl, cin, cout, d, h, w, ks, s = dims
+    ws = _ws(L.icl_conv3d_wgrad_ws_bytes_live(n, nl, cin, cout, ks), x)
+    with _timed("conv3d_mfma_wgrad_kernel", *cost, x):
+        if gb is None and DeferredWgradReduce.wants(weight):
+            # the slab sum is a leaf of the pass: queued, one launch for all of them when backward has ended
+            ns = ctypes.c_int32(0)
+            _lib.check(L.icl_conv3d_wgrad_slabs_live(_ptr(x), _ptr(gy), _ptr(ws), n, nl, cin, cout, d, h, w, ks, cin * s, cout * s,
+                                                     ctypes.byref(ns), _stream(x)), "conv3d_wgrad_slabs")
+            DeferredWgradReduce.defer(ws, gw, cout, cin, ks, ns.value, weight)
+        else:
+            _lib.check(L.icl_conv3d_wgrad_live(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), n, nl, cin, cout, d, h, w, ks, cin * s, cout * s,
+                                               _stream(x)), "conv3d_wgrad")
+
+
+_WGRAD_FORMS = {"rows": _wgrad_rows, "cin1": _wgrad_cin1, "planes": _wgrad_planes, "product6": _wgrad_product6,
+                "exchanged": _wgrad_exchanged, "mfma": _wgrad_mfma}
+
+
+def _conv_wgrad(route, x, weight, gy, k, lane):
+    """(gw, gb) by the route's weight-gradient form; ``lane``: on the WgradLane, which the caller forked where dY was complete."""
+    (n, cin, d, h, w), cout, ks = x.shape, weight.shape[0], weight.shape[2]
+    s, nl = d * h * w, n if k is None else k
+    gw = torch.empty_like(weight)
+    gb = gb_arg = torch.empty(cout, dtype=torch.float32, device=x.device) if route.has_bias else None
+    if route.has_bias and route.zero_bias_grad:
+        # the conv feeds an InstanceNorm: its output is invariant to the bias, so dL/dbias == 0 exactly (the reference holds ~1e-8 rounding
+        # noise there); skip the reduction pass over dY.  The zero vector is a cached constant (nothing ever writes a non-zero into it), not a
+        # fill kernel per layer and step; a fresh view, so that AccumulateGrad adopts it instead of cloning a tensor it sees other references
+        # to.  Only inside a step bracket, where FusedSGD is the sole consumer; anywhere else every bias gets its own zero tensor.
+        gb = _cached_zeros(cout, str(x.device)).view(cout) if getattr(StepScope.current, "packed", None) is not None else x.new_zeros(cout)
+        gb_arg = None
+    cost = (2.0 * ks ** 3 * cin * cout * s * nl, 4.0 * (nl * s * (cin + cout) + 2 * ks ** 3 * cin * cout))
+    form = _WGRAD_FORMS["cin1" if route.wgrad_cin1 and gy.data_ptr() % 16 == 0 else route.wgrad]
+    args = (_lib.lib(), x, weight, gy, gw, gb_arg, (n, nl, cin, cout, d, h, w, ks, s), cost)
+    if lane:
+        with WgradLane.on_lane(x, gy, gw, gb_arg):      # deep level: beside the input gradient instead of behind it
+            form(*args)
+        if not WgradLane.adoptable(weight):
+            WgradLane.sync_to_current(gw)      # accumulated / hooked gradient: no race with the lane (ADVICE round 4)
+    else:
+        form(*args)
+    return gw, gb
 
 
 class _Im2Col3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         _require(x)
-        L = _lib.lib()
         x = x.contiguous()
         n, c, d, h, w = x.shape
         cols = torch.empty((n * d * h * w, c * 27), dtype=torch.float32, device=x.device)
-        _lib.check(L.icl_im2col3(_ptr(x), _ptr(cols), n, c, d, h, w, _stream(x)), "im2col3")
+        _lib.check(_lib.lib().icl_im2col3(_ptr(x), _ptr(cols), n, c, d, h, w, _stream(x)), "im2col3")
         ctx.shape = (n, c, d, h, w)
         return cols
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib.lib()
         n, c, d, h, w = ctx.shape
         g = g.contiguous()
         dx = torch.empty((n, c, d, h, w), dtype=torch.float32, device=g.device)
-        _lib.check(L.icl_col2im3(_ptr(g), _ptr(dx), n, c, d, h, w, _stream(g)), "col2im3")
+        _lib.check(_lib.lib().icl_col2im3(_ptr(g), _ptr(dx), n, c, d, h, w, _stream(g)), "col2im3")
         return dx
-
-
-SMALL_CONV_MAX_VOXELS = 216      # 6^3
-WGRAD_SWAP_MIN_VOXELS = 24 ** 3    # exchanged-roles weight gradient (see _Conv3d.backward): only where the split-product kernels run
-SMALL_CONV_MIN_WEIGHTS = 128 * 128 * 27
-
-
-def _f6_split_ok(x, weight) -> bool:
-    """A 3^3 convolution on a whole 6^3 volume that the split-product kernel takes as ONE flat tile, split over the channel chunks
-    (csrc/kernels/conv_bf16x3.h Bf3F6, round 6): the centre block of the 3-D U-Net.  Forward and input gradient then are one launch + a
-    slab sum each instead of im2col / col2im around a skinny product; the weight gradient keeps the product form."""
-    cout, cin = weight.shape[0], weight.shape[1]
-    return (tuple(x.shape[2:]) == (6, 6, 6) and cin % 16 == 0 and cin >= 32 and ((cout + 15) // 16 * 16) % 32 == 0
-            and os.environ.get("ICL_CONV_SPLIT", "1") != "0" and os.environ.get("ICL_CONV_SPLIT_FLAT6", "1") != "0"
-            and os.environ.get("ICL_CONV_SPLIT_KSPLIT", "-1") != "0" and int(os.environ.get("ICL_CONV_SPLIT_MIN", 216)) <= 216)
 
 
 def _conv3d_tiny_volume(x, weight, bias):
@@ -645,14 +680,22 @@ def _conv3d_tiny_volume(x, weight, bias):
     return y.view(n, d * h * w, cout).permute(0, 2, 1).reshape(n, cout, d, h, w)
 
 
+def _conv3d_routed(x, weight, bias, zero_bias_grad, want_stats=False, tiny_ok=True):
+    """(y, the InstanceNorm statistics of y from the convolution's epilogue where they were asked for and produced, else None)"""
+    route = plan_conv3d(x.shape, weight.shape, x_needs_grad=x.requires_grad, has_bias=bias is not None, zero_bias_grad=zero_bias_grad)
+    if route.tiny and tiny_ok:
+        return _conv3d_tiny_volume(x, weight, bias), None
+    if not want_stats:
+        return _Conv3d.apply(x, weight, bias, route), None
+    y, stats = _Conv3d.apply(x, weight, bias, route, True)
+    return y, (stats if stats.numel() else None)
+
+
 def conv3d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
            zero_bias_grad: bool = False) -> torch.Tensor:
     """Conv3d, kernel 3 (pad 1) or 1 (pad 0), stride 1.  ``zero_bias_grad``: the caller guarantees the output goes
     straight into a mean-removing normalisation, so the bias gradient is identically zero."""
-    if (weight.shape[2] == 3 and x.shape[2] * x.shape[3] * x.shape[4] <= SMALL_CONV_MAX_VOXELS
-            and weight.numel() >= SMALL_CONV_MIN_WEIGHTS and not _f6_split_ok(x, weight)):
-        return _conv3d_tiny_volume(x, weight, bias)
-    return _Conv3d.apply(x, weight, bias, zero_bias_grad)
+    return _conv3d_routed(x, weight, bias, zero_bias_grad)[0]
 
 
 def conv3d_instance_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: int = 1, eps: float = 1e-5):
@@ -660,11 +703,8 @@ def conv3d_instance_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: Option
     (/root/reference/code/networks/utils.py:104-106).  Where the convolution runs on the split-product kernels inside a trainer step,
     its epilogue hands the normalisation the per-(sample, channel) statistics and the stand-alone statistics pass is skipped; everywhere
     else this is conv3d followed by instance_norm_act."""
-    if (weight.shape[2] == 3 and x.shape[2] * x.shape[3] * x.shape[4] <= SMALL_CONV_MAX_VOXELS
-            and weight.numel() >= SMALL_CONV_MIN_WEIGHTS and not _f6_split_ok(x, weight)):
-        return _NormAct.apply(_conv3d_tiny_volume(x, weight, bias), None, None, None, None, 0, True, int(act), eps, 0.0, None)
-    y, stats = _Conv3d.apply(x, weight, bias, True, True)
-    return _NormAct.apply(y, None, None, None, None, 0, True, int(act), eps, 0.0, stats if stats.numel() else None)
+    y, stats = _conv3d_routed(x, weight, bias, True, True)
+    return _NormAct.apply(y, None, None, None, None, 0, True, int(act), eps, 0.0, stats)
 
 
 # --------------------------------------------------------------------------------------
@@ -834,8 +874,8 @@ def conv3d_instance_norm_act_lazy(x: torch.Tensor, weight: torch.Tensor, bias: O
     s = x.shape[2] * x.shape[3] * x.shape[4]
     if weight.shape[2] != 3 or s < _lazy_norm_min_voxels() or s % 4 or not torch.is_grad_enabled():
         return conv3d_instance_norm_act(x, weight, bias, act=1, eps=eps)
-    y, stats = _Conv3d.apply(x, weight, bias, True, True)
-    if not stats.numel():
+    y, stats = _conv3d_routed(x, weight, bias, True, True, tiny_ok=False)
+    if stats is None:
         return _NormAct.apply(y, None, None, None, None, 0, True, 1, eps, 0.0, None)
     av, ss = _NormActLazy.apply(y, stats, eps)
     return LazyAct(av, ss)
@@ -890,11 +930,8 @@ def instance_norm_add_act(x: torch.Tensor, res: torch.Tensor, act: int = 2, eps:
 def conv3d_instance_norm_add_act(x: torch.Tensor, weight: torch.Tensor, res: torch.Tensor, act: int = 2, eps: float = 1e-5) -> torch.Tensor:
     """act(InstanceNorm3d(Conv3d(x)) + res): the second half of MONAI's UnetResBlock (swinunetr_icl.py:128-229), the convolution's
     epilogue handing the normalisation its statistics where it can (see conv3d_instance_norm_act)."""
-    if (weight.shape[2] == 3 and x.shape[2] * x.shape[3] * x.shape[4] <= SMALL_CONV_MAX_VOXELS
-            and weight.numel() >= SMALL_CONV_MIN_WEIGHTS and not _f6_split_ok(x, weight)):
-        return _InstanceNormAddAct.apply(_conv3d_tiny_volume(x, weight, None), res, int(act), eps)
-    y, stats = _Conv3d.apply(x, weight, None, True, True)
-    return _InstanceNormAddAct.apply(y, res, int(act), eps, stats if stats.numel() else None)
+    y, stats = _conv3d_routed(x, weight, None, True, True)
+    return _InstanceNormAddAct.apply(y, res, int(act), eps, stats)
 
 
 def batch_norm_relu(x, gamma, beta, running_mean, running_var, training: bool, relu: bool = True,
@@ -1385,14 +1422,47 @@ def drop_path_add(res: torch.Tensor, x: torch.Tensor, p: float, training: bool =
 def dropout(x: torch.Tensor, p: float, seed: Optional[int] = None) -> torch.Tensor:
     """Training-mode dropout.  Eager: the seed advances with torch's CPU generator (reproducible under manual_seed).
     With StepRNG enabled (graph capture): seed = call index, varied per step by the device-resident counter."""
-    seed_dev = None
-    if seed is None:
-        if StepRNG.tensor is not None and StepRNG.tensor.device == x.device:
-            seed = StepRNG.next_seed()
-            seed_dev = StepRNG.tensor
+    seed, seed_dev = _step_seed(x, seed)
+    return _Dropout.apply(x, float(p), seed, seed_dev)
+
+
+def _conv1x1_fusable(t, weight, also: bool) -> bool:
+    """A 1x1x1 convolution of <= 16 -> <= 16 channels on a big volume that the fused dropout kernels take; ``also``: what the call site
+    asks on top (dropout_conv1x1: autograd is recording; conv1x1_lazy: the raw tensor is contiguous)."""
+    n, cin = t.shape[0], t.shape[1]
+    s = t.numel() // max(n * cin, 1)
+    return ((t.is_cuda or _lib.host_pointers_ok()) and weight.shape[2:].numel() == 1 and cin <= 16 and weight.shape[0] <= 16
+            and s % 4 == 0 and n * s >= 65536 and also)
+
+
+def _dropout_conv1x1_backward(ctx, x, weight, gy, needs, mask_dgrad, wgrad, what):
+    """(gx, gw, gb) of _DropoutConv1x1 / _DropoutConv1x1Lazy.  ``needs``: (x, weight, bias) want a gradient; ``mask_dgrad``: the input
+    gradient applies the dropout mask on its stores; ``wgrad``: the weight-gradient entry point, its operand pointers bound."""
+    p, seed, has_bias = ctx.cfg
+    L = _lib.lib()
+    gy = gy.contiguous()
+    n, cin, cout = x.shape[0], x.shape[1], weight.shape[0]
+    s = x.numel() // (n * cin)
+    gx = gw = gb = None
+    k = live_of(gy, n)
+    nl = n if k is None else k
+    if needs[0]:
+        gx = torch.empty_like(x)
+        if mask_dgrad:
+            _lib.check(L.icl_conv1x1_dropout_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, nl, cout, cin, s, 1, cin, 2, seed, p,
+                                                  _ptr(ctx.seed_dev), _stream(x)), "conv1x1_dropout dgrad")
         else:
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-    return _Dropout.apply(x, float(p), int(seed) & 0xFFFFFFFF, seed_dev)
+            _lib.check(L.icl_conv1x1_small_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, nl, cout, cin, s, 1, cin, _stream(x)),
+                       "conv1x1_small dgrad")
+        mark_live(gx, k)
+    if needs[1] or (has_bias and needs[2]):
+        gw = torch.empty_like(weight)
+        gb = torch.empty(cout, dtype=torch.float32, device=x.device) if has_bias else None
+        ws = _ws(L.icl_conv1x1_wgrad_ws_bytes(n, s, cin, cout), x)
+        with _timed("conv1x1_wgrad_kernel", 2.0 * cin * cout * s * nl, 4.0 * nl * s * (cin + cout), x):
+            _lib.check(wgrad(_ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), n, nl, cin, cout, s, cout * s, seed, p, _ptr(ctx.seed_dev), _stream(x)),
+                       what)
+    return gx, gw, gb
 
 
 class _DropoutConv1x1(torch.autograd.Function):
@@ -1404,42 +1474,20 @@ class _DropoutConv1x1(torch.autograd.Function):
         _require(x, weight, bias)
         L = _lib.lib()
         x = x.contiguous()
-        n, cin = x.shape[0], x.shape[1]
-        cout = weight.shape[0]
+        n, cin, cout = x.shape[0], x.shape[1], weight.shape[0]
         s = x.numel() // (n * cin)
         y = torch.empty((n, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
         _lib.check(L.icl_conv1x1_dropout(_ptr(x), _ptr(weight), _ptr(bias), _ptr(y), n, cin, cout, s, cin, 1, 1, seed, p, _ptr(seed_dev),
                                          _stream(x)), "conv1x1_dropout")
         ctx.save_for_backward(x, weight)
-        ctx.cfg = (p, seed, bias is not None)
-        ctx.seed_dev = seed_dev
+        ctx.cfg, ctx.seed_dev = (p, seed, bias is not None), seed_dev
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
-        p, seed, has_bias = ctx.cfg
-        L = _lib.lib()
-        gy = gy.contiguous()
-        n, cin = x.shape[0], x.shape[1]
-        cout = weight.shape[0]
-        s = x.numel() // (n * cin)
-        gx = gw = gb = None
-        k = live_of(gy, n)
-        nl = n if k is None else k
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            # (the `_live` entry points with n_live == n ARE the plain ones)
-            _lib.check(L.icl_conv1x1_dropout_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, nl, cout, cin, s, 1, cin, 2, seed, p,
-                                                  _ptr(ctx.seed_dev), _stream(x)), "conv1x1_dropout dgrad")
-            mark_live(gx, k)
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            gw = torch.empty_like(weight)
-            gb = torch.empty(cout, dtype=torch.float32, device=x.device) if has_bias else None
-            ws = _ws(L.icl_conv1x1_wgrad_ws_bytes(n, s, cin, cout), x)
-            with _timed("conv1x1_wgrad_kernel", 2.0 * cin * cout * s * nl, 4.0 * nl * s * (cin + cout), x):
-                _lib.check(L.icl_conv1x1_wgrad_dropout_live(_ptr(x), _ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), n, nl, cin, cout, s, cout * s, seed,
-                                                            p, _ptr(ctx.seed_dev), _stream(x)), "conv1x1_wgrad_dropout")
+        gx, gw, gb = _dropout_conv1x1_backward(ctx, x, weight, gy, ctx.needs_input_grad, True,
+                                               lambda *a: _lib.lib().icl_conv1x1_wgrad_dropout_live(_ptr(x), *a), "conv1x1_wgrad_dropout")
         return gx, gw, gb, None, None, None
 
 
@@ -1450,47 +1498,22 @@ class _DropoutConv1x1Lazy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, ss, weight, bias, p, seed, seed_dev):
         L = _lib.lib()
-        n, cin = t.shape[0], t.shape[1]
-        cout = weight.shape[0]
+        n, cin, cout = t.shape[0], t.shape[1], weight.shape[0]
         s = t.numel() // (n * cin)
         y = torch.empty((n, cout) + tuple(t.shape[2:]), dtype=torch.float32, device=t.device)
         _lib.check(L.icl_conv1x1_dropout_norm(_ptr(t), _ptr(ss), _ptr(weight), _ptr(bias), _ptr(y), n, cin, cout, s, cin, 1, seed, p,
                                               _ptr(seed_dev), _stream(t)), "conv1x1_dropout_norm")
         ctx.save_for_backward(t, ss, weight)
-        ctx.cfg = (p, seed, bias is not None)
-        ctx.seed_dev = seed_dev
+        ctx.cfg, ctx.seed_dev = (p, seed, bias is not None), seed_dev
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        t, ss, weight = ctx.saved_tensors
-        p, seed, has_bias = ctx.cfg
-        L = _lib.lib()
-        gy = gy.contiguous()
-        n, cin = t.shape[0], t.shape[1]
-        cout = weight.shape[0]
-        s = t.numel() // (n * cin)
-        gx = gw = gb = None
-        k = live_of(gy, n)
-        nl = n if k is None else k
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(t)      # the gradient of the NORMALISED activation (what `t` stands for in the autograd graph)
-            # (the `_live` entry points with n_live == n ARE the plain ones)
-            if p > 0.0:
-                _lib.check(L.icl_conv1x1_dropout_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, nl, cout, cin, s, 1, cin, 2, seed, p,
-                                                      _ptr(ctx.seed_dev), _stream(t)), "conv1x1_dropout dgrad")
-            else:
-                _lib.check(L.icl_conv1x1_small_live(_ptr(gy), _ptr(weight), None, _ptr(gx), n, nl, cout, cin, s, 1, cin, _stream(t)),
-                           "conv1x1_small dgrad")
-            mark_live(gx, k)
-        if ctx.needs_input_grad[2] or (has_bias and ctx.needs_input_grad[3]):
-            gw = torch.empty_like(weight)
-            gb = torch.empty(cout, dtype=torch.float32, device=t.device) if has_bias else None
-            ws = _ws(L.icl_conv1x1_wgrad_ws_bytes(n, s, cin, cout), t)
-            with _timed("conv1x1_wgrad_kernel", 2.0 * cin * cout * s * nl, 4.0 * nl * s * (cin + cout), t):
-                _lib.check(L.icl_conv1x1_wgrad_dropout_norm_live(_ptr(t), _ptr(ss), _ptr(gy), _ptr(gw), _ptr(gb), _ptr(ws), n, nl, cin, cout, s,
-                                                                 cout * s, seed, p, _ptr(ctx.seed_dev), _stream(t)),
-                           "conv1x1_wgrad_dropout_norm")
+        t, ss, weight = ctx.saved_tensors      # (gx: the gradient of the NORMALISED activation — what `t` stands for in the autograd graph)
+        needs = ctx.needs_input_grad
+        gx, gw, gb = _dropout_conv1x1_backward(ctx, t, weight, gy, (needs[0], needs[2], needs[3]), ctx.cfg[0] > 0.0,
+                                               lambda *a: _lib.lib().icl_conv1x1_wgrad_dropout_norm_live(_ptr(t), _ptr(ss), *a),
+                                               "conv1x1_wgrad_dropout_norm")
         return gx, None, gw, gb, None, None, None
 
 
@@ -1501,54 +1524,28 @@ def conv1x1_lazy(x, weight: torch.Tensor, bias: Optional[torch.Tensor], p: float
     if not isinstance(x, LazyAct):
         return dropout_conv1x1(x, weight, bias, p, seed) if p > 0.0 else conv3d(x, weight, bias)
     t = x.t
-    n, cin = t.shape[0], t.shape[1]
-    s = t.numel() // max(n * cin, 1)
-    fusable = ((t.is_cuda or _lib.host_pointers_ok()) and weight.shape[2:].numel() == 1 and cin <= 16 and weight.shape[0] <= 16
-               and s % 4 == 0 and n * s >= 65536 and t.is_contiguous())
-    if not fusable:
+    if not _conv1x1_fusable(t, weight, t.is_contiguous()):
         a = x.materialize()
         return dropout_conv1x1(a, weight, bias, p, seed) if p > 0.0 else conv3d(a, weight, bias)
-    seed_dev = None
-    if p > 0.0 and seed is None:
-        if StepRNG.tensor is not None and StepRNG.tensor.device == t.device:
-            seed = StepRNG.next_seed()
-            seed_dev = StepRNG.tensor
-        else:
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-    return _DropoutConv1x1Lazy.apply(t, x.ss, weight.contiguous(), bias, float(p), int(seed or 0) & 0xFFFFFFFF, seed_dev)
+    seed, seed_dev = _step_seed(t, seed) if p > 0.0 else (int(seed or 0) & 0xFFFFFFFF, None)      # p = 0: no mask, no seed drawn
+    return _DropoutConv1x1Lazy.apply(t, x.ss, weight.contiguous(), bias, float(p), seed, seed_dev)
 
 
 def dropout_conv1x1(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], p: float, seed: Optional[int] = None) -> torch.Tensor:
     """``conv3d(dropout(x, p), weight, bias)`` for a 1x1x1 (or 1x1) convolution of <= 16 channels on a big volume — `final(dropout2(up1))` of
     the backbones (unet_3D_icl.py:67-68,117) — without materialising the dropped tensor.  Same seed protocol and the same mask as
     ``dropout`` (so the results are those of the two-op form, bit for bit); other shapes take the two-op form."""
-    n, cin = x.shape[0], x.shape[1]
-    s = x.numel() // max(n * cin, 1)
-    fusable = (x.is_cuda or _lib.host_pointers_ok()) and weight.shape[2:].numel() == 1 and cin <= 16 and weight.shape[0] <= 16 \
-        and s % 4 == 0 and n * s >= 65536 and torch.is_grad_enabled()
-    if not fusable:
+    if not _conv1x1_fusable(x, weight, torch.is_grad_enabled()):
         return conv3d(dropout(x, p, seed), weight, bias)
-    seed_dev = None
-    if seed is None:
-        if StepRNG.tensor is not None and StepRNG.tensor.device == x.device:
-            seed = StepRNG.next_seed()
-            seed_dev = StepRNG.tensor
-        else:
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-    return _DropoutConv1x1.apply(x, weight, bias, float(p), int(seed) & 0xFFFFFFFF, seed_dev)
+    seed, seed_dev = _step_seed(x, seed)
+    return _DropoutConv1x1.apply(x, weight, bias, float(p), seed, seed_dev)
 
 
 def drop_path(x: torch.Tensor, p: float, seed: Optional[int] = None) -> torch.Tensor:
     """Per-sample stochastic depth (timm / MONAI DropPath): each sample of the batch keeps its branch with probability 1-p (scaled
     by 1/(1-p)) or drops it entirely — one kernel instead of empty + bernoulli_ + div + mul; same seeding scheme as ``dropout``."""
-    seed_dev = None
-    if seed is None:
-        if StepRNG.tensor is not None and StepRNG.tensor.device == x.device:
-            seed = StepRNG.next_seed()
-            seed_dev = StepRNG.tensor
-        else:
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-    return _Dropout.apply(x, float(p), int(seed) & 0xFFFFFFFF, seed_dev, x.numel() // x.shape[0])
+    seed, seed_dev = _step_seed(x, seed)
+    return _Dropout.apply(x, float(p), seed, seed_dev, x.numel() // x.shape[0])
 
 
 # --------------------------------------------------------------------------------------

@@ -23,6 +23,7 @@
 #include "kernels/gemm.h"
 #include "kernels/datafeed.h"
 #include "kernels/rankindex.h"
+#include "kernels/prefix.h"
 #include "kernels/qchain.h"
 #include "kernels/metrics.h"
 #include "kernels/metrics_surface.h"
@@ -37,6 +38,7 @@ extern template __global__ void conv3d_bf16x3_fwd_ws_kernel<1, false, false>(con
 #endif
 
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -2523,6 +2525,143 @@ int icl_rank_select(const void* const* images, const void* const* labels, const 
   }
   ICL_LAUNCH(icl::rank_select_kernel, dim3(batch), dim3(icl::kRankThreads), 0, (hipStream_t)stream, sb, threshold, (int*)origins);
   return check_launch("rank_select");
+}
+
+namespace {
+
+// A prefix plan as the caller hands it over, checked once for icl_prefix_resample and icl_prefix_restore.  int_params [24] = {raw
+// extents n[3], box lo[3], box hi[3] (exclusive), perm[3], sign[3], pad front f[3], padded extents m[3], output extents o[3]};
+// double_params [6] = {source spacing s[3], target spacing p[3]}, both per ORIENTED axis.
+struct PrefixPlanArgs {
+  int n[3], lo[3], hi[3], perm[3], sign[3], f[3], m[3], o[3], e[3];
+  double s[3], p[3];
+};
+
+int prefix_plan_args(const char* what, const int32_t* q, const double* d, PrefixPlanArgs& a) {
+  for (int k = 0; k < 3; ++k) {
+    a.n[k] = q[k]; a.lo[k] = q[3 + k]; a.hi[k] = q[6 + k]; a.perm[k] = q[9 + k]; a.sign[k] = q[12 + k];
+    a.f[k] = q[15 + k]; a.m[k] = q[18 + k]; a.o[k] = q[21 + k];
+    a.s[k] = d[k]; a.p[k] = d[3 + k];
+  }
+  if (a.n[0] < 1 || a.n[1] < 1 || a.n[2] < 1 || a.n[0] > 65535 || a.n[1] > 65535 || a.n[2] > 65535)
+    return fail(-1, "%s: raw extents %d x %d x %d (each must be in 1..65535)", what, a.n[0], a.n[1], a.n[2]);
+  if ((long)a.n[0] * a.n[1] * a.n[2] > 0x7fffffffL)
+    return fail(-1, "%s: raw extents %d x %d x %d (more than 2^31 - 1 voxels)", what, a.n[0], a.n[1], a.n[2]);
+  int seen = 0;
+  for (int k = 0; k < 3; ++k) {
+    if (a.perm[k] < 0 || a.perm[k] > 2) return fail(-1, "%s: perm (%d, %d, %d) is not a permutation of 0, 1, 2", what, a.perm[0], a.perm[1], a.perm[2]);
+    seen |= 1 << a.perm[k];
+    if (a.sign[k] != 1 && a.sign[k] != -1) return fail(-1, "%s: sign %d of oriented axis %d (1 or -1)", what, a.sign[k], k);
+  }
+  if (seen != 7) return fail(-1, "%s: perm (%d, %d, %d) is not a permutation of 0, 1, 2", what, a.perm[0], a.perm[1], a.perm[2]);
+  for (int k = 0; k < 3; ++k)
+    if (a.lo[k] < 0 || a.hi[k] <= a.lo[k] || a.hi[k] > a.n[k])
+      return fail(-1, "%s: box [%d, %d) of raw axis %d outside the extent %d", what, a.lo[k], a.hi[k], k, a.n[k]);
+  for (int k = 0; k < 3; ++k) {
+    if (!std::isfinite(a.s[k]) || !std::isfinite(a.p[k]) || !(a.s[k] > 0.0) || !(a.p[k] > 0.0) || !std::isfinite(a.p[k] / a.s[k]) ||
+        !(a.s[k] / a.p[k] > 0.0))
+      return fail(-1, "%s: spacing %g -> %g of oriented axis %d (both must be finite and positive)", what, a.s[k], a.p[k], k);
+    a.e[k] = a.hi[a.perm[k]] - a.lo[a.perm[k]];
+    if (a.f[k] < 0 || a.m[k] > 65535 || (long)a.f[k] + a.e[k] > a.m[k])
+      return fail(-1, "%s: pad front %d + crop extent %d of oriented axis %d outside the padded extent %d (at most 65535)", what, a.f[k],
+                  a.e[k], k, a.m[k]);
+    const double want = std::nearbyint((double)(a.m[k] - 1) * (a.s[k] / a.p[k]) + 1.0);      // round half to even
+    if (!(want >= 1.0 && want <= 65535.0) || a.o[k] != (int)want)
+      return fail(-1, "%s: output extent %d of oriented axis %d: rint((%d - 1) * (%g / %g) + 1) = %.0f (must be in 1..65535)", what, a.o[k], k,
+                  a.m[k], a.s[k], a.p[k], want);
+  }
+  if ((long)a.o[0] * a.o[1] * a.o[2] > 0x7fffffffL)
+    return fail(-1, "%s: output extents %d x %d x %d (more than 2^31 - 1 voxels)", what, a.o[0], a.o[1], a.o[2]);
+  return 0;
+}
+
+int prefix_window_args(const char* what, const float* window, int clip, icl::PrefixWindow& w) {
+  w.a_min = window[0]; w.a_range = window[1]; w.b_min = window[2]; w.b_range = window[3]; w.b_max = window[4];
+  w.clip = clip ? 1 : 0;
+  for (int i = 0; i < 5; ++i)
+    if (!std::isfinite(window[i])) return fail(-1, "%s: window constant %d is not finite", what, i);
+  if (w.a_range == 0.f) return fail(-1, "%s: a_max - a_min is 0", what);
+  return 0;
+}
+
+}  // namespace
+
+int icl_prefix_box(const float* image, int n0, int n1, int n2, const float* window, int clip, int32_t* box, int32_t* ws, void* stream) {
+  if (!image || !window || !box || !ws) return fail(-1, "prefix_box: null pointer");
+  if (n0 < 1 || n1 < 1 || n2 < 1 || n0 > 65535 || n1 > 65535 || n2 > 65535)
+    return fail(-1, "prefix_box: extents %d x %d x %d (each must be in 1..65535)", n0, n1, n2);
+  if ((long)n0 * n1 * n2 > 0x7fffffffL) return fail(-1, "prefix_box: extents %d x %d x %d (more than 2^31 - 1 voxels)", n0, n1, n2);
+  icl::PrefixWindow w;
+  if (const int rc = prefix_window_args("prefix_box", window, clip, w)) return rc;
+  const long total = (long)n0 * n1 * n2;
+  const int blocks = grid_for(cdivl(total, 4), icl::kPrefixThreads, icl::kPrefixBoxBlocks);
+  ICL_LAUNCH(icl::prefix_box_partial_kernel, dim3(blocks), dim3(icl::kPrefixThreads), 0, (hipStream_t)stream, image, n1, n2, total, w,
+             aligned16(image) ? 1 : 0, (int*)ws);
+  if (const int rc = check_launch("prefix_box_partial")) return rc;
+  ICL_LAUNCH(icl::prefix_box_finish_kernel, dim3(1), dim3(icl::kPrefixThreads), 0, (hipStream_t)stream, (const int*)ws, blocks, (int*)box);
+  return check_launch("prefix_box_finish");
+}
+
+int icl_prefix_resample(const float* image, const uint8_t* label, const int32_t* int_params, const double* double_params, const float* window,
+                        int clip, float* image_out, uint8_t* label_out, void* stream) {
+  if (!image || !label || !int_params || !double_params || !window || !image_out || !label_out) return fail(-1, "prefix_resample: null pointer");
+  PrefixPlanArgs a;
+  if (const int rc = prefix_plan_args("prefix_resample", int_params, double_params, a)) return rc;
+  icl::PrefixWindow w;
+  if (const int rc = prefix_window_args("prefix_resample", window, clip, w)) return rc;
+  icl::PrefixGeom g{};
+  const long raw_stride[3] = {(long)a.n[1] * a.n[2], (long)a.n[2], 1L};
+  for (int k = 0; k < 3; ++k) {
+    const int r = a.perm[k];
+    g.step[k] = a.sign[k] > 0 ? raw_stride[r] : -raw_stride[r];
+    g.base += (long)(a.sign[k] > 0 ? a.lo[r] : a.hi[r] - 1) * raw_stride[r];
+    g.e[k] = a.e[k]; g.f[k] = a.f[k]; g.m[k] = a.m[k]; g.o[k] = a.o[k];
+    g.fwd[k] = a.p[k] / a.s[k];
+  }
+  // axis-2 outputs per tile: the taps of `tile2` consecutive outputs span at most floor((tile2 - 1) * fwd) + 3 slots (the two ends'
+  // floors differ by at most floor(distance) + 1, and i1 adds one); one slot of margin is kept
+  const double room = (double)(icl::kPrefixSlots - 4) / g.fwd[2];
+  int tile2 = room >= (double)(icl::kPrefixTile2 - 1) ? icl::kPrefixTile2 : (int)room + 1;
+  if (tile2 > a.o[2]) tile2 = a.o[2];
+  const bool quads = (a.o[2] & 3) == 0 && aligned16(image_out) && ((uintptr_t)label_out & 3) == 0 && tile2 >= 4;
+  if (quads) tile2 &= ~3;
+  const long tiles = (long)a.o[0] * cdivl(a.o[1], icl::kPrefixRows) * cdivl(a.o[2], tile2);
+  const dim3 grid(grid_for(tiles, 1, 65536));
+  if (quads) {
+    ICL_LAUNCH(icl::prefix_resample_kernel<4>, grid, dim3(icl::kPrefixThreads), 0, (hipStream_t)stream, image, label, g, w, tile2, image_out,
+               label_out);
+  } else {
+    ICL_LAUNCH(icl::prefix_resample_kernel<1>, grid, dim3(icl::kPrefixThreads), 0, (hipStream_t)stream, image, label, g, w, tile2, image_out,
+               label_out);
+  }
+  return check_launch("prefix_resample");
+}
+
+int icl_prefix_restore(const void* prediction, int elem_kind, const int32_t* int_params, const double* double_params, uint8_t* out,
+                       void* stream) {
+  if (!prediction || !int_params || !double_params || !out) return fail(-1, "prefix_restore: null pointer");
+  if (elem_kind != 0 && elem_kind != 1) return fail(-1, "prefix_restore: unknown element kind %d (0 uint8, 1 int64)", elem_kind);
+  PrefixPlanArgs a;
+  if (const int rc = prefix_plan_args("prefix_restore", int_params, double_params, a)) return rc;
+  icl::PrefixRestoreGeom g{};
+  const long pred_stride[3] = {(long)a.o[1] * a.o[2], (long)a.o[2], 1L};
+  for (int k = 0; k < 3; ++k) {          // oriented axis k is raw axis r
+    const int r = a.perm[k];
+    g.n[r] = a.n[r]; g.lo[r] = a.lo[r]; g.hi[r] = a.hi[r];
+    g.rev[r] = a.sign[k] < 0 ? 1 : 0;
+    g.f[r] = a.f[k]; g.o[r] = a.o[k];
+    g.pstride[r] = pred_stride[k];
+    g.inv[r] = a.s[k] / a.p[k];
+  }
+  const long voxels = (long)a.n[0] * a.n[1] * a.n[2];
+  const dim3 grid(grid_for(voxels, icl::kPrefixThreads, 8192));
+  if (elem_kind == 0) {
+    ICL_LAUNCH(icl::prefix_restore_kernel<uint8_t>, grid, dim3(icl::kPrefixThreads), 0, (hipStream_t)stream, (const uint8_t*)prediction, g, out);
+  } else {
+    ICL_LAUNCH(icl::prefix_restore_kernel<long long>, grid, dim3(icl::kPrefixThreads), 0, (hipStream_t)stream, (const long long*)prediction, g,
+               out);
+  }
+  return check_launch("prefix_restore");
 }
 
 int icl_slice_augment(const void* const* images, const void* const* labels, const int32_t* int_params, const double* double_params,

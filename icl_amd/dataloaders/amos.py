@@ -9,8 +9,17 @@ host threads for every sample of every batch:
 
 Here the cached volumes stay resident in HBM (``DeviceVolumeStore``, filled by ``amos_volume_store``), the host draws the random
 parameters of a batch (``draw_amos_params``) and ONE gather kernel (``volume_feed_kernel`` in ``csrc/kernels/datafeed.h``, through
-``icl_volume_feed``) produces the batch.  ``AMOSDeviceLoader`` stands where the ``ThreadDataLoader`` stood.  The cached prefix stays
-MONAI's: it needs NIfTI affines and is not restated.
+``icl_volume_feed``) produces the batch.  ``AMOSDeviceLoader`` stands where the ``ThreadDataLoader`` stood.
+
+**The cached prefix** (``ScaleIntensityRanged -> CropForegroundd -> Orientationd("RAS") -> Spacingd``, ``:86-101``; validation, ``:141-154``,
+with ``SpatialPadd(96^3)`` before ``Spacingd``) runs on the device too, from the raw arrays and the affine the caller read from the file
+(no NIfTI is read here).  ``plan_prefix`` describes a case as a value on the host (``PrefixPlan``: foreground box, permutation and signs
+from ``orientation_from_affine`` — nibabel's ``io_orientation`` restated —, spacings, pad, extents); ``amos_prefix`` finds the box
+(``icl_prefix_box``; its six integers are the only read-back), then windows, crops, reorients, pads and respaces image and label in ONE
+gather from the raw arrays (``icl_prefix_resample``, ``csrc/kernels/prefix.h``); ``amos_volume_store_from_raw`` fills the store that way
+and ``amos_val_cases_from_raw`` makes the validation items; ``restore_label`` is the inverse for label maps (MONAI's ``Invertd`` on a
+prediction).  The definition is in DESIGN.md §2 "AMOS cached prefix"; ``tests/amos_prefix_ref.py`` restates it as the literal numpy
+chain, which the emulated kernels and the GPU equal bit for bit.  Parity with MONAI's own code is unpinned here as well.
 
 **Parity with MONAI's own code is unpinned.**  MONAI is not installed where this package is built and tested, so the transform
 semantics are restated from MONAI 1.0.1's published definitions (as the window grid and the Gaussian map of ``val_3D`` are) and no golden
@@ -29,6 +38,7 @@ code is unpinned here too; what ``tests/posneg_feed_ref.py`` pins is the algorit
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -384,3 +394,286 @@ class AMOSDeviceLoader:
     def __iter__(self):
         for indices in self.batch_sampler:
             yield self.augment.batch(list(indices))
+
+
+# ---- the cached prefix: ScaleIntensityRanged -> CropForegroundd -> Orientationd("RAS") -> [SpatialPadd] -> Spacingd, and back -----------
+
+PREFIX_WINDOW = (-175.0, 250.0, 0.0, 1.0, True)     # a_min, a_max, b_min, b_max, clip (:88-90 of the trainer)
+PREFIX_PIXDIM = (1.5, 1.5, 2.0)                     # Spacingd(pixdim=…) (:95-99)
+PREFIX_BOX_WS_INTS = 6 * 1024                       # int32 words of scratch icl_prefix_box takes (6 * kPrefixBoxBlocks)
+_AXCODE = {"R": (0, 1), "L": (0, -1), "A": (1, 1), "P": (1, -1), "S": (2, 1), "I": (2, -1)}
+
+
+def orientation_from_affine(affine) -> Tuple[Tuple[int, int, int], Tuple[int, int, int], Tuple[float, float, float]]:
+    """nibabel's ``io_orientation`` restated, for a 4x4 (or 3x3) affine of a 3-D volume: ``(perm, sign, zooms)`` where RAS-oriented
+    axis ``a`` is source axis ``perm[a]``, reversed when ``sign[a]`` is -1, and ``zooms[k]`` is the voxel size of SOURCE axis ``k``.
+
+    ``RZS = A[:3, :3]``; ``zooms = sqrt(sum(RZS ** 2, axis 0))`` (a zero column is a ``ValueError``); ``RS = RZS / zooms``;
+    ``P, S, Qt = svd(RS)``; ``tol = S.max() * 3 * eps``; ``R = P[:, keep] @ Qt[keep]`` with ``keep = S > tol``; then for source axis
+    0, 1, 2 in turn ``out = argmax |R[:, in]|``, the sign is that of ``R[out, in]``, and row ``out`` of ``R`` is zeroed."""
+    A = np.asarray(affine, dtype=np.float64)
+    if A.shape not in ((4, 4), (3, 3)) or not np.isfinite(A).all():
+        raise ValueError(f"orientation_from_affine: a finite 4x4 (or 3x3) affine expected, got shape {A.shape}")
+    RZS = A[:3, :3]
+    zooms = np.sqrt(np.sum(RZS * RZS, axis=0))
+    if (zooms == 0).any():
+        raise ValueError("orientation_from_affine: the affine has a zero column")
+    RS = RZS / zooms
+    P, S, Qt = np.linalg.svd(RS)
+    keep = S > S.max() * 3 * np.finfo(S.dtype).eps
+    R = np.dot(P[:, keep], Qt[keep])
+    perm, sign = [-1, -1, -1], [0, 0, 0]
+    for in_ax in range(3):
+        col = R[:, in_ax]
+        if np.allclose(col, 0):
+            raise ValueError(f"orientation_from_affine: source axis {in_ax} has no direction left (a degenerate affine)")
+        out_ax = int(np.argmax(np.abs(col)))
+        if perm[out_ax] != -1:
+            raise ValueError("orientation_from_affine: two source axes map to one oriented axis")
+        perm[out_ax] = in_ax
+        sign[out_ax] = -1 if col[out_ax] < 0 else 1
+        R[out_ax, :] = 0
+    return tuple(perm), tuple(sign), tuple(float(z) for z in zooms)
+
+
+def orientation_from_axcodes(axcodes) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
+    """``(perm, sign)`` as ``orientation_from_affine`` gives them, from three letters naming where source axes 0, 1, 2 point:
+    R / A / S positive, L / P / I negative (``"LPS"``: axis 0 runs to the left, axis 1 to the back, axis 2 up)."""
+    codes = [str(c).upper() for c in axcodes] if not isinstance(axcodes, str) else list(axcodes.upper())
+    if len(codes) != 3 or any(c not in _AXCODE for c in codes):
+        raise ValueError(f"orientation_from_axcodes: three letters out of R, L, A, P, S, I expected, got {axcodes!r}")
+    perm, sign = [-1, -1, -1], [0, 0, 0]
+    for in_ax, c in enumerate(codes):
+        out_ax, s = _AXCODE[c]
+        if perm[out_ax] != -1:
+            raise ValueError(f"orientation_from_axcodes: {axcodes!r} names one anatomical axis twice")
+        perm[out_ax], sign[out_ax] = in_ax, s
+    return tuple(perm), tuple(sign)
+
+
+def _window_constants(window) -> Tuple[Tuple[float, float, float, float, float], bool]:
+    """``(a_min, a_max, b_min, b_max, clip)`` -> the five fp32 constants of the kernels ``(a_min, a_max - a_min, b_min, b_max - b_min,
+    b_max)`` (the differences formed in double, then rounded) and the clip flag."""
+    if len(window) != 5:
+        raise ValueError(f"plan_prefix: window {window!r}: (a_min, a_max, b_min, b_max, clip) expected")
+    a_min, a_max, b_min, b_max = (float(v) for v in window[:4])
+    consts = tuple(float(np.float32(v)) for v in (a_min, a_max - a_min, b_min, b_max - b_min, b_max))
+    if not all(np.isfinite(consts)) or consts[1] == 0.0:
+        raise ValueError(f"plan_prefix: window {window!r}: finite values with a_max != a_min expected")
+    return consts, bool(window[4])
+
+
+@dataclasses.dataclass(frozen=True)
+class PrefixPlan:
+    """The cached prefix of one case as a value (frozen; made by ``plan_prefix``): ``shape`` raw extents; ``box`` ``(lo0, lo1, lo2, hi0,
+    hi1, hi2)`` in raw axes, ``hi`` exclusive; ``perm`` / ``sign``: oriented axis ``a`` is raw axis ``perm[a]`` of the box, reversed when
+    ``sign[a]`` is -1; ``spacing`` the source voxel size and ``pixdim`` the target, per ORIENTED axis; ``pad_front`` zeros in front of
+    each oriented axis and ``padded_shape`` the extents after ``SpatialPad``; ``out_shape`` the extents after ``Spacing``; ``window`` the
+    five fp32 constants ``(a_min, a_max - a_min, b_min, b_max - b_min, b_max)`` and ``clip``."""
+    shape: Tuple[int, int, int]
+    box: Tuple[int, int, int, int, int, int]
+    perm: Tuple[int, int, int]
+    sign: Tuple[int, int, int]
+    spacing: Tuple[float, float, float]
+    pixdim: Tuple[float, float, float]
+    pad_front: Tuple[int, int, int]
+    padded_shape: Tuple[int, int, int]
+    out_shape: Tuple[int, int, int]
+    window: Tuple[float, float, float, float, float]
+    clip: bool
+
+    @property
+    def crop_shape(self) -> Tuple[int, int, int]:
+        """Extents of the oriented crop (before the pad)."""
+        return tuple(self.box[3 + self.perm[a]] - self.box[self.perm[a]] for a in range(3))
+
+    def int_params(self):
+        """The 24 integers ``icl_prefix_resample`` / ``icl_prefix_restore`` take."""
+        return (ctypes.c_int32 * 24)(*self.shape, *self.box, *self.perm, *self.sign, *self.pad_front, *self.padded_shape, *self.out_shape)
+
+    def double_params(self):
+        return (ctypes.c_double * 6)(*self.spacing, *self.pixdim)
+
+    def window_params(self):
+        return (ctypes.c_float * 5)(*self.window)
+
+
+def prefix_out_extent(extent: int, spacing: float, pixdim: float) -> int:
+    """``Spacing``'s output extent of one axis: ``int(rint((extent - 1) * (spacing / pixdim) + 1.0))`` in double, half to even."""
+    return int(np.rint(np.float64(extent - 1) * (np.float64(spacing) / np.float64(pixdim)) + 1.0))
+
+
+def plan_prefix(shape: Sequence[int], box: Sequence[int], affine=None, spacing: Optional[Sequence[float]] = None, axcodes=None,
+                pixdim: Sequence[float] = PREFIX_PIXDIM, pad_to: Optional[Sequence[int]] = None, window=PREFIX_WINDOW) -> PrefixPlan:
+    """The plan of one case, on the host alone (no device, no library).  ``shape``: raw extents; ``box``: the foreground box ``(lo0, lo1,
+    lo2, hi0, hi1, hi2)`` in raw axes, ``hi`` exclusive (``icl_prefix_box`` finds it; an empty one is the ``ValueError`` of a case without
+    foreground); the orientation either from ``affine`` (``orientation_from_affine``, which also gives the voxel sizes) or from
+    ``spacing=(s0, s1, s2)`` per SOURCE axis together with ``axcodes``; ``pixdim``: the target voxel size per RAS axis; ``pad_to``: None, or
+    the extents ``SpatialPad`` grows the oriented crop to before the respacing (validation: ``(96, 96, 96)``), ``w = max(pad_to - extent,
+    0)`` zeros per axis of which ``w // 2`` in front; ``window``: ``(a_min, a_max, b_min, b_max, clip)``."""
+    n = tuple(int(v) for v in shape)
+    if len(n) != 3 or min(n) < 1 or max(n) > 65535 or n[0] * n[1] * n[2] > 2 ** 31 - 1:
+        raise ValueError(f"plan_prefix: shape {tuple(shape)}: three extents in 1..65535 and at most 2^31 - 1 voxels expected")
+    b = tuple(int(v) for v in box)
+    if len(b) != 6:
+        raise ValueError(f"plan_prefix: box {tuple(box)}: (lo0, lo1, lo2, hi0, hi1, hi2) expected")
+    if any(b[3 + k] <= b[k] for k in range(3)):
+        raise ValueError(f"plan_prefix: empty foreground box {b}: no voxel of the volume is above 0 after the intensity window")
+    if any(b[k] < 0 or b[3 + k] > n[k] for k in range(3)):
+        raise ValueError(f"plan_prefix: box {b} outside the volume {n}")
+    if (affine is None) == (spacing is None and axcodes is None):
+        raise ValueError("plan_prefix: give either affine=, or spacing= together with axcodes=")
+    if affine is not None:
+        perm, sign, zooms = orientation_from_affine(affine)
+    else:
+        if spacing is None or axcodes is None:
+            raise ValueError("plan_prefix: spacing= and axcodes= go together")
+        perm, sign = orientation_from_axcodes(axcodes)
+        zooms = tuple(float(v) for v in spacing)
+        if len(zooms) != 3:
+            raise ValueError(f"plan_prefix: spacing {tuple(spacing)}: three voxel sizes expected")
+    p = tuple(float(v) for v in pixdim)
+    if len(p) != 3 or not all(np.isfinite(v) and v > 0 for v in zooms + p):
+        raise ValueError(f"plan_prefix: spacing {zooms} and pixdim {tuple(pixdim)} must be three finite positive values each")
+    s = tuple(zooms[perm[a]] for a in range(3))
+    e = tuple(b[3 + perm[a]] - b[perm[a]] for a in range(3))
+    if pad_to is None:
+        front, m = (0, 0, 0), e
+    else:
+        t = tuple(int(v) for v in pad_to)
+        if len(t) != 3 or min(t) < 1:
+            raise ValueError(f"plan_prefix: pad_to {tuple(pad_to)}: three positive extents expected")
+        front = tuple(max(t[a] - e[a], 0) // 2 for a in range(3))
+        m = tuple(max(t[a], e[a]) for a in range(3))
+    o = tuple(prefix_out_extent(m[a], s[a], p[a]) for a in range(3))
+    if max(m) > 65535 or min(o) < 1 or max(o) > 65535 or o[0] * o[1] * o[2] > 2 ** 31 - 1:
+        raise ValueError(f"plan_prefix: padded extents {m} -> output extents {o}: each must be in 1..65535 and the output at most 2^31 - 1 voxels")
+    consts, clip = _window_constants(window)
+    return PrefixPlan(shape=n, box=b, perm=perm, sign=sign, spacing=s, pixdim=p, pad_front=front, padded_shape=m, out_shape=o,
+                      window=consts, clip=clip)
+
+
+def _stream_of(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+
+
+def _refuse_host_memory(dev, who: str):
+    """The prefix kernels read device memory: anything but a HIP device is refused (only the tests' emulation library takes host
+    pointers), before a host address could reach a launch."""
+    if dev.type != "cuda" and not _lib.host_pointers_ok():
+        raise ValueError(f"{who}: the data must be on a HIP device, got {dev}")
+
+
+def _raw_pair(image, label, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The raw pair on the device: image fp32 [n0, n1, n2], label uint8 (host arrays through ``_as_label_u8``; a device label must be
+    uint8 already).  A leading channel axis of 1 is dropped."""
+    def squeeze(x):
+        return x[0] if x.ndim == 4 and x.shape[0] == 1 else x
+
+    if torch.is_tensor(image) and image.device.type != "cpu":
+        image_d = squeeze(image).to(device=device, dtype=torch.float32).contiguous()
+    else:
+        image_d = torch.as_tensor(np.ascontiguousarray(squeeze(_host_array(image)), dtype=np.float32)).to(device)
+    if torch.is_tensor(label) and label.device.type != "cpu":
+        if label.dtype != torch.uint8:
+            raise ValueError(f"amos_prefix: a label on the device must be uint8, got {label.dtype}")
+        label_d = squeeze(label).to(device).contiguous()
+    else:
+        label_d = torch.as_tensor(np.ascontiguousarray(_as_label_u8(squeeze(_host_array(label))))).to(device)
+    if image_d.ndim != 3 or image_d.shape != label_d.shape:
+        raise ValueError(f"amos_prefix: image {tuple(image_d.shape)} and label {tuple(label_d.shape)} must be [W,H,D] (or [1,W,H,D]) of one extent")
+    return image_d, label_d
+
+
+def amos_prefix(image, label, device=None, affine=None, spacing=None, axcodes=None, pixdim: Sequence[float] = PREFIX_PIXDIM,
+                pad_to: Optional[Sequence[int]] = None, window=PREFIX_WINDOW, out=None):
+    """The cached prefix of one case on the device: ``(image_t fp32 [o0, o1, o2], label_t uint8 [o0, o1, o2], plan)``.  ``image`` /
+    ``label``: the raw volume ``[n0, n1, n2]`` as read from the file (host arrays or tensors; the label by the rules of
+    ``amos_volume_store``) with its ``affine`` (or ``spacing`` and ``axcodes``); the other arguments are ``plan_prefix``'s.  The raw
+    pair goes up, ``icl_prefix_box`` finds the foreground box, the six integers are read back ONCE (they size the output; no foreground:
+    ``ValueError``), and one ``icl_prefix_resample`` launch writes both outputs.  ``out=(image_t, label_t)``: write into the caller's
+    contiguous tensors of exactly the planned shape.  ``device``: default the image's, if it is a device tensor, else ``cuda``."""
+    if device is None:
+        device = image.device if torch.is_tensor(image) and image.device.type != "cpu" else torch.device("cuda")
+    dev = torch.device(device)
+    _refuse_host_memory(dev, "amos_prefix")
+    image_d, label_d = _raw_pair(image, label, dev)
+    n = tuple(int(v) for v in image_d.shape)
+    if max(n) > 65535 or n[0] * n[1] * n[2] > 2 ** 31 - 1:
+        raise ValueError(f"amos_prefix: extents {n}: each must be below 65,536 and the volume at most 2^31 - 1 voxels")
+    consts, clip = _window_constants(window)
+    L = _lib.lib()
+    stream = _stream_of(dev)
+    box_d = torch.empty(6, dtype=torch.int32, device=dev)
+    ws = torch.empty(PREFIX_BOX_WS_INTS, dtype=torch.int32, device=dev)
+    _lib.check(L.icl_prefix_box(image_d.data_ptr(), *n, (ctypes.c_float * 5)(*consts), int(clip), box_d.data_ptr(), ws.data_ptr(), stream),
+               "prefix_box")
+    found = [int(v) for v in box_d.cpu()]                                   # the single read-back of a case
+    plan = plan_prefix(n, (*found[:3], *(v + 1 for v in found[3:])), affine=affine, spacing=spacing, axcodes=axcodes, pixdim=pixdim,
+                       pad_to=pad_to, window=window)
+    if out is None:
+        image_t = torch.empty(plan.out_shape, dtype=torch.float32, device=dev)
+        label_t = torch.empty(plan.out_shape, dtype=torch.uint8, device=dev)
+    else:
+        image_t, label_t = out
+        for name, t, dtype in (("image", image_t, torch.float32), ("label", label_t, torch.uint8)):
+            if not torch.is_tensor(t) or t.device.type != dev.type or t.dtype != dtype or tuple(t.shape) != plan.out_shape or not t.is_contiguous():
+                raise ValueError(f"amos_prefix: out {name} must be a contiguous {dtype} tensor of shape {plan.out_shape} on {dev}")
+    _lib.check(L.icl_prefix_resample(image_d.data_ptr(), label_d.data_ptr(), plan.int_params(), plan.double_params(), plan.window_params(),
+                                     int(plan.clip), image_t.data_ptr(), label_t.data_ptr(), stream), "prefix_resample")
+    return image_t, label_t, plan
+
+
+def _case_fields(case) -> tuple:
+    """``(image, label, orientation keywords)`` of one raw case: a dictionary with ``image``, ``label`` and ``affine`` (or ``spacing`` and
+    ``axcodes``), or an ``(image, label, affine)`` triple."""
+    if isinstance(case, dict):
+        how = {k: case[k] for k in ("affine", "spacing", "axcodes") if case.get(k) is not None}
+        return case["image"], case["label"], how
+    if len(case) != 3:
+        raise ValueError("a raw case is a dictionary with image, label and affine (or spacing and axcodes), or an (image, label, affine) triple")
+    return case[0], case[1], {"affine": case[2]}
+
+
+def amos_volume_store_from_raw(cases: Iterable, device, pixdim: Sequence[float] = PREFIX_PIXDIM, window=PREFIX_WINDOW):
+    """``(store, plans)``: the ``DeviceVolumeStore`` of the training set from RAW cases, what ``CacheDataset`` caches for the AMOS trainer
+    (``:86-101``), computed by ``amos_prefix``: the preprocessed volumes never visit the host.  ``cases``: see ``_case_fields``."""
+    images, labels, plans = [], [], []
+    for case in cases:
+        image, label, how = _case_fields(case)
+        image_t, label_t, plan = amos_prefix(image, label, device, pixdim=pixdim, window=window, **how)
+        images.append(image_t)
+        labels.append(label_t)
+        plans.append(plan)
+    return DeviceVolumeStore.from_device_tensors(images, labels, device), plans
+
+
+def amos_val_cases_from_raw(cases: Iterable, device, pad_to: Optional[Sequence[int]] = (96, 96, 96), pixdim: Sequence[float] = PREFIX_PIXDIM,
+                            window=PREFIX_WINDOW):
+    """``(items, plans)``: the validation chain (``:141-154``: the prefix with ``SpatialPadd(96^3)`` before ``Spacingd``) of RAW cases as
+    the items ``val_3D.test_all_case_amos`` iterates, ``{'image': [1,1,o0,o1,o2] fp32, 'label': [1,1,o0,o1,o2] uint8}`` on the device
+    (batch and channel axes as MONAI's loader of batch size 1 gives them), and the plans ``restore_label`` needs."""
+    items, plans = [], []
+    for case in cases:
+        image, label, how = _case_fields(case)
+        image_t, label_t, plan = amos_prefix(image, label, device, pixdim=pixdim, pad_to=pad_to, window=window, **how)
+        items.append({"image": image_t[None, None], "label": label_t[None, None]})
+        plans.append(plan)
+    return items, plans
+
+
+def restore_label(prediction, plan: PrefixPlan) -> torch.Tensor:
+    """A label map on the respaced grid back on the scanner's: what MONAI's ``Invertd`` does to a prediction.  ``prediction``: a uint8
+    or int64 tensor of ``plan.out_shape`` (leading axes of 1 are dropped; of an int64 value the low byte is kept) on a HIP device; a host array or CPU tensor is a ``ValueError``.  Returns uint8 ``plan.shape``: 0
+    outside the foreground box, inside it the prediction at ``rint(min(max(u * (s / p), 0), o - 1))`` per oriented axis."""
+    pred = prediction if torch.is_tensor(prediction) else torch.as_tensor(np.ascontiguousarray(prediction))
+    pred = pred.reshape(pred.shape[-3:]) if pred.ndim > 3 and all(v == 1 for v in pred.shape[:-3]) else pred
+    if tuple(pred.shape) != plan.out_shape or pred.dtype not in (torch.uint8, torch.int64):
+        raise ValueError(f"restore_label: a uint8 or int64 prediction of shape {plan.out_shape} expected, got {tuple(pred.shape)} {pred.dtype}")
+    pred = pred.contiguous()
+    dev = pred.device
+    _refuse_host_memory(dev, "restore_label")
+    out = torch.empty(plan.shape, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().icl_prefix_restore(pred.data_ptr(), 0 if pred.dtype == torch.uint8 else 1, plan.int_params(), plan.double_params(),
+                                             out.data_ptr(), _stream_of(dev)), "prefix_restore")
+    return out

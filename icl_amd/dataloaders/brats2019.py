@@ -154,6 +154,23 @@ class DeviceVolumeStore:
     def from_dataset(cls, dataset: BraTS2019, device):
         return cls([dataset.read_case(i) for i in range(len(dataset))], device)
 
+    @classmethod
+    def from_device_tensors(cls, images: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], device):
+        """Adopts volumes that are on ``device`` already (``amos_volume_store_from_raw``): contiguous fp32 ``[W,H,D]`` images and uint8
+        labels of the same extents.  Nothing is copied."""
+        store = cls([], device)
+        if len(images) != len(labels):
+            raise ValueError("one label per image")
+        for image, label in zip(images, labels):
+            ok = (torch.is_tensor(image) and torch.is_tensor(label) and image.ndim == 3 and image.shape == label.shape
+                  and image.dtype == torch.float32 and label.dtype == torch.uint8 and image.is_contiguous() and label.is_contiguous()
+                  and image.device.type == store.device.type and label.device == image.device)
+            if not ok:
+                raise ValueError(f"a volume is a contiguous (image fp32 [W,H,D], label uint8 [W,H,D]) pair of tensors on {store.device}")
+            store.images.append(image)
+            store.labels.append(label)
+        return store
+
     def __len__(self):
         return len(self.images)
 

@@ -519,6 +519,31 @@ int icl_rank_select(const void* const* images, const void* const* labels, const 
 int icl_volume_feed_origins(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params,
                             int batch, const int32_t* origins, float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream);
 
+/* ---- the CACHED prefix of the AMOS trainer (train_inherent_consistent_unet_3D_AMOS22.py:86-101, validation :141-154):
+ * ScaleIntensityRanged -> CropForegroundd -> Orientationd("RAS") -> [SpatialPadd] -> Spacingd(bilinear / nearest, border), and its inverse
+ * for label maps (csrc/kernels/prefix.h; the definition is in DESIGN.md "AMOS cached prefix").  A case is planned on the host
+ * (icl_amd.dataloaders.amos.plan_prefix) and handed over as
+ *   int_params:    HOST int32 [24] = {raw extents n[3], box lo[3], box hi[3] (exclusive, raw axes), perm[3] (oriented axis a is raw axis
+ *                  perm[a]), sign[3] (1, or -1: reversed), pad front f[3], padded extents m[3], output extents o[3]}, the last four per
+ *                  ORIENTED axis;
+ *   double_params: HOST double [6] = {source spacing s[3], target spacing p[3]} per oriented axis;
+ *   window:        HOST fp32 [5] = {a_min, fp32(a_max - a_min), b_min, fp32(b_max - b_min), b_max}; clip: clamp into [b_min, b_max].
+ * Both plan-taking functions return -1, launching nothing, for a null pointer, a raw extent outside 1..65535 or more than 2^31 - 1 raw
+ * or output voxels, a perm that is no permutation, a sign other than 1 / -1, a non-finite or non-positive spacing, a box that is empty or
+ * outside the volume, f < 0 or f + (box extent) > m, or an output extent other than rint((m - 1) * (s / p) + 1) (half to even). */
+/* The foreground box: the smallest box holding every voxel whose windowed value is > 0.  image: DEVICE fp32 [n0,n1,n2]; box: DEVICE
+ * int32 [6] = {lo0, lo1, lo2, hi0, hi1, hi2}, hi INCLUSIVE ({INT_MAX x 3, -1 x 3} when no voxel qualifies); ws: DEVICE int32
+ * [6 * 1024] of scratch.  Two launches, integer min / max in a fixed order, no atomics. */
+int icl_prefix_box(const float* image, int n0, int n1, int n2, const float* window, int clip, int32_t* box, int32_t* ws, void* stream);
+/* One launch writes image_out fp32 [o0,o1,o2] and label_out uint8 [o0,o1,o2] from the raw DEVICE arrays image fp32 / label uint8
+ * [n0,n1,n2]: fp64 coordinates, eight windowed taps summed in a fixed order in double and rounded once; label at rint(x). */
+int icl_prefix_resample(const float* image, const uint8_t* label, const int32_t* int_params, const double* double_params, const float* window,
+                        int clip, float* image_out, uint8_t* label_out, void* stream);
+/* The inverse for a label map on the respaced grid: prediction DEVICE [o0,o1,o2], elem_kind 0 = uint8, 1 = int64 (the low byte is kept);
+ * out DEVICE uint8 [n0,n1,n2]: 0 outside the box, inside the prediction at rint(min(max(u * (s / p), 0), o - 1)) per oriented axis. */
+int icl_prefix_restore(const void* prediction, int elem_kind, const int32_t* int_params, const double* double_params, uint8_t* out,
+                       void* stream);
+
 /* ---- on-device RandomGenerator of the 2-D trainers (dataloaders/dataset.py:147-166; composed at
  * train_inherent_consistent_unet_2D.py:75 and ..._swinunet_2D.py): "maybe rot90 + flip, else maybe ndimage.rotate by an integer
  * angle, then ndimage.zoom to the patch", all order 0, as ONE gather over slices resident in HBM, bit for bit scipy's result.

@@ -123,6 +123,8 @@ _SIGNATURES = {
     "icl_rank_index_build": (c_int, [P, P, I, I, I, F, P, P, P]),
     "icl_rank_select": (c_int, [P, P, P, P, P, F, I, P, P]),
     "icl_volume_feed_origins": (c_int, [P, P, P, P, I, P, P, P, I, I, I, P]),
+    "icl_volume_feed_affine": (c_int, [P, P, P, P, P, I, P, P, I, I, I, P]),
+    "icl_volume_feed_affine_origins": (c_int, [P, P, P, P, P, I, P, P, P, I, I, I, P]),
     "icl_prefix_box": (c_int, [P, I, I, I, P, I, P, P, P]),
     "icl_prefix_resample": (c_int, [P, P, P, P, P, I, P, P, P]),
     "icl_prefix_restore": (c_int, [P, I, P, P, P, P]),

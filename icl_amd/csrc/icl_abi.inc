@@ -2485,6 +2485,73 @@ int icl_volume_feed_origins(const void* const* images, const void* const* labels
   return check_launch("volume_feed_origins");
 }
 
+namespace {
+
+// The records of icl_volume_feed_affine / icl_volume_feed_affine_origins: volume_feed_records' rows and checks, then the affine rows.
+int volume_feed_affine_records(const char* what, const void* const* images, const void* const* labels, const int32_t* int_params,
+                               const float* float_params, const double* affine_params, int batch, int R0, int R1, int R2, bool device_origins,
+                               icl::VolumeFeedAffineBatch& ab) {
+  if (!affine_params) return fail(-1, "%s: affine_params is a null pointer", what);
+  icl::VolumeFeedBatch fb{};
+  if (const int rc = volume_feed_records(what, images, labels, int_params, float_params, batch, R0, R1, R2, device_origins, fb)) return rc;
+  for (int b = 0; b < batch; ++b) {
+    const double* q = affine_params + 10 * b;      // flag, M row-major
+    icl::VolumeFeedAffineSample& s = ab.s[b];
+    s.f = fb.s[b];
+    s.n0 = int_params[14 * b];
+    if (!(q[0] == 0.0 || q[0] == 1.0)) return fail(-1, "%s: sample %d: affine flag %g (must be 0 or 1)", what, b, q[0]);
+    s.affine = q[0] == 1.0 ? 1 : 0;
+    for (int e = 0; e < 9; ++e) {
+      const double m = q[1 + e];
+      if (!std::isfinite(m)) return fail(-1, "%s: sample %d: affine matrix entry M[%d][%d] = %g is not finite", what, b, e / 3, e % 3, m);
+      if (std::fabs(m) > 16.0)
+        return fail(-1, "%s: sample %d: affine matrix entry M[%d][%d] = %g outside [-16, 16]", what, b, e / 3, e % 3, m);
+      s.m[e] = m;
+    }
+  }
+  return 0;
+}
+
+}  // namespace
+
+int icl_volume_feed_affine(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params,
+                           const double* affine_params, int batch, float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream) {
+  if (!images || !labels || !int_params || !float_params || !image_out || !label_out) return fail(-1, "volume_feed_affine: null pointer");
+  icl::VolumeFeedAffineBatch ab{};
+  if (const int rc = volume_feed_affine_records("volume_feed_affine", images, labels, int_params, float_params, affine_params, batch, R0, R1,
+                                                R2, false, ab))
+    return rc;
+  const long voxels = (long)R0 * R1 * R2;      // per sample; one grid row per sample
+  if ((R2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
+    ICL_LAUNCH((icl::volume_feed_affine_kernel<4, false>), dim3(grid_for(voxels / 4, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, ab,
+               (const int*)nullptr, image_out, (long long*)label_out, R0, R1, R2);
+  } else {
+    ICL_LAUNCH((icl::volume_feed_affine_kernel<1, false>), dim3(grid_for(voxels, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, ab,
+               (const int*)nullptr, image_out, (long long*)label_out, R0, R1, R2);
+  }
+  return check_launch("volume_feed_affine");
+}
+
+int icl_volume_feed_affine_origins(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params,
+                                   const double* affine_params, int batch, const int32_t* origins, float* image_out, int64_t* label_out,
+                                   int R0, int R1, int R2, void* stream) {
+  if (!images || !labels || !int_params || !float_params || !origins || !image_out || !label_out)
+    return fail(-1, "volume_feed_affine_origins: null pointer");
+  icl::VolumeFeedAffineBatch ab{};
+  if (const int rc = volume_feed_affine_records("volume_feed_affine_origins", images, labels, int_params, float_params, affine_params, batch,
+                                                R0, R1, R2, true, ab))
+    return rc;
+  const long voxels = (long)R0 * R1 * R2;
+  if ((R2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
+    ICL_LAUNCH((icl::volume_feed_affine_kernel<4, true>), dim3(grid_for(voxels / 4, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, ab,
+               (const int*)origins, image_out, (long long*)label_out, R0, R1, R2);
+  } else {
+    ICL_LAUNCH((icl::volume_feed_affine_kernel<1, true>), dim3(grid_for(voxels, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, ab,
+               (const int*)origins, image_out, (long long*)label_out, R0, R1, R2);
+  }
+  return check_launch("volume_feed_affine_origins");
+}
+
 int icl_rank_tile(void) { return icl::kRankTile; }
 
 int icl_rank_index_build(const float* image, const uint8_t* label, int n0, int n1, int n2, float threshold, uint32_t* fg_index,

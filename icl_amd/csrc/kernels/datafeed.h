@@ -260,4 +260,166 @@ __global__ __launch_bounds__(256) void volume_feed_kernel(VolumeFeedBatch fb, co
   }
 }
 
+// ---- the same chain with an AFFINE stage between the pad and the flips (MONAI RandAffined, nnU-Net's rotation and scaling):
+// crop -> symmetric pad -> affine about the patch centre -> flips -> rot90 -> intensity.  The definition is in DESIGN.md §2 "Affine
+// stage of the 3-D feed"; tests/affine_feed_ref.py restates it in numpy.  A sample either has the stage (`affine` = 1) or it does not:
+// without it the sample takes the integer gather of volume_feed_kernel, bit for bit.  With it, the output voxel is mapped back through
+// rot90 and the flips to integer patch coordinates p as above, and then, every fp64 product and sum rounded on its own,
+//   u_a = p_a - (R_a - 1) / 2,  t_a = (c_a - l_a) + (R_a - 1) / 2                (both exact),
+//   x_a = t_a + ((M_a0 u_0 + M_a1 u_1) + M_a2 u_2)                               (a coordinate of the WHOLE volume, not of the crop),
+//   image: i_a = floor(x_a), f_a = x_a - i_a; the eight taps in the order (0,0,0), (0,0,1), ..., (1,1,1), a tap outside [0, n_a - 1]
+//          on any axis counting as 0; sum of double(tap) * ((w_0 w_1) w_2), w_a = f_a for bit 1 and 1 - f_a for bit 0, left to right
+//          in double, rounded once to fp32; then fp32(fp32(v * mul) + add);
+//   label: the voxel at rint(x_a) per axis (half to even); 0 when a rounded index is outside [0, n_a - 1].
+// Every range test is made on the DOUBLE, before any conversion to int, so no M and no content of `origins` can send a read outside
+// the volume (the launcher bounds |M_ab| by 16 all the same, which keeps |x| far below 2^31).
+struct VolumeFeedAffineSample {
+  VolumeFeedSample f;        // as for volume_feed_kernel
+  int n0;                    // source extent of axis 0: the affine gather reads the whole volume
+  int affine;                // 1: the sample has the affine stage; 0: m is not read
+  double m[9];               // M, row-major
+};
+
+struct VolumeFeedAffineBatch {
+  VolumeFeedAffineSample s[kFeedMaxBatch];     // 160 B a record: 2,560 B of the 4 KB kernel-argument block
+};
+
+// one axis of one voxel: the two image taps i0, i0 + 1 with their weights, and the label's index
+struct AffineAxis {
+  double w0, w1;             // 1 - f, f
+  int i0;                    // floor(x) where one of the taps is inside, else 0 (and both flags are false)
+  int nn;                    // rint(x), or -1 outside [0, n - 1]
+  bool in0, in1;             // tap i0 / i0 + 1 lies in [0, n - 1]
+};
+
+__device__ __forceinline__ AffineAxis affine_axis(double x, int n) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double top = (double)(n - 1);
+  const double fl = floor(x);
+  const double f = x - fl;
+  AffineAxis a;
+  a.in0 = fl >= 0.0 && fl <= top;                    // on the double: a NaN or a huge x fails both
+  a.in1 = fl >= -1.0 && fl <= top - 1.0;
+  a.i0 = (a.in0 || a.in1) ? (int)fl : 0;             // -1 .. n - 1
+  a.w0 = 1.0 - f;
+  a.w1 = f;
+  const double rn = rint(x);                         // half to even
+  a.nn = (rn >= 0.0 && rn <= top) ? (int)rn : -1;
+  return a;
+}
+
+// Arguments, grid and stores of volume_feed_kernel<V, DEV>; one sample per blockIdx.y, so `affine` is wave-uniform.  An affine sample
+// takes one thread per V consecutive OUTPUT depth voxels as well: every voxel's coordinates come from the definition (the part of x_a
+// that the V voxels share, M_a0 u_0 + M_a1 u_1, is the same value for each of them), eight fp32 tap loads and one label load a voxel.
+// DEV = true: t_a is formed on the device from the clamped origin.  No LDS, no atomics.
+template <int V, bool DEV>
+__global__ __launch_bounds__(256) void volume_feed_affine_kernel(VolumeFeedAffineBatch fb, const int* __restrict__ origins,
+                                                                 float* __restrict__ image_out, long long* __restrict__ label_out, int R0, int R1,
+                                                                 int R2) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  static_assert(V == 1 || V == 4, "one voxel or one quad per thread");
+  const int q2 = R2 / V;
+  const unsigned per = (unsigned)R0 * R1 * q2;                                // the launcher keeps R0 * R1 * R2 below 2^31
+  const int b = blockIdx.y;
+  const VolumeFeedAffineSample& rec = fb.s[b];
+  const VolumeFeedSample& s = rec.f;
+  int c0 = s.c0, c1 = s.c1, c2 = s.c2;
+  if constexpr (DEV) {
+    const int* __restrict__ o = origins + 3 * b;
+    c0 = o[0] < 0 ? 0 : (o[0] > s.c0 ? s.c0 : o[0]);
+    c1 = o[1] < 0 ? 0 : (o[1] > s.c1 ? s.c1 : o[1]);
+    c2 = o[2] < 0 ? 0 : (o[2] > s.c2 ? s.c2 : o[2]);
+  }
+  const bool affine = rec.affine != 0;
+  const double h0 = (double)(R0 - 1) * 0.5, h1 = (double)(R1 - 1) * 0.5, h2 = (double)(R2 - 1) * 0.5;
+  const double t0 = (double)(c0 - s.l0) + h0, t1 = (double)(c1 - s.l1) + h1, t2 = (double)(c2 - s.l2) + h2;
+  const bool rev = (s.flip & 4) != 0;
+  for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < per; r += gridDim.x * blockDim.x) {
+    const long e = (long)b * per + r;
+    const int l = (int)(r % q2) * V;
+    const unsigned rj = r / q2;
+    const int j = (int)(rj % R1), i = (int)(rj / R1);
+    int fa, fc;                                                               // rot90 and the flips of axes 0, 1, as in volume_feed_kernel
+    switch (s.k & 3) {
+      case 0: fa = i; fc = j; break;
+      case 1: fa = j; fc = R1 - 1 - i; break;
+      case 2: fa = R0 - 1 - i; fc = R1 - 1 - j; break;
+      default: fa = R0 - 1 - j; fc = i; break;
+    }
+    if (s.flip & 1) fa = R0 - 1 - fa;
+    if (s.flip & 2) fc = R1 - 1 - fc;
+    float v[V];
+    unsigned lab[V];
+    if (!affine) {                                                            // the integer gather of volume_feed_kernel
+      const int a = fa - s.l0, c = fc - s.l1;
+      const int d0 = (rev ? R2 - 1 - l : l) - s.l2, step = rev ? -1 : 1;
+      const bool row = a >= 0 && a < s.s0 && c >= 0 && c < s.s1;
+      const long base = row ? ((long)(c0 + a) * s.n1 + (c1 + c)) * s.n2 + c2 : 0;
+#pragma unroll
+      for (int t = 0; t < V; ++t) {
+        const int d = d0 + t * step;
+        float x = 0.f;
+        lab[t] = 0u;
+        if (row && d >= 0 && d < s.s2) {
+          x = s.image[base + d];
+          lab[t] = s.label[base + d];
+        }
+        const float m = x * s.mul;
+        v[t] = m + s.add;
+      }
+    } else {
+      const double u0 = (double)fa - h0, u1 = (double)fc - h1;
+      const double g0 = rec.m[0] * u0 + rec.m[1] * u1;                         // two products and a sum, each rounded (contraction off)
+      const double g1 = rec.m[3] * u0 + rec.m[4] * u1;
+      const double g2 = rec.m[6] * u0 + rec.m[7] * u1;
+#pragma unroll
+      for (int t = 0; t < V; ++t) {
+        const int p2 = rev ? R2 - 1 - (l + t) : l + t;
+        const double u2 = (double)p2 - h2;
+        const AffineAxis a0 = affine_axis(t0 + (g0 + rec.m[2] * u2), rec.n0);
+        const AffineAxis a1 = affine_axis(t1 + (g1 + rec.m[5] * u2), s.n1);
+        const AffineAxis a2 = affine_axis(t2 + (g2 + rec.m[8] * u2), s.n2);
+        const long r00 = ((long)a0.i0 * s.n1 + a1.i0) * s.n2 + a2.i0;          // tap (0,0,0); read only where its flags allow
+        const long d0s = (long)s.n1 * s.n2, d1s = s.n2;
+        const bool k00 = a0.in0 && a1.in0, k01 = a0.in0 && a1.in1, k10 = a0.in1 && a1.in0, k11 = a0.in1 && a1.in1;
+        const double x000 = k00 && a2.in0 ? (double)s.image[r00] : 0.0;
+        const double x001 = k00 && a2.in1 ? (double)s.image[r00 + 1] : 0.0;
+        const double x010 = k01 && a2.in0 ? (double)s.image[r00 + d1s] : 0.0;
+        const double x011 = k01 && a2.in1 ? (double)s.image[r00 + d1s + 1] : 0.0;
+        const double x100 = k10 && a2.in0 ? (double)s.image[r00 + d0s] : 0.0;
+        const double x101 = k10 && a2.in1 ? (double)s.image[r00 + d0s + 1] : 0.0;
+        const double x110 = k11 && a2.in0 ? (double)s.image[r00 + d0s + d1s] : 0.0;
+        const double x111 = k11 && a2.in1 ? (double)s.image[r00 + d0s + d1s + 1] : 0.0;
+        const double w00 = a0.w0 * a1.w0, w01 = a0.w0 * a1.w1, w10 = a0.w1 * a1.w0, w11 = a0.w1 * a1.w1;
+        double acc = x000 * (w00 * a2.w0);
+        acc = acc + x001 * (w00 * a2.w1);
+        acc = acc + x010 * (w01 * a2.w0);
+        acc = acc + x011 * (w01 * a2.w1);
+        acc = acc + x100 * (w10 * a2.w0);
+        acc = acc + x101 * (w10 * a2.w1);
+        acc = acc + x110 * (w11 * a2.w0);
+        acc = acc + x111 * (w11 * a2.w1);
+        const float x = (float)acc;
+        const float m = x * s.mul;
+        v[t] = m + s.add;
+        lab[t] = 0u;
+        if (a0.nn >= 0 && a1.nn >= 0 && a2.nn >= 0) lab[t] = s.label[((long)a0.nn * s.n1 + a1.nn) * s.n2 + a2.nn];
+      }
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(image_out + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
+      uint4* lp = reinterpret_cast<uint4*>(label_out + e * 4);                 // labels are 0..255: the high dwords are 0
+      lp[0] = make_uint4(lab[0], 0u, lab[1], 0u);
+      lp[1] = make_uint4(lab[2], 0u, lab[3], 0u);
+    } else {
+      image_out[e] = v[0];
+      label_out[e] = (long long)lab[0];
+    }
+  }
+}
+
 }  // namespace icl

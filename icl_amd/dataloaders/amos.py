@@ -27,6 +27,13 @@ vector of MONAI's output exists.  What the tests pin is the kernel against a num
 (``tests/amos_feed_ref.py``) and the order and number of the random draws documented at ``draw_amos_params``.  MONAI gives every
 transform a generator of its own; here one generator serves all of them, so the batches are distributed like MONAI's, not equal to them.
 
+**Random rotation and zoom** (MONAI ``RandAffined``, nnU-Net's rotation and scaling; off by default: ``affine_prob=0``).  Both feeds
+take an affine stage between the pad and the flips: the host draws three angles and one or three zooms, ``affine_matrix`` forms the 3x3
+``M`` in double, and ``volume_feed_affine_kernel`` (``icl_volume_feed_affine`` / ``icl_volume_feed_affine_origins``) interpolates the
+image trilinearly and takes the label's nearest voxel, about the patch centre, from the WHOLE volume (zeros only outside it).  The
+definition is in DESIGN.md §2 "Affine stage of the 3-D feed"; ``tests/affine_feed_ref.py`` restates it in numpy, which the emulated
+kernel and the GPU equal bit for bit.  MONAI's ``RandAffine`` samples the cropped patch, this gather samples the volume: unpinned too.
+
 **Foreground-balanced crops** (``utils/data_utils.py:84-99``, ``get_loader``: ``RandCropByPosNegLabeld(pos=1, neg=1, num_samples=4,
 image_threshold=0)``, the crop of every MONAI recipe for AMOS or BTCV).  MONAI keeps two int64 index lists per cached volume on the host.
 Here ``ForegroundIndex`` builds a rank index per volume on the device (``csrc/kernels/rankindex.h``: one prefix count per 1,024 voxels
@@ -52,13 +59,18 @@ FEED_MAX_BATCH = 16         # icl_volume_feed takes up to 16 samples per launch 
 
 def draw_amos_params(shape: Sequence[int], roi: Sequence[int], rng=np.random, flip_prob: float = 0.10, rot_prob: float = 0.10,
                      max_k: int = 3, shift_offset: float = 0.10, shift_prob: float = 0.50, scale_factor: float = 0.0,
-                     scale_prob: float = 0.0) -> tuple:
+                     scale_prob: float = 0.0, affine_prob: float = 0.0, rotate_range=(0, 0, 0), zoom_range=(1.0, 1.0),
+                     zoom_isotropic: bool = True) -> tuple:
     """The random draws of the AMOS trainer's transforms (``:102-133``) for one volume of ``shape``, from ``rng`` (``np.random`` or a
     ``RandomState``), in this fixed order:
 
     1. crop (``RandSpatialCrop``, ``random_size=False``): the size is ``s = min(roi, n)`` per axis; per axis, in order,
        ``origin = rng.randint(0, n - s + 1)`` ONLY IF ``n > s``, otherwise the origin is 0 and nothing is drawn;
     2. pad (``SpatialPad``, symmetric): ``w = roi - s``, ``w // 2`` on the left, the rest on the right; nothing is drawn;
+    2a. affine (rotation and zoom about the patch centre, off by default): with ``affine_prob == 0`` nothing is drawn at all; otherwise
+       ``rng.rand() < affine_prob`` and, only if true, ``theta_a = rng.uniform(-r_a, r_a)`` for a = 0, 1, 2 (always three draws;
+       ``rotate_range`` in radians, one number meaning all three axes), then ONE ``z = rng.uniform(lo, hi)`` of ``zoom_range`` when
+       ``zoom_isotropic``, or three when not; the sample's matrix is ``affine_matrix(theta, z)``;
     3. flips: for axis 0, 1, 2 in turn, ``rng.rand() < flip_prob``;
     4. rotation: ``rng.rand() < rot_prob``; ONLY IF true, ``k = rng.randint(max_k) + 1`` (otherwise ``k = 0``);
     5. scale (``RandScaleIntensity``; off by default — the AMOS trainer has none, ``utils/data_utils.py:98`` has one): with
@@ -67,7 +79,9 @@ def draw_amos_params(shape: Sequence[int], roi: Sequence[int], rng=np.random, fl
     6. shift (``RandShiftIntensity``): ``rng.rand() < shift_prob``; ONLY IF true, ``add = float32(rng.uniform(-o, o))``.
 
     Returns one ``icl_volume_feed`` parameter row: 14 integers ``(n0, n1, n2, c0, c1, c2, s0, s1, s2, l0, l1, l2, flip mask, k)``
-    followed by the two floats ``(mul, add)``."""
+    followed by the two floats ``(mul, add)``: 16 values.  A sample that drew an affine carries the nine entries of ``M``, row-major,
+    behind them: 25 values."""
+    affine = _affine_arguments(affine_prob, rotate_range, zoom_range, zoom_isotropic)
     n = [int(v) for v in shape]
     r = [int(v) for v in roi]
     if len(n) != 3 or len(r) != 3 or min(n) < 1 or min(r) < 1:
@@ -75,7 +89,81 @@ def draw_amos_params(shape: Sequence[int], roi: Sequence[int], rng=np.random, fl
     size = [min(r[a], n[a]) for a in range(3)]
     origin = [int(rng.randint(0, n[a] - size[a] + 1)) if n[a] > size[a] else 0 for a in range(3)]
     left = [(r[a] - size[a]) // 2 for a in range(3)]
-    return (*n, *origin, *size, *left, *_draw_tail(rng, flip_prob, rot_prob, max_k, shift_offset, shift_prob, scale_factor, scale_prob))
+    matrix = _draw_affine(rng, *affine)
+    return (*n, *origin, *size, *left, *_draw_tail(rng, flip_prob, rot_prob, max_k, shift_offset, shift_prob, scale_factor, scale_prob), *matrix)
+
+
+AFFINE_MAX_ENTRY = 16.0     # icl_volume_feed_affine refuses |M_ab| above this: |x| then stays far below 2^31 for every legal extent
+
+
+def affine_matrix(theta: Sequence[float], zoom) -> np.ndarray:
+    """``M = R_0(theta_0) @ R_1(theta_1) @ R_2(theta_2) @ diag(1 / z_0, 1 / z_1, 1 / z_2)`` in double: the 3x3 matrix that takes an
+    OUTPUT offset from the patch centre to the SOURCE offset the affine stage samples.  ``R_a`` is the right-handed rotation about patch
+    axis ``a`` (radians); ``zoom``: one number or three, ``z > 1`` magnifies the content."""
+    t = np.asarray(theta, dtype=np.float64).reshape(-1)
+    z = np.asarray(zoom, dtype=np.float64).reshape(-1)
+    if z.size == 1:
+        z = np.repeat(z, 3)
+    if t.size != 3 or z.size != 3 or not np.isfinite(t).all() or not np.isfinite(z).all() or (z <= 0).any():
+        raise ValueError(f"affine_matrix: three finite angles and one or three finite positive zooms expected, got {theta!r} and {zoom!r}")
+    c, s = np.cos(t), np.sin(t)
+    r0 = np.array([[1.0, 0.0, 0.0], [0.0, c[0], -s[0]], [0.0, s[0], c[0]]])
+    r1 = np.array([[c[1], 0.0, s[1]], [0.0, 1.0, 0.0], [-s[1], 0.0, c[1]]])
+    r2 = np.array([[c[2], -s[2], 0.0], [s[2], c[2], 0.0], [0.0, 0.0, 1.0]])
+    return r0 @ r1 @ r2 @ np.diag(1.0 / z)
+
+
+def _affine_arguments(affine_prob: float = 0.0, rotate_range=(0, 0, 0), zoom_range=(1.0, 1.0), zoom_isotropic: bool = True) -> tuple:
+    """The affine keywords of ``draw_amos_params``, checked and in ``_draw_affine``'s order: the probability in [0, 1], three
+    non-negative finite angles (one number means all three axes), ``0 < lo <= hi`` finite."""
+    prob = float(affine_prob)
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"affine_prob {affine_prob!r} must be in [0, 1]")
+    r = np.asarray(rotate_range, dtype=np.float64).reshape(-1)
+    if r.size == 1:
+        r = np.repeat(r, 3)
+    if r.size != 3 or not np.isfinite(r).all() or (r < 0).any():
+        raise ValueError(f"rotate_range {rotate_range!r} must be one or three non-negative finite angles (radians)")
+    z = np.asarray(zoom_range, dtype=np.float64).reshape(-1)
+    if z.size != 2 or not np.isfinite(z).all() or not 0.0 < z[0] <= z[1]:
+        raise ValueError(f"zoom_range {zoom_range!r} must be (lo, hi) with 0 < lo <= hi")
+    return prob, tuple(float(v) for v in r), (float(z[0]), float(z[1])), bool(zoom_isotropic)
+
+
+def _draw_affine(rng, prob, rotate, zoom, isotropic) -> tuple:
+    """Step 2a of ``draw_amos_params``: ``()`` for a sample without an affine, else the nine entries of ``M``, row-major."""
+    if prob == 0 or not rng.rand() < prob:
+        return ()
+    theta = [rng.uniform(-rotate[a], rotate[a]) for a in range(3)]
+    z = [rng.uniform(zoom[0], zoom[1]) for _ in range(1 if isotropic else 3)]
+    return tuple(float(v) for v in affine_matrix(theta, z).reshape(-1))
+
+
+def _affine_suffixes(who: str, params, base: int, expected: str) -> List[tuple]:
+    """The affine suffix of every row, ``()`` or nine floats: a row has ``base`` values, or ``base + 9`` with a finite ``M`` whose
+    entries are at most ``AFFINE_MAX_ENTRY`` in magnitude; anything else is a ``ValueError`` (``expected``: what the rows should be)."""
+    out = []
+    for j, row in enumerate(params):
+        if len(row) == base:
+            out.append(())
+            continue
+        if len(row) != base + 9:
+            raise ValueError(f"{who}: {expected} ({base + 9} with an affine matrix); row {j} has {len(row)}")
+        m = tuple(float(v) for v in row[base:])
+        for e, v in enumerate(m):
+            if not np.isfinite(v) or abs(v) > AFFINE_MAX_ENTRY:
+                raise ValueError(f"{who}: parameter row {j}: affine matrix entry M[{e // 3}][{e % 3}] = {v} must be finite and at most "
+                                 f"{AFFINE_MAX_ENTRY:g} in magnitude")
+        out.append(m)
+    return out
+
+
+def _affine_block(suffixes: Sequence[tuple]):
+    """``affine_params`` of one launch, ``[m][10]`` doubles = {flag, M row-major}, or None when no sample of it has an affine."""
+    if not any(suffixes):
+        return None
+    flat = [v for m in suffixes for v in ((1.0, *m) if m else (0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0))]
+    return (ctypes.c_double * len(flat))(*flat)
 
 
 def _draw_tail(rng, flip_prob, rot_prob, max_k, shift_offset, shift_prob, scale_factor, scale_prob) -> tuple:
@@ -143,7 +231,9 @@ class OnDeviceAugmentAMOS:
     already and the ``.long()`` calls are no-ops.
 
     The keyword arguments are those of ``draw_amos_params`` (``flip_prob``, ``rot_prob``, ``max_k``, ``shift_offset``, ``shift_prob``,
-    ``scale_factor``, ``scale_prob``) plus ``rng`` (default: numpy's global generator)."""
+    ``scale_factor``, ``scale_prob``, and the affine stage's ``affine_prob``, ``rotate_range``, ``zoom_range``, ``zoom_isotropic``, which
+    are checked here) plus ``rng`` (default: numpy's global generator).  With ``affine_prob=0`` (the default) nothing is drawn for
+    the stage and ``batch`` launches what it launched before the stage existed."""
 
     def __init__(self, store: DeviceVolumeStore, roi: Sequence[int] = (96, 96, 96), rng=np.random, **probabilities):
         self.store = store
@@ -188,8 +278,9 @@ class OnDeviceAugmentAMOS:
             raise ValueError("OnDeviceAugmentAMOS.batch: no indices")
         if params is None:
             params = self.draw(indices)
-        if len(params) != n or any(len(row) != 16 for row in params):
+        if len(params) != n:
             raise ValueError("OnDeviceAugmentAMOS.batch: one parameter row of 16 values per index")
+        suffixes = _affine_suffixes("OnDeviceAugmentAMOS.batch", params, 16, "one parameter row of 16 values per index")
         for i, row in zip(indices, params):
             if tuple(int(v) for v in row[:3]) != tuple(st.images[i].shape):
                 raise ValueError(f"OnDeviceAugmentAMOS.batch: parameter row for extents {tuple(row[:3])}, volume {i} is {tuple(st.images[i].shape)}")
@@ -206,10 +297,15 @@ class OnDeviceAugmentAMOS:
             m = len(chunk)
             ptrs = ctypes.c_void_p * m
             ints = (ctypes.c_int32 * (14 * m))(*[int(v) for row in params[lo:lo + m] for v in row[:14]])
-            floats = (ctypes.c_float * (2 * m))(*[float(v) for row in params[lo:lo + m] for v in row[14:]])
-            _lib.check(L.icl_volume_feed(ptrs(*[st.images[i].data_ptr() for i in chunk]), ptrs(*[st.labels[i].data_ptr() for i in chunk]),
-                                         ints, floats, m, flat_image[lo:].data_ptr(), flat_label[lo:].data_ptr(), *self.roi, stream),
-                       "volume_feed")
+            floats = (ctypes.c_float * (2 * m))(*[float(v) for row in params[lo:lo + m] for v in row[14:16]])
+            images, labels = ptrs(*[st.images[i].data_ptr() for i in chunk]), ptrs(*[st.labels[i].data_ptr() for i in chunk])
+            affine = _affine_block(suffixes[lo:lo + m])
+            if affine is None:                   # no sample of the launch has an affine: the launch of a loader without the stage
+                _lib.check(L.icl_volume_feed(images, labels, ints, floats, m, flat_image[lo:].data_ptr(), flat_label[lo:].data_ptr(),
+                                             *self.roi, stream), "volume_feed")
+            else:
+                _lib.check(L.icl_volume_feed_affine(images, labels, ints, floats, affine, m, flat_image[lo:].data_ptr(),
+                                                    flat_label[lo:].data_ptr(), *self.roi, stream), "volume_feed_affine")
         return {"image": image, "label": label.view((n, 1) + self.roi)}
 
 
@@ -269,12 +365,14 @@ def draw_posneg_params(shape: Sequence[int], roi: Sequence[int], n_fg: int, n_bg
        ``pos_ratio`` becomes 0 (no foreground) or 1 (no background), and the draws below are still made;
     2. centres, for each of the ``num_samples`` crops in order: ``use_fg = rng.rand() < pos_ratio``, then
        ``rank = rng.randint(len(list))`` of the chosen list: the centre is ``unravel_index(list[rank], shape)``;
-    3. then, for crop 0, 1, ..., the tail draws, steps 3-6 of ``draw_amos_params`` (flips, rotation, scale, shift).
+    3. then, for crop 0, 1, ..., the affine draw (step 2a of ``draw_amos_params``; nothing with ``affine_prob == 0``) followed by the
+       tail draws, steps 3-6 of ``draw_amos_params`` (flips, rotation, scale, shift).
 
     The crop has the size ``s = min(roi, n)`` and the origin ``clamp(centre - s // 2, 0, n - s)`` per axis (``correct_crop_centers``
     followed by ``SpatialCrop(roi_center, roi_size)``); the device computes it from the rank, so the origin fields of a row are unused
     (0).  Returns ``num_samples`` rows: the 16 values of a ``draw_amos_params`` row followed by ``(kind, rank)``, ``kind`` being
-    ``KIND_FG`` (0) or ``KIND_BG`` (1).  The keyword arguments are the probabilities of ``draw_amos_params``."""
+    ``KIND_FG`` (0) or ``KIND_BG`` (1): 18 values, and behind them the nine entries of ``M`` for a crop that drew an affine (27).  The
+    keyword arguments are the probabilities of ``draw_amos_params``, its four affine keywords included."""
     n = [int(v) for v in shape]
     r = [int(v) for v in roi]
     if len(n) != 3 or len(r) != 3 or min(n) < 1 or min(r) < 1:
@@ -284,6 +382,8 @@ def draw_posneg_params(shape: Sequence[int], roi: Sequence[int], n_fg: int, n_bg
     num_samples, n_fg, n_bg = int(num_samples), int(n_fg), int(n_bg)
     if num_samples < 1 or n_fg < 0 or n_bg < 0:
         raise ValueError(f"draw_posneg_params: num_samples {num_samples}, n_fg {n_fg}, n_bg {n_bg}")
+    probabilities = dict(probabilities)
+    affine = _affine_arguments(**{key: probabilities.pop(key) for key in _AFFINE_KEYWORDS if key in probabilities})
     tail = _tail_arguments(**probabilities)
     pos_ratio = pos / (pos + neg)
     if n_fg == 0 or n_bg == 0:
@@ -296,7 +396,14 @@ def draw_posneg_params(shape: Sequence[int], roi: Sequence[int], n_fg: int, n_bg
         centres.append((kind, int(rng.randint(n_fg if kind == KIND_FG else n_bg))))
     size = [min(r[a], n[a]) for a in range(3)]
     left = [(r[a] - size[a]) // 2 for a in range(3)]
-    return [(*n, 0, 0, 0, *size, *left, *_draw_tail(rng, *tail), kind, rank) for kind, rank in centres]
+    rows = []
+    for kind, rank in centres:
+        matrix = _draw_affine(rng, *affine)                      # drawn before the crop's flips, as in draw_amos_params
+        rows.append((*n, 0, 0, 0, *size, *left, *_draw_tail(rng, *tail), kind, rank, *matrix))
+    return rows
+
+
+_AFFINE_KEYWORDS = ("affine_prob", "rotate_range", "zoom_range", "zoom_isotropic")
 
 
 def _tail_arguments(flip_prob: float = 0.10, rot_prob: float = 0.10, max_k: int = 3, shift_offset: float = 0.10, shift_prob: float = 0.50,
@@ -341,8 +448,9 @@ class OnDeviceAugmentPosNeg(OnDeviceAugmentAMOS):
             params = self.draw(indices)
         sample_of = [i for i in indices for _ in range(k)]          # the volume of every sample
         n = len(sample_of)
-        if len(params) != n or any(len(row) != 18 for row in params):
+        if len(params) != n:
             raise ValueError(f"OnDeviceAugmentPosNeg.batch: {k} parameter rows of 18 values per index")
+        suffixes = _affine_suffixes("OnDeviceAugmentPosNeg.batch", params, 18, f"{k} parameter rows of 18 values per index")
         for i, row in zip(sample_of, params):
             if tuple(int(v) for v in row[:3]) != tuple(st.images[i].shape):
                 raise ValueError(f"OnDeviceAugmentPosNeg.batch: parameter row for extents {tuple(row[:3])}, volume {i} is {tuple(st.images[i].shape)}")
@@ -373,8 +481,14 @@ class OnDeviceAugmentPosNeg(OnDeviceAugmentAMOS):
                                          select, ix.image_threshold, m, origins[lo:].data_ptr(), stream), "rank_select")
             ints = (ctypes.c_int32 * (14 * m))(*[int(v) for row in rows for v in row[:14]])
             floats = (ctypes.c_float * (2 * m))(*[float(v) for row in rows for v in row[14:16]])
-            _lib.check(L.icl_volume_feed_origins(images, labels, ints, floats, m, origins[lo:].data_ptr(), flat_image[lo:].data_ptr(),
-                                                 flat_label[lo:].data_ptr(), *self.roi, stream), "volume_feed_origins")
+            affine = _affine_block(suffixes[lo:lo + m])
+            if affine is None:
+                _lib.check(L.icl_volume_feed_origins(images, labels, ints, floats, m, origins[lo:].data_ptr(), flat_image[lo:].data_ptr(),
+                                                     flat_label[lo:].data_ptr(), *self.roi, stream), "volume_feed_origins")
+            else:
+                _lib.check(L.icl_volume_feed_affine_origins(images, labels, ints, floats, affine, m, origins[lo:].data_ptr(),
+                                                            flat_image[lo:].data_ptr(), flat_label[lo:].data_ptr(), *self.roi, stream),
+                           "volume_feed_affine_origins")
         return {"image": image, "label": label.view((n, 1) + self.roi)}
 
 

@@ -519,6 +519,24 @@ int icl_rank_select(const void* const* images, const void* const* labels, const 
 int icl_volume_feed_origins(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params,
                             int batch, const int32_t* origins, float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream);
 
+/* ---- the 3-D feed with an AFFINE stage (arbitrary rotation and zoom: MONAI RandAffined, nnU-Net's rotation and scaling) between the
+ * pad and the flips: crop -> symmetric pad -> affine about the patch centre -> flips -> rot90 -> intensity (volume_feed_affine_kernel,
+ * csrc/kernels/datafeed.h; the definition is in DESIGN.md "Affine stage of the 3-D feed").  The arguments of icl_volume_feed /
+ * icl_volume_feed_origins, plus affine_params: HOST double [batch][10] = {flag, M row-major (3x3)}.  flag 0: the sample is gathered as
+ * icl_volume_feed gathers it, bit for bit.  flag 1: the output voxel is mapped back through rot90 and the flips to patch coordinates p,
+ * then x_a = t_a + ((M_a0 u_0 + M_a1 u_1) + M_a2 u_2) with u_a = p_a - (R_a - 1) / 2 and t_a = (c_a - l_a) + (R_a - 1) / 2, in double,
+ * every product and sum rounded on its own; the image is interpolated trilinearly (eight taps in the order (0,0,0) .. (1,1,1), summed
+ * left to right in double, one rounding to fp32, then fp32(fp32(v * mul) + add)) and the label is the voxel at rint(x_a) (half to
+ * even).  x is a coordinate of the WHOLE volume: voxels outside the crop window are read, and only what lies outside the volume counts
+ * as 0 (grid_sample's padding_mode="zeros").  Return -1, launching nothing, for whatever the siblings refuse and for a null
+ * affine_params, a flag other than 0 or 1, or an entry of M (of any sample, whatever its flag) that is not finite or exceeds 16 in
+ * magnitude.  All range tests of the kernel are made on the double coordinate, so no M and no origin can cause a read outside the volume. */
+int icl_volume_feed_affine(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params,
+                           const double* affine_params, int batch, float* image_out, int64_t* label_out, int R0, int R1, int R2, void* stream);
+int icl_volume_feed_affine_origins(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params,
+                                   const double* affine_params, int batch, const int32_t* origins, float* image_out, int64_t* label_out,
+                                   int R0, int R1, int R2, void* stream);
+
 /* ---- the CACHED prefix of the AMOS trainer (train_inherent_consistent_unet_3D_AMOS22.py:86-101, validation :141-154):
  * ScaleIntensityRanged -> CropForegroundd -> Orientationd("RAS") -> [SpatialPadd] -> Spacingd(bilinear / nearest, border), and its inverse
  * for label maps (csrc/kernels/prefix.h; the definition is in DESIGN.md "AMOS cached prefix").  A case is planned on the host

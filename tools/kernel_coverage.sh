@@ -3,6 +3,8 @@
 # (volume_feed_kernel<1, false> and <4, false>, the AMOS data feed, are launched by tests/test_gpu_amos_feed.py: the (6, 6, 5) and (6, 6, 8) sweeps)
 # (rank_count_kernel, rank_scan_kernel, rank_select_kernel of rankindex.h and volume_feed_kernel<1, true> and <4, true> of datafeed.h, the
 #  pos/neg feed, are launched by tests/test_gpu_posneg_feed.py: the index and select tests, and the (6, 6, 5) and (6, 6, 8) batches)
+# (volume_feed_affine_kernel<1, false>, <4, false>, <1, true> and <4, true> of datafeed.h, the affine stage of both feeds, are launched by
+#  tests/test_gpu_affine_feed.py: the random-matrix cases on aligned and misaligned outputs, and the device-origin test at both ROIs)
 # (prefix_box_partial_kernel, prefix_box_finish_kernel, prefix_resample_kernel<1> and <4>, prefix_restore_kernel<uint8_t> and <long long> of
 #  prefix.h, the AMOS cached prefix, are launched by tests/test_gpu_amos_prefix.py: the case list, the quad cases and the restore tests)
 # (the surface-metric kernels of metrics_surface.h — surf_edt_axis2/1/0, surf_reduce, surf_radix<0..5>, surf_finish — are launched by

@@ -24,6 +24,7 @@
 #include "kernels/datafeed.h"
 #include "kernels/rankindex.h"
 #include "kernels/prefix.h"
+#include "kernels/intensity.h"
 #include "kernels/qchain.h"
 #include "kernels/metrics.h"
 #include "kernels/metrics_surface.h"
@@ -2729,6 +2730,162 @@ int icl_prefix_restore(const void* prediction, int elem_kind, const int32_t* int
                out);
   }
   return check_launch("prefix_restore");
+}
+
+namespace {
+
+// what the four intensity entry points share: the batch pointer, the batch size and the patch extents
+int intensity_common(const char* what, const void* image, int batch, int R0, int R1, int R2) {
+  if (!image) return fail(-1, "%s: null pointer", what);
+  if (batch < 1 || batch > icl::kFeedMaxBatch) return fail(-1, "%s: batch %d out of range (1 <= batch <= %d)", what, batch, icl::kFeedMaxBatch);
+  if (R0 < 1 || R1 < 1 || R2 < 1) return fail(-1, "%s: extents %d x %d x %d (each must be >= 1)", what, R0, R1, R2);
+  if ((long)R0 * R1 * R2 > 0x7fffffffL) return fail(-1, "%s: extents %d x %d x %d (more than 2^31 - 1 voxels a sample)", what, R0, R1, R2);
+  return 0;
+}
+
+// a flag travels as a double beside the other values of its row: exactly 0 or 1
+int intensity_flag(const char* what, int b, const char* name, double v, int& out) {
+  if (!(v == 0.0 || v == 1.0)) return fail(-1, "%s: sample %d: %s flag %g (must be 0 or 1)", what, b, name, v);
+  out = v == 1.0 ? 1 : 0;
+  return 0;
+}
+
+}  // namespace
+
+int icl_intensity_noise(float* image, const double* params, int batch, int R0, int R1, int R2, void* stream) {
+  if (!params) return fail(-1, "intensity_noise: null pointer");
+  if (const int rc = intensity_common("intensity_noise", image, batch, R0, R1, R2)) return rc;
+  icl::NoiseBatch nb{};
+  bool any = false;
+  for (int b = 0; b < batch; ++b) {
+    const double* q = params + 4 * b;      // flag, seed, sigma, clip
+    icl::NoiseSample& s = nb.s[b];
+    if (const int rc = intensity_flag("intensity_noise", b, "noise", q[0], s.on)) return rc;
+    if (!(q[1] >= 0.0 && q[1] <= 4294967295.0) || q[1] != std::floor(q[1]))
+      return fail(-1, "intensity_noise: sample %d: seed %g (must be an integer in 0 .. 2^32 - 1)", b, q[1]);
+    if (!std::isfinite(q[2]) || !(q[2] > 0.0)) return fail(-1, "intensity_noise: sample %d: sigma %g (must be finite and positive)", b, q[2]);
+    if (!std::isfinite(q[3]) || q[3] < 0.0) return fail(-1, "intensity_noise: sample %d: clip %g (must be finite; 0 means none)", b, q[3]);
+    s.seed = (unsigned)q[1];
+    s.sigma = q[2];
+    s.clip = q[3] > 0.0 ? 1 : 0;
+    s.limit = (float)(q[3] * q[2]);
+    any = any || s.on;
+  }
+  if (!any) return 0;
+  const long voxels = (long)R0 * R1 * R2;
+  if ((R2 & 3) == 0 && aligned16(image)) {
+    ICL_LAUNCH((icl::intensity_noise_kernel<4>), dim3(grid_for(voxels / 4, icl::kIntensityThreads, 8192), batch), dim3(icl::kIntensityThreads), 0,
+               (hipStream_t)stream, nb, image, (unsigned)voxels);
+  } else {
+    ICL_LAUNCH((icl::intensity_noise_kernel<1>), dim3(grid_for(voxels, icl::kIntensityThreads, 8192), batch), dim3(icl::kIntensityThreads), 0,
+               (hipStream_t)stream, nb, image, (unsigned)voxels);
+  }
+  return check_launch("intensity_noise");
+}
+
+int icl_intensity_blur(float* image, float* scratch, const double* params, int batch, int R0, int R1, int R2, void* stream) {
+  if (!scratch || !params) return fail(-1, "intensity_blur: null pointer");
+  if (const int rc = intensity_common("intensity_blur", image, batch, R0, R1, R2)) return rc;
+  if (image == scratch) return fail(-1, "intensity_blur: the scratch buffer is the batch itself");
+  if (R2 > icl::kBlurLineFloats) return fail(-1, "intensity_blur: extent %d of the contiguous axis (at most %d)", R2, icl::kBlurLineFloats);
+  const int smallest = R0 < R1 ? (R0 < R2 ? R0 : R2) : (R1 < R2 ? R1 : R2);
+  icl::BlurBatch bb{};
+  bool any = false;
+  for (int b = 0; b < batch; ++b) {
+    const double* q = params + (2 + icl::kBlurMaxRadius + 1) * b;      // flag, sigma, w_0 .. w_12
+    icl::BlurSample& s = bb.s[b];
+    int flag = 0;
+    if (const int rc = intensity_flag("intensity_blur", b, "blur", q[0], flag)) return rc;
+    if (!std::isfinite(q[1]) || !(q[1] > 0.0)) return fail(-1, "intensity_blur: sample %d: sigma %g (must be finite and positive)", b, q[1]);
+    const double rr = std::floor(4.0 * q[1] + 0.5);                   // int(4 sigma + 0.5), on the double
+    if (rr > (double)icl::kBlurMaxRadius)
+      return fail(-1, "intensity_blur: sample %d: sigma %g gives the radius %.0f (at most %d)", b, q[1], rr, icl::kBlurMaxRadius);
+    s.r = (int)rr;
+    if (s.r > smallest)
+      return fail(-1, "intensity_blur: sample %d: radius %d above the smallest extent of %d x %d x %d", b, s.r, R0, R1, R2);
+    for (int k = 0; k <= s.r; ++k) {
+      if (!(q[2 + k] >= 0.0 && q[2 + k] <= 1.0)) return fail(-1, "intensity_blur: sample %d: weight w[%d] = %g outside [0, 1]", b, k, q[2 + k]);
+      s.w[k] = q[2 + k];
+    }
+    s.on = flag && s.r > 0 ? 1 : 0;                                   // r = 0: w_0 = 1, the identity
+    any = any || s.on;
+  }
+  if (!any) return 0;
+  const long voxels = (long)R0 * R1 * R2;
+  const dim3 block(icl::kIntensityThreads);
+  {   // axis 0: batch -> scratch
+    const long tiles = cdivl(R0, icl::kBlurTileL) * cdivl((long)R1 * R2, icl::kBlurTileI);
+    ICL_LAUNCH(icl::intensity_blur_strided_kernel, dim3(grid_for(tiles, 1, 8192), batch), block, 0, (hipStream_t)stream, bb, (const float*)image,
+               scratch, 1, R0, R1 * R2, (unsigned)voxels);
+    if (const int rc = check_launch("intensity_blur axis 0")) return rc;
+  }
+  {   // axis 1: scratch -> batch
+    const long tiles = (long)R0 * cdivl(R1, icl::kBlurTileL) * cdivl(R2, icl::kBlurTileI);
+    ICL_LAUNCH(icl::intensity_blur_strided_kernel, dim3(grid_for(tiles, 1, 8192), batch), block, 0, (hipStream_t)stream, bb, (const float*)scratch,
+               image, R0, R1, R2, (unsigned)voxels);
+    if (const int rc = check_launch("intensity_blur axis 1")) return rc;
+  }
+  const int lines = R0 * R1;                                          // axis 2: in place, whole lines through LDS
+  const int lpb = icl::kBlurLineFloats / R2;
+  const dim3 grid(grid_for(cdivl(lines, lpb), 1, 8192), batch);
+  if ((R2 & 3) == 0 && aligned16(image)) {
+    ICL_LAUNCH((icl::intensity_blur_line_kernel<4>), grid, block, 0, (hipStream_t)stream, bb, image, lines, R2, lpb, (unsigned)voxels);
+  } else {
+    ICL_LAUNCH((icl::intensity_blur_line_kernel<1>), grid, block, 0, (hipStream_t)stream, bb, image, lines, R2, lpb, (unsigned)voxels);
+  }
+  return check_launch("intensity_blur axis 2");
+}
+
+int icl_intensity_stats(const float* image, const int32_t* flags, int batch, int R0, int R1, int R2, float* stats, double* ws, void* stream) {
+  if (!flags || !stats || !ws) return fail(-1, "intensity_stats: null pointer");
+  if (const int rc = intensity_common("intensity_stats", image, batch, R0, R1, R2)) return rc;
+  icl::IntensityFlags fl{};
+  bool any = false;
+  for (int b = 0; b < batch; ++b) {
+    if (flags[b] != 0 && flags[b] != 1) return fail(-1, "intensity_stats: sample %d: flag %d (must be 0 or 1)", b, flags[b]);
+    fl.on[b] = flags[b];
+    any = any || fl.on[b];
+  }
+  if (!any) return 0;
+  const long voxels = (long)R0 * R1 * R2;
+  const int blocks = grid_for(cdivl(voxels, 4), icl::kIntensityThreads, icl::kIntensityStatBlocks);
+  ICL_LAUNCH(icl::intensity_stats_partial_kernel, dim3(blocks, batch), dim3(icl::kIntensityThreads), 0, (hipStream_t)stream, fl, image,
+             (unsigned)voxels, (voxels & 3) == 0 && aligned16(image) ? 1 : 0, ws);
+  if (const int rc = check_launch("intensity_stats_partial")) return rc;
+  ICL_LAUNCH(icl::intensity_stats_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, fl, (const double*)ws, batch, blocks,
+             (unsigned)voxels, stats);
+  return check_launch("intensity_stats_finish");
+}
+
+int icl_intensity_point(float* image, const float* stats, const double* params, int batch, int R0, int R1, int R2, void* stream) {
+  if (!stats || !params) return fail(-1, "intensity_point: null pointer");
+  if (const int rc = intensity_common("intensity_point", image, batch, R0, R1, R2)) return rc;
+  icl::PointBatch pb{};
+  bool any = false;
+  for (int b = 0; b < batch; ++b) {
+    const double* q = params + 5 * b;      // contrast flag, f, gamma flag, g, invert flag
+    icl::PointSample& s = pb.s[b];
+    if (const int rc = intensity_flag("intensity_point", b, "contrast", q[0], s.contrast)) return rc;
+    if (const int rc = intensity_flag("intensity_point", b, "gamma", q[2], s.gamma)) return rc;
+    if (const int rc = intensity_flag("intensity_point", b, "invert", q[4], s.invert)) return rc;
+    s.f = (float)q[1];
+    if (!std::isfinite(q[1]) || !std::isfinite(s.f) || !(s.f > 0.f))
+      return fail(-1, "intensity_point: sample %d: contrast factor %g (must be finite and positive in fp32)", b, q[1]);
+    if (!std::isfinite(q[3]) || !(q[3] > 0.0)) return fail(-1, "intensity_point: sample %d: gamma %g (must be finite and positive)", b, q[3]);
+    s.g = q[3];
+    if (!s.gamma) s.invert = 0;
+    any = any || s.contrast || s.gamma;
+  }
+  if (!any) return 0;
+  const long voxels = (long)R0 * R1 * R2;
+  if ((R2 & 3) == 0 && aligned16(image)) {
+    ICL_LAUNCH((icl::intensity_point_kernel<4>), dim3(grid_for(voxels / 4, icl::kIntensityThreads, 8192), batch), dim3(icl::kIntensityThreads), 0,
+               (hipStream_t)stream, pb, stats, image, (unsigned)voxels);
+  } else {
+    ICL_LAUNCH((icl::intensity_point_kernel<1>), dim3(grid_for(voxels, icl::kIntensityThreads, 8192), batch), dim3(icl::kIntensityThreads), 0,
+               (hipStream_t)stream, pb, stats, image, (unsigned)voxels);
+  }
+  return check_launch("intensity_point");
 }
 
 int icl_slice_augment(const void* const* images, const void* const* labels, const int32_t* int_params, const double* double_params,

@@ -53,6 +53,7 @@ import torch
 
 from .. import _lib
 from .brats2019 import DeviceVolumeStore
+from .intensity import _check_stage, _intensity_rows
 
 FEED_MAX_BATCH = 16         # icl_volume_feed takes up to 16 samples per launch (kFeedMaxBatch)
 
@@ -233,14 +234,21 @@ class OnDeviceAugmentAMOS:
     The keyword arguments are those of ``draw_amos_params`` (``flip_prob``, ``rot_prob``, ``max_k``, ``shift_offset``, ``shift_prob``,
     ``scale_factor``, ``scale_prob``, and the affine stage's ``affine_prob``, ``rotate_range``, ``zoom_range``, ``zoom_isotropic``, which
     are checked here) plus ``rng`` (default: numpy's global generator).  With ``affine_prob=0`` (the default) nothing is drawn for
-    the stage and ``batch`` launches what it launched before the stage existed."""
+    the stage and ``batch`` launches what it launched before the stage existed.
 
-    def __init__(self, store: DeviceVolumeStore, roi: Sequence[int] = (96, 96, 96), rng=np.random, **probabilities):
+    ``intensity``: None, or an ``IntensityAugment`` for the same ``roi`` (``dataloaders/intensity.py``: Gaussian noise, blur, contrast
+    and gamma).  ``batch`` then draws the batch's intensity rows AFTER all of its geometric rows, in sample order, from the stage's own
+    ``rng`` (pass the loader's generator to the stage to keep one stream), and applies the stage in place behind the gather, on the
+    same stream.  With None, or a stage whose probabilities are all 0, nothing is drawn or launched for it."""
+
+    def __init__(self, store: DeviceVolumeStore, roi: Sequence[int] = (96, 96, 96), rng=np.random, intensity=None, **probabilities):
         self.store = store
         self.roi = tuple(int(v) for v in roi)
         if len(self.roi) != 3 or min(self.roi) < 1:
             raise ValueError(f"OnDeviceAugmentAMOS: roi {tuple(roi)}")
         self.rng = rng
+        _check_stage(intensity, self.roi, type(self).__name__)
+        self.intensity = intensity
         draw_amos_params((1, 1, 1), self.roi, np.random.RandomState(0), **probabilities)      # rejects unknown keywords here, not mid-epoch
         self.probabilities = probabilities
         if self.roi[0] != self.roi[1] and probabilities.get("rot_prob", 0.10) > 0 and probabilities.get("max_k", 3) >= 1:
@@ -265,9 +273,10 @@ class OnDeviceAugmentAMOS:
                                  f"{' or '.join(map(str, shapes))} on {dev}, got {got}")
         return image, label
 
-    def batch(self, indices: Sequence[int], params: Optional[Sequence[Sequence[float]]] = None, out=None):
+    def batch(self, indices: Sequence[int], params: Optional[Sequence[Sequence[float]]] = None, out=None, intensity_params=None):
         """One batch for the volumes ``indices`` of the store.  ``params``: one ``draw_amos_params`` row per index (drawn here when
-        not given).  ``out=(image, label)``: write into the caller's tensors — for example ``ICLTrainer.static_vol`` /
+        not given).  ``intensity_params``: one ``draw_intensity_params`` row per sample for the loader's intensity stage (drawn here,
+        after ``params``, when not given).  ``out=(image, label)``: write into the caller's tensors — for example ``ICLTrainer.static_vol`` /
         ``static_lab`` after ``capture()``, so that a captured step needs no extra copy — and return views of them; shape
         (``[B,1,*roi]``; the label may also be ``[B,*roi]``), dtype, device and contiguity are checked.  More than 16 indices are
         handled as chunks of 16."""
@@ -280,6 +289,7 @@ class OnDeviceAugmentAMOS:
             params = self.draw(indices)
         if len(params) != n:
             raise ValueError("OnDeviceAugmentAMOS.batch: one parameter row of 16 values per index")
+        intensity_params = _intensity_rows(self.intensity, self.roi, n, intensity_params, "OnDeviceAugmentAMOS.batch")
         suffixes = _affine_suffixes("OnDeviceAugmentAMOS.batch", params, 16, "one parameter row of 16 values per index")
         for i, row in zip(indices, params):
             if tuple(int(v) for v in row[:3]) != tuple(st.images[i].shape):
@@ -306,6 +316,8 @@ class OnDeviceAugmentAMOS:
             else:
                 _lib.check(L.icl_volume_feed_affine(images, labels, ints, floats, affine, m, flat_image[lo:].data_ptr(),
                                                     flat_label[lo:].data_ptr(), *self.roi, stream), "volume_feed_affine")
+        if intensity_params is not None:
+            self.intensity.apply(image, intensity_params)
         return {"image": image, "label": label.view((n, 1) + self.roi)}
 
 
@@ -423,8 +435,8 @@ class OnDeviceAugmentPosNeg(OnDeviceAugmentAMOS):
     same keyword arguments."""
 
     def __init__(self, store: DeviceVolumeStore, index: ForegroundIndex, roi: Sequence[int] = (96, 96, 96), pos: float = 1, neg: float = 1,
-                 num_samples: int = 4, rng=np.random, **probabilities):
-        super().__init__(store, roi, rng, **probabilities)
+                 num_samples: int = 4, rng=np.random, intensity=None, **probabilities):
+        super().__init__(store, roi, rng, intensity, **probabilities)
         if index.store is not store or len(index) != len(store):
             raise ValueError("OnDeviceAugmentPosNeg: the ForegroundIndex was not built from this store")
         self.index = index
@@ -436,10 +448,10 @@ class OnDeviceAugmentPosNeg(OnDeviceAugmentAMOS):
         return [row for i in indices for row in draw_posneg_params(self.store.images[i].shape, self.roi, ix.n_fg[i], ix.n_bg[i], self.rng,
                                                                    self.pos, self.neg, self.num_samples, **self.probabilities)]
 
-    def batch(self, indices: Sequence[int], params: Optional[Sequence[Sequence[float]]] = None, out=None):
+    def batch(self, indices: Sequence[int], params: Optional[Sequence[Sequence[float]]] = None, out=None, intensity_params=None):
         """One batch of ``len(indices) * num_samples`` samples.  ``params``: ``num_samples`` ``draw_posneg_params`` rows per index,
         volume-major (drawn here when not given); a rank at or past the length of its list is refused here, since only the host
-        knows the lengths.  ``out=(image, label)`` as in ``OnDeviceAugmentAMOS.batch``.  More than 16 samples go as chunks of 16."""
+        knows the lengths.  ``out=(image, label)`` and ``intensity_params`` (one row per SAMPLE) as in ``OnDeviceAugmentAMOS.batch``.  More than 16 samples go as chunks of 16."""
         st, ix, k = self.store, self.index, self.num_samples
         indices = [int(i) for i in indices]
         if len(indices) < 1:
@@ -450,6 +462,7 @@ class OnDeviceAugmentPosNeg(OnDeviceAugmentAMOS):
         n = len(sample_of)
         if len(params) != n:
             raise ValueError(f"OnDeviceAugmentPosNeg.batch: {k} parameter rows of 18 values per index")
+        intensity_params = _intensity_rows(self.intensity, self.roi, n, intensity_params, "OnDeviceAugmentPosNeg.batch")
         suffixes = _affine_suffixes("OnDeviceAugmentPosNeg.batch", params, 18, f"{k} parameter rows of 18 values per index")
         for i, row in zip(sample_of, params):
             if tuple(int(v) for v in row[:3]) != tuple(st.images[i].shape):
@@ -489,6 +502,8 @@ class OnDeviceAugmentPosNeg(OnDeviceAugmentAMOS):
                 _lib.check(L.icl_volume_feed_affine_origins(images, labels, ints, floats, affine, m, origins[lo:].data_ptr(),
                                                             flat_image[lo:].data_ptr(), flat_label[lo:].data_ptr(), *self.roi, stream),
                            "volume_feed_affine_origins")
+        if intensity_params is not None:
+            self.intensity.apply(image, intensity_params)
         return {"image": image, "label": label.view((n, 1) + self.roi)}
 
 
@@ -496,7 +511,8 @@ class AMOSDeviceLoader:
     """Stands where the AMOS trainer's ``ThreadDataLoader(train_ds, batch_sampler=batch_sampler, …)`` stood (``:196-197``): an
     iterable with ``__len__`` that yields ``augment.batch(indices)`` for the index batches of ``batch_sampler``
     (``TwoStreamBatchSampler``), so ``for i_batch, sampled_batch in enumerate(train_loader)`` runs as written and the loop's ``.cuda()``
-    calls are no-ops.  ``augment`` may be an ``OnDeviceAugmentPosNeg``: a batch then holds ``num_samples`` crops per index."""
+    calls are no-ops.  ``augment`` may be an ``OnDeviceAugmentPosNeg``: a batch then holds ``num_samples`` crops per index.  An
+    intensity stage travels with ``augment`` (its ``intensity=``): every batch of the loader passes through it."""
 
     def __init__(self, augment: OnDeviceAugmentAMOS, batch_sampler):
         self.augment = augment

@@ -26,6 +26,7 @@ from torch.utils.data import Dataset
 from torch.utils.data.sampler import Sampler
 
 from .. import _lib
+from .intensity import _check_stage, _intensity_rows
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -193,17 +194,23 @@ def draw_rotflip_crop(shape: Sequence[int], output_size: Sequence[int]) -> List[
 
 class OnDeviceAugment:
     """``Compose([RandomRotFlip(), RandomCrop(patch), ToTensor()])`` + batch collation on the GPU: ``batch(indices)`` returns
-    ``{'image': [B,1,*patch] fp32, 'label': [B,*patch] int64}`` like the reference DataLoader's ``sampled_batch``."""
+    ``{'image': [B,1,*patch] fp32, 'label': [B,*patch] int64}`` like the reference DataLoader's ``sampled_batch``.
+    ``intensity``: None, or an ``IntensityAugment`` for ``patch_size`` (``dataloaders/intensity.py``; the reference's ``RandomNoise``,
+    ``:150-161``, is its noise with ``noise_sigma=0.1, noise_clip=2``): its rows (``intensity_params``, one per sample) are drawn after
+    all geometric rows of the batch, from the stage's own ``rng``, and it runs in place behind the gather on the same stream."""
 
-    def __init__(self, store: DeviceVolumeStore, patch_size: Sequence[int] = (96, 96, 96)):
+    def __init__(self, store: DeviceVolumeStore, patch_size: Sequence[int] = (96, 96, 96), intensity=None):
         self.store = store
         self.patch = tuple(int(v) for v in patch_size)
+        _check_stage(intensity, self.patch, "OnDeviceAugment")
+        self.intensity = intensity
 
-    def batch(self, indices: Sequence[int], params: Optional[Sequence[Sequence[int]]] = None):
+    def batch(self, indices: Sequence[int], params: Optional[Sequence[Sequence[int]]] = None, intensity_params=None):
         st = self.store
         n = len(indices)
         if params is None:
             params = [draw_rotflip_crop(st.images[i].shape, self.patch) for i in indices]
+        intensity_params = _intensity_rows(self.intensity, self.patch, n, intensity_params, "OnDeviceAugment.batch")
         dev = st.device
         image = torch.empty((n, 1) + self.patch, dtype=torch.float32, device=dev)
         label = torch.empty((n,) + self.patch, dtype=torch.int64, device=dev)
@@ -216,6 +223,8 @@ class OnDeviceAugment:
             flat = (ctypes.c_int32 * (11 * m))(*[int(v) for row in params[lo:lo + m] for v in row])
             _lib.check(L.icl_crop_rotflip(ptrs(*[st.images[i].data_ptr() for i in chunk]), ptrs(*[st.labels[i].data_ptr() for i in chunk]),
                                           flat, m, image[lo:].data_ptr(), label[lo:].data_ptr(), *self.patch, stream), "crop_rotflip")
+        if intensity_params is not None:
+            self.intensity.apply(image, intensity_params)
         return {"image": image, "label": label}
 
 

@@ -562,6 +562,37 @@ int icl_prefix_resample(const float* image, const uint8_t* label, const int32_t*
 int icl_prefix_restore(const void* prediction, int elem_kind, const int32_t* int_params, const double* double_params, uint8_t* out,
                        void* stream);
 
+/* ---- the INTENSITY stage of the 3-D feed (csrc/kernels/intensity.h; the definition is in DESIGN.md "Intensity stage of the 3-D feed"):
+ * four entry points that act IN PLACE on the image batch the gather has written, image DEVICE fp32 [batch][R0][R1][R2], in the order
+ * noise, blur, stats, point, on the caller's stream.  Every row of `params` is a HOST double row per sample whose flags are exactly 0 or
+ * 1; EVERY field of EVERY row is checked, whatever the flags (a caller fills the rows of a sample without the transform with legal
+ * values); a launch whose samples all have the flag 0 launches nothing and returns 0.  All four return -1, launching nothing, for a null
+ * pointer, batch outside 1..16, an extent below 1, or more than 2^31 - 1 voxels a sample. */
+/* Gaussian noise (nnU-Net GaussianNoiseTransform, MONAI RandGaussianNoised, the reference's RandomNoise, brats2019.py:150-161):
+ * params [batch][4] = {flag, seed (an integer in 0 .. 2^32 - 1), sigma, clip}.  x = fp32(x + n), n = fp32(sigma z) clipped to
+ * +- fp32(clip sigma) when clip > 0; z from the mix32 counter hash of (seed, flat voxel index) and a Box-Muller step in double, one pair
+ * of uniforms per voxel.  Refused: a seed that is no such integer, a non-finite or non-positive sigma, a non-finite or negative clip. */
+int icl_intensity_noise(float* image, const double* params, int batch, int R0, int R1, int R2, void* stream);
+/* Gaussian blur (nnU-Net GaussianBlurTransform, MONAI RandGaussianSmoothd): scipy.ndimage.gaussian_filter(x, sigma, mode="reflect",
+ * truncate=4.0) per sample.  params [batch][15] = {flag, sigma, w_0 .. w_12}: the radius is r = int(4 sigma + 0.5) and w_0 .. w_r are
+ * the normalised weights the caller formed in double (w_k beyond r is not read).  Axis 0 goes batch -> scratch, axis 1 scratch -> batch,
+ * axis 2 in place through LDS; scratch: DEVICE fp32 of the batch's size, distinct from it.  r = 0 is the identity and is not launched.
+ * Refused: a non-finite or non-positive sigma, r above 12, r above the smallest of R0, R1, R2 (one reflection must suffice), a weight
+ * outside [0, 1] (or NaN), R2 above 4096. */
+int icl_intensity_blur(float* image, float* scratch, const double* params, int batch, int R0, int R1, int R2, void* stream);
+/* Statistics of the samples whose flag is 1 (those that drew contrast or gamma; nnU-Net ContrastAugmentationTransform's mean, minimum
+ * and maximum, MONAI RandAdjustContrast's minimum and maximum): flags HOST int32 [batch]; stats DEVICE fp32 [batch][4] = {min, max,
+ * mean, 0}, mean = fp32(double sum / N) with the sum in the fixed order documented at intensity_stats_partial_kernel; the row of a
+ * sample whose flag is 0 is not written.  ws: DEVICE double [16 * 64 * 3] of scratch.  Two launches, no atomics.  Refused: a flag
+ * outside {0, 1}. */
+int icl_intensity_stats(const float* image, const int32_t* flags, int batch, int R0, int R1, int R2, float* stats, double* ws, void* stream);
+/* Contrast (nnU-Net ContrastAugmentationTransform, preserve_range) and gamma (MONAI RandAdjustContrast's formula, nnU-Net GammaTransform's
+ * invert_image as a flag), pointwise, from the rows of `stats` that icl_intensity_stats left: params [batch][5] = {contrast flag, f,
+ * gamma flag, g, invert flag}.  contrast: y = fp32(fp32(fp32(x - mean) f) + mean) clipped to [min, max]; gamma, on that result, with mn
+ * and mx the images of min and max: t = (x - mn) / ((mx - mn) + 1e-7), y = fp32(fp32(pow(t, g) (mx - mn)) + mn) in double (g = 1:
+ * pow(t, 1) is t), with invert on -x and negated again.  Refused: f or g that is not finite and positive (f as fp32). */
+int icl_intensity_point(float* image, const float* stats, const double* params, int batch, int R0, int R1, int R2, void* stream);
+
 /* ---- on-device RandomGenerator of the 2-D trainers (dataloaders/dataset.py:147-166; composed at
  * train_inherent_consistent_unet_2D.py:75 and ..._swinunet_2D.py): "maybe rot90 + flip, else maybe ndimage.rotate by an integer
  * angle, then ndimage.zoom to the patch", all order 0, as ONE gather over slices resident in HBM, bit for bit scipy's result.

@@ -5,6 +5,10 @@
 #  pos/neg feed, are launched by tests/test_gpu_posneg_feed.py: the index and select tests, and the (6, 6, 5) and (6, 6, 8) batches)
 # (volume_feed_affine_kernel<1, false>, <4, false>, <1, true> and <4, true> of datafeed.h, the affine stage of both feeds, are launched by
 #  tests/test_gpu_affine_feed.py: the random-matrix cases on aligned and misaligned outputs, and the device-origin test at both ROIs)
+# (intensity_noise_kernel<1> and <4>, intensity_blur_strided_kernel, intensity_blur_line_kernel<1> and <4>, intensity_stats_partial_kernel,
+#  intensity_stats_finish_kernel, intensity_point_kernel<1> and <4> of intensity.h, the intensity stage of the 3-D feeds, are launched by
+#  tests/test_gpu_intensity_feed.py: every check runs (7, 9, 10) for the one-voxel kernels and (8, 12, 16) for the quad kernels, and the
+#  blur test repeats each shape on a batch that starts 4 bytes past a 16-byte boundary)
 # (prefix_box_partial_kernel, prefix_box_finish_kernel, prefix_resample_kernel<1> and <4>, prefix_restore_kernel<uint8_t> and <long long> of
 #  prefix.h, the AMOS cached prefix, are launched by tests/test_gpu_amos_prefix.py: the case list, the quad cases and the restore tests)
 # (the surface-metric kernels of metrics_surface.h — surf_edt_axis2/1/0, surf_reduce, surf_radix<0..5>, surf_finish — are launched by

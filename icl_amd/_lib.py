@@ -130,6 +130,7 @@ _SIGNATURES = {
     "icl_prefix_restore": (c_int, [P, I, P, P, P, P]),
     "icl_intensity_noise": (c_int, [P, P, I, I, I, I, P]),
     "icl_intensity_blur": (c_int, [P, P, P, I, I, I, I, P]),
+    "icl_intensity_lowres": (c_int, [P, P, P, I, I, I, I, P]),
     "icl_intensity_stats": (c_int, [P, P, I, I, I, I, P, P, P]),
     "icl_intensity_point": (c_int, [P, P, P, I, I, I, I, P]),
     "icl_slice_augment": (c_int, [P, P, P, P, I, P, P, I, I, P]),

@@ -2734,7 +2734,7 @@ int icl_prefix_restore(const void* prediction, int elem_kind, const int32_t* int
 
 namespace {
 
-// what the four intensity entry points share: the batch pointer, the batch size and the patch extents
+// what the intensity entry points share: the batch pointer, the batch size and the patch extents
 int intensity_common(const char* what, const void* image, int batch, int R0, int R1, int R2) {
   if (!image) return fail(-1, "%s: null pointer", what);
   if (batch < 1 || batch > icl::kFeedMaxBatch) return fail(-1, "%s: batch %d out of range (1 <= batch <= %d)", what, batch, icl::kFeedMaxBatch);
@@ -2834,6 +2834,48 @@ int icl_intensity_blur(float* image, float* scratch, const double* params, int b
     ICL_LAUNCH((icl::intensity_blur_line_kernel<1>), grid, block, 0, (hipStream_t)stream, bb, image, lines, R2, lpb, (unsigned)voxels);
   }
   return check_launch("intensity_blur axis 2");
+}
+
+int icl_intensity_lowres(float* image, float* scratch, const int32_t* params, int batch, int R0, int R1, int R2, void* stream) {
+  if (!scratch || !params) return fail(-1, "intensity_lowres: null pointer");
+  if (const int rc = intensity_common("intensity_lowres", image, batch, R0, R1, R2)) return rc;
+  if (image == scratch) return fail(-1, "intensity_lowres: the scratch buffer is the batch itself");
+  const int R[3] = {R0, R1, R2};
+  icl::LowresBatch lb{};
+  bool any = false;
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* q = params + 4 * b;     // flag, L0, L1, L2
+    icl::LowresSample& s = lb.s[b];
+    if (q[0] != 0 && q[0] != 1) return fail(-1, "intensity_lowres: sample %d: flag %d (must be 0 or 1)", b, q[0]);
+    bool smaller = false;
+    for (int a = 0; a < 3; ++a) {
+      if (q[1 + a] < 1 || q[1 + a] > R[a])
+        return fail(-1, "intensity_lowres: sample %d: low extent %d of axis %d (must be in 1 .. %d)", b, q[1 + a], a, R[a]);
+      s.L[a] = q[1 + a];
+      s.sn[a] = (float)R[a] / (float)q[1 + a];
+      s.sl[a] = (float)q[1 + a] / (float)R[a];
+      smaller = smaller || q[1 + a] < R[a];
+    }
+    s.on = q[0] == 1 && smaller ? 1 : 0;                              // every L = R: the identity
+    any = any || s.on;
+  }
+  if (!any) return 0;
+  const long voxels = (long)R0 * R1 * R2;
+  const dim3 block(icl::kIntensityThreads);
+  if ((R2 & 3) == 0 && aligned16(image) && aligned16(scratch)) {
+    const dim3 grid(grid_for(voxels / 4, icl::kIntensityThreads, 8192), batch);
+    ICL_LAUNCH((icl::intensity_lowres_kernel<4>), grid, block, 0, (hipStream_t)stream, lb, (const float*)image, scratch, R0, R1, R2,
+               (unsigned)voxels);
+    if (const int rc = check_launch("intensity_lowres gather")) return rc;
+    ICL_LAUNCH((icl::intensity_lowres_copy_kernel<4>), grid, block, 0, (hipStream_t)stream, lb, (const float*)scratch, image, (unsigned)voxels);
+  } else {
+    const dim3 grid(grid_for(voxels, icl::kIntensityThreads, 8192), batch);
+    ICL_LAUNCH((icl::intensity_lowres_kernel<1>), grid, block, 0, (hipStream_t)stream, lb, (const float*)image, scratch, R0, R1, R2,
+               (unsigned)voxels);
+    if (const int rc = check_launch("intensity_lowres gather")) return rc;
+    ICL_LAUNCH((icl::intensity_lowres_copy_kernel<1>), grid, block, 0, (hipStream_t)stream, lb, (const float*)scratch, image, (unsigned)voxels);
+  }
+  return check_launch("intensity_lowres copy");
 }
 
 int icl_intensity_stats(const float* image, const int32_t* flags, int batch, int R0, int R1, int R2, float* stats, double* ws, void* stream) {

@@ -1,4 +1,4 @@
-// intensity.h — the INTENSITY stage of the 3-D device feed: Gaussian noise, Gaussian blur, contrast and gamma, in place on the image batch
+// intensity.h — the INTENSITY stage of the 3-D device feed: Gaussian noise, Gaussian blur, simulated low resolution, contrast and gamma on the image batch
 // [B][1][R0][R1][R2] fp32 that the geometric gather (datafeed.h) has written.  nnU-Net's GaussianNoise / GaussianBlur / ContrastAugmentation /
 // Gamma transforms, MONAI's RandGaussianNoised / RandGaussianSmoothd / RandAdjustContrastd and the reference's RandomNoise
 // (dataloaders/brats2019.py:150-161).  The definition is in DESIGN.md §2 "Intensity stage of the 3-D feed"; tests/intensity_feed_ref.py
@@ -11,6 +11,9 @@
 //   blur      scipy.ndimage.gaussian_filter(x, sigma, mode="reflect", truncate=4.0): axes 0, 1, 2 in turn, each pass reading the previous
 //             pass's fp32 result; per output, in double, acc = w_0 x[c], then acc = acc + (x[c - k] + x[c + k]) w_k for k = 1 .. r, rounded
 //             once to fp32; an index outside the patch is reflected about the edge (d c b a | a b c d | d c b a); the weights come from the host
+//   lowres    (off unless asked for) nnU-Net's SimulateLowResolutionTransform as two interpolate calls, "nearest-exact" down to the low
+//             extents L and "trilinear" back up, as one gather of 8 patch voxels per output: the formulas are at lowres_near / lowres_tap
+//             and the value at intensity_lowres_kernel; batch -> scratch, and a second launch copies the samples that drew it back
 //   stats     min, max (exact) and mean = fp32(double sum / N) of the sample, the sum in the fixed order given at the kernels
 //   contrast  y = fp32(fp32(fp32(x - mean) f) + mean), clipped to [min, max]
 //   gamma     on the result of contrast, whose extremes mn, mx are the images of min and max (the map is monotone); with invert x -> -x
@@ -189,6 +192,131 @@ __global__ __launch_bounds__(kIntensityThreads) void intensity_blur_line_kernel(
       for (int e = threadIdx.x; e < count; e += kIntensityThreads) g[e] = out[e];
     }
     // the next round writes `in` (last read before the barrier above) and writes `out` only behind its own first barrier
+  }
+}
+
+struct LowresSample {
+  int on;                    // 1: the sample drew low resolution and some L[a] < R[a] (all equal is the identity and is not launched)
+  int L[3];                  // low extents, 1 <= L[a] <= R[a]
+  float sn[3];               // fp32(R[a]) / fp32(L[a]), formed by the launcher
+  float sl[3];               // fp32(L[a]) / fp32(R[a]), formed by the launcher
+};
+struct LowresBatch {
+  LowresSample s[kFeedMaxBatch];        // 40 B a record
+};
+
+// the patch voxel that low-resolution cell i stands for (interpolate's "nearest-exact"): min(floor(fp32(fp32(i + 0.5) sn)), R - 1)
+__device__ __forceinline__ int lowres_near(int i, float sn, int R) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float c = (float)i + 0.5f;                                              // exact below 2^23
+  const float p = c * sn;                                                       // >= 0: the conversion below is the floor
+  const int v = p < 2147483648.f ? (int)p : R - 1;                              // 2^31 and above is beyond every R - 1
+  return v < R - 1 ? v : R - 1;
+}
+
+struct LowresTap {
+  int s0, s1;                // the two patch voxels along one axis
+  float w0, w1;              // their weights
+};
+
+// one axis of output index o (interpolate's "linear" with align_corners=False on the low-resolution cells, then lowres_near): src is
+// sl (o + 0.5) - 0.5 rounded ONCE (one fma), negative -> 0; i0 = min(int(src), L - 1), i1 = i0 + (i0 < L - 1); w1 = src - i0 clipped to
+// [0, 1], w0 = 1 - w1.  Both voxels lie in [0, R - 1] whatever the arguments.
+__device__ __forceinline__ LowresTap lowres_tap(int o, int L, int R, float sn, float sl) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  float src = fmaf(sl, (float)o + 0.5f, -0.5f);
+  src = src < 0.f ? 0.f : src;
+  int i0 = src < 2147483648.f ? (int)src : L - 1;
+  i0 = i0 < L - 1 ? i0 : L - 1;
+  const int i1 = i0 + (i0 < L - 1 ? 1 : 0);
+  float w1 = src - (float)i0;
+  w1 = w1 < 0.f ? 0.f : w1;
+  w1 = w1 > 1.f ? 1.f : w1;
+  LowresTap t;
+  t.s0 = lowres_near(i0, sn, R);
+  t.s1 = lowres_near(i1, sn, R);
+  t.w0 = 1.f - w1;
+  t.w1 = w1;
+  return t;
+}
+
+// a v0 + b v1 in double, the two products rounded (exact when a and b came from fp32 values), then the sum
+__device__ __forceinline__ double lowres_mix(double a, float v0, double b, float v1) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double p = a * (double)v0;
+  const double q = b * (double)v1;
+  return p + q;
+}
+
+// Simulated low resolution (nnU-Net's SimulateLowResolutionTransform as batchgeneratorsv2 defines it: interpolate "nearest-exact" down
+// to L, "trilinear" back up to R) as ONE gather: src -> dst, both [B][R0][R1][R2] fp32 and distinct; the low-resolution volume is never
+// written, each output reads the 8 patch voxels its 8 low-resolution cells stand for.  grid (x, B), 256 threads.  V = 4: R2 % 4 == 0 and
+// dst is 16-byte aligned, a thread forms the four outputs of one quad along axis 2 (they share the taps of axes 0 and 1) and writes 16
+// bytes; V = 1: one voxel.  The value: along axis 2, then 1, then 0, in double, one rounding to fp32 at the end.  No LDS.
+template <int V>
+__global__ __launch_bounds__(kIntensityThreads) void intensity_lowres_kernel(LowresBatch lb, const float* __restrict__ src,
+                                                                             float* __restrict__ dst, int R0, int R1, int R2, unsigned per) {
+  static_assert(V == 1 || V == 4, "one voxel or one quad per thread");
+  const int b = blockIdx.y;
+  const LowresSample& s = lb.s[b];
+  if (!s.on) return;
+  const float* __restrict__ x = src + (long)b * per;
+  float* __restrict__ y = dst + (long)b * per;
+  const unsigned row = (unsigned)R2 / V;                                        // groups along axis 2
+  const unsigned groups = per / V;
+  for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += gridDim.x * blockDim.x) {
+    const unsigned line = q / row;
+    const int o2 = (int)(q - line * row) * V;
+    const int o0 = (int)(line / (unsigned)R1), o1 = (int)(line - (unsigned)o0 * (unsigned)R1);
+    const LowresTap t0 = lowres_tap(o0, s.L[0], R0, s.sn[0], s.sl[0]);
+    const LowresTap t1 = lowres_tap(o1, s.L[1], R1, s.sn[1], s.sl[1]);
+    const float* __restrict__ p00 = x + ((long)t0.s0 * R1 + t1.s0) * R2;
+    const float* __restrict__ p01 = x + ((long)t0.s0 * R1 + t1.s1) * R2;
+    const float* __restrict__ p10 = x + ((long)t0.s1 * R1 + t1.s0) * R2;
+    const float* __restrict__ p11 = x + ((long)t0.s1 * R1 + t1.s1) * R2;
+    float v[V];
+#pragma unroll
+    for (int t = 0; t < V; ++t) {
+      const LowresTap t2 = lowres_tap(o2 + t, s.L[2], R2, s.sn[2], s.sl[2]);
+      const double a00 = lowres_mix((double)p00[t2.s0], t2.w0, (double)p00[t2.s1], t2.w1);
+      const double a01 = lowres_mix((double)p01[t2.s0], t2.w0, (double)p01[t2.s1], t2.w1);
+      const double a10 = lowres_mix((double)p10[t2.s0], t2.w0, (double)p10[t2.s1], t2.w1);
+      const double a11 = lowres_mix((double)p11[t2.s0], t2.w0, (double)p11[t2.s1], t2.w1);
+      const double c0 = lowres_mix(a00, t1.w0, a01, t1.w1);
+      const double c1 = lowres_mix(a10, t1.w0, a11, t1.w1);
+      v[t] = (float)lowres_mix(c0, t0.w0, c1, t0.w1);
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(y + (long)q * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+      y[q] = v[0];
+    }
+  }
+}
+
+// the way back: src -> dst for the samples that drew low resolution, the others are not touched.  grid (x, B), 256 threads; V = 4: per % 4
+// == 0 and both are 16-byte aligned.
+template <int V>
+__global__ __launch_bounds__(kIntensityThreads) void intensity_lowres_copy_kernel(LowresBatch lb, const float* __restrict__ src,
+                                                                                  float* __restrict__ dst, unsigned per) {
+  static_assert(V == 1 || V == 4, "4 or 16 bytes per thread");
+  const int b = blockIdx.y;
+  if (!lb.s[b].on) return;
+  const float* __restrict__ x = src + (long)b * per;
+  float* __restrict__ y = dst + (long)b * per;
+  const unsigned groups = per / V;
+  for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += gridDim.x * blockDim.x) {
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(y + (long)q * 4) = *reinterpret_cast<const float4*>(x + (long)q * 4);
+    } else {
+      y[q] = x[q];
+    }
   }
 }
 

@@ -1,22 +1,28 @@
-"""Intensity stage of the 3-D device feed: Gaussian noise, Gaussian blur, contrast and gamma on the patch.
+"""Intensity stage of the 3-D device feed: Gaussian noise, Gaussian blur, simulated low resolution, contrast and gamma on the patch.
 
 The geometric feeds (``OnDeviceAugment``, ``OnDeviceAugmentAMOS``, ``OnDeviceAugmentPosNeg``) write the image batch ``[B,1,R0,R1,R2]``
 fp32; ``IntensityAugment.apply`` then acts on it IN PLACE, on the same stream, without a word from the host.  Labels are untouched.  The
-transforms stand for nnU-Net's ``GaussianNoiseTransform``, ``GaussianBlurTransform``, ``ContrastAugmentationTransform`` (with
-``preserve_range``) and ``GammaTransform`` (with ``invert_image``), MONAI's ``RandGaussianNoised``, ``RandGaussianSmoothd`` and
+transforms stand for nnU-Net's ``GaussianNoiseTransform``, ``GaussianBlurTransform``, ``SimulateLowResolutionTransform``,
+``ContrastAugmentationTransform`` (with ``preserve_range``) and ``GammaTransform`` (with ``invert_image``), MONAI's
+``RandGaussianNoised``, ``RandGaussianSmoothd`` and
 ``RandAdjustContrastd``, and the reference's own ``RandomNoise`` (``dataloaders/brats2019.py:150-161``, clipped Gaussian noise).  Per
 sample, in this order, each drawn independently and OFF by default:
 
 1. noise: ``x += n``, ``n ~ N(0, sigma^2)``, optionally clipped to ``+-clip * sigma``;
 2. blur: ``scipy.ndimage.gaussian_filter(x, sigma, mode="reflect", truncate=4.0)``;
-3. contrast: ``(x - mean) * f + mean`` clipped to the sample's ``[min, max]``;
-4. gamma: ``((x - mn) / (mx - mn + 1e-7)) ** g * (mx - mn) + mn``, on ``-x`` and negated again with ``invert``.
+3. low resolution: ``interpolate(interpolate(x, size=L, mode="nearest-exact"), size=R, mode="trilinear")`` with the low extents
+   ``L = lowres_extents(R, zooms)``; nnU-Net applies it behind contrast, here it stands BEFORE the statistics, so that one statistics
+   pass serves contrast and gamma (DESIGN.md says why that is deliberate);
+4. contrast: ``(x - mean) * f + mean`` clipped to the sample's ``[min, max]``;
+5. gamma: ``((x - mn) / (mx - mn + 1e-7)) ** g * (mx - mn) + mn``, on ``-x`` and negated again with ``invert``.
 
 The definition, rounding by rounding, is in DESIGN.md §2 "Intensity stage of the 3-D feed"; ``tests/intensity_feed_ref.py`` restates it
-in numpy.  Blur, statistics and contrast equal the restatement bit for bit; noise and gamma go through ``log`` / ``cos`` / ``pow`` in
+in numpy (``tests/lowres_feed_ref.py`` for low resolution, which is also compared with torch's own ``interpolate`` on the CPU).  Blur, low
+resolution, statistics and contrast equal the restatement bit for bit; noise and gamma go through ``log`` / ``cos`` / ``pow`` in
 double and may differ from numpy's only where a double result sits on an fp32 rounding tie.  With every probability 0 nothing is drawn
 and nothing is launched.  **Parity with MONAI's and nnU-Net's own code is unpinned**: neither is installed where this package is built
-and tested; MONAI's smoothing kernel, for one, is truncated and normalised differently from scipy's.
+and tested; MONAI's smoothing kernel, for one, is truncated and normalised differently from scipy's.  For low resolution what is pinned
+is the ``interpolate`` chain that batchgeneratorsv2's class is made of, not the class.
 """
 from __future__ import annotations
 
@@ -33,9 +39,11 @@ BLUR_MAX_RADIUS = 12                # kBlurMaxRadius: r = int(4 sigma + 0.5) <= 
 BLUR_MAX_LINE = 4096                # kBlurLineFloats: the largest extent of the contiguous axis the blur takes
 INTENSITY_WS_DOUBLES = 16 * 64 * 3  # doubles of scratch icl_intensity_stats takes (kFeedMaxBatch * kIntensityStatBlocks * 3)
 ROW_LENGTH = 11
+LOWRES_ROW_LENGTH = 15              # a row that carries low resolution: the 11, then (lowres, z0, z1, z2)
 
 # a row of draw_intensity_params: (noise, seed, noise sigma, noise clip, blur, blur sigma, contrast, f, gamma, g, invert)
 _NOISE, _SEED, _NSIGMA, _NCLIP, _BLUR, _BSIGMA, _CONTRAST, _F, _GAMMA, _G, _INVERT = range(ROW_LENGTH)
+_LOWRES, _Z0 = 11, 12
 OFF_ROW = (0, 0, 1.0, 0.0, 0, 1.0, 0, 1.0, 0, 1.0, 0)      # no transform; every field legal for the C ABI
 
 
@@ -53,6 +61,14 @@ def blur_weights(sigma: float) -> np.ndarray:
     phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
     phi = phi / phi.sum()
     return phi[r:].copy()
+
+
+def lowres_extents(roi: Sequence[int], zooms: Sequence[float]) -> Tuple[int, ...]:
+    """The low extents of a patch of ``roi`` under ``zooms``: ``max(1, int(np.rint(R_a * z_a)))`` per axis, the product in double and
+    ties to even, as Python's ``round`` in nnU-Net."""
+    if len(roi) != len(zooms):
+        raise ValueError(f"lowres_extents: {len(roi)} extents, {len(zooms)} zooms")
+    return tuple(max(1, int(np.rint(float(r) * float(z)))) for r, z in zip(roi, zooms))
 
 
 def _probability(name: str, p) -> float:
@@ -77,8 +93,27 @@ def _factor_range(name: str, v) -> Tuple[float, float]:
     return float(a[0]), float(a[1])
 
 
+def _zoom_range(name: str, v) -> Tuple[float, float]:
+    a = np.asarray(v, dtype=np.float64).reshape(-1)
+    if a.size != 2 or not np.isfinite(a).all() or not 0.0 < a[0] <= a[1] <= 1.0:
+        raise ValueError(f"{name} {v!r} must be (lo, hi) with 0 < lo <= hi <= 1")
+    return float(a[0]), float(a[1])
+
+
+def _axes(name: str, v) -> Tuple[int, ...]:
+    try:
+        axes = [int(a) for a in v]
+        ok = len(axes) >= 1 and len(set(axes)) == len(axes) and all(a in (0, 1, 2) and a == b for a, b in zip(axes, v))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{name} {v!r} must name one to three distinct axes out of 0, 1, 2")
+    return tuple(sorted(axes))
+
+
 def _intensity_arguments(noise_prob=0.0, noise_sigma=0.1, noise_clip=0.0, blur_prob=0.0, blur_sigma=(0.5, 1.0), contrast_prob=0.0,
-                         contrast_range=(0.75, 1.25), gamma_prob=0.0, gamma_range=(0.7, 1.5), invert_prob=0.0) -> tuple:
+                         contrast_range=(0.75, 1.25), gamma_prob=0.0, gamma_range=(0.7, 1.5), invert_prob=0.0, lowres_prob=0.0,
+                         lowres_zoom=(0.5, 1.0), lowres_per_axis=False, lowres_axes=(0, 1, 2)) -> tuple:
     """The keywords of ``draw_intensity_params``, checked, in ``_draw_row``'s order; an unknown keyword is a ``TypeError``."""
     clip = float(noise_clip)
     if not np.isfinite(clip) or clip < 0:
@@ -88,7 +123,9 @@ def _intensity_arguments(noise_prob=0.0, noise_sigma=0.1, noise_clip=0.0, blur_p
         raise ValueError(f"blur_sigma {blur_sigma!r}: the radius int(4 sigma + 0.5) = {blur_radius(blur[-1])} exceeds {BLUR_MAX_RADIUS}")
     return (_probability("noise_prob", noise_prob), _sigma_range("noise_sigma", noise_sigma), clip, _probability("blur_prob", blur_prob), blur,
             _probability("contrast_prob", contrast_prob), _factor_range("contrast_range", contrast_range),
-            _probability("gamma_prob", gamma_prob), _factor_range("gamma_range", gamma_range), _probability("invert_prob", invert_prob))
+            _probability("gamma_prob", gamma_prob), _factor_range("gamma_range", gamma_range), _probability("invert_prob", invert_prob),
+            _probability("lowres_prob", lowres_prob), _zoom_range("lowres_zoom", lowres_zoom), bool(lowres_per_axis),
+            _axes("lowres_axes", lowres_axes))
 
 
 def _draw_sigma(rng, spec) -> float:
@@ -104,7 +141,7 @@ def _draw_factor(rng, lo: float, hi: float) -> float:
 
 
 def _draw_row(rng, noise_prob, noise_sigma, noise_clip, blur_prob, blur_sigma, contrast_prob, contrast_range, gamma_prob, gamma_range,
-              invert_prob) -> tuple:
+              invert_prob, lowres_prob=0.0, lowres_zoom=(0.5, 1.0), lowres_per_axis=False, lowres_axes=(0, 1, 2)) -> tuple:
     row = list(OFF_ROW)
     if noise_prob > 0 and rng.rand() < noise_prob:
         row[_NOISE] = 1
@@ -114,6 +151,18 @@ def _draw_row(rng, noise_prob, noise_sigma, noise_clip, blur_prob, blur_sigma, c
     if blur_prob > 0 and rng.rand() < blur_prob:
         row[_BLUR] = 1
         row[_BSIGMA] = _draw_sigma(rng, blur_sigma)
+    lowres = None
+    if lowres_prob > 0:                                  # drawn here, between blur and contrast; kept behind the 11 fields
+        lowres = [0, 1.0, 1.0, 1.0]
+        if rng.rand() < lowres_prob:
+            lowres[0] = 1
+            if lowres_per_axis:
+                for a in lowres_axes:
+                    lowres[1 + a] = float(rng.uniform(*lowres_zoom))
+            else:
+                z = float(rng.uniform(*lowres_zoom))
+                for a in lowres_axes:
+                    lowres[1 + a] = z
     if contrast_prob > 0 and rng.rand() < contrast_prob:
         row[_CONTRAST] = 1
         row[_F] = float(np.float32(_draw_factor(rng, *contrast_range)))
@@ -122,6 +171,8 @@ def _draw_row(rng, noise_prob, noise_sigma, noise_clip, blur_prob, blur_sigma, c
         if invert_prob > 0:
             row[_INVERT] = int(rng.rand() < invert_prob)
         row[_G] = _draw_factor(rng, *gamma_range)
+    if lowres is not None:
+        row += lowres
     return tuple(row)
 
 
@@ -132,16 +183,24 @@ def draw_intensity_params(rng=np.random, n: int = 1, **keywords) -> List[tuple]:
     1. noise (``noise_prob > 0``): ``rng.rand() < noise_prob``; ONLY IF true, ``seed = rng.randint(0, 2**32)``, then
        ``sigma = rng.uniform(lo, hi)`` ONLY IF ``noise_sigma`` is a pair (a single number is used as it is, without a draw);
     2. blur (``blur_prob > 0``): ``rng.rand() < blur_prob``; ONLY IF true, ``sigma = rng.uniform(lo, hi)`` ONLY IF ``blur_sigma`` is a pair;
-    3. contrast (``contrast_prob > 0``): ``rng.rand() < contrast_prob``; ONLY IF true, nnU-Net's factor: ``rng.rand() < 0.5 and lo < 1``
+    3. low resolution (``lowres_prob > 0``): ``rng.rand() < lowres_prob``; ONLY IF true, the zoom: ONE ``rng.uniform(lo, hi)`` shared by
+       the axes of ``lowres_axes``, or with ``lowres_per_axis`` one ``rng.uniform(lo, hi)`` per listed axis in increasing axis order;
+       an axis that is not listed gets the zoom 1;
+    4. contrast (``contrast_prob > 0``): ``rng.rand() < contrast_prob``; ONLY IF true, nnU-Net's factor: ``rng.rand() < 0.5 and lo < 1``
        chooses ``rng.uniform(lo, 1)``, otherwise ``rng.uniform(max(lo, 1), hi)``; the factor is rounded to fp32;
-    4. gamma (``gamma_prob > 0``): ``rng.rand() < gamma_prob``; ONLY IF true, ``invert = rng.rand() < invert_prob`` ONLY IF
+    5. gamma (``gamma_prob > 0``): ``rng.rand() < gamma_prob``; ONLY IF true, ``invert = rng.rand() < invert_prob`` ONLY IF
        ``invert_prob > 0``, then ``g`` from ``gamma_range`` as the contrast factor is drawn (kept in double).
 
     Returns ``n`` rows of 11 values ``(noise, seed, noise sigma, noise clip, blur, blur sigma, contrast, f, gamma, g, invert)``: the
     five flags are 0 or 1, and the fields of a transform that was not drawn hold neutral legal values (``OFF_ROW``).  Keywords and
     defaults: ``noise_prob=0, noise_sigma=0.1, noise_clip=0`` (0: no clipping; the reference's ``RandomNoise`` is ``noise_sigma=0.1,
     noise_clip=2``), ``blur_prob=0, blur_sigma=(0.5, 1.0), contrast_prob=0, contrast_range=(0.75, 1.25), gamma_prob=0,
-    gamma_range=(0.7, 1.5), invert_prob=0``."""
+    gamma_range=(0.7, 1.5), invert_prob=0``.
+
+    While ``lowres_prob`` is 0 the rows are these 11 values.  With ``lowres_prob > 0`` EVERY row has 15: the 11, then ``(lowres, z0, z1,
+    z2)``, the flag and the zoom per axis in (0, 1] (1, 1, 1 where the transform was not drawn); ``lowres_extents(roi, (z0, z1, z2))``
+    gives the low extents.  Keywords: ``lowres_prob=0, lowres_zoom=(0.5, 1.0)`` (``0 < lo <= hi <= 1``), ``lowres_per_axis=False,
+    lowres_axes=(0, 1, 2)`` (nnU-Net's ``ignore_axes`` are the axes left out)."""
     args = _intensity_arguments(**keywords)
     n = int(n)
     if n < 0:
@@ -150,14 +209,16 @@ def draw_intensity_params(rng=np.random, n: int = 1, **keywords) -> List[tuple]:
 
 
 def _checked_rows(params, n: int) -> List[tuple]:
-    """Rows as ``apply`` takes them: ``n`` rows of 11 values, flags 0 or 1, every field what the C ABI accepts."""
+    """Rows as ``apply`` takes them: ``n`` rows of 11 values, or of 15 with low resolution, flags 0 or 1, every field what the C ABI
+    accepts."""
     if len(params) != n:
         raise ValueError(f"IntensityAugment.apply: one intensity row of {ROW_LENGTH} values per sample ({n}), got {len(params)}")
     rows = []
     for j, row in enumerate(params):
-        if len(row) != ROW_LENGTH:
-            raise ValueError(f"IntensityAugment.apply: intensity row {j} has {len(row)} values, {ROW_LENGTH} expected")
-        for k in (_NOISE, _BLUR, _CONTRAST, _GAMMA, _INVERT):
+        if len(row) not in (ROW_LENGTH, LOWRES_ROW_LENGTH):
+            raise ValueError(f"IntensityAugment.apply: intensity row {j} has {len(row)} values, {ROW_LENGTH} expected "
+                             f"(or {LOWRES_ROW_LENGTH} with low resolution)")
+        for k in (_NOISE, _BLUR, _CONTRAST, _GAMMA, _INVERT) + ((_LOWRES,) if len(row) == LOWRES_ROW_LENGTH else ()):
             if row[k] not in (0, 1):
                 raise ValueError(f"IntensityAugment.apply: intensity row {j}: flag {row[k]!r} in field {k} (must be 0 or 1)")
         seed = row[_SEED]
@@ -168,6 +229,9 @@ def _checked_rows(params, n: int) -> List[tuple]:
                 raise ValueError(f"IntensityAugment.apply: intensity row {j}: {name} {row[k]!r} must be finite and positive")
         if not np.isfinite(row[_NCLIP]) or row[_NCLIP] < 0:
             raise ValueError(f"IntensityAugment.apply: intensity row {j}: noise clip {row[_NCLIP]!r} must be finite and non-negative")
+        for z in row[_Z0:]:
+            if not np.isfinite(z) or not 0.0 < z <= 1.0:
+                raise ValueError(f"IntensityAugment.apply: intensity row {j}: low-resolution zoom {z!r} must be finite and in (0, 1]")
         rows.append(tuple(row))
     return rows
 
@@ -177,10 +241,11 @@ class IntensityAugment:
     fp32 IN PLACE with the rows ``params`` (``draw(B)`` when not given) and returns it; batches of more than 16 go as chunks of 16.
     The keyword arguments are those of ``draw_intensity_params``; every one is checked here, and so is the blur's reach: the largest
     radius ``int(4 * sigma + 0.5)`` must not exceed 12 nor the smallest extent of ``roi`` (one reflection must suffice), and
-    ``roi[2] <= 4096`` when the blur is on.  The object owns the blur's scratch buffer (16 patches, allocated at the first blurred
-    batch and kept), the statistics' workspace, and ``stats``: after an ``apply`` in which some sample drew a transform, a device
-    tensor ``[B,4]`` fp32 whose row ``b`` holds ``(min, max, mean, 0)`` of sample ``b`` as contrast and gamma saw it (after noise and
-    blur); rows of samples that drew neither are 0.  ``enabled`` is False when every probability is 0: ``draw`` then draws nothing,
+    ``roi[2] <= 4096`` when the blur is on.  The object owns the scratch buffer of blur and low resolution (16 patches, allocated at
+    the first batch that needs it and kept), the statistics' workspace, and ``stats``: after an ``apply`` in which some sample drew a
+    transform, a device tensor ``[B,4]`` fp32 whose row ``b`` holds ``(min, max, mean, 0)`` of sample ``b`` as contrast and gamma saw it
+    (after noise, blur and low resolution); rows of samples that drew neither are 0.  With ``lowres_prob > 0`` the rows of ``draw``
+    have 15 values, otherwise 11; ``apply`` takes both.  ``enabled`` is False when every probability is 0: ``draw`` then draws nothing,
     and an ``apply`` whose rows are all off launches nothing and leaves ``stats`` as it was."""
 
     def __init__(self, roi: Sequence[int] = (96, 96, 96), rng=np.random, **keywords):
@@ -197,7 +262,7 @@ class IntensityAugment:
                 raise ValueError(f"IntensityAugment: blur_sigma {blur_sigma}: the radius {r} exceeds the smallest extent of roi {self.roi}")
             if self.roi[2] > BLUR_MAX_LINE:
                 raise ValueError(f"IntensityAugment: roi {self.roi}: the blur takes at most {BLUR_MAX_LINE} voxels along the last axis")
-        self.enabled = any(self._args[k] > 0 for k in (0, 3, 5, 7))
+        self.enabled = any(self._args[k] > 0 for k in (0, 3, 5, 7, 10))
         self.stats: Optional[torch.Tensor] = None
         self._scratch: Optional[torch.Tensor] = None
         self._ws: Optional[torch.Tensor] = None
@@ -223,7 +288,9 @@ class IntensityAugment:
             raise ValueError(f"IntensityAugment.apply: the batch must be on a HIP device, got {dev}")
         n = int(image.shape[0])
         rows = _checked_rows(self.draw(n) if params is None else params, n)
-        if not any(r[k] for r in rows for k in (_NOISE, _BLUR, _CONTRAST, _GAMMA)):
+        # the low extents per sample; roi itself where the sample did not draw low resolution (and where every zoom rounds to it)
+        extents = [lowres_extents(roi, r[_Z0:]) if len(r) == LOWRES_ROW_LENGTH and r[_LOWRES] else roi for r in rows]
+        if not any(r[k] for r in rows for k in (_NOISE, _BLUR, _CONTRAST, _GAMMA)) and all(e == roi for e in extents):
             return image                                 # nothing drawn: nothing is launched, not even a fill
         need_stats = [int(bool(r[_CONTRAST] or r[_GAMMA])) for r in rows]
         self.stats = torch.zeros((n, 4), dtype=torch.float32, device=dev)
@@ -246,6 +313,11 @@ class IntensityAugment:
                     vals += [float(r[_BLUR]), float(r[_BSIGMA]), *w, *([0.0] * (BLUR_MAX_RADIUS + 1 - len(w)))]
                 p = (ctypes.c_double * len(vals))(*vals)
                 _lib.check(L.icl_intensity_blur(ptr, scratch.data_ptr(), p, m, *roi, stream), "intensity_blur")
+            low = extents[lo:lo + m]
+            if any(e != roi for e in low):
+                scratch = self._buffer("_scratch", INTENSITY_MAX_BATCH * per, torch.float32, dev)
+                p = (ctypes.c_int32 * (4 * m))(*[v for e in low for v in (int(e != roi), *e)])
+                _lib.check(L.icl_intensity_lowres(ptr, scratch.data_ptr(), p, m, *roi, stream), "intensity_lowres")
             if any(need_stats[lo:lo + m]):
                 ws = self._buffer("_ws", INTENSITY_WS_DOUBLES, torch.float64, dev)
                 flags = (ctypes.c_int32 * m)(*need_stats[lo:lo + m])

@@ -563,10 +563,10 @@ int icl_prefix_restore(const void* prediction, int elem_kind, const int32_t* int
                        void* stream);
 
 /* ---- the INTENSITY stage of the 3-D feed (csrc/kernels/intensity.h; the definition is in DESIGN.md "Intensity stage of the 3-D feed"):
- * four entry points that act IN PLACE on the image batch the gather has written, image DEVICE fp32 [batch][R0][R1][R2], in the order
- * noise, blur, stats, point, on the caller's stream.  Every row of `params` is a HOST double row per sample whose flags are exactly 0 or
- * 1; EVERY field of EVERY row is checked, whatever the flags (a caller fills the rows of a sample without the transform with legal
- * values); a launch whose samples all have the flag 0 launches nothing and returns 0.  All four return -1, launching nothing, for a null
+ * five entry points that act on the image batch the gather has written and leave their result in it, image DEVICE fp32
+ * [batch][R0][R1][R2], in the order noise, blur, lowres, stats, point, on the caller's stream.  Every row of `params` is a HOST row per
+ * sample (double; int32 for lowres and stats) whose flags are exactly 0 or 1; EVERY field of EVERY row is checked, whatever the flags (a caller fills the rows of a sample without the transform with legal
+ * values); a launch whose samples all have the flag 0 launches nothing and returns 0.  All five return -1, launching nothing, for a null
  * pointer, batch outside 1..16, an extent below 1, or more than 2^31 - 1 voxels a sample. */
 /* Gaussian noise (nnU-Net GaussianNoiseTransform, MONAI RandGaussianNoised, the reference's RandomNoise, brats2019.py:150-161):
  * params [batch][4] = {flag, seed (an integer in 0 .. 2^32 - 1), sigma, clip}.  x = fp32(x + n), n = fp32(sigma z) clipped to
@@ -580,6 +580,14 @@ int icl_intensity_noise(float* image, const double* params, int batch, int R0, i
  * Refused: a non-finite or non-positive sigma, r above 12, r above the smallest of R0, R1, R2 (one reflection must suffice), a weight
  * outside [0, 1] (or NaN), R2 above 4096. */
 int icl_intensity_blur(float* image, float* scratch, const double* params, int batch, int R0, int R1, int R2, void* stream);
+/* Simulated low resolution (nnU-Net SimulateLowResolutionTransform as batchgeneratorsv2 defines it: interpolate "nearest-exact" down to
+ * the low extents, "trilinear" with align_corners=False back up), between blur and stats.  params HOST int32 [batch][4] = {flag, L0, L1,
+ * L2}, 1 <= L_a <= R_a.  One gather, batch -> scratch, reads per output the 8 patch voxels its 8 low-resolution cells stand for (no
+ * low-resolution volume is written) and combines them in double along axis 2, 1, 0 with one rounding to fp32; a second launch copies
+ * the samples that drew the transform back into the batch.  scratch: DEVICE fp32 of the batch's size, distinct from it.  A sample whose
+ * L_a = R_a on all three axes is the identity and is not launched; L_a = R_a on one axis leaves that axis alone.  Refused: a flag
+ * outside {0, 1}, an L_a outside 1 .. R_a (of ANY row, whatever its flag), scratch == image. */
+int icl_intensity_lowres(float* image, float* scratch, const int32_t* params, int batch, int R0, int R1, int R2, void* stream);
 /* Statistics of the samples whose flag is 1 (those that drew contrast or gamma; nnU-Net ContrastAugmentationTransform's mean, minimum
  * and maximum, MONAI RandAdjustContrast's minimum and maximum): flags HOST int32 [batch]; stats DEVICE fp32 [batch][4] = {min, max,
  * mean, 0}, mean = fp32(double sum / N) with the sum in the fixed order documented at intensity_stats_partial_kernel; the row of a

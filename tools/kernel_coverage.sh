@@ -9,6 +9,9 @@
 #  intensity_stats_finish_kernel, intensity_point_kernel<1> and <4> of intensity.h, the intensity stage of the 3-D feeds, are launched by
 #  tests/test_gpu_intensity_feed.py: every check runs (7, 9, 10) for the one-voxel kernels and (8, 12, 16) for the quad kernels, and the
 #  blur test repeats each shape on a batch that starts 4 bytes past a 16-byte boundary)
+# (intensity_lowres_kernel<1> and <4>, intensity_lowres_copy_kernel<1> and <4> of intensity.h, the simulated low resolution of that stage,
+#  are launched by tests/test_gpu_lowres_feed.py: (7, 9, 10), (9, 11, 13) and a misaligned (8, 12, 16) for the one-voxel kernels, (8, 12, 16)
+#  and 96^3 for the quad kernels)
 # (prefix_box_partial_kernel, prefix_box_finish_kernel, prefix_resample_kernel<1> and <4>, prefix_restore_kernel<uint8_t> and <long long> of
 #  prefix.h, the AMOS cached prefix, are launched by tests/test_gpu_amos_prefix.py: the case list, the quad cases and the restore tests)
 # (the surface-metric kernels of metrics_surface.h — surf_edt_axis2/1/0, surf_reduce, surf_radix<0..5>, surf_finish — are launched by

@@ -27,6 +27,7 @@ _SIGNATURES = {
     "icl_abi_version": (c_int, []),
     "icl_last_error": (c_char_p, []),
     "icl_last_kernel_name": (c_char_p, []),
+    "icl_last_resample_route": (c_char_p, []),
     "icl_conv3d_packed_elems": (c_int64, [I, I, I, I]),
     "icl_conv3d_pack_weights": (c_int, [P, P, I, I, I, I, P]),
     "icl_conv3d_pack_weights_both": (c_int, [P, P, P, I, I, I, P]),

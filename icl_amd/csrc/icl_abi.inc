@@ -49,6 +49,17 @@ namespace {
 
 thread_local char g_err[512] = "";
 thread_local char g_kernel[160] = "";  // name of the conv kernel instantiation chosen by the last launch (bench.py roofline)
+// route of the last pooling / resize / depth-to-space launcher (kernels/pool_resize.h), for the tests: the kernel's name; the three-pass
+// resize backward "x:<k>|y:<k>|z:<k>"; the depth-to-space pair the name + "+big_lds" / "+lds".  Not g_kernel: ops.py reads that one at the
+// end of a timed convolution region.
+thread_local char g_resample[192] = "";
+
+void note_resample(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_resample, sizeof(g_resample), fmt, ap);
+  va_end(ap);
+}
 
 int fail(int code, const char* fmt, ...) {
   va_list ap;
@@ -1054,6 +1065,7 @@ extern "C" {
 int icl_abi_version(void) { return 1; }
 const char* icl_last_error(void) { return g_err; }
 const char* icl_last_kernel_name(void) { return g_kernel; }
+const char* icl_last_resample_route(void) { return g_resample; }
 
 int64_t icl_conv3d_packed_elems(int cout, int cin, int ks, int mode) {
   const int k = mode ? cout : cin, nn = mode ? cin : cout;
@@ -1371,8 +1383,10 @@ int maxpool2_fwd_run(const float* x, const float* ss, float* y, uint8_t* idx, in
   const long total = nc * dout * hout * wout;
   const char* e_x2 = getenv("ICL_MAXPOOL_BWD_X2");
   if ((wout & 1) == 0 && aligned16(x) && ((uintptr_t)y & 7) == 0 && (e_x2 ? atoi(e_x2) : 1)) {
+    note_resample("maxpool2_fwd_x2_kernel");
     ICL_LAUNCH(icl::maxpool2_fwd_x2_kernel, dim3(grid_for(total / 2, 256)), dim3(256), 0, st, x, y, idx, (long)nc, dout, hout, wout, pool_depth, ss);
   } else {
+    note_resample("maxpool2_fwd_kernel");
     ICL_LAUNCH(icl::maxpool2_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, x, y, idx, (long)nc, dout, hout, wout, pool_depth, ss);
   }
   return check_launch(what);
@@ -1416,14 +1430,15 @@ int icl_upsample2x_concat_norm(const float* skip, const float* skip_ss, const fl
   if (!aligned16(skip) || !aligned16(deep) || !aligned16(out)) return fail(-1, "upsample2x_concat_norm: 16-byte alignment");
   hipStream_t st = (hipStream_t)stream;
   const long s = (long)d * h * w, obs = (long)(cs + cd) * s;
+  const long total = (long)n * cd * s;
+  const int di = d / 2, hi = h / 2, wi = w / 2;
+  note_resample("%s|%s", skip_ss ? "copy_rows_norm_kernel" : "copy_rows_kernel", wi % 4 == 0 ? "upsample2x_fwd_x4_kernel" : "upsample2x_fwd_kernel");
   if (skip_ss) {
     ICL_LAUNCH(icl::copy_rows_norm_kernel, dim3(grid_for((long)n * cs * (s >> 2), 256, 1 << 16)), dim3(256), 0, st, skip, out, n, cs, s, obs, skip_ss);
   } else {
     ICL_LAUNCH(icl::copy_rows_kernel, dim3(grid_for((long)n * cs * s, 256)), dim3(256), 0, st, skip, out, (long)n, (long)cs * s, (long)cs * s, obs);
   }
   if (int rc = check_launch("upsample2x_concat_norm: skip")) return rc;
-  const long total = (long)n * cd * s;
-  const int di = d / 2, hi = h / 2, wi = w / 2;
   if (wi % 4 == 0)
     ICL_LAUNCH(icl::upsample2x_fwd_x4_kernel, dim3(grid_for(total / 32, 256, 1 << 16)), dim3(256), 0, st, deep, out + (long)cs * s, n, cd, di, hi, wi, obs,
                deep_ss);
@@ -1436,6 +1451,7 @@ int icl_upsample2x_concat_norm(const float* skip, const float* skip_ss, const fl
 int icl_maxpool2_bwd(const float* gy, const uint8_t* idx, float* gx, int64_t nc, int dout, int hout, int wout, int pool_depth, void* stream) {
   if (!gy || !gx || !idx || nc < 1 || dout < 1 || hout < 1 || wout < 1 || (pool_depth != 1 && pool_depth != 2)) return fail(-1, "maxpool2_bwd: bad argument");
   const long total = nc * dout * hout * wout;
+  note_resample("maxpool2_bwd_kernel");
   ICL_LAUNCH(icl::maxpool2_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, gy, idx, gx, (long)nc, dout, hout, wout,
              pool_depth);
   return check_launch("maxpool2_bwd");
@@ -1456,10 +1472,12 @@ int icl_maxpool2_bwd_add_live(const float* gy, const uint8_t* idx, const float* 
   // two x-neighbouring outputs per thread (16-byte accesses) where the rows allow it; ICL_MAXPOOL_BWD_X2=0: the 8-byte form (A/B)
   const char* e_x2 = getenv("ICL_MAXPOOL_BWD_X2");
   if ((wout & 1) == 0 && aligned16(add) && aligned16(gx) && ((uintptr_t)gy & 7) == 0 && (add_bstride & 3) == 0 && (e_x2 ? atoi(e_x2) : 1)) {
+    note_resample("maxpool2_bwd_add_x2_kernel");
     ICL_LAUNCH(icl::maxpool2_bwd_add_x2_kernel, dim3(grid_for(total / 2, 256)), dim3(256), 0, (hipStream_t)stream, gy, idx, add, gx, (long)n * c, c,
                dout, hout, wout, pool_depth, (long)add_bstride, ncskip);
     return check_launch("maxpool2_bwd_add_x2");
   }
+  note_resample("maxpool2_bwd_add_kernel");
   ICL_LAUNCH(icl::maxpool2_bwd_add_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, gy, idx, add, gx, (long)n * c, c, dout,
              hout, wout, pool_depth, (long)add_bstride, ncskip);
   return check_launch("maxpool2_bwd_add");
@@ -1480,6 +1498,7 @@ int icl_trilinear_fwd(const float* x, float* y, int n, int c, int di, int hi, in
   if (!align_corners && dout == 2 * di && hout == 2 * hi && wout == 2 * wi && wi % 2 == 0 && y_bstride % 4 == 0 && aligned16(y) &&
       total / 16 < (1L << 31)) {   // the decoder's exact 2x upsampling: 2 x 2 x 4 outputs per thread, 2 x 2 x 8 where the rows allow 16-byte loads
     constexpr int x4 = 1;
+    note_resample(x4 && wi % 4 == 0 && aligned16(x) ? "upsample2x_fwd_x4_kernel" : "upsample2x_fwd_kernel");
     if (x4 && wi % 4 == 0 && aligned16(x))
       ICL_LAUNCH(icl::upsample2x_fwd_x4_kernel, dim3(grid_for(total / 32, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x, y, n, c, di, hi,
                  wi, (long)y_bstride, (const float*)nullptr);
@@ -1487,9 +1506,11 @@ int icl_trilinear_fwd(const float* x, float* y, int n, int c, int di, int hi, in
       ICL_LAUNCH(icl::upsample2x_fwd_kernel, dim3(grid_for(total / 16, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x, y, n, c, di, hi, wi,
                  (long)y_bstride, (const float*)nullptr);
   } else if (wout % 4 == 0 && y_bstride % 4 == 0 && aligned16(y) && total / 4 < (1L << 31)) {
+    note_resample("trilinear_fwd_quad_kernel");
     ICL_LAUNCH(icl::trilinear_fwd_quad_kernel, dim3(grid_for(total / 4, 256, 1 << 16)), dim3(256), 0, (hipStream_t)stream, x, y, n, c, di, hi,
                wi, dout, hout, wout, rz, ry, rx, (long)y_bstride, align_corners);
   } else {
+    note_resample("trilinear_fwd_kernel");
     ICL_LAUNCH(icl::trilinear_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, n, c, di, hi, wi, dout, hout,
                wout, rz, ry, rx, (long)y_bstride, align_corners);
   }
@@ -1512,29 +1533,37 @@ int icl_trilinear_bwd(const float* gy, float* gx, void* ws, int n, int c, int di
   int rc;
   if (!al && dout == 2 * di && hout == 2 * hi && wout == 2 * wi && wi % 4 == 0 && gy_bstride % 4 == 0 && aligned16(gy) && aligned16(gx) &&
       (long)n * c * di * hi * wi / 4 < (1L << 31)) {   // exact 2x: one pass, four inputs per thread, no workspace traffic
+    note_resample("upsample2x_bwd_kernel");
     ICL_LAUNCH(icl::upsample2x_bwd_kernel, dim3(grid_for((long)n * c * ((di + icl::kUpSeg - 1) / icl::kUpSeg) * hi * wi / 4, 256, 1 << 16)),
                dim3(256), 0, st, gy, gx, n, c, di, hi,
                wi, (long)gy_bstride);
     return check_launch("upsample2x_bwd");
   }
   // one axis per launch; the vectorised kernels need 16-byte rows and a quad count that fits 32 bits
+  const char* used[3] = {"", "", ""};   // the kernel of each axis pass, for the route record
+  int pass = 0;
   auto axis = [&](const float* src, float* dst, long rows, int li, int lo, long inner, float rs, long sbs, const char* what) -> int {
     const long total = (long)n * rows * li * inner;
     const bool small = total / 4 < (1L << 31) && rows < (1L << 31);
     if (small && inner % 4 == 0 && sbs % 4 == 0 && aligned16(src) && aligned16(dst)) {
+      used[pass++] = "resize_bwd_axis_t4_kernel";
       ICL_LAUNCH(icl::resize_bwd_axis_t4_kernel, dim3(grid_for(total / 4, 256, 1 << 16)), dim3(256), 0, st, src, dst, n, (unsigned)rows, li, lo,
                  (unsigned)(inner / 4), rs, sbs, al);
     } else if (inner == 1 && lo >= 4 * li && lo % 4 == 0 && lo <= 1024 && sbs % 4 == 0 && aligned16(src) && rows * li >= 4096) {
       // big x pass of a >= 4x upscale: rows of dY staged in LDS with coalesced loads
       const long nrows = (long)n * rows;
+      used[pass++] = "resize_bwd_axis_x_lds_kernel";
       ICL_LAUNCH(icl::resize_bwd_axis_x_lds_kernel, dim3((unsigned)cdivl(nrows, icl::kRbxRows)), dim3(256),
                  (size_t)icl::kRbxRows * (lo + 4) * 4, st, src, dst, n, rows, li, lo, rs, sbs, al);
     } else if (small && inner == 1 && li % 4 == 0 && aligned16(dst)) {
+      used[pass++] = "resize_bwd_axis_i4_kernel";
       ICL_LAUNCH(icl::resize_bwd_axis_i4_kernel, dim3(grid_for(total / 4, 256, 1 << 16)), dim3(256), 0, st, src, dst, n, (unsigned)rows, li, lo,
                  rs, sbs, al);
     } else {
+      used[pass++] = "resize_bwd_axis_kernel";
       ICL_LAUNCH(icl::resize_bwd_axis_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, src, dst, n, rows, li, lo, inner, rs, sbs, al);
     }
+    note_resample("x:%s|y:%s|z:%s", used[0], used[1], used[2]);
     return check_launch(what);
   };
   if ((rc = axis(gy, t1, (long)c * dout * hout, wi, wout, 1L, rx, (long)gy_bstride, "resize_bwd_x"))) return rc;
@@ -1563,6 +1592,7 @@ int icl_depth_to_space2(const float* yt, float* out, int n, int d, int h, int w,
   const size_t lds = (size_t)w * (cout * 8 + 2) * 4;
   if (lds > (size_t)kMaxDynLdsBig) return fail(-1, "depth_to_space2: token row does not fit LDS (w * cout too large)");
   if (lds > (size_t)kMaxDynLds) ICL_SET_MAX_DYN_LDS(icl::depth_to_space2_kernel, kMaxDynLdsBig);
+  note_resample("depth_to_space2_kernel%s", lds > (size_t)kMaxDynLds ? "+big_lds" : "+lds");
   ICL_LAUNCH(icl::depth_to_space2_kernel, dim3(h, d, n), dim3(256), lds, (hipStream_t)stream, yt, out, d, h, w, cout, (long)out_bstride);
   return check_launch("depth_to_space2");
 }
@@ -1572,6 +1602,7 @@ int icl_space_to_depth2(const float* g, float* gt, int n, int d, int h, int w, i
   const size_t lds = (size_t)w * (cout * 8 + 2) * 4;
   if (lds > (size_t)kMaxDynLdsBig) return fail(-1, "space_to_depth2: token row does not fit LDS (w * cout too large)");
   if (lds > (size_t)kMaxDynLds) ICL_SET_MAX_DYN_LDS(icl::space_to_depth2_kernel, kMaxDynLdsBig);
+  note_resample("space_to_depth2_kernel%s", lds > (size_t)kMaxDynLds ? "+big_lds" : "+lds");
   ICL_LAUNCH(icl::space_to_depth2_kernel, dim3(h, d, n), dim3(256), lds, (hipStream_t)stream, g, gt, d, h, w, cout, (long)g_bstride);
   return check_launch("space_to_depth2");
 }

@@ -10,9 +10,12 @@
 namespace icl {
 
 // ---- max pooling, window pd x 2 x 2 (pd = 2: MaxPool3d(2); pd = 1: MaxPool2d(2) on a D=1 volume), stride = window.
-// idx = argmax in (dz,dy,dx) scan order with strict '>' so the first maximum wins, as ATen's max_pool does.
+// idx = argmax in (dz,dy,dx) scan order with strict '>' so the first maximum wins, as ATen's max_pool does; a NaN replaces whatever
+// was held (ATen: `(val > maxval) || isnan(val)`), so the LAST NaN of a window in scan order is its value and its index.
 // ss != nullptr: x is a RAW convolution output whose InstanceNorm + ReLU is applied on load (norm.h norm_finalize_stats_kernel): the
 // maximum and its index are those of the normalised tensor (ReLU ties resolve to the first maximum, as on a materialised tensor).
+__device__ __forceinline__ bool pool_takes(float v, float best) { return v > best || v != v; }
+
 __global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                            unsigned char* __restrict__ idx, long NC, int Do, int Ho, int Wo, int pd,
                                                            const float* __restrict__ ss) {
@@ -33,7 +36,7 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const float* __restri
     for (int k = 1; k < nk; ++k) {
       float v = p[((k >> 2) * H + ((k >> 1) & 1)) * (long)W + (k & 1)];
       if (ss) v = norm_relu1(v, sc, sh);
-      if (v > best) { best = v; bi = k; }
+      if (pool_takes(v, best)) { best = v; bi = k; }
     }
     y[o] = best;
     idx[o] = (unsigned char)bi;
@@ -67,11 +70,11 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_x2_kernel(const float* __res
       if (ss) { v.x = norm_relu1(v.x, sc, sh); v.y = norm_relu1(v.y, sc, sh); v.z = norm_relu1(v.z, sc, sh); v.w = norm_relu1(v.w, sc, sh); }
       if (k == 0) { b0 = v.x; b1 = v.z; }
       else {
-        if (v.x > b0) { b0 = v.x; i0 = k; }
-        if (v.z > b1) { b1 = v.z; i1 = k; }
+        if (pool_takes(v.x, b0)) { b0 = v.x; i0 = k; }
+        if (pool_takes(v.z, b1)) { b1 = v.z; i1 = k; }
       }
-      if (v.y > b0) { b0 = v.y; i0 = k + 1; }
-      if (v.w > b1) { b1 = v.w; i1 = k + 1; }
+      if (pool_takes(v.y, b0)) { b0 = v.y; i0 = k + 1; }
+      if (pool_takes(v.w, b1)) { b1 = v.w; i1 = k + 1; }
     }
     *reinterpret_cast<float2*>(y + o) = make_float2(b0, b1);
     idx[o] = (unsigned char)i0;

@@ -24,6 +24,10 @@ int icl_abi_version(void);
 const char* icl_last_error(void);
 /* name of the convolution kernel instantiation picked by the most recent icl_conv3d_* call on this thread (profiling aid) */
 const char* icl_last_kernel_name(void);
+/* For the tests (per thread): which kernel(s) the last pooling / resize / depth-to-space launcher chose (kernels/pool_resize.h).  The
+ * kernel's name; icl_upsample2x_concat_norm "<skip copy>|<deep resize>"; the three-pass icl_trilinear_bwd "x:<k>|y:<k>|z:<k>";
+ * icl_depth_to_space2 / icl_space_to_depth2 the name + "+big_lds" when the launch raised the dynamic-LDS limit, "+lds" otherwise. */
+const char* icl_last_resample_route(void);
 
 /* ---- Conv3d k=3 pad=1 / k=1, stride 1 (networks/utils.py:104,107; networks/unet_3D_icl.py:65,178,196,327).
  * Weights are used in packed form Wp[taps][KP][NP]: mode 0 (forward) K=Cin,N=Cout; mode 1 (dgrad) K=Cout,N=Cin

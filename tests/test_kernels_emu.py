@@ -382,7 +382,9 @@ def test_maxpool_ties_and_grad():
 
 @pytest.mark.parametrize("ins,outs", [((3, 4, 5), (6, 8, 10)), ((2, 2, 2), (12, 12, 12)), ((6, 6, 6), (24, 24, 24)),
                                       ((4, 4, 8), (8, 12, 16)), ((5, 3, 12), (7, 6, 20)),
-                                      ((3, 6, 6), (12, 24, 48)),      # >= 4x along x: LDS-staged x pass of the backward, ragged last row block
+                                      # >= 4x along x, but rows * li = 576 * 6 < 4096 and li % 4 != 0: scalar x and y passes, t4 z pass (the route
+                                      # record says so; the LDS-staged x pass and its ragged last row block are in tests/resample_ref.py)
+                                      ((3, 6, 6), (12, 24, 48)),
                                       # exact 2x: the specialised one-pass kernels (bwd needs W % 4 == 0), incl. size-1 / size-2 axes
                                       ((4, 6, 8), (8, 12, 16)), ((1, 2, 4), (2, 4, 8)), ((6, 6, 6), (12, 12, 12)), ((3, 5, 12), (6, 10, 24))])
 def test_trilinear(ins, outs):

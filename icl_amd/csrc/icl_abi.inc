@@ -2429,6 +2429,86 @@ int icl_crop_rotflip(const void* const* images, const void* const* labels, const
   return check_launch("crop_rotflip");
 }
 
+int icl_crop_rotflip_channels(const void* const* images, const void* const* labels, const int32_t* params, int batch, int channels,
+                              float* image_out, int64_t* label_out, int o0, int o1, int o2, void* stream) {
+  if (!images || !labels || !params || !image_out || !label_out) return fail(-1, "crop_rotflip_channels: null pointer");
+  if (batch < 1 || batch > icl::kFeedMaxBatch)
+    return fail(-1, "crop_rotflip_channels: batch %d out of range (1 <= batch <= %d)", batch, icl::kFeedMaxBatch);
+  if (channels < 1 || channels > icl::kChannelNormMaxChannels)
+    return fail(-1, "crop_rotflip_channels: channels %d out of range (1 <= channels <= %d)", channels, icl::kChannelNormMaxChannels);
+  if (o0 < 1 || o1 < 1 || o2 < 1) return fail(-1, "crop_rotflip_channels: output extents %d x %d x %d (each must be >= 1)", o0, o1, o2);
+  if ((long)o0 * o1 * o2 > 0x7fffffffL)
+    return fail(-1, "crop_rotflip_channels: output extents %d x %d x %d (more than 2^31 - 1 voxels a sample)", o0, o1, o2);
+  icl::FeedBatch fb{};
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* q = params + 11 * b;
+    icl::FeedSample& s = fb.s[b];
+    s.image = (const float*)images[b];
+    s.label = (const uint8_t*)labels[b];
+    s.n0 = q[0]; s.n1 = q[1]; s.n2 = q[2]; s.k = q[3]; s.flip_axis = q[4];
+    s.p0 = q[5]; s.p1 = q[6]; s.p2 = q[7]; s.c0 = q[8]; s.c1 = q[9]; s.c2 = q[10];
+    if (!s.image || !s.label) return fail(-1, "crop_rotflip_channels: sample %d: null volume pointer", b);
+    if (s.n0 < 1 || s.n1 < 1 || s.n2 < 1 || s.k < 0 || s.k > 3 || s.flip_axis > 1 || s.p0 < 0 || s.p1 < 0 || s.p2 < 0)
+      return fail(-1, "crop_rotflip_channels: bad sample %d", b);
+  }
+  const long voxels = (long)o0 * o1 * o2;      // per sample and channel; one grid row per sample
+  const int cap = 2048 / batch;                // 2048 workgroups of 256 threads: every wave slot of the 256 CUs once, the rest by stride
+  if ((o2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
+    ICL_LAUNCH(icl::crop_rotflip_channels_kernel<4>, dim3(grid_for(voxels / 4, 256, cap), batch), dim3(256), 0, (hipStream_t)stream, fb, image_out,
+               (long long*)label_out, channels, o0, o1, o2);
+  } else {
+    ICL_LAUNCH(icl::crop_rotflip_channels_kernel<1>, dim3(grid_for(voxels, 256, cap), batch), dim3(256), 0, (hipStream_t)stream, fb, image_out,
+               (long long*)label_out, channels, o0, o1, o2);
+  }
+  return check_launch("crop_rotflip_channels");
+}
+
+namespace {
+
+int channel_norm_args(const char* what, const float* image, int channels, int64_t voxels, int mask_mode) {
+  if (!image) return fail(-1, "%s: null pointer", what);
+  if (channels < 1 || channels > icl::kChannelNormMaxChannels)
+    return fail(-1, "%s: channels %d out of range (1 <= channels <= %d)", what, channels, icl::kChannelNormMaxChannels);
+  if (voxels < 1 || voxels > 0x7fffffffL) return fail(-1, "%s: %lld voxels a channel (must be in 1 .. 2^31 - 1)", what, (long long)voxels);
+  if (mask_mode < icl::kNormNonzero || mask_mode > icl::kNormAll)
+    return fail(-1, "%s: mask mode %d (0 nonzero, 1 positive, 2 all)", what, mask_mode);
+  return 0;
+}
+
+}  // namespace
+
+int icl_channel_norm_stats(const float* image, int channels, int64_t voxels, int mask_mode, double* stats_out, double* ws, void* stream) {
+  if (!stats_out || !ws) return fail(-1, "channel_norm_stats: null pointer");
+  if (const int rc = channel_norm_args("channel_norm_stats", image, channels, voxels, mask_mode)) return rc;
+  const int blocks = grid_for(cdivl(voxels, 4), icl::kChannelNormThreads, icl::kChannelNormBlocks);
+  const int vec = (voxels & 3) == 0 && aligned16(image) ? 1 : 0;
+  const dim3 grid(blocks, channels), block(icl::kChannelNormThreads);
+  ICL_LAUNCH(icl::channel_norm_partial_kernel<1>, grid, block, 0, (hipStream_t)stream, image, (long)voxels, mask_mode, vec,
+             (const double*)stats_out, ws);
+  if (const int rc = check_launch("channel_norm_partial<1>")) return rc;
+  ICL_LAUNCH(icl::channel_norm_finish_kernel<1>, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)ws, channels, blocks, stats_out);
+  if (const int rc = check_launch("channel_norm_finish<1>")) return rc;
+  ICL_LAUNCH(icl::channel_norm_partial_kernel<2>, grid, block, 0, (hipStream_t)stream, image, (long)voxels, mask_mode, vec,
+             (const double*)stats_out, ws);
+  if (const int rc = check_launch("channel_norm_partial<2>")) return rc;
+  ICL_LAUNCH(icl::channel_norm_finish_kernel<2>, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)ws, channels, blocks, stats_out);
+  return check_launch("channel_norm_finish<2>");
+}
+
+int icl_channel_norm_apply(float* image, int channels, int64_t voxels, int mask_mode, int apply_mode, const double* stats, void* stream) {
+  if (!stats) return fail(-1, "channel_norm_apply: null pointer");
+  if (const int rc = channel_norm_args("channel_norm_apply", image, channels, voxels, mask_mode)) return rc;
+  if (apply_mode != 0 && apply_mode != 1) return fail(-1, "channel_norm_apply: apply mode %d (0 mask, 1 all)", apply_mode);
+  if ((voxels & 3) == 0 && aligned16(image)) {
+    ICL_LAUNCH(icl::channel_norm_apply_kernel<4>, dim3(grid_for(voxels / 4, icl::kChannelNormThreads, 8192), channels),
+               dim3(icl::kChannelNormThreads), 0, (hipStream_t)stream, image, (long)voxels, mask_mode, apply_mode, stats);
+  } else {
+    ICL_LAUNCH(icl::channel_norm_apply_kernel<1>, dim3(grid_for(voxels, icl::kChannelNormThreads, 8192), channels),
+               dim3(icl::kChannelNormThreads), 0, (hipStream_t)stream, image, (long)voxels, mask_mode, apply_mode, stats);
+  }
+  return check_launch("channel_norm_apply");
+}
+
 namespace {
 
 // The argument record of icl_volume_feed / icl_volume_feed_origins from the caller's rows, with every check of both.  device_origins:

@@ -62,6 +62,222 @@ __global__ __launch_bounds__(256) void crop_rotflip_kernel(FeedBatch fb, float* 
   }
 }
 
+// ---- multi-modal volumes: the chain of crop_rotflip_kernel on images [C][n0][n1][n2] (co-registered channels, BraTS's four MR
+// modalities) with ONE label [n0][n1][n2].  The map output voxel -> crop -> padding -> flip -> rot90 -> source index does not depend on
+// the channel, so it is computed once per output position and used for all C channels (channel stride n0 * n1 * n2) and for the
+// label, which is read and written once.  image_out [B][C][o0][o1][o2] fp32, label_out [B][o0][o1][o2] int64.  grid (x, B): one sample
+// per blockIdx.y, so its record is wave-uniform.  One thread per V consecutive depth voxels (V = 4: o2 % 4 == 0 and both outputs 16-byte
+// aligned; the store is always a quad per channel and two 16-byte label stores; the load is a quad where the four sources lie inside
+// the row at a 16-byte aligned address, four guarded scalar loads otherwise: the scheme of window_gather_kernel<4>).  No LDS, no
+// atomics.  With C = 1 the result is crop_rotflip_kernel's bit for bit (the values are copied, never computed with).
+template <int V>
+__global__ __launch_bounds__(256) void crop_rotflip_channels_kernel(FeedBatch fb, float* __restrict__ image_out, long long* __restrict__ label_out,
+                                                                    int C, int o0, int o1, int o2) {
+  static_assert(V == 1 || V == 4, "one voxel or one quad per thread");
+  const int q2 = o2 / V;
+  const unsigned per = (unsigned)o0 * o1 * q2;                                // the launcher keeps o0 * o1 * o2 below 2^31
+  const int b = blockIdx.y;
+  const FeedSample& s = fb.s[b];
+  const long vox = (long)o0 * o1 * o2;                                        // channel stride of the output
+  const long cs = (long)s.n0 * s.n1 * s.n2;                                   // channel stride of the source
+  // extents after rot90: odd k swaps axes 0 and 1
+  const int r0 = (s.k & 1) ? s.n1 : s.n0, r1 = (s.k & 1) ? s.n0 : s.n1;
+  float* __restrict__ img = image_out + (long)b * C * vox;
+  long long* __restrict__ lab = label_out + (long)b * vox;
+  for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < per; r += gridDim.x * blockDim.x) {
+    const int l = (int)(r % q2) * V;
+    const unsigned rj = r / q2;
+    const int j = (int)(rj % o1), i = (int)(rj / o1);
+    const long e = (long)r * V;                                               // = (i * o1 + j) * o2 + l
+    // crop -> padded coordinates -> unpadded (rotated + flipped) coordinates
+    int a = s.c0 + i - s.p0, c = s.c1 + j - s.p1;
+    const int d = s.c2 + l - s.p2;
+    const bool row = a >= 0 && a < r0 && c >= 0 && c < r1;
+    long base = 0;
+    if (row) {
+      if (s.flip_axis == 0) a = r0 - 1 - a;
+      else if (s.flip_axis == 1) c = r1 - 1 - c;
+      int sa, sc;                                                             // rot90 on axes (0, 1): the maps of crop_rotflip_kernel
+      switch (s.k & 3) {
+        case 0: sa = a; sc = c; break;
+        case 1: sa = c; sc = s.n1 - 1 - a; break;
+        case 2: sa = s.n0 - 1 - a; sc = s.n1 - 1 - c; break;
+        default: sa = s.n0 - 1 - c; sc = a; break;
+      }
+      base = ((long)sa * s.n1 + sc) * s.n2;
+    }
+    bool in[V];
+    unsigned lv[V];
+#pragma unroll
+    for (int t = 0; t < V; ++t) {
+      in[t] = row && d + t >= 0 && d + t < s.n2;
+      lv[t] = in[t] ? (unsigned)s.label[base + d + t] : 0u;
+    }
+    const bool inside = V == 4 && row && d >= 0 && d + V <= s.n2;             // the whole quad lies in the row
+    for (int ch = 0; ch < C; ++ch) {
+      const float* __restrict__ src = s.image + ch * cs + base + d;           // dereferenced only where in[t]
+      float v[V];
+      if (inside && ((uintptr_t)src & 15) == 0) {
+        const float4 f = *reinterpret_cast<const float4*>(src);
+        v[0] = f.x;
+        if constexpr (V == 4) { v[1] = f.y; v[2] = f.z; v[3] = f.w; }
+      } else {
+#pragma unroll
+        for (int t = 0; t < V; ++t) v[t] = in[t] ? src[t] : 0.f;
+      }
+      if constexpr (V == 4) {
+        *reinterpret_cast<float4*>(img + ch * vox + e) = make_float4(v[0], v[1], v[2], v[3]);
+      } else {
+        img[ch * vox + e] = v[0];
+      }
+    }
+    if constexpr (V == 4) {
+      uint4* lp = reinterpret_cast<uint4*>(lab + e);                          // labels are 0..255: the high dwords are 0
+      lp[0] = make_uint4(lv[0], 0u, lv[1], 0u);
+      lp[1] = make_uint4(lv[2], 0u, lv[3], 0u);
+    } else {
+      lab[e] = (long long)lv[0];
+    }
+  }
+}
+
+// ---- channel-wise intensity normalisation of a resident volume [C][voxels] (MONAI NormalizeIntensityd(nonzero, channel_wise); the
+// reference's itensity_normalize_one_volume): per channel, over the voxels of the mask (kNormNonzero: x != 0, kNormPositive: x > 0,
+// kNormAll), count, mean and POPULATION standard deviation in double, two passes: sum and count, then sum of (x - mean)^2 with the mean
+// read from `stats`.  No atomics.  The fixed order of every sum (that of intensity_stats_partial_kernel): voxel i belongs to slot (i / 4)
+// mod (256 G), G = gridDim.x a function of `voxels` alone; every slot adds its voxels in increasing i to a double that starts at 0; the
+// 256 slots of a workgroup are halved eight times, slot t += slot t + d for d = 128, 64, ..., 1; channel_norm_finish_kernel adds the
+// G workgroup sums in index order.  stats [C][4] double = {count, mean, std, 0}; an empty mask gives {0, 0, 0, 0}.
+constexpr int kChannelNormThreads = 256;
+constexpr int kChannelNormBlocks = 256;      // most workgroups per channel: ws holds [C][kChannelNormBlocks][2] doubles
+constexpr int kChannelNormMaxChannels = 16;
+enum ChannelNormMask { kNormNonzero = 0, kNormPositive = 1, kNormAll = 2 };
+
+__device__ __forceinline__ bool channel_norm_in_mask(float x, int mask_mode) {
+  return mask_mode == kNormAll || (mask_mode == kNormPositive ? x > 0.f : x != 0.f);
+}
+
+// grid (G, C), 256 threads.  PASS 1: ws[c][g] = {sum of x, count}.  PASS 2: ws[c][g] = {sum of (x - mean_c)^2, count}, mean_c = stats[4 c + 1].
+// vec: the volume is 16-byte aligned and voxels % 4 == 0, so every group of every channel is one 16-byte load.
+template <int PASS>
+__global__ __launch_bounds__(kChannelNormThreads) void channel_norm_partial_kernel(const float* __restrict__ image, long voxels, int mask_mode, int vec,
+                                                                                   const double* __restrict__ stats, double* __restrict__ ws) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  __shared__ double ssum[kChannelNormThreads], scnt[kChannelNormThreads];
+  const int ch = blockIdx.y;
+  const float* __restrict__ x = image + (long)ch * voxels;
+  double mean = 0.0;
+  if constexpr (PASS == 2) mean = stats[4 * ch + 1];
+  double acc = 0.0, cnt = 0.0;
+  const unsigned groups = (unsigned)((voxels + 3) / 4);                       // the launcher keeps voxels below 2^31
+  for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += gridDim.x * blockDim.x) {
+    const long first = (long)q * 4;
+    float v[4];
+    int n = 4;
+    if (vec) {
+      const float4 f = *reinterpret_cast<const float4*>(x + first);
+      v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+    } else {
+      n = voxels - first < 4 ? (int)(voxels - first) : 4;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) v[t] = t < n ? x[first + t] : 0.f;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (t < n && channel_norm_in_mask(v[t], mask_mode)) {
+        if constexpr (PASS == 1) {
+          acc = acc + (double)v[t];
+        } else {
+          const double dv = (double)v[t] - mean;
+          acc = acc + dv * dv;
+        }
+        cnt = cnt + 1.0;
+      }
+    }
+  }
+  ssum[threadIdx.x] = acc; scnt[threadIdx.x] = cnt;
+  __syncthreads();
+  for (int d = kChannelNormThreads / 2; d >= 1; d >>= 1) {
+    if ((int)threadIdx.x < d) {
+      ssum[threadIdx.x] = ssum[threadIdx.x] + ssum[threadIdx.x + d];
+      scnt[threadIdx.x] = scnt[threadIdx.x] + scnt[threadIdx.x + d];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double* o = ws + ((long)ch * kChannelNormBlocks + blockIdx.x) * 2;
+    o[0] = ssum[0]; o[1] = scnt[0];
+  }
+}
+
+// grid (1), 64 threads, thread c finishes channel c.  PASS 1: stats[c] = {count, sum / count, 0, 0}.  PASS 2: stats[c][2] = sqrt(sum / count).
+// A channel whose mask is empty gets {0, 0, 0, 0}.
+template <int PASS>
+__global__ __launch_bounds__(64) void channel_norm_finish_kernel(const double* __restrict__ ws, int channels, int blocks, double* __restrict__ stats) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int ch = threadIdx.x;
+  if (ch >= channels) return;
+  const double* p = ws + (long)ch * kChannelNormBlocks * 2;
+  double sum = p[0], cnt = p[1];
+  for (int g = 1; g < blocks; ++g) {
+    sum = sum + p[2 * g];
+    cnt = cnt + p[2 * g + 1];
+  }
+  double* o = stats + 4 * ch;
+  if constexpr (PASS == 1) {
+    o[0] = cnt;
+    o[1] = cnt > 0.0 ? sum / cnt : 0.0;
+    o[2] = 0.0;
+    o[3] = 0.0;
+  } else {
+    o[2] = cnt > 0.0 ? sqrt(sum / cnt) : 0.0;
+  }
+}
+
+// x <- (x - m) / s in fp32, m = fp32(mean), s = fp32(std) with 0 -> 1: a true subtraction and a true division, each rounded on its own.
+// apply_all = 0: only the voxels of the mask change; 1: every voxel.  A channel with an empty mask is left as it is.  grid (x, C).
+template <int V>
+__global__ __launch_bounds__(kChannelNormThreads) void channel_norm_apply_kernel(float* __restrict__ image, long voxels, int mask_mode, int apply_all,
+                                                                                 const double* __restrict__ stats) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  static_assert(V == 1 || V == 4, "4 or 16 bytes per thread");
+  const int ch = blockIdx.y;
+  const double* st = stats + 4 * ch;
+  if (!(st[0] > 0.0)) return;
+  const float m = (float)st[1];
+  float sd = (float)st[2];
+  if (sd == 0.f) sd = 1.f;
+  float* __restrict__ x = image + (long)ch * voxels;
+  const unsigned groups = (unsigned)(voxels / V);
+  for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += gridDim.x * blockDim.x) {
+    float v[V];
+    if constexpr (V == 4) {
+      const float4 f = *reinterpret_cast<const float4*>(x + (long)q * 4);
+      v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+    } else {
+      v[0] = x[q];
+    }
+#pragma unroll
+    for (int t = 0; t < V; ++t) {
+      if (apply_all || channel_norm_in_mask(v[t], mask_mode)) {
+        const float dv = v[t] - m;
+        v[t] = dv / sd;
+      }
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(x + (long)q * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+      x[q] = v[0];
+    }
+  }
+}
+
 // ---- 2-D trainers: RandomGenerator (dataloaders/dataset.py:147-166 of the reference) as ONE gather over slices resident in HBM.
 // The reference chain is "maybe rot90 + flip, else maybe ndimage.rotate by an integer angle, then ndimage.zoom to the patch", all
 // order 0.  Two nearest-neighbour samplings compose into one gather: the zoom maps the output pixel to an INTEGER pixel (a, b) of

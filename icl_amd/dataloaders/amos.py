@@ -224,6 +224,13 @@ def amos_volume_store(samples: Iterable, device) -> DeviceVolumeStore:
     return DeviceVolumeStore(volumes, device)
 
 
+def _single_channel_store(store, who: str):
+    """The AMOS feeds, the rank index and the cached prefix take ``[W,H,D]`` volumes only."""
+    if getattr(store, "multichannel", False):
+        raise ValueError(f"{who}: the store holds multi-channel [{store.channels},W,H,D] volumes; the AMOS feeds are single-channel "
+                         "(CT is one channel): use dataloaders.brats2019.OnDeviceAugment for multi-modal volumes")
+
+
 class OnDeviceAugmentAMOS:
     """The random transforms of the AMOS trainer (``:102-133``) + batch collation on the GPU.  ``batch(indices)`` returns
     ``{'image': [B,1,*roi] fp32, 'label': [B,1,*roi] int64}``: the label carries MONAI's channel axis, so the trainer's
@@ -239,9 +246,13 @@ class OnDeviceAugmentAMOS:
     ``intensity``: None, or an ``IntensityAugment`` for the same ``roi`` (``dataloaders/intensity.py``: Gaussian noise, blur, contrast
     and gamma).  ``batch`` then draws the batch's intensity rows AFTER all of its geometric rows, in sample order, from the stage's own
     ``rng`` (pass the loader's generator to the stage to keep one stream), and applies the stage in place behind the gather, on the
-    same stream.  With None, or a stage whose probabilities are all 0, nothing is drawn or launched for it."""
+    same stream.  With None, or a stage whose probabilities are all 0, nothing is drawn or launched for it.
+
+    Single-channel only (CT is one channel): a store of ``[C,W,H,D]`` volumes is refused with a ``ValueError``, by this feed, its
+    affine stage and ``OnDeviceAugmentPosNeg`` alike; multi-modal volumes go through ``dataloaders.brats2019.OnDeviceAugment``."""
 
     def __init__(self, store: DeviceVolumeStore, roi: Sequence[int] = (96, 96, 96), rng=np.random, intensity=None, **probabilities):
+        _single_channel_store(store, type(self).__name__)
         self.store = store
         self.roi = tuple(int(v) for v in roi)
         if len(self.roi) != 3 or min(self.roi) < 1:
@@ -335,9 +346,11 @@ class ForegroundIndex:
     ``int32`` tensors of ``tiles + 1`` entries holding the uint32 prefix counts of ``csrc/kernels/rankindex.h`` (``tiles =
     ceil(voxels / rank_tile())``; the last entry is the length of the list), ``n_fg[i]`` / ``n_bg[i]`` those lengths on the host.
     Building it is the single read-back of the pos/neg feed: all totals travel in one copy after the last launch.  An extent of
-    65,536 or more (MONAI's ``uint16`` centres) or more than 2^31 - 1 voxels is refused."""
+    65,536 or more (MONAI's ``uint16`` centres) or more than 2^31 - 1 voxels is refused, and so is a store of multi-channel
+    ``[C,W,H,D]`` volumes (``ValueError``): the index, like the feeds it serves, is single-channel."""
 
     def __init__(self, store: DeviceVolumeStore, image_threshold: float = 0.0):
+        _single_channel_store(store, "ForegroundIndex")
         self.store = store
         self.image_threshold = float(image_threshold)
         self.fg: List[torch.Tensor] = []

@@ -109,7 +109,9 @@ class TwoStreamBatchSampler(Sampler):
 
 class BraTS2019(Dataset):
     """``<base_dir>/train.txt`` | ``val.txt`` list the cases, ``<base_dir>/data/<case>.h5`` holds ``image`` (fp32 [W,H,D]) and
-    ``label`` (reference: ``dataloaders/brats2019.py:11-46``).  ``split='test'`` reads ``val.txt`` as the reference does."""
+    ``label`` (reference: ``dataloaders/brats2019.py:11-46``).  ``split='test'`` reads ``val.txt`` as the reference does.
+    ``read_case`` returns whatever the h5 holds: a multi-modal case is stored channel-first, ``image`` fp32 ``[C,W,H,D]`` (BraTS: FLAIR,
+    T1, T1ce, T2) beside ``label`` ``[W,H,D]``, and the transforms below, ``DeviceVolumeStore`` and the validation take that layout."""
 
     def __init__(self, base_dir=None, split="train", num=None, transform=None):
         self._base_dir = base_dir
@@ -139,17 +141,37 @@ class BraTS2019(Dataset):
 # --------------------------------------------------------------------------------------------------------------------
 
 class DeviceVolumeStore:
-    """All volumes of a split resident in HBM: ``images[i]`` fp32 [W,H,D], ``labels[i]`` uint8 [W,H,D] (the h5 dtypes)."""
+    """All volumes of a split resident in HBM: ``images[i]`` fp32 [W,H,D], ``labels[i]`` uint8 [W,H,D] (the h5 dtypes).
+
+    Multi-modal volumes: an image may be channel-first ``[C,W,H,D]`` (BraTS: FLAIR, T1, T1ce, T2, co-registered) beside ONE label
+    ``[W,H,D]``.  All volumes of a store have the same layout and the same C; ``channels`` is C for a 4-D store and 1 for a 3-D one,
+    ``multichannel`` says which of the two it is (a ``[1,W,H,D]`` store is 4-D: its batches come from the channel kernel)."""
+
+    MAX_CHANNELS = 16               # kChannelNormMaxChannels: what icl_crop_rotflip_channels takes
 
     def __init__(self, volumes: Sequence[Tuple[np.ndarray, np.ndarray]], device):
         self.device = torch.device(device)
         self.images: List[torch.Tensor] = []
         self.labels: List[torch.Tensor] = []
+        self.channels = 1
+        self.multichannel = False
         for image, label in volumes:
-            if image.shape != label.shape or image.ndim != 3:
-                raise ValueError("a volume is an (image [W,H,D], label [W,H,D]) pair")
+            self._admit(tuple(image.shape), tuple(label.shape))
             self.images.append(torch.as_tensor(np.ascontiguousarray(image, dtype=np.float32)).to(self.device))
             self.labels.append(torch.as_tensor(np.ascontiguousarray(label, dtype=np.uint8)).to(self.device))
+
+    def _admit(self, image_shape: tuple, label_shape: tuple):
+        """Checks the layout of the next volume against the store's (the first volume decides it)."""
+        if len(image_shape) not in (3, 4) or image_shape[-3:] != label_shape:
+            raise ValueError("a volume is an (image [W,H,D] or [C,W,H,D], label [W,H,D]) pair")
+        multi = len(image_shape) == 4
+        channels = image_shape[0] if multi else 1
+        if not 1 <= channels <= self.MAX_CHANNELS:
+            raise ValueError(f"a volume has 1 to {self.MAX_CHANNELS} channels, got {channels}")
+        if self.images and (multi != self.multichannel or channels != self.channels):
+            have = f"[{self.channels},W,H,D]" if self.multichannel else "[W,H,D]"
+            raise ValueError(f"all volumes of a store have the same channels: the store holds {have} images, got {list(image_shape)}")
+        self.multichannel, self.channels = multi, channels
 
     @classmethod
     def from_dataset(cls, dataset: BraTS2019, device):
@@ -157,17 +179,20 @@ class DeviceVolumeStore:
 
     @classmethod
     def from_device_tensors(cls, images: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], device):
-        """Adopts volumes that are on ``device`` already (``amos_volume_store_from_raw``): contiguous fp32 ``[W,H,D]`` images and uint8
-        labels of the same extents.  Nothing is copied."""
+        """Adopts volumes that are on ``device`` already (``amos_volume_store_from_raw``): contiguous fp32 ``[W,H,D]`` (or ``[C,W,H,D]``)
+        images and uint8 ``[W,H,D]`` labels of the same extents.  Nothing is copied."""
         store = cls([], device)
         if len(images) != len(labels):
             raise ValueError("one label per image")
         for image, label in zip(images, labels):
-            ok = (torch.is_tensor(image) and torch.is_tensor(label) and image.ndim == 3 and image.shape == label.shape
+            ok = (torch.is_tensor(image) and torch.is_tensor(label) and image.ndim in (3, 4) and label.ndim == 3
+                  and image.shape[-3:] == label.shape
                   and image.dtype == torch.float32 and label.dtype == torch.uint8 and image.is_contiguous() and label.is_contiguous()
                   and image.device.type == store.device.type and label.device == image.device)
             if not ok:
-                raise ValueError(f"a volume is a contiguous (image fp32 [W,H,D], label uint8 [W,H,D]) pair of tensors on {store.device}")
+                raise ValueError("a volume is a contiguous (image fp32 [W,H,D] or [C,W,H,D], label uint8 [W,H,D]) pair of tensors on "
+                                 f"{store.device}")
+            store._admit(tuple(image.shape), tuple(label.shape))
             store.images.append(image)
             store.labels.append(label)
         return store
@@ -194,10 +219,13 @@ def draw_rotflip_crop(shape: Sequence[int], output_size: Sequence[int]) -> List[
 
 class OnDeviceAugment:
     """``Compose([RandomRotFlip(), RandomCrop(patch), ToTensor()])`` + batch collation on the GPU: ``batch(indices)`` returns
-    ``{'image': [B,1,*patch] fp32, 'label': [B,*patch] int64}`` like the reference DataLoader's ``sampled_batch``.
+    ``{'image': [B,C,*patch] fp32, 'label': [B,*patch] int64}`` like the reference DataLoader's ``sampled_batch`` (C = 1 for a store
+    of ``[W,H,D]`` volumes, which goes through ``icl_crop_rotflip`` as ever; a store of ``[C,W,H,D]`` volumes goes through
+    ``icl_crop_rotflip_channels``: one launch, one geometry per sample for all of its channels, the label read once).
     ``intensity``: None, or an ``IntensityAugment`` for ``patch_size`` (``dataloaders/intensity.py``; the reference's ``RandomNoise``,
-    ``:150-161``, is its noise with ``noise_sigma=0.1, noise_clip=2``): its rows (``intensity_params``, one per sample) are drawn after
-    all geometric rows of the batch, from the stage's own ``rng``, and it runs in place behind the gather on the same stream."""
+    ``:150-161``, is its noise with ``noise_sigma=0.1, noise_clip=2``): its rows (``intensity_params``: one per sample, or with the
+    stage's ``per_channel`` one per sample and channel, sample-major) are drawn after all geometric rows of the batch, from the
+    stage's own ``rng``, and it runs in place behind the gather on the same stream."""
 
     def __init__(self, store: DeviceVolumeStore, patch_size: Sequence[int] = (96, 96, 96), intensity=None):
         self.store = store
@@ -209,23 +237,93 @@ class OnDeviceAugment:
         st = self.store
         n = len(indices)
         if params is None:
-            params = [draw_rotflip_crop(st.images[i].shape, self.patch) for i in indices]
-        intensity_params = _intensity_rows(self.intensity, self.patch, n, intensity_params, "OnDeviceAugment.batch")
+            params = [draw_rotflip_crop(st.images[i].shape[-3:], self.patch) for i in indices]
+        channels = st.channels
+        intensity_params = _intensity_rows(self.intensity, self.patch, n, intensity_params, "OnDeviceAugment.batch", channels)
         dev = st.device
-        image = torch.empty((n, 1) + self.patch, dtype=torch.float32, device=dev)
+        image = torch.empty((n, channels) + self.patch, dtype=torch.float32, device=dev)
         label = torch.empty((n,) + self.patch, dtype=torch.int64, device=dev)
         L = _lib.lib()
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
-        for lo in range(0, n, 16):                        # icl_crop_rotflip takes up to 16 samples per launch
+        for lo in range(0, n, 16):                        # both entries take up to 16 samples per launch
             chunk = list(indices[lo:lo + 16])
             m = len(chunk)
             ptrs = ctypes.c_void_p * m
             flat = (ctypes.c_int32 * (11 * m))(*[int(v) for row in params[lo:lo + m] for v in row])
-            _lib.check(L.icl_crop_rotflip(ptrs(*[st.images[i].data_ptr() for i in chunk]), ptrs(*[st.labels[i].data_ptr() for i in chunk]),
-                                          flat, m, image[lo:].data_ptr(), label[lo:].data_ptr(), *self.patch, stream), "crop_rotflip")
+            images, labels = ptrs(*[st.images[i].data_ptr() for i in chunk]), ptrs(*[st.labels[i].data_ptr() for i in chunk])
+            if st.multichannel:
+                for i, row in zip(chunk, params[lo:lo + m]):      # the kernel strides the channels by the row's extents
+                    if tuple(int(v) for v in row[:3]) != tuple(st.images[i].shape[-3:]):
+                        raise ValueError(f"OnDeviceAugment.batch: the row of volume {i} names the extents {tuple(row[:3])}, the volume "
+                                         f"has {tuple(st.images[i].shape[-3:])}")
+                _lib.check(L.icl_crop_rotflip_channels(images, labels, flat, m, channels, image[lo:].data_ptr(), label[lo:].data_ptr(),
+                                                       *self.patch, stream), "crop_rotflip_channels")
+            else:
+                _lib.check(L.icl_crop_rotflip(images, labels, flat, m, image[lo:].data_ptr(), label[lo:].data_ptr(), *self.patch, stream),
+                           "crop_rotflip")
         if intensity_params is not None:
             self.intensity.apply(image, intensity_params)
         return {"image": image, "label": label}
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# channel-wise normalisation of a resident volume
+# --------------------------------------------------------------------------------------------------------------------
+
+NORM_MASKS = {"nonzero": 0, "positive": 1, "all": 2}
+NORM_APPLY = {"mask": 0, "all": 1}
+NORM_WS_DOUBLES = 16 * 256 * 2      # kChannelNormMaxChannels * kChannelNormBlocks * 2
+
+
+def _norm_volume(volume, mask: str, who: str):
+    if mask not in NORM_MASKS:
+        raise ValueError(f"{who}: mask {mask!r} must be one of {sorted(NORM_MASKS)}")
+    if not torch.is_tensor(volume) or volume.dtype != torch.float32 or not volume.is_contiguous() or volume.ndim not in (3, 4) \
+            or volume.numel() < 1:
+        got = f"{tuple(volume.shape)} {volume.dtype}" if torch.is_tensor(volume) else type(volume).__name__
+        raise ValueError(f"{who}: a contiguous fp32 tensor [C,W,H,D] or [W,H,D] expected, got {got}")
+    if volume.device.type != "cuda" and not _lib.host_pointers_ok():
+        raise ValueError(f"{who}: the volume must be on a HIP device, got {volume.device}")
+    channels = int(volume.shape[0]) if volume.ndim == 4 else 1
+    if not 1 <= channels <= DeviceVolumeStore.MAX_CHANNELS:
+        raise ValueError(f"{who}: 1 to {DeviceVolumeStore.MAX_CHANNELS} channels, got {channels}")
+    return channels, volume.numel() // channels
+
+
+def channel_norm_stats(volume: torch.Tensor, mask: str = "nonzero") -> torch.Tensor:
+    """Per channel of a device fp32 ``[C,W,H,D]`` (or ``[W,H,D]``) volume: a device fp64 tensor ``[C,4]`` = ``(count, mean, std, 0)``
+    of the voxels in ``mask`` (``"nonzero"``: ``x != 0``; ``"positive"``: ``x > 0``; ``"all"``), the POPULATION standard deviation,
+    in double and in two passes (the mean, then the sum of ``(x - mean)**2``), every sum in a fixed order without atomics
+    (``channel_norm_partial_kernel`` in ``csrc/kernels/datafeed.h``).  An empty mask gives four zeros.  Nothing is read back."""
+    channels, voxels = _norm_volume(volume, mask, "channel_norm_stats")
+    dev = volume.device
+    stats = torch.empty((channels, 4), dtype=torch.float64, device=dev)
+    ws = torch.empty(NORM_WS_DOUBLES, dtype=torch.float64, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+    _lib.check(_lib.lib().icl_channel_norm_stats(volume.data_ptr(), channels, voxels, NORM_MASKS[mask], stats.data_ptr(), ws.data_ptr(),
+                                                 stream), "channel_norm_stats")
+    return stats
+
+
+def normalize_channels_(volume: torch.Tensor, mask: str = "nonzero", apply_to: str = "mask") -> torch.Tensor:
+    """Channel-wise z-score of a device fp32 ``[C,W,H,D]`` (or ``[W,H,D]``) volume IN PLACE, before it enters a ``DeviceVolumeStore``;
+    returns ``volume``.  ``("nonzero", "mask")`` restates MONAI's ``NormalizeIntensityd(nonzero=True, channel_wise=True)``, the first
+    transform of every multi-modal BraTS recipe; ``("positive", "all")`` restates the statistics and the formula of the reference's
+    ``itensity_normalize_one_volume`` (``dataloaders/brats_proprecessing.py:62-78``).  Per channel: ``m, s = channel_norm_stats``'s
+    mean and std rounded to fp32, ``s = 1`` where it is 0, then ``x = (x - m) / s`` in fp32 (a true subtraction, a true division) on
+    the voxels of the mask (``apply_to="mask"``) or on every voxel (``"all"``).  A channel with an empty mask is left untouched.
+    Everything stays on the stream; the host reads nothing back.  DESIGN.md §2 "Multi-modal feed" has the definition rounding by
+    rounding; ``tests/multimodal_feed_ref.py`` restates it in numpy, and the result equals that bit for bit.  **Parity with MONAI's own
+    code is unpinned**: MONAI is not installed where this package is built and tested."""
+    if apply_to not in NORM_APPLY:
+        raise ValueError(f"normalize_channels_: apply_to {apply_to!r} must be one of {sorted(NORM_APPLY)}")
+    channels, voxels = _norm_volume(volume, mask, "normalize_channels_")
+    stats = channel_norm_stats(volume, mask)
+    dev = volume.device
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+    _lib.check(_lib.lib().icl_channel_norm_apply(volume.data_ptr(), channels, voxels, NORM_MASKS[mask], NORM_APPLY[apply_to],
+                                                 stats.data_ptr(), stream), "channel_norm_apply")
+    return volume
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -233,35 +331,39 @@ class OnDeviceAugment:
 # --------------------------------------------------------------------------------------------------------------------
 
 def _pad_to_patch(arrays, output_size):
-    """Zero-pad every array on both sides of each axis by ``max((out - dim) // 2 + 3, 0)`` when ANY axis of the volume does not
-    exceed the patch (brats2019.py:53-62,97-109)."""
-    shape = arrays[0].shape
+    """Zero-pad every array on both sides of each spatial axis (its last three: a channel-first 4-D image keeps its channel axis) by
+    ``max((out - dim) // 2 + 3, 0)`` when ANY axis of the volume does not exceed the patch (brats2019.py:53-62,97-109)."""
+    shape = arrays[0].shape[-3:]
     if all(shape[a] > output_size[a] for a in range(3)):
         return arrays
     widths = [(max((output_size[a] - shape[a]) // 2 + 3, 0),) * 2 for a in range(3)]
-    return [np.pad(v, widths, mode="constant", constant_values=0) for v in arrays]
+    return [np.pad(v, [(0, 0)] * (v.ndim - 3) + widths, mode="constant", constant_values=0) for v in arrays]
 
 
 def _window(arrays, origin, output_size):
     sl = tuple(slice(origin[a], origin[a] + output_size[a]) for a in range(3))
-    return [v[sl] for v in arrays]
+    return [v[(Ellipsis,) + sl] for v in arrays]
 
 
 class RandomRotFlip:
-    """k = randint(0, 4) quarter turns in the (0, 1) plane, then a flip along axis randint(0, 2) (brats2019.py:128-144)."""
+    """k = randint(0, 4) quarter turns in the (0, 1) plane, then a flip along axis randint(0, 2) (brats2019.py:128-144).  A
+    channel-first 4-D ``image`` ``[C,W,H,D]`` beside a 3-D ``label`` is turned and flipped in its spatial axes (the first two of its
+    last three), all channels alike; the draws are the same two."""
 
     def __call__(self, sample):
         k = np.random.randint(0, 4)
         axis = np.random.randint(0, 2)
         out = dict(sample)
         for key in ("image", "label"):
-            out[key] = np.flip(np.rot90(sample[key], k), axis=axis).copy()
+            v = sample[key]
+            lead = v.ndim - 3                                # 1 for a channel-first image, else 0
+            out[key] = np.flip(np.rot90(v, k, axes=(lead, lead + 1)), axis=lead + axis).copy()
         return out
 
 
 class RandomCrop:
     """Patch at a uniformly drawn origin, after padding small volumes (brats2019.py:80-127; the ``sdf`` channel is carried along
-    when ``with_sdf``)."""
+    when ``with_sdf``).  Padding and window act on the last three axes, so a channel-first 4-D ``image`` keeps its channels."""
 
     def __init__(self, output_size, with_sdf=False):
         self.output_size = output_size
@@ -270,28 +372,31 @@ class RandomCrop:
     def __call__(self, sample):
         keys = ["image", "label"] + (["sdf"] if self.with_sdf else [])
         arrays = _pad_to_patch([sample[k] for k in keys], self.output_size)
-        origin = [np.random.randint(0, arrays[0].shape[a] - self.output_size[a]) for a in range(3)]
+        origin = [np.random.randint(0, arrays[0].shape[-3:][a] - self.output_size[a]) for a in range(3)]
         return dict(zip(keys, _window(arrays, origin, self.output_size)))
 
 
 class CenterCrop:
-    """Centred patch, same padding rule (brats2019.py:49-77)."""
+    """Centred patch, same padding rule (brats2019.py:49-77), on the last three axes."""
 
     def __init__(self, output_size):
         self.output_size = output_size
 
     def __call__(self, sample):
         arrays = _pad_to_patch([sample["image"], sample["label"]], self.output_size)
-        origin = [int(round((arrays[0].shape[a] - self.output_size[a]) / 2.)) for a in range(3)]
+        origin = [int(round((arrays[0].shape[-3:][a] - self.output_size[a]) / 2.)) for a in range(3)]
         image, label = _window(arrays, origin, self.output_size)
         return {"image": image, "label": label}
 
 
 class ToTensor:
-    """image -> fp32 tensor [1,W,H,D], label -> int64 tensor (brats2019.py:177-189)."""
+    """image -> fp32 tensor [1,W,H,D], label -> int64 tensor (brats2019.py:177-189).  A 4-D image is channel-first already and gets
+    no new axis: [C,W,H,D]."""
 
     def __call__(self, sample):
-        image = np.ascontiguousarray(sample["image"], dtype=np.float32)[None]
+        image = np.ascontiguousarray(sample["image"], dtype=np.float32)
+        if image.ndim == 3:
+            image = image[None]
         out = {"image": torch.from_numpy(image), "label": torch.from_numpy(np.ascontiguousarray(sample["label"])).long()}
         if "onehot_label" in sample:
             out["onehot_label"] = torch.from_numpy(sample["onehot_label"]).long()

@@ -1,7 +1,7 @@
 """Intensity stage of the 3-D device feed: Gaussian noise, Gaussian blur, simulated low resolution, contrast and gamma on the patch.
 
 The geometric feeds (``OnDeviceAugment``, ``OnDeviceAugmentAMOS``, ``OnDeviceAugmentPosNeg``) write the image batch ``[B,1,R0,R1,R2]``
-fp32; ``IntensityAugment.apply`` then acts on it IN PLACE, on the same stream, without a word from the host.  Labels are untouched.  The
+fp32 (``OnDeviceAugment`` over a multi-modal store: ``[B,C,R0,R1,R2]``, every channel a patch of its own to this stage);``IntensityAugment.apply`` then acts on it IN PLACE, on the same stream, without a word from the host.  Labels are untouched.  The
 transforms stand for nnU-Net's ``GaussianNoiseTransform``, ``GaussianBlurTransform``, ``SimulateLowResolutionTransform``,
 ``ContrastAugmentationTransform`` (with ``preserve_range``) and ``GammaTransform`` (with ``invert_image``), MONAI's
 ``RandGaussianNoised``, ``RandGaussianSmoothd`` and
@@ -246,9 +246,18 @@ class IntensityAugment:
     transform, a device tensor ``[B,4]`` fp32 whose row ``b`` holds ``(min, max, mean, 0)`` of sample ``b`` as contrast and gamma saw it
     (after noise, blur and low resolution); rows of samples that drew neither are 0.  With ``lowres_prob > 0`` the rows of ``draw``
     have 15 values, otherwise 11; ``apply`` takes both.  ``enabled`` is False when every probability is 0: ``draw`` then draws nothing,
-    and an ``apply`` whose rows are all off launches nothing and leaves ``stats`` as it was."""
+    and an ``apply`` whose rows are all off launches nothing and leaves ``stats`` as it was.
 
-    def __init__(self, roi: Sequence[int] = (96, 96, 96), rng=np.random, **keywords):
+    Multi-modal batches: ``apply`` also takes ``[B,C,*roi]``.  The kernels treat a batch as independent patches of ``roi``, so it is
+    ``B * C`` of them, sample-major and channel-minor, in chunks of 16 as ever, and ``stats`` is ``[B * C, 4]``.  ``per_channel=True``
+    (the default; nnU-Net's ``per_channel``): ``draw(B, channels=C)`` returns ``B * C`` rows, each drawn exactly as a row is drawn for a
+    single-channel sample, in that order, and contrast, gamma and their min / max / mean are per channel.  ``per_channel=False``: ``B``
+    rows, each used for the ``C`` channels of its sample (the statistics are still per channel), except that channel ``c`` takes the
+    noise seed ``(seed + c) mod 2^32``, so that the channels do not receive the same noise field.  With ``C = 1`` both settings draw and
+    compute exactly what a single-channel batch always did."""
+
+    def __init__(self, roi: Sequence[int] = (96, 96, 96), rng=np.random, per_channel: bool = True, **keywords):
+        self.per_channel = bool(per_channel)
         self.roi = tuple(int(v) for v in roi)
         if len(self.roi) != 3 or min(self.roi) < 1 or self.roi[0] * self.roi[1] * self.roi[2] > 2 ** 31 - 1:
             raise ValueError(f"IntensityAugment: roi {tuple(roi)}: three positive extents of at most 2^31 - 1 voxels expected")
@@ -267,8 +276,27 @@ class IntensityAugment:
         self._scratch: Optional[torch.Tensor] = None
         self._ws: Optional[torch.Tensor] = None
 
-    def draw(self, n: int) -> List[tuple]:
-        return [_draw_row(self.rng, *self._args) for _ in range(int(n))]
+    def draw(self, n: int, channels: int = 1) -> List[tuple]:
+        """The rows of ``n`` samples of ``channels`` channels: with ``per_channel`` ``n * channels`` rows, sample-major and
+        channel-minor, each drawn exactly as a single row is (so they are ``n * channels`` consecutive draws); without it ``n`` rows."""
+        return [_draw_row(self.rng, *self._args) for _ in range(int(n) * (int(channels) if self.per_channel else 1))]
+
+    def _patch_rows(self, params, n: int, channels: int) -> List[tuple]:
+        """One checked row per patch of a ``[n, channels, *roi]`` batch, sample-major and channel-minor.  ``per_channel``: ``params``
+        are those rows.  Otherwise ``params`` are ``n`` rows and channel ``c`` of a sample takes the sample's row with the noise seed
+        ``(seed + c) mod 2^32``: one decision and one factor for the sample, but no two channels receive the same noise field."""
+        want = n * channels if self.per_channel else n
+        if channels > 1 and len(params) != want:
+            what = f"per sample and channel ({n} x {channels})" if self.per_channel else f"per sample ({n}; per_channel is off)"
+            raise ValueError(f"IntensityAugment.apply: a contiguous fp32 batch [{n},{channels},*roi] takes one intensity row of "
+                             f"{ROW_LENGTH} values {what}, got {len(params)}")
+        if self.per_channel or channels == 1:
+            return _checked_rows(params, n * channels)
+        rows = []
+        for row in _checked_rows(params, n):
+            for c in range(channels):
+                rows.append(row[:_SEED] + ((int(row[_SEED]) + c) % 2 ** 32,) + row[_SEED + 1:])
+        return rows
 
     def _buffer(self, name: str, numel: int, dtype, dev) -> torch.Tensor:
         t = getattr(self, name)
@@ -280,14 +308,16 @@ class IntensityAugment:
     def apply(self, image: torch.Tensor, params: Optional[Sequence[Sequence[float]]] = None) -> torch.Tensor:
         roi = self.roi
         if not torch.is_tensor(image) or image.dtype != torch.float32 or not image.is_contiguous() or image.ndim not in (4, 5) \
-                or tuple(image.shape[-3:]) != roi or (image.ndim == 5 and image.shape[1] != 1) or image.shape[0] < 1:
+                or tuple(image.shape[-3:]) != roi or (image.ndim == 5 and image.shape[1] < 1) or image.shape[0] < 1:
             got = f"{tuple(image.shape)} {image.dtype}, contiguous {image.is_contiguous()}" if torch.is_tensor(image) else type(image).__name__
-            raise ValueError(f"IntensityAugment.apply: a contiguous fp32 tensor [B,1,{roi[0]},{roi[1]},{roi[2]}] expected, got {got}")
+            raise ValueError(f"IntensityAugment.apply: a contiguous fp32 tensor [B,C,{roi[0]},{roi[1]},{roi[2]}] expected, got {got}")
         dev = image.device
         if dev.type != "cuda" and not _lib.host_pointers_ok():
             raise ValueError(f"IntensityAugment.apply: the batch must be on a HIP device, got {dev}")
-        n = int(image.shape[0])
-        rows = _checked_rows(self.draw(n) if params is None else params, n)
+        channels = int(image.shape[1]) if image.ndim == 5 else 1
+        samples = int(image.shape[0])
+        rows = self._patch_rows(self.draw(samples, channels) if params is None else params, samples, channels)
+        n = samples * channels                           # the kernels see n independent patches of roi, sample-major and channel-minor
         # the low extents per sample; roi itself where the sample did not draw low resolution (and where every zoom rounds to it)
         extents = [lowres_extents(roi, r[_Z0:]) if len(r) == LOWRES_ROW_LENGTH and r[_LOWRES] else roi for r in rows]
         if not any(r[k] for r in rows for k in (_NOISE, _BLUR, _CONTRAST, _GAMMA)) and all(e == roi for e in extents):
@@ -328,16 +358,16 @@ class IntensityAugment:
         return image
 
 
-def _intensity_rows(intensity: Optional[IntensityAugment], roi: Sequence[int], n: int, intensity_params, who: str):
-    """What the loaders share: the intensity rows of a batch of ``n`` samples, drawn here (after the batch's geometric rows) when the
-    caller gave none; None without a stage."""
+def _intensity_rows(intensity: Optional[IntensityAugment], roi: Sequence[int], n: int, intensity_params, who: str, channels: int = 1):
+    """What the loaders share: the intensity rows of a batch of ``n`` samples of ``channels`` channels, drawn here (after the batch's
+    geometric rows) when the caller gave none; None without a stage."""
     if intensity is None:
         if intensity_params is not None:
             raise ValueError(f"{who}: intensity_params given, but the loader has no intensity stage")
         return None
     if tuple(intensity.roi) != tuple(roi):
         raise ValueError(f"{who}: the intensity stage is for patches of {intensity.roi}, the loader's are {tuple(roi)}")
-    return intensity.draw(n) if intensity_params is None else intensity_params
+    return intensity.draw(n, channels) if intensity_params is None else intensity_params
 
 
 def _check_stage(intensity, roi: Sequence[int], who: str):

@@ -106,7 +106,8 @@ def _window_kernels_apply(t, num_classes=1) -> bool:
 @torch.no_grad()
 def test_single_case_base(net, net_type, image, stride_xy, stride_z, patch_size, num_classes=1, windows_per_batch=4,
                           return_score=False, mode="constant", mirror_axes=None):
-    """image: numpy [W,H,D] (the reference's h5 layout).  Returns the label map (numpy int64 [W,H,D]).  ``mode``: ``constant`` (the
+    """image: numpy [W,H,D] (the reference's h5 layout), or channel-first [C,W,H,D] for a multi-modal net.  Returns the label map
+    (numpy int64 [W,H,D]).  ``mode``: ``constant`` (the
     reference's plain average over overlapping windows) or ``gaussian`` (``gaussian_importance_map`` at sigma_scale 0.125).
     ``mirror_axes``: None, or the axes out of 0, 1, 2 (W, H, D) of mirror test-time augmentation (``_run_windows``); ``windows_per_batch``
     then counts passes."""
@@ -233,16 +234,21 @@ def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size
     """``test_single_case_base`` up to the copy to the host: (label map int64 [W,H,D], score [C,W,H,D]) on the net's device.  On a HIP
     device the windows are gathered, soft-maxed, accumulated, divided and arg-maxed by the window kernels (``ICL_VAL_WINDOWS``; the score
     is None when ``want_score`` is false — the kernel then writes the label map alone); elsewhere, and when the network's output is not
-    fp32 [n, num_classes, *patch_size], in ATen (``_run_windows``).  Both walk the same window grid — with ``mirror_axes``, the same passes of mirror test-time augmentation."""
+    fp32 [n, num_classes, *patch_size], in ATen (``_run_windows``).  Both walk the same window grid — with ``mirror_axes``, the same passes of mirror test-time augmentation.
+    ``image``: [W,H,D], or channel-first [C,W,H,D] for a multi-modal net (``in_channels = C``): pads and window grid come from the last
+    three extents, and the windows the net sees are [n, C, *patch_size]."""
     masks = _mirror_masks(mirror_axes)
     dev = next(net.parameters()).device
+    if image.ndim not in (3, 4):
+        raise ValueError(f"a case is an image [W,H,D] or [C,W,H,D], got shape {tuple(image.shape)}")
+    extents = tuple(image.shape[-3:])
     pads = []
-    for dim, p in zip(image.shape, patch_size):
+    for dim, p in zip(extents, patch_size):
         tot = max(p - dim, 0)
         pads.append((tot // 2, tot - tot // 2))
     vol = torch.as_tensor(np.ascontiguousarray(image), dtype=torch.float32, device=dev)
     imp = _importance_map(mode, patch_size, 0.125, dev)
-    ww, hh, dd = (n + a + b for n, (a, b) in zip(image.shape, pads))      # the padded extents
+    ww, hh, dd = (n + a + b for n, (a, b) in zip(extents, pads))          # the padded extents
     sx = math.ceil((ww - patch_size[0]) / stride_xy) + 1
     sy = math.ceil((hh - patch_size[1]) / stride_xy) + 1
     sz = math.ceil((dd - patch_size[2]) / stride_z) + 1
@@ -256,7 +262,8 @@ def _single_case_on_device(net, net_type, image, stride_xy, stride_z, patch_size
                 starts.append((0, xs, ys, zs))
     icl = net_type in ("swinunetr_icl", "unet_3D_icl")
     (label_map, score), _ = _run_windows(
-        vol[None, None], patch_size, pads, (ww, hh, dd), starts, windows_per_batch, lambda win: net(win, inference=True) if icl else net(win),
+        vol[None] if vol.ndim == 4 else vol[None, None], patch_size, pads, (ww, hh, dd), starts, windows_per_batch,
+        lambda win: net(win, inference=True) if icl else net(win),
         imp, True, "both" if want_score else "label", _window_kernels_apply(vol, num_classes), _fits_brats(num_classes, patch_size), num_classes, masks)
     return label_map[0], None if score is None else score[0]
 
@@ -657,7 +664,8 @@ def _score_prediction(prediction, label, num_classes, dev, voxelspacing=None, po
 
 def test_all_case_base(net, net_type, base_dir, test_list="full_test.list", num_classes=4, patch_size=(48, 160, 160),
                        stride_xy=32, stride_z=24, cases=None, voxelspacing=None, postprocess=None, mirror_axes=None):
-    """val_3D.py:100-118.  ``cases`` (iterable of (image, label) numpy pairs) replaces the h5 files when given; otherwise
+    """val_3D.py:100-118.  ``cases`` (iterable of (image, label) numpy pairs, the image [W,H,D] or channel-first [C,W,H,D] beside a
+    label [W,H,D]) replaces the h5 files when given; otherwise
     the reference's ``{base_dir}/data/{id}.h5`` layout is read with h5py (not installed in the build image).  ``voxelspacing`` (a number
     or three, the voxel size along the label map's axes) gives HD95 in its units (``cal_metric_multiclass``); None: voxels, as the reference.
     ``postprocess``: None (the reference), ``"largest"`` or a dict of ``keep_components``' keywords — the predicted label map goes through

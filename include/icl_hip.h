@@ -485,6 +485,29 @@ int icl_relpos_bias_bwd_sum(float* dbias, int chunks, const int32_t* inv, const 
 int icl_crop_rotflip(const void* const* images, const void* const* labels, const int32_t* params, int batch, float* image_out,
                      int64_t* label_out, int o0, int o1, int o2, void* stream);
 
+/* ---- the same chain on multi-modal volumes (BraTS's four co-registered MR modalities; the reference feeds FLAIR only, its transforms
+ * are the ones above, dataloaders/brats2019.py:80-147,177-189): images[b] points to a contiguous fp32 [channels,n0,n1,n2] volume,
+ * labels[b] to ONE uint8 [n0,n1,n2] label; params as for icl_crop_rotflip, one geometry for all channels of a sample.  image_out
+ * [batch,channels,o0,o1,o2] fp32, label_out [batch,o0,o1,o2] int64.  One launch: the source index of an output position is computed once
+ * and used for every channel and for the label.  With channels == 1 the result is icl_crop_rotflip's bit for bit.  Returns -1, launching
+ * nothing, for a null pointer, a batch outside 1..16, channels outside 1..16, an output extent < 1 or more than 2^31 - 1 output voxels
+ * a sample, and for what icl_crop_rotflip refuses in a row. */
+int icl_crop_rotflip_channels(const void* const* images, const void* const* labels, const int32_t* params, int batch, int channels,
+                              float* image_out, int64_t* label_out, int o0, int o1, int o2, void* stream);
+
+/* ---- channel-wise intensity normalisation of a resident volume, in place (MONAI's NormalizeIntensityd(nonzero=True,
+ * channel_wise=True): mask 0, apply 0; the reference's itensity_normalize_one_volume, dataloaders/brats_proprecessing.py:62-78:
+ * mask 1, apply 1).  image: DEVICE fp32 [channels][voxels], channels in 1..16, voxels in 1..2^31 - 1.  mask_mode: 0 x != 0, 1 x > 0,
+ * 2 every voxel.
+ * icl_channel_norm_stats (four launches, no atomics, nothing read back): stats_out DEVICE double [channels][4] = {count, mean, std, 0}
+ *   of the voxels in the mask: mean = sum / count and std = sqrt(sum (x - mean)^2 / count) (population), every sum in double in the
+ *   fixed order documented at channel_norm_partial_kernel; an empty mask gives four zeros.  ws: DEVICE scratch of channels * 256 * 2
+ *   doubles.
+ * icl_channel_norm_apply: x <- fp32(fp32(x - m) / s) with m = fp32(mean), s = fp32(std) and s = 1 where that is 0: a true subtraction
+ *   and a true division.  apply_mode 0: the voxels of the mask only; 1: every voxel.  A channel whose count is 0 is left untouched. */
+int icl_channel_norm_stats(const float* image, int channels, int64_t voxels, int mask_mode, double* stats_out, double* ws, void* stream);
+int icl_channel_norm_apply(float* image, int channels, int64_t voxels, int mask_mode, int apply_mode, const double* stats, void* stream);
+
 /* ---- on-device random transforms of the 3-D AMOS trainer (train_inherent_consistent_unet_3D_AMOS22.py:102-133: RandSpatialCropd ->
  * SpatialPadd -> RandFlipd on axis 0, 1, 2 -> RandRotate90d -> RandShiftIntensityd) as one gather over volumes resident in HBM.
  * images[b] / labels[b]: HOST arrays of device pointers to the fp32 [n0,n1,n2] volume and its uint8 label; int_params: HOST int32

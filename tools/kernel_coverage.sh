@@ -21,6 +21,10 @@
 #  tests/test_gpu_components.py: test_case and test_scattered_prediction_64x80x72 run both element sizes under each connectivity)
 # (the live batch of the upper decoder's backward, DESIGN.md §4.4, adds no kernel: its launches are the same kernels on fewer samples plus
 #  fill nodes; maxpool2_bwd_add_kernel / maxpool2_bwd_add_x2_kernel gained one argument — tests/test_gpu_live_batch.py runs both sides of it)
+# (crop_rotflip_channels_kernel<1> and <4>, channel_norm_partial_kernel<1> and <2>, channel_norm_finish_kernel<1> and <2>,
+#  channel_norm_apply_kernel<1> and <4> of datafeed.h, the multi-modal feed and its channel-wise normalisation, are launched by
+#  tests/test_gpu_multimodal.py: the (6, 6, 5) and (6, 6, 8) sweeps at 1..4 channels, and the (3, 5, 7, 9) / misaligned volumes for the
+#  one-voxel kernels, (3, 5, 6, 8) and (3, 24, 40, 41) for the quad kernels of the normalisation)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/cov

@@ -224,6 +224,11 @@ def _use_library_for_tests(path: str | None, host_pointers: bool = True):
     _lib, _lib_path, _host_pointers_ok = _load(path), path, host_pointers
 
 
+def stream_of(device):
+    """The `stream` argument of a launcher: the handle of torch's current stream on a HIP device, None (the null stream) otherwise."""
+    return c_void_p(torch.cuda.current_stream(device).cuda_stream) if device.type == "cuda" else None
+
+
 def check(rc: int, what: str = ""):
     if rc != 0:
         msg = lib().icl_last_error()

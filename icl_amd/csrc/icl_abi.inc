@@ -44,6 +44,7 @@ extern template __global__ void conv3d_bf16x3_fwd_ws_kernel<1, false, false>(con
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -2409,11 +2410,11 @@ int icl_linear_wgrad_small(const float* gy, const float* x, float* dw, void* ws,
   return gemm_run(gy, x, dw, nullptr, ws, out, in, (int)rows, out, in, in, 0, 0, 0, 1, 0, 0, 0, (hipStream_t)stream);
 }
 
-int icl_crop_rotflip(const void* const* images, const void* const* labels, const int32_t* params, int batch, float* image_out,
-                     int64_t* label_out, int o0, int o1, int o2, void* stream) {
-  if (!images || !labels || !params || !image_out || !label_out || batch < 1 || batch > icl::kFeedMaxBatch || o0 < 1 || o1 < 1 || o2 < 1)
-    return fail(-1, "crop_rotflip: bad argument (1 <= batch <= %d)", icl::kFeedMaxBatch);
-  icl::FeedBatch fb{};
+namespace {
+
+// The record of icl_crop_rotflip / icl_crop_rotflip_channels from the caller's rows of 11 integers.  Returns -1, or the first sample
+// that is refused (a null volume pointer or a value of its row out of range): each entry words its own refusal.
+int crop_feed_records(const void* const* images, const void* const* labels, const int32_t* params, int batch, icl::FeedBatch& fb) {
   for (int b = 0; b < batch; ++b) {
     const int32_t* q = params + 11 * b;
     icl::FeedSample& s = fb.s[b];
@@ -2421,9 +2422,20 @@ int icl_crop_rotflip(const void* const* images, const void* const* labels, const
     s.label = (const uint8_t*)labels[b];
     s.n0 = q[0]; s.n1 = q[1]; s.n2 = q[2]; s.k = q[3]; s.flip_axis = q[4];
     s.p0 = q[5]; s.p1 = q[6]; s.p2 = q[7]; s.c0 = q[8]; s.c1 = q[9]; s.c2 = q[10];
-    if (!s.image || !s.label || s.n0 < 1 || s.n1 < 1 || s.n2 < 1 || s.k < 0 || s.k > 3 || s.flip_axis > 1 || s.p0 < 0 || s.p1 < 0 || s.p2 < 0)
-      return fail(-1, "crop_rotflip: bad sample %d", b);
+    if (!s.image || !s.label || s.n0 < 1 || s.n1 < 1 || s.n2 < 1 || s.k < 0 || s.k > 3 || s.flip_axis > 1 || s.p0 < 0 || s.p1 < 0 || s.p2 < 0) return b;
   }
+  return -1;
+}
+
+}  // namespace
+
+int icl_crop_rotflip(const void* const* images, const void* const* labels, const int32_t* params, int batch, float* image_out,
+                     int64_t* label_out, int o0, int o1, int o2, void* stream) {
+  if (!images || !labels || !params || !image_out || !label_out || batch < 1 || batch > icl::kFeedMaxBatch || o0 < 1 || o1 < 1 || o2 < 1)
+    return fail(-1, "crop_rotflip: bad argument (1 <= batch <= %d)", icl::kFeedMaxBatch);
+  icl::FeedBatch fb{};
+  const int bad = crop_feed_records(images, labels, params, batch, fb);
+  if (bad >= 0) return fail(-1, "crop_rotflip: bad sample %d", bad);
   ICL_LAUNCH(icl::crop_rotflip_kernel, dim3(grid_for((long)batch * o0 * o1 * o2, 256, 8192)), dim3(256), 0, (hipStream_t)stream, fb, image_out,
              (long long*)label_out, batch, o0, o1, o2);
   return check_launch("crop_rotflip");
@@ -2440,17 +2452,9 @@ int icl_crop_rotflip_channels(const void* const* images, const void* const* labe
   if ((long)o0 * o1 * o2 > 0x7fffffffL)
     return fail(-1, "crop_rotflip_channels: output extents %d x %d x %d (more than 2^31 - 1 voxels a sample)", o0, o1, o2);
   icl::FeedBatch fb{};
-  for (int b = 0; b < batch; ++b) {
-    const int32_t* q = params + 11 * b;
-    icl::FeedSample& s = fb.s[b];
-    s.image = (const float*)images[b];
-    s.label = (const uint8_t*)labels[b];
-    s.n0 = q[0]; s.n1 = q[1]; s.n2 = q[2]; s.k = q[3]; s.flip_axis = q[4];
-    s.p0 = q[5]; s.p1 = q[6]; s.p2 = q[7]; s.c0 = q[8]; s.c1 = q[9]; s.c2 = q[10];
-    if (!s.image || !s.label) return fail(-1, "crop_rotflip_channels: sample %d: null volume pointer", b);
-    if (s.n0 < 1 || s.n1 < 1 || s.n2 < 1 || s.k < 0 || s.k > 3 || s.flip_axis > 1 || s.p0 < 0 || s.p1 < 0 || s.p2 < 0)
-      return fail(-1, "crop_rotflip_channels: bad sample %d", b);
-  }
+  const int bad = crop_feed_records(images, labels, params, batch, fb);
+  if (bad >= 0 && !(fb.s[bad].image && fb.s[bad].label)) return fail(-1, "crop_rotflip_channels: sample %d: null volume pointer", bad);
+  if (bad >= 0) return fail(-1, "crop_rotflip_channels: bad sample %d", bad);
   const long voxels = (long)o0 * o1 * o2;      // per sample and channel; one grid row per sample
   const int cap = 2048 / batch;                // 2048 workgroups of 256 threads: every wave slot of the 256 CUs once, the rest by stride
   if ((o2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
@@ -2551,6 +2555,32 @@ int volume_feed_records(const char* what, const void* const* images, const void*
   return 0;
 }
 
+extern "C++" template <int V, bool DEV, typename Batch>
+void volume_feed_launch_as(const Batch& fb, int batch, const int32_t* origins, float* image_out, int64_t* label_out, int R0, int R1, int R2,
+                           void* stream) {
+  const dim3 grid(grid_for((long)R0 * R1 * R2 / V, 256, 8192), batch);      // one grid row per sample
+  if constexpr (std::is_same_v<Batch, icl::VolumeFeedBatch>) {
+    ICL_LAUNCH((icl::volume_feed_kernel<V, DEV>), grid, dim3(256), 0, (hipStream_t)stream, fb, (const int*)origins, image_out,
+               (long long*)label_out, R0, R1, R2);
+  } else {
+    ICL_LAUNCH((icl::volume_feed_affine_kernel<V, DEV>), grid, dim3(256), 0, (hipStream_t)stream, fb, (const int*)origins, image_out,
+               (long long*)label_out, R0, R1, R2);
+  }
+}
+
+// The launch of a filled batch, VolumeFeedBatch through volume_feed_kernel and VolumeFeedAffineBatch through volume_feed_affine_kernel:
+// a quad per thread where the depth and both outputs allow 16-byte stores; origins: the device origins, or nullptr for the records' own.
+extern "C++" template <typename Batch>
+int volume_feed_launch(const char* what, const Batch& fb, int batch, const int32_t* origins, float* image_out, int64_t* label_out, int R0,
+                       int R1, int R2, void* stream) {
+  const bool quad = (R2 & 3) == 0 && aligned16(image_out) && aligned16(label_out);
+  if (quad && origins) volume_feed_launch_as<4, true>(fb, batch, origins, image_out, label_out, R0, R1, R2, stream);
+  else if (quad) volume_feed_launch_as<4, false>(fb, batch, origins, image_out, label_out, R0, R1, R2, stream);
+  else if (origins) volume_feed_launch_as<1, true>(fb, batch, origins, image_out, label_out, R0, R1, R2, stream);
+  else volume_feed_launch_as<1, false>(fb, batch, origins, image_out, label_out, R0, R1, R2, stream);
+  return check_launch(what);
+}
+
 // extents of a volume the rank index takes: MONAI casts crop centres to uint16, and the index counts in uint32
 int rank_extents_ok(const char* what, int b, int n0, int n1, int n2) {
   if (n0 < 1 || n1 < 1 || n2 < 1 || n0 > 65535 || n1 > 65535 || n2 > 65535)
@@ -2568,15 +2598,7 @@ int icl_volume_feed(const void* const* images, const void* const* labels, const 
   if (!images || !labels || !int_params || !float_params || !image_out || !label_out) return fail(-1, "volume_feed: null pointer");
   icl::VolumeFeedBatch fb{};
   if (const int rc = volume_feed_records("volume_feed", images, labels, int_params, float_params, batch, R0, R1, R2, false, fb)) return rc;
-  const long voxels = (long)R0 * R1 * R2;      // per sample; one grid row per sample
-  if ((R2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
-    ICL_LAUNCH((icl::volume_feed_kernel<4, false>), dim3(grid_for(voxels / 4, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb,
-               (const int*)nullptr, image_out, (long long*)label_out, R0, R1, R2);
-  } else {
-    ICL_LAUNCH((icl::volume_feed_kernel<1, false>), dim3(grid_for(voxels, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb,
-               (const int*)nullptr, image_out, (long long*)label_out, R0, R1, R2);
-  }
-  return check_launch("volume_feed");
+  return volume_feed_launch("volume_feed", fb, batch, nullptr, image_out, label_out, R0, R1, R2, stream);
 }
 
 int icl_volume_feed_origins(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params,
@@ -2586,15 +2608,7 @@ int icl_volume_feed_origins(const void* const* images, const void* const* labels
   icl::VolumeFeedBatch fb{};
   if (const int rc = volume_feed_records("volume_feed_origins", images, labels, int_params, float_params, batch, R0, R1, R2, true, fb))
     return rc;
-  const long voxels = (long)R0 * R1 * R2;
-  if ((R2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
-    ICL_LAUNCH((icl::volume_feed_kernel<4, true>), dim3(grid_for(voxels / 4, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb,
-               (const int*)origins, image_out, (long long*)label_out, R0, R1, R2);
-  } else {
-    ICL_LAUNCH((icl::volume_feed_kernel<1, true>), dim3(grid_for(voxels, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, fb,
-               (const int*)origins, image_out, (long long*)label_out, R0, R1, R2);
-  }
-  return check_launch("volume_feed_origins");
+  return volume_feed_launch("volume_feed_origins", fb, batch, origins, image_out, label_out, R0, R1, R2, stream);
 }
 
 namespace {
@@ -2633,15 +2647,7 @@ int icl_volume_feed_affine(const void* const* images, const void* const* labels,
   if (const int rc = volume_feed_affine_records("volume_feed_affine", images, labels, int_params, float_params, affine_params, batch, R0, R1,
                                                 R2, false, ab))
     return rc;
-  const long voxels = (long)R0 * R1 * R2;      // per sample; one grid row per sample
-  if ((R2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
-    ICL_LAUNCH((icl::volume_feed_affine_kernel<4, false>), dim3(grid_for(voxels / 4, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, ab,
-               (const int*)nullptr, image_out, (long long*)label_out, R0, R1, R2);
-  } else {
-    ICL_LAUNCH((icl::volume_feed_affine_kernel<1, false>), dim3(grid_for(voxels, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, ab,
-               (const int*)nullptr, image_out, (long long*)label_out, R0, R1, R2);
-  }
-  return check_launch("volume_feed_affine");
+  return volume_feed_launch("volume_feed_affine", ab, batch, nullptr, image_out, label_out, R0, R1, R2, stream);
 }
 
 int icl_volume_feed_affine_origins(const void* const* images, const void* const* labels, const int32_t* int_params, const float* float_params,
@@ -2653,15 +2659,7 @@ int icl_volume_feed_affine_origins(const void* const* images, const void* const*
   if (const int rc = volume_feed_affine_records("volume_feed_affine_origins", images, labels, int_params, float_params, affine_params, batch,
                                                 R0, R1, R2, true, ab))
     return rc;
-  const long voxels = (long)R0 * R1 * R2;
-  if ((R2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
-    ICL_LAUNCH((icl::volume_feed_affine_kernel<4, true>), dim3(grid_for(voxels / 4, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, ab,
-               (const int*)origins, image_out, (long long*)label_out, R0, R1, R2);
-  } else {
-    ICL_LAUNCH((icl::volume_feed_affine_kernel<1, true>), dim3(grid_for(voxels, 256, 8192), batch), dim3(256), 0, (hipStream_t)stream, ab,
-               (const int*)origins, image_out, (long long*)label_out, R0, R1, R2);
-  }
-  return check_launch("volume_feed_affine_origins");
+  return volume_feed_launch("volume_feed_affine_origins", ab, batch, origins, image_out, label_out, R0, R1, R2, stream);
 }
 
 int icl_rank_tile(void) { return icl::kRankTile; }

@@ -24,6 +24,40 @@ struct FeedBatch {
   FeedSample s[kFeedMaxBatch];
 };
 
+// np.rot90(x, k) on axes (0, 1) of an array x of extents e0 x e1, read backwards: rotated[a][c] = x[sa][sc].  Every gather of this
+// header uses it: the crop and slice kernels with the source extents n0, n1, the volume kernels with the patch extents R0, R1.
+__device__ __forceinline__ void rot90_source(int k, int a, int c, int e0, int e1, int& sa, int& sc) {
+  switch (k & 3) {
+    case 0: sa = a; sc = c; break;
+    case 1: sa = c; sc = e1 - 1 - a; break;
+    case 2: sa = e0 - 1 - a; sc = e1 - 1 - c; break;
+    default: sa = e0 - 1 - c; sc = a; break;
+  }
+}
+
+// V labels (0..255) as int64 at p; V = 4: p is 16-byte aligned, two 16-byte stores whose high dwords are 0
+template <int V>
+__device__ __forceinline__ void feed_store_labels(long long* p, const unsigned (&lab)[V]) {
+  if constexpr (V == 4) {
+    uint4* lp = reinterpret_cast<uint4*>(p);
+    lp[0] = make_uint4(lab[0], 0u, lab[1], 0u);
+    lp[1] = make_uint4(lab[2], 0u, lab[3], 0u);
+  } else {
+    p[0] = (long long)lab[0];
+  }
+}
+
+// V image voxels at `image` (V = 4: one 16-byte store to a 16-byte aligned address) and their labels at `label`
+template <int V>
+__device__ __forceinline__ void feed_store(float* image, long long* label, const float (&v)[V], const unsigned (&lab)[V]) {
+  if constexpr (V == 4) {
+    *reinterpret_cast<float4*>(image) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    image[0] = v[0];
+  }
+  feed_store_labels<V>(label, lab);
+}
+
 // image_out [B][1][o0][o1][o2] fp32, label_out [B][o0][o1][o2] int64.  grid (ceil(o2/64)... flat), one thread per output voxel.
 __global__ __launch_bounds__(256) void crop_rotflip_kernel(FeedBatch fb, float* __restrict__ image_out, long long* __restrict__ label_out, int B,
                                                            int o0, int o1, int o2) {
@@ -45,14 +79,8 @@ __global__ __launch_bounds__(256) void crop_rotflip_kernel(FeedBatch fb, float* 
     if (a >= 0 && a < r0 && c >= 0 && c < r1 && d >= 0 && d < s.n2) {
       if (s.flip_axis == 0) a = r0 - 1 - a;
       else if (s.flip_axis == 1) c = r1 - 1 - c;
-      // rot90 on axes (0, 1): rotated[a][c] = source[sa][sc]
       int sa, sc;
-      switch (s.k & 3) {
-        case 0: sa = a; sc = c; break;
-        case 1: sa = c; sc = s.n1 - 1 - a; break;
-        case 2: sa = s.n0 - 1 - a; sc = s.n1 - 1 - c; break;
-        default: sa = s.n0 - 1 - c; sc = a; break;
-      }
+      rot90_source(s.k, a, c, s.n0, s.n1, sa, sc);
       const long src = ((long)sa * s.n1 + sc) * s.n2 + d;
       v = s.image[src];
       lab = (long long)s.label[src];
@@ -67,7 +95,7 @@ __global__ __launch_bounds__(256) void crop_rotflip_kernel(FeedBatch fb, float* 
 // the channel, so it is computed once per output position and used for all C channels (channel stride n0 * n1 * n2) and for the
 // label, which is read and written once.  image_out [B][C][o0][o1][o2] fp32, label_out [B][o0][o1][o2] int64.  grid (x, B): one sample
 // per blockIdx.y, so its record is wave-uniform.  One thread per V consecutive depth voxels (V = 4: o2 % 4 == 0 and both outputs 16-byte
-// aligned; the store is always a quad per channel and two 16-byte label stores; the load is a quad where the four sources lie inside
+// aligned; the store is always a quad per channel and feed_store_labels; the load is a quad where the four sources lie inside
 // the row at a 16-byte aligned address, four guarded scalar loads otherwise: the scheme of window_gather_kernel<4>).  No LDS, no
 // atomics.  With C = 1 the result is crop_rotflip_kernel's bit for bit (the values are copied, never computed with).
 template <int V>
@@ -97,13 +125,8 @@ __global__ __launch_bounds__(256) void crop_rotflip_channels_kernel(FeedBatch fb
     if (row) {
       if (s.flip_axis == 0) a = r0 - 1 - a;
       else if (s.flip_axis == 1) c = r1 - 1 - c;
-      int sa, sc;                                                             // rot90 on axes (0, 1): the maps of crop_rotflip_kernel
-      switch (s.k & 3) {
-        case 0: sa = a; sc = c; break;
-        case 1: sa = c; sc = s.n1 - 1 - a; break;
-        case 2: sa = s.n0 - 1 - a; sc = s.n1 - 1 - c; break;
-        default: sa = s.n0 - 1 - c; sc = a; break;
-      }
+      int sa, sc;
+      rot90_source(s.k, a, c, s.n0, s.n1, sa, sc);
       base = ((long)sa * s.n1 + sc) * s.n2;
     }
     bool in[V];
@@ -131,13 +154,7 @@ __global__ __launch_bounds__(256) void crop_rotflip_channels_kernel(FeedBatch fb
         img[ch * vox + e] = v[0];
       }
     }
-    if constexpr (V == 4) {
-      uint4* lp = reinterpret_cast<uint4*>(lab + e);                          // labels are 0..255: the high dwords are 0
-      lp[0] = make_uint4(lv[0], 0u, lv[1], 0u);
-      lp[1] = make_uint4(lv[2], 0u, lv[3], 0u);
-    } else {
-      lab[e] = (long long)lv[0];
-    }
+    feed_store_labels<V>(lab + e, lv);
   }
 }
 
@@ -336,12 +353,7 @@ __global__ __launch_bounds__(256) void slice_augment_kernel(SliceBatch sb, float
       if (s.branch == kSliceRotFlip) {
         if (s.flip_axis == 0) a = r0 - 1 - a;
         else c = r1 - 1 - c;
-        switch (s.k & 3) {          // rot90: rotated[a][c] = source[sa][sc] (the maps of crop_rotflip_kernel)
-          case 0: sa = a; sc = c; break;
-          case 1: sa = c; sc = s.n1 - 1 - a; break;
-          case 2: sa = s.n0 - 1 - a; sc = s.n1 - 1 - c; break;
-          default: sa = s.n0 - 1 - c; sc = a; break;
-        }
+        rot90_source(s.k, a, c, s.n0, s.n1, sa, sc);
       } else if (s.branch == kSliceRotate) {
         const double da = (double)a, dc = (double)c;
         const double p00 = da * s.m00, p01 = dc * s.m01, p10 = da * s.m10, p11 = dc * s.m11;
@@ -386,9 +398,9 @@ __global__ __launch_bounds__(256) void slice_resize_kernel(const T* __restrict__
 // differs from crop_rotflip_kernel's (symmetric padding AFTER the crop, three independent flips with the depth axis among them,
 // an intensity term that also lands on the padded voxels), so it has a kernel of its own.  Forward, per sample:
 //   x = src[c : c + s];  x = zero-pad to R with l_a on the left;  flip axis 0 / 1 / 2 for bits 0 / 1 / 2 of `flip`;
-//   x = np.rot90(x, k, axes=(0, 1));  image only: fp32(fp32(x * mul) + add) on EVERY voxel (two roundings: contraction off).
-// Every output voxel is mapped backwards through rot90 -> flips -> padding -> crop origin.  Odd k needs R0 == R1 (the launcher
-// checks), so the flipped patch always has the output's extents.
+//   x = np.rot90(x, k, axes=(0, 1));  image only: fp32(fp32(x * mul) + add) on EVERY voxel.
+// Every output voxel is mapped backwards through rot90 -> flips -> padding -> crop origin (volume_feed_gather).  Odd k needs
+// R0 == R1 (the launcher checks), so the flipped patch always has the output's extents.
 struct VolumeFeedSample {
   const float* image;        // [n0][n1][n2] fp32
   const uint8_t* label;      // [n0][n1][n2] uint8
@@ -405,81 +417,80 @@ struct VolumeFeedBatch {
   VolumeFeedSample s[kFeedMaxBatch];     // 80 B a record: 1,280 B of the 4 KB kernel-argument block
 };
 
-// image_out [B][1][R0][R1][R2] fp32, label_out [B][R0][R1][R2] int64.  grid (x, B).  One thread per V consecutive depth voxels (V = 4: R2 % 4 == 0,
-// both outputs 16-byte aligned; one 16-byte image store and two 16-byte label stores; the source is walked forwards or, with flip
-// bit 2, backwards along depth).  No LDS, no atomics.  DEV = false (icl_volume_feed): the crop origin is the record's c0, c1, c2 and
-// `origins` is not read.  DEV = true (icl_volume_feed_origins): it comes from device memory, origins [B][3] int32, as
-// rank_select_kernel (rankindex.h) left it on the same stream: read once per workgroup at a wave-uniform address; the record's c0, c1,
-// c2 then hold the LARGEST legal origin n - s and an origin outside [0, n - s] is clamped into it, so no content of that buffer can
-// send a read outside the volume.
-template <int V, bool DEV>
-__global__ __launch_bounds__(256) void volume_feed_kernel(VolumeFeedBatch fb, const int* __restrict__ origins, float* __restrict__ image_out,
-                                                          long long* __restrict__ label_out, int R0, int R1, int R2) {
+// The crop origin of sample b from device memory (DEV kernels): origins [B][3] int32, as rank_select_kernel (rankindex.h) left it on
+// the same stream, read once per workgroup at a wave-uniform address.  On entry c0, c1, c2 hold the LARGEST legal origin n - s (the
+// launcher put it in the record); an origin outside [0, n - s] is clamped into it, so no content of that buffer can send a read
+// outside the volume.
+__device__ __forceinline__ void clamp_device_origin(const int* __restrict__ origins, int b, int& c0, int& c1, int& c2) {
+  const int* __restrict__ o = origins + 3 * b;
+  c0 = o[0] < 0 ? 0 : (o[0] > c0 ? c0 : o[0]);
+  c1 = o[1] < 0 ? 0 : (o[1] > c1 ? c1 : o[1]);
+  c2 = o[2] < 0 ? 0 : (o[2] > c2 ? c2 : o[2]);
+}
+
+// The integer gather, the only one of volume_feed_kernel and the path of a sample without the affine stage in
+// volume_feed_affine_kernel: V consecutive output depth voxels from l on, at the flipped patch coordinates (fa, fc) of axes 0, 1.
+// Padded -> cropped coordinates -> source at the crop origin (c0, c1, c2); the source is walked forwards or, with flip bit 2,
+// backwards along depth; a voxel of the padding is 0 with label 0; then fp32(fp32(x * mul) + add) on EVERY voxel (two roundings:
+// the pragma is repeated here because it binds to the compound statement it stands in, not to the caller's).
+template <int V>
+__device__ __forceinline__ void volume_feed_gather(const VolumeFeedSample& s, int c0, int c1, int c2, int fa, int fc, int l, int R2,
+                                                   float (&v)[V], unsigned (&lab)[V]) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
+  const int a = fa - s.l0, c = fc - s.l1;
+  const bool rev = (s.flip & 4) != 0;
+  const int d0 = (rev ? R2 - 1 - l : l) - s.l2, step = rev ? -1 : 1;
+  const bool row = a >= 0 && a < s.s0 && c >= 0 && c < s.s1;
+  const long base = row ? ((long)(c0 + a) * s.n1 + (c1 + c)) * s.n2 + c2 : 0;
+#pragma unroll
+  for (int t = 0; t < V; ++t) {
+    const int d = d0 + t * step;
+    float x = 0.f;
+    lab[t] = 0u;
+    if (row && d >= 0 && d < s.s2) {
+      x = s.image[base + d];
+      lab[t] = s.label[base + d];
+    }
+    const float m = x * s.mul;
+    v[t] = m + s.add;
+  }
+}
+
+// image_out [B][1][R0][R1][R2] fp32, label_out [B][R0][R1][R2] int64.  grid (x, B).  One thread per V consecutive depth voxels (V = 4:
+// R2 % 4 == 0, both outputs 16-byte aligned).  No LDS, no atomics.  DEV = false (icl_volume_feed): the crop origin is the record's c0,
+// c1, c2 and `origins` is not read.  DEV = true (icl_volume_feed_origins): clamp_device_origin.
+template <int V, bool DEV>
+__global__ __launch_bounds__(256) void volume_feed_kernel(VolumeFeedBatch fb, const int* __restrict__ origins, float* __restrict__ image_out,
+                                                          long long* __restrict__ label_out, int R0, int R1, int R2) {
   static_assert(V == 1 || V == 4, "one voxel or one quad per thread");
   const int q2 = R2 / V;
   const unsigned per = (unsigned)R0 * R1 * q2;                                // the launcher keeps R0 * R1 * R2 below 2^31
   const int b = blockIdx.y;                                                   // one sample per grid row: its record is wave-uniform
   const VolumeFeedSample& s = fb.s[b];
-  int o0 = 0, o1 = 0, o2 = 0;
-  if constexpr (DEV) {
-    const int* __restrict__ o = origins + 3 * b;
-    o0 = o[0] < 0 ? 0 : (o[0] > s.c0 ? s.c0 : o[0]);
-    o1 = o[1] < 0 ? 0 : (o[1] > s.c1 ? s.c1 : o[1]);
-    o2 = o[2] < 0 ? 0 : (o[2] > s.c2 ? s.c2 : o[2]);
-  }
+  int c0 = s.c0, c1 = s.c1, c2 = s.c2;
+  if constexpr (DEV) clamp_device_origin(origins, b, c0, c1, c2);
   for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < per; r += gridDim.x * blockDim.x) {
     const long e = (long)b * per + r;
     const int l = (int)(r % q2) * V;
     const unsigned rj = r / q2;
     const int j = (int)(rj % R1), i = (int)(rj / R1);
-    // rot90 on axes (0, 1): out[i][j] = flipped[fa][fc] (the maps of crop_rotflip_kernel, with the patch extents R0, R1)
-    int fa, fc;
-    switch (s.k & 3) {
-      case 0: fa = i; fc = j; break;
-      case 1: fa = j; fc = R1 - 1 - i; break;
-      case 2: fa = R0 - 1 - i; fc = R1 - 1 - j; break;
-      default: fa = R0 - 1 - j; fc = i; break;
-    }
+    int fa, fc;                                                               // out[i][j] = flipped[fa][fc]
+    rot90_source(s.k, i, j, R0, R1, fa, fc);
     if (s.flip & 1) fa = R0 - 1 - fa;
     if (s.flip & 2) fc = R1 - 1 - fc;
-    const int a = fa - s.l0, c = fc - s.l1;                                   // padded -> cropped coordinates
-    const bool rev = (s.flip & 4) != 0;
-    const int d0 = (rev ? R2 - 1 - l : l) - s.l2, step = rev ? -1 : 1;
-    const bool row = a >= 0 && a < s.s0 && c >= 0 && c < s.s1;
-    const long base = row ? ((long)((DEV ? o0 : s.c0) + a) * s.n1 + ((DEV ? o1 : s.c1) + c)) * s.n2 + (DEV ? o2 : s.c2) : 0;
     float v[V];
     unsigned lab[V];
-#pragma unroll
-    for (int t = 0; t < V; ++t) {
-      const int d = d0 + t * step;
-      float x = 0.f;
-      lab[t] = 0u;
-      if (row && d >= 0 && d < s.s2) {
-        x = s.image[base + d];
-        lab[t] = s.label[base + d];
-      }
-      const float m = x * s.mul;
-      v[t] = m + s.add;
-    }
-    if constexpr (V == 4) {
-      *reinterpret_cast<float4*>(image_out + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
-      uint4* lp = reinterpret_cast<uint4*>(label_out + e * 4);                 // labels are 0..255: the high dwords are 0
-      lp[0] = make_uint4(lab[0], 0u, lab[1], 0u);
-      lp[1] = make_uint4(lab[2], 0u, lab[3], 0u);
-    } else {
-      image_out[e] = v[0];
-      label_out[e] = (long long)lab[0];
-    }
+    volume_feed_gather<V>(s, c0, c1, c2, fa, fc, l, R2, v, lab);
+    feed_store<V>(image_out + e * V, label_out + e * V, v, lab);
   }
 }
 
 // ---- the same chain with an AFFINE stage between the pad and the flips (MONAI RandAffined, nnU-Net's rotation and scaling):
 // crop -> symmetric pad -> affine about the patch centre -> flips -> rot90 -> intensity.  The definition is in DESIGN.md §2 "Affine
 // stage of the 3-D feed"; tests/affine_feed_ref.py restates it in numpy.  A sample either has the stage (`affine` = 1) or it does not:
-// without it the sample takes the integer gather of volume_feed_kernel, bit for bit.  With it, the output voxel is mapped back through
+// without it the sample goes through volume_feed_gather, as in volume_feed_kernel.  With it, the output voxel is mapped back through
 // rot90 and the flips to integer patch coordinates p as above, and then, every fp64 product and sum rounded on its own,
 //   u_a = p_a - (R_a - 1) / 2,  t_a = (c_a - l_a) + (R_a - 1) / 2                (both exact),
 //   x_a = t_a + ((M_a0 u_0 + M_a1 u_1) + M_a2 u_2)                               (a coordinate of the WHOLE volume, not of the crop),
@@ -529,7 +540,7 @@ __device__ __forceinline__ AffineAxis affine_axis(double x, int n) {
 // Arguments, grid and stores of volume_feed_kernel<V, DEV>; one sample per blockIdx.y, so `affine` is wave-uniform.  An affine sample
 // takes one thread per V consecutive OUTPUT depth voxels as well: every voxel's coordinates come from the definition (the part of x_a
 // that the V voxels share, M_a0 u_0 + M_a1 u_1, is the same value for each of them), eight fp32 tap loads and one label load a voxel.
-// DEV = true: t_a is formed on the device from the clamped origin.  No LDS, no atomics.
+// DEV = true: t_a is formed on the device from the clamped origin (clamp_device_origin).  No LDS, no atomics.
 template <int V, bool DEV>
 __global__ __launch_bounds__(256) void volume_feed_affine_kernel(VolumeFeedAffineBatch fb, const int* __restrict__ origins,
                                                                  float* __restrict__ image_out, long long* __restrict__ label_out, int R0, int R1,
@@ -544,12 +555,7 @@ __global__ __launch_bounds__(256) void volume_feed_affine_kernel(VolumeFeedAffin
   const VolumeFeedAffineSample& rec = fb.s[b];
   const VolumeFeedSample& s = rec.f;
   int c0 = s.c0, c1 = s.c1, c2 = s.c2;
-  if constexpr (DEV) {
-    const int* __restrict__ o = origins + 3 * b;
-    c0 = o[0] < 0 ? 0 : (o[0] > s.c0 ? s.c0 : o[0]);
-    c1 = o[1] < 0 ? 0 : (o[1] > s.c1 ? s.c1 : o[1]);
-    c2 = o[2] < 0 ? 0 : (o[2] > s.c2 ? s.c2 : o[2]);
-  }
+  if constexpr (DEV) clamp_device_origin(origins, b, c0, c1, c2);
   const bool affine = rec.affine != 0;
   const double h0 = (double)(R0 - 1) * 0.5, h1 = (double)(R1 - 1) * 0.5, h2 = (double)(R2 - 1) * 0.5;
   const double t0 = (double)(c0 - s.l0) + h0, t1 = (double)(c1 - s.l1) + h1, t2 = (double)(c2 - s.l2) + h2;
@@ -559,34 +565,14 @@ __global__ __launch_bounds__(256) void volume_feed_affine_kernel(VolumeFeedAffin
     const int l = (int)(r % q2) * V;
     const unsigned rj = r / q2;
     const int j = (int)(rj % R1), i = (int)(rj / R1);
-    int fa, fc;                                                               // rot90 and the flips of axes 0, 1, as in volume_feed_kernel
-    switch (s.k & 3) {
-      case 0: fa = i; fc = j; break;
-      case 1: fa = j; fc = R1 - 1 - i; break;
-      case 2: fa = R0 - 1 - i; fc = R1 - 1 - j; break;
-      default: fa = R0 - 1 - j; fc = i; break;
-    }
+    int fa, fc;                                                               // out[i][j] = flipped[fa][fc]
+    rot90_source(s.k, i, j, R0, R1, fa, fc);
     if (s.flip & 1) fa = R0 - 1 - fa;
     if (s.flip & 2) fc = R1 - 1 - fc;
     float v[V];
     unsigned lab[V];
-    if (!affine) {                                                            // the integer gather of volume_feed_kernel
-      const int a = fa - s.l0, c = fc - s.l1;
-      const int d0 = (rev ? R2 - 1 - l : l) - s.l2, step = rev ? -1 : 1;
-      const bool row = a >= 0 && a < s.s0 && c >= 0 && c < s.s1;
-      const long base = row ? ((long)(c0 + a) * s.n1 + (c1 + c)) * s.n2 + c2 : 0;
-#pragma unroll
-      for (int t = 0; t < V; ++t) {
-        const int d = d0 + t * step;
-        float x = 0.f;
-        lab[t] = 0u;
-        if (row && d >= 0 && d < s.s2) {
-          x = s.image[base + d];
-          lab[t] = s.label[base + d];
-        }
-        const float m = x * s.mul;
-        v[t] = m + s.add;
-      }
+    if (!affine) {
+      volume_feed_gather<V>(s, c0, c1, c2, fa, fc, l, R2, v, lab);
     } else {
       const double u0 = (double)fa - h0, u1 = (double)fc - h1;
       const double g0 = rec.m[0] * u0 + rec.m[1] * u1;                         // two products and a sum, each rounded (contraction off)
@@ -626,15 +612,7 @@ __global__ __launch_bounds__(256) void volume_feed_affine_kernel(VolumeFeedAffin
         if (a0.nn >= 0 && a1.nn >= 0 && a2.nn >= 0) lab[t] = s.label[((long)a0.nn * s.n1 + a1.nn) * s.n2 + a2.nn];
       }
     }
-    if constexpr (V == 4) {
-      *reinterpret_cast<float4*>(image_out + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
-      uint4* lp = reinterpret_cast<uint4*>(label_out + e * 4);                 // labels are 0..255: the high dwords are 0
-      lp[0] = make_uint4(lab[0], 0u, lab[1], 0u);
-      lp[1] = make_uint4(lab[2], 0u, lab[3], 0u);
-    } else {
-      image_out[e] = v[0];
-      label_out[e] = (long long)lab[0];
-    }
+    feed_store<V>(image_out + e * V, label_out + e * V, v, lab);
   }
 }
 

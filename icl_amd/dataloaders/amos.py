@@ -52,10 +52,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .brats2019 import DeviceVolumeStore
+from .brats2019 import FEED_MAX_BATCH, DeviceVolumeStore      # noqa: F401  (FEED_MAX_BATCH is re-exported)
 from .intensity import _check_stage, _intensity_rows
-
-FEED_MAX_BATCH = 16         # icl_volume_feed takes up to 16 samples per launch (kFeedMaxBatch)
 
 
 def draw_amos_params(shape: Sequence[int], roi: Sequence[int], rng=np.random, flip_prob: float = 0.10, rot_prob: float = 0.10,
@@ -284,49 +282,70 @@ class OnDeviceAugmentAMOS:
                                  f"{' or '.join(map(str, shapes))} on {dev}, got {got}")
         return image, label
 
+    ROW_VALUES = 16             # the fixed part of a parameter row; nine matrix entries may follow it
+
+    def _row_wording(self) -> str:
+        return "one parameter row of 16 values per index"
+
+    def _sample_volumes(self, indices: List[int]) -> List[int]:
+        """The volume of every sample of the batch."""
+        return indices
+
+    def _check_row(self, who: str, i: int, row) -> None:
+        """What a subclass checks of a row of volume ``i`` beyond the extents and the quarter turn."""
+
+    def _launch(self, L, chunk, rows, args, affine, outs, stream):
+        """The launches of one chunk of at most ``FEED_MAX_BATCH`` samples: ``chunk`` their volumes, ``rows`` their parameter rows,
+        ``args = (images, labels, ints, floats)`` as the gather entries take them, ``affine`` the ``_affine_block`` or None, ``outs``
+        the image and label addresses of the chunk's first sample."""
+        if affine is None:                       # no sample of the launch has an affine: the launch of a loader without the stage
+            _lib.check(L.icl_volume_feed(*args, len(chunk), *outs, *self.roi, stream), "volume_feed")
+        else:
+            _lib.check(L.icl_volume_feed_affine(*args, affine, len(chunk), *outs, *self.roi, stream), "volume_feed_affine")
+
     def batch(self, indices: Sequence[int], params: Optional[Sequence[Sequence[float]]] = None, out=None, intensity_params=None):
         """One batch for the volumes ``indices`` of the store.  ``params``: one ``draw_amos_params`` row per index (drawn here when
         not given).  ``intensity_params``: one ``draw_intensity_params`` row per sample for the loader's intensity stage (drawn here,
         after ``params``, when not given).  ``out=(image, label)``: write into the caller's tensors — for example ``ICLTrainer.static_vol`` /
         ``static_lab`` after ``capture()``, so that a captured step needs no extra copy — and return views of them; shape
         (``[B,1,*roi]``; the label may also be ``[B,*roi]``), dtype, device and contiguity are checked.  More than 16 indices are
-        handled as chunks of 16."""
-        st = self.store
+        handled as chunks of 16.
+
+        ``OnDeviceAugmentPosNeg``: one batch of ``len(indices) * num_samples`` samples.  ``params``: ``num_samples``
+        ``draw_posneg_params`` rows per index, volume-major; a rank at or past the length of its list is refused here, since only the
+        host knows the lengths.  ``intensity_params``: one row per SAMPLE.  More than 16 samples go as chunks of 16."""
+        st, who, base = self.store, f"{type(self).__name__}.batch", self.ROW_VALUES
         indices = [int(i) for i in indices]
-        n = len(indices)
-        if n < 1:
-            raise ValueError("OnDeviceAugmentAMOS.batch: no indices")
+        if len(indices) < 1:
+            raise ValueError(f"{who}: no indices")
         if params is None:
             params = self.draw(indices)
+        sample_of = self._sample_volumes(indices)
+        n = len(sample_of)
         if len(params) != n:
-            raise ValueError("OnDeviceAugmentAMOS.batch: one parameter row of 16 values per index")
-        intensity_params = _intensity_rows(self.intensity, self.roi, n, intensity_params, "OnDeviceAugmentAMOS.batch")
-        suffixes = _affine_suffixes("OnDeviceAugmentAMOS.batch", params, 16, "one parameter row of 16 values per index")
-        for i, row in zip(indices, params):
+            raise ValueError(f"{who}: {self._row_wording()}")
+        intensity_params = _intensity_rows(self.intensity, self.roi, n, intensity_params, who)
+        suffixes = _affine_suffixes(who, params, base, self._row_wording())
+        for i, row in zip(sample_of, params):
             if tuple(int(v) for v in row[:3]) != tuple(st.images[i].shape):
-                raise ValueError(f"OnDeviceAugmentAMOS.batch: parameter row for extents {tuple(row[:3])}, volume {i} is {tuple(st.images[i].shape)}")
+                raise ValueError(f"{who}: parameter row for extents {tuple(row[:3])}, volume {i} is {tuple(st.images[i].shape)}")
             if int(row[13]) & 1 and self.roi[0] != self.roi[1]:
-                raise ValueError(f"OnDeviceAugmentAMOS.batch: k = {int(row[13])} with roi {self.roi}: an odd quarter turn needs roi[0] == roi[1]")
+                raise ValueError(f"{who}: k = {int(row[13])} with roi {self.roi}: an odd quarter turn needs roi[0] == roi[1]")
+            self._check_row(who, i, row)
         image, label = self._outputs(n, out)
-        dev = st.device
         per = self.roi[0] * self.roi[1] * self.roi[2]
         flat_image, flat_label = image.view(n, per), label.view(n, per)
         L = _lib.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+        stream = _lib.stream_of(st.device)
         for lo in range(0, n, FEED_MAX_BATCH):
-            chunk = indices[lo:lo + FEED_MAX_BATCH]
+            chunk, rows = sample_of[lo:lo + FEED_MAX_BATCH], params[lo:lo + FEED_MAX_BATCH]
             m = len(chunk)
             ptrs = ctypes.c_void_p * m
-            ints = (ctypes.c_int32 * (14 * m))(*[int(v) for row in params[lo:lo + m] for v in row[:14]])
-            floats = (ctypes.c_float * (2 * m))(*[float(v) for row in params[lo:lo + m] for v in row[14:16]])
-            images, labels = ptrs(*[st.images[i].data_ptr() for i in chunk]), ptrs(*[st.labels[i].data_ptr() for i in chunk])
-            affine = _affine_block(suffixes[lo:lo + m])
-            if affine is None:                   # no sample of the launch has an affine: the launch of a loader without the stage
-                _lib.check(L.icl_volume_feed(images, labels, ints, floats, m, flat_image[lo:].data_ptr(), flat_label[lo:].data_ptr(),
-                                             *self.roi, stream), "volume_feed")
-            else:
-                _lib.check(L.icl_volume_feed_affine(images, labels, ints, floats, affine, m, flat_image[lo:].data_ptr(),
-                                                    flat_label[lo:].data_ptr(), *self.roi, stream), "volume_feed_affine")
+            args = (ptrs(*[st.images[i].data_ptr() for i in chunk]), ptrs(*[st.labels[i].data_ptr() for i in chunk]),
+                    (ctypes.c_int32 * (14 * m))(*[int(v) for row in rows for v in row[:14]]),
+                    (ctypes.c_float * (2 * m))(*[float(v) for row in rows for v in row[14:16]]))
+            self._launch(L, chunk, rows, args, _affine_block(suffixes[lo:lo + m]), (flat_image[lo:].data_ptr(), flat_label[lo:].data_ptr()),
+                         stream)
         if intensity_params is not None:
             self.intensity.apply(image, intensity_params)
         return {"image": image, "label": label.view((n, 1) + self.roi)}
@@ -358,7 +377,7 @@ class ForegroundIndex:
         dev = store.device
         L = _lib.lib()
         tile = rank_tile()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+        stream = _lib.stream_of(dev)
         for image, label in zip(store.images, store.labels):
             n = tuple(int(v) for v in image.shape)
             if max(n) > 65535 or n[0] * n[1] * n[2] > 2 ** 31 - 1:
@@ -461,63 +480,35 @@ class OnDeviceAugmentPosNeg(OnDeviceAugmentAMOS):
         return [row for i in indices for row in draw_posneg_params(self.store.images[i].shape, self.roi, ix.n_fg[i], ix.n_bg[i], self.rng,
                                                                    self.pos, self.neg, self.num_samples, **self.probabilities)]
 
-    def batch(self, indices: Sequence[int], params: Optional[Sequence[Sequence[float]]] = None, out=None, intensity_params=None):
-        """One batch of ``len(indices) * num_samples`` samples.  ``params``: ``num_samples`` ``draw_posneg_params`` rows per index,
-        volume-major (drawn here when not given); a rank at or past the length of its list is refused here, since only the host
-        knows the lengths.  ``out=(image, label)`` and ``intensity_params`` (one row per SAMPLE) as in ``OnDeviceAugmentAMOS.batch``.  More than 16 samples go as chunks of 16."""
-        st, ix, k = self.store, self.index, self.num_samples
-        indices = [int(i) for i in indices]
-        if len(indices) < 1:
-            raise ValueError("OnDeviceAugmentPosNeg.batch: no indices")
-        if params is None:
-            params = self.draw(indices)
-        sample_of = [i for i in indices for _ in range(k)]          # the volume of every sample
-        n = len(sample_of)
-        if len(params) != n:
-            raise ValueError(f"OnDeviceAugmentPosNeg.batch: {k} parameter rows of 18 values per index")
-        intensity_params = _intensity_rows(self.intensity, self.roi, n, intensity_params, "OnDeviceAugmentPosNeg.batch")
-        suffixes = _affine_suffixes("OnDeviceAugmentPosNeg.batch", params, 18, f"{k} parameter rows of 18 values per index")
-        for i, row in zip(sample_of, params):
-            if tuple(int(v) for v in row[:3]) != tuple(st.images[i].shape):
-                raise ValueError(f"OnDeviceAugmentPosNeg.batch: parameter row for extents {tuple(row[:3])}, volume {i} is {tuple(st.images[i].shape)}")
-            if int(row[13]) & 1 and self.roi[0] != self.roi[1]:
-                raise ValueError(f"OnDeviceAugmentPosNeg.batch: k = {int(row[13])} with roi {self.roi}: an odd quarter turn needs roi[0] == roi[1]")
-            kind, rank = int(row[16]), int(row[17])
-            if kind not in (KIND_FG, KIND_BG):
-                raise ValueError(f"OnDeviceAugmentPosNeg.batch: kind {kind} (0 foreground, 1 background)")
-            total = ix.n_fg[i] if kind == KIND_FG else ix.n_bg[i]
-            if not 0 <= rank < total:
-                raise ValueError(f"OnDeviceAugmentPosNeg.batch: rank {rank} outside the {'foreground' if kind == KIND_FG else 'background'} "
-                                 f"list of volume {i} ({total} voxels)")
-        image, label = self._outputs(n, out)
-        dev = st.device
-        per = self.roi[0] * self.roi[1] * self.roi[2]
-        flat_image, flat_label = image.view(n, per), label.view(n, per)
-        origins = torch.empty((n, 3), dtype=torch.int32, device=dev)
-        L = _lib.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
-        for lo in range(0, n, FEED_MAX_BATCH):
-            chunk = sample_of[lo:lo + FEED_MAX_BATCH]
-            rows = params[lo:lo + FEED_MAX_BATCH]
-            m = len(chunk)
-            ptrs = ctypes.c_void_p * m
-            images, labels = ptrs(*[st.images[i].data_ptr() for i in chunk]), ptrs(*[st.labels[i].data_ptr() for i in chunk])
-            select = (ctypes.c_int32 * (8 * m))(*[int(v) for row in rows for v in (*row[:3], row[16], row[17], *row[6:9])])
-            _lib.check(L.icl_rank_select(images, labels, ptrs(*[ix.fg[i].data_ptr() for i in chunk]), ptrs(*[ix.bg[i].data_ptr() for i in chunk]),
-                                         select, ix.image_threshold, m, origins[lo:].data_ptr(), stream), "rank_select")
-            ints = (ctypes.c_int32 * (14 * m))(*[int(v) for row in rows for v in row[:14]])
-            floats = (ctypes.c_float * (2 * m))(*[float(v) for row in rows for v in row[14:16]])
-            affine = _affine_block(suffixes[lo:lo + m])
-            if affine is None:
-                _lib.check(L.icl_volume_feed_origins(images, labels, ints, floats, m, origins[lo:].data_ptr(), flat_image[lo:].data_ptr(),
-                                                     flat_label[lo:].data_ptr(), *self.roi, stream), "volume_feed_origins")
-            else:
-                _lib.check(L.icl_volume_feed_affine_origins(images, labels, ints, floats, affine, m, origins[lo:].data_ptr(),
-                                                            flat_image[lo:].data_ptr(), flat_label[lo:].data_ptr(), *self.roi, stream),
-                           "volume_feed_affine_origins")
-        if intensity_params is not None:
-            self.intensity.apply(image, intensity_params)
-        return {"image": image, "label": label.view((n, 1) + self.roi)}
+    ROW_VALUES = 18             # a draw_amos_params row, then (kind, rank)
+
+    def _row_wording(self) -> str:
+        return f"{self.num_samples} parameter rows of 18 values per index"
+
+    def _sample_volumes(self, indices: List[int]) -> List[int]:
+        return [i for i in indices for _ in range(self.num_samples)]
+
+    def _check_row(self, who: str, i: int, row) -> None:
+        kind, rank = int(row[16]), int(row[17])
+        if kind not in (KIND_FG, KIND_BG):
+            raise ValueError(f"{who}: kind {kind} (0 foreground, 1 background)")
+        total = self.index.n_fg[i] if kind == KIND_FG else self.index.n_bg[i]
+        if not 0 <= rank < total:
+            raise ValueError(f"{who}: rank {rank} outside the {'foreground' if kind == KIND_FG else 'background'} "
+                             f"list of volume {i} ({total} voxels)")
+
+    def _launch(self, L, chunk, rows, args, affine, outs, stream):
+        ix, m = self.index, len(chunk)
+        ptrs = ctypes.c_void_p * m
+        origins = torch.empty((m, 3), dtype=torch.int32, device=self.store.device)
+        select = (ctypes.c_int32 * (8 * m))(*[int(v) for row in rows for v in (*row[:3], row[16], row[17], *row[6:9])])
+        _lib.check(L.icl_rank_select(args[0], args[1], ptrs(*[ix.fg[i].data_ptr() for i in chunk]), ptrs(*[ix.bg[i].data_ptr() for i in chunk]),
+                                     select, ix.image_threshold, m, origins.data_ptr(), stream), "rank_select")
+        if affine is None:
+            _lib.check(L.icl_volume_feed_origins(*args, m, origins.data_ptr(), *outs, *self.roi, stream), "volume_feed_origins")
+        else:
+            _lib.check(L.icl_volume_feed_affine_origins(*args, affine, m, origins.data_ptr(), *outs, *self.roi, stream),
+                       "volume_feed_affine_origins")
 
 
 class AMOSDeviceLoader:
@@ -696,8 +687,7 @@ def plan_prefix(shape: Sequence[int], box: Sequence[int], affine=None, spacing: 
                       window=consts, clip=clip)
 
 
-def _stream_of(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+_stream_of = _lib.stream_of
 
 
 def _refuse_host_memory(dev, who: str):

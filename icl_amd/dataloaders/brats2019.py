@@ -28,6 +28,8 @@ from torch.utils.data.sampler import Sampler
 from .. import _lib
 from .intensity import _check_stage, _intensity_rows
 
+FEED_MAX_BATCH = 16         # samples per launch of the 3-D gather entries, icl_crop_rotflip* and icl_volume_feed* (kFeedMaxBatch)
+
 
 # --------------------------------------------------------------------------------------------------------------------
 # index streams
@@ -244,9 +246,9 @@ class OnDeviceAugment:
         image = torch.empty((n, channels) + self.patch, dtype=torch.float32, device=dev)
         label = torch.empty((n,) + self.patch, dtype=torch.int64, device=dev)
         L = _lib.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
-        for lo in range(0, n, 16):                        # both entries take up to 16 samples per launch
-            chunk = list(indices[lo:lo + 16])
+        stream = _lib.stream_of(dev)
+        for lo in range(0, n, FEED_MAX_BATCH):            # both entries take up to FEED_MAX_BATCH samples per launch
+            chunk = list(indices[lo:lo + FEED_MAX_BATCH])
             m = len(chunk)
             ptrs = ctypes.c_void_p * m
             flat = (ctypes.c_int32 * (11 * m))(*[int(v) for row in params[lo:lo + m] for v in row])
@@ -299,7 +301,7 @@ def channel_norm_stats(volume: torch.Tensor, mask: str = "nonzero") -> torch.Ten
     dev = volume.device
     stats = torch.empty((channels, 4), dtype=torch.float64, device=dev)
     ws = torch.empty(NORM_WS_DOUBLES, dtype=torch.float64, device=dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+    stream = _lib.stream_of(dev)
     _lib.check(_lib.lib().icl_channel_norm_stats(volume.data_ptr(), channels, voxels, NORM_MASKS[mask], stats.data_ptr(), ws.data_ptr(),
                                                  stream), "channel_norm_stats")
     return stats
@@ -320,7 +322,7 @@ def normalize_channels_(volume: torch.Tensor, mask: str = "nonzero", apply_to: s
     channels, voxels = _norm_volume(volume, mask, "normalize_channels_")
     stats = channel_norm_stats(volume, mask)
     dev = volume.device
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+    stream = _lib.stream_of(dev)
     _lib.check(_lib.lib().icl_channel_norm_apply(volume.data_ptr(), channels, voxels, NORM_MASKS[mask], NORM_APPLY[apply_to],
                                                  stats.data_ptr(), stream), "channel_norm_apply")
     return volume

@@ -191,10 +191,6 @@ class DeviceSliceStore:
         return len(self.images)
 
 
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
-
-
 class OnDeviceAugment2D:
     """``RandomGenerator(patch)`` + batch collation on the GPU: ``batch(indices)`` returns
     ``{'image': [B,1,O0,O1] fp32, 'label': [B,O0,O1] uint8}`` like the reference DataLoader's ``sampled_batch`` (without ``idx``:
@@ -215,7 +211,7 @@ class OnDeviceAugment2D:
         image = torch.empty((n, 1) + self.patch, dtype=torch.float32, device=dev)
         label = torch.empty((n,) + self.patch, dtype=torch.uint8, device=dev)
         L = _lib.lib()
-        stream = _stream(dev)
+        stream = _lib.stream_of(dev)
         for lo in range(0, n, SLICE_MAX_BATCH):
             chunk = list(indices[lo:lo + SLICE_MAX_BATCH])
             m = len(chunk)
@@ -239,5 +235,5 @@ def resize_slices(src: torch.Tensor, output_size: Sequence[int]) -> torch.Tensor
     zoom_factor(n0, o0), zoom_factor(n1, o1)             # the output extents are the ones scipy derives
     dst = torch.empty((b, o0, o1), dtype=src.dtype, device=src.device)
     _lib.check(_lib.lib().icl_slice_resize(src.data_ptr(), dst.data_ptr(), b, n0, n1, o0, o1, 0 if src.dtype == torch.float32 else 1,
-                                           _stream(src.device)), "slice_resize")
+                                           _lib.stream_of(src.device)), "slice_resize")
     return dst

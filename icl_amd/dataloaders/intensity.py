@@ -327,7 +327,7 @@ class IntensityAugment:
         per = roi[0] * roi[1] * roi[2]
         flat = image.view(n, per)
         L = _lib.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+        stream = _lib.stream_of(dev)
         for lo in range(0, n, INTENSITY_MAX_BATCH):
             chunk = rows[lo:lo + INTENSITY_MAX_BATCH]
             m = len(chunk)

@@ -161,3 +161,83 @@ def big_reference():
     volumes, rows = big_batch()
     want = [forward_chain(*v, row, BIG_ROI) for v, row in zip(volumes, rows)]
     return np.stack([w[0] for w in want]), np.stack([w[1] for w in want])
+
+
+# ---- intensity: two roundings, told apart from one ----------------------------------------------------------------------------------
+
+TWICE_SOURCES = [(9, 7, 8), (5, 3, 2)]                # larger than both small ROIs on every axis but the last | padded on every axis
+TWICE_MUL, TWICE_ADD = np.float32(1.1), np.float32(0.07)
+TWICE_DIFFERING = [146, 10]                           # voxels of each whole source at which one rounding and two give different fp32
+
+
+@functools.lru_cache(maxsize=None)
+def twice_volume(shape):
+    """Hash-filled image (its products with 1.1 are inexact, unlike ``source_volume``'s) with ``source_volume``'s labels (never 0)."""
+    return hash_uniform_np(int(np.prod(shape)), 7, 1.0).reshape(shape), source_volume(shape)[1]
+
+
+def fused_intensity(x):
+    """``x * mul + add`` rounded ONCE to fp32: what a contracted multiply-add would give."""
+    return (x.astype(np.float64) * np.float64(TWICE_MUL) + np.float64(TWICE_ADD)).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def twice_rows(roi):
+    """16 samples, volume-major (8 of each source): all eight flip masks, k = 0..3 spread over them, origins walking their ranges.
+    Returns (indices, rows, want_image, want_label) with ``forward_chain``'s values; asserts that a fused multiply-add would differ from
+    them at one un-padded voxel or more of EVERY sample."""
+    for shape, count in zip(TWICE_SOURCES, TWICE_DIFFERING):
+        x = twice_volume(shape)[0]
+        assert int((fused_intensity(x) != ((x * TWICE_MUL).astype(np.float32) + TWICE_ADD).astype(np.float32)).sum()) == count, shape
+    indices, rows, want = [], [], []
+    for src, shape in enumerate(TWICE_SOURCES):
+        span = [max(n - r, 0) for n, r in zip(shape, roi)]
+        for flip in range(8):
+            origin = [(flip + a) % (span[a] + 1) for a in range(3)]
+            row = make_row(shape, roi, origin, flip, (flip + src) % 4, TWICE_MUL, TWICE_ADD)
+            image, label = twice_volume(shape)
+            w = forward_chain(image, label, row, roi)
+            plain, lab = forward_chain(image, label, (*row[:14], 1.0, 0.0), roi)       # the geometry alone
+            source = lab != 0                                                          # the un-padded region
+            assert (fused_intensity(plain)[source] != w[0][source]).any(), ("no voxel tells one rounding from two", shape, row)
+            indices.append(src)
+            rows.append(row)
+            want.append(w)
+    assert {r[12] for r in rows} == set(range(8)) and {r[13] for r in rows} == {0, 1, 2, 3}
+    return indices, rows, np.stack([w[0] for w in want]), np.stack([w[1] for w in want])
+
+
+def check_twice_rounded_intensity(device, roi):
+    """``fp32(fp32(x * mul) + add)`` with values whose product is inexact (mul = 1.1, add = 0.07, hash-filled sources), so that a
+    multiply-add contracted into one fma, in a kernel or in a helper it calls, gives other bits: the feed equals ``forward_chain``
+    exactly through ``icl_volume_feed``, through ``icl_volume_feed_origins`` (``OnDeviceAugmentPosNeg``; every voxel is foreground, so
+    rank = flat index of the crop's centre), and as the plain samples of an ``icl_volume_feed_affine`` launch; the affine samples of
+    that launch equal ``affine_feed_ref.affine_chain``."""
+    import affine_feed_ref as affine_ref
+    from icl_amd.dataloaders.amos import KIND_FG, ForegroundIndex, OnDeviceAugmentPosNeg, affine_matrix
+    indices, rows, want_image, want_label = twice_rows(roi)
+    store = DeviceVolumeStore([twice_volume(s) for s in TWICE_SOURCES], device)
+
+    def equal(got, what, expect=(want_image, want_label)):
+        gi, gl = got["image"].cpu().numpy(), got["label"].cpu().numpy()
+        for j, row in enumerate(rows):
+            assert np.array_equal(gi[j], expect[0][j]), (what, "image", roi, j, row)
+            assert np.array_equal(gl[j], expect[1][j]), (what, "label", roi, j, row)
+
+    equal(OnDeviceAugmentAMOS(store, roi).batch(indices, params=rows), "volume_feed")
+
+    posneg = []
+    for row in rows:
+        n, c, s = row[:3], row[3:6], row[6:9]
+        centre = [c[a] + s[a] // 2 for a in range(3)]                                  # origin = clamp(centre - s // 2, 0, n - s) = c
+        posneg.append((*n, 0, 0, 0, *row[6:16], KIND_FG, (centre[0] * n[1] + centre[1]) * n[2] + centre[2]))
+    feed = OnDeviceAugmentPosNeg(store, ForegroundIndex(store), roi, num_samples=8)
+    equal(feed.batch([0, 1], params=posneg), "volume_feed_origins")
+
+    M = tuple(float(v) for v in affine_matrix((0.3, -0.2, 0.1), (1.1, 0.9, 1.0)).reshape(-1))
+    with_affine = {3, 11}                                                              # one sample of each source
+    mixed = [(*row, *M) if j in with_affine else row for j, row in enumerate(rows)]
+    expect_image, expect_label = want_image.copy(), want_label.copy()
+    for j in with_affine:
+        expect_image[j], expect_label[j] = affine_ref.affine_chain(*twice_volume(TWICE_SOURCES[indices[j]]), rows[j], M, roi)
+    equal(OnDeviceAugmentAMOS(store, roi).batch(indices, params=mixed), "volume_feed_affine", (expect_image, expect_label))

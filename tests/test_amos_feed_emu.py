@@ -52,6 +52,13 @@ def test_padded_voxels_hold_the_shift_and_label_zero(store, roi):
     ref.check_padded_voxels(store, roi)
 
 
+@pytest.mark.parametrize("roi", [ref.ROI_SCALAR, ref.ROI_QUAD])
+def test_inexact_products_are_rounded_twice_on_every_route(emu_library, roi):
+    """mul = 1.1, add = 0.07 on hash-filled volumes: plain, device-origin and mixed affine launches (the emulator never contracts; the
+    GPU run of the same check is the one that can fail)."""
+    ref.check_twice_rounded_intensity("cpu", roi)
+
+
 def test_out_tensors_are_filled_and_returned_as_views(store):
     roi = ref.ROI_QUAD
     indices, rows, want_image, want_label = ref.sweep(roi)

@@ -48,6 +48,13 @@ def test_quad_path_sweep_on_the_gpu(small_store):
     ref.check_padded_voxels(small_store, ref.ROI_QUAD)
 
 
+@pytest.mark.parametrize("roi", [ref.ROI_SCALAR, ref.ROI_QUAD])
+def test_inexact_products_are_rounded_twice_on_every_route(dev, roi):
+    """mul = 1.1, add = 0.07 on hash-filled volumes, where one rounding and two differ: a multiply-add contracted into an fma in
+    volume_feed_gather or the affine path changes these bits.  Plain, device-origin and mixed affine launches."""
+    ref.check_twice_rounded_intensity(dev, roi)
+
+
 def test_batch_of_four_at_the_trainers_roi_equals_the_forward_chain(big_store):
     """(130, 101, 70), (96, 96, 96), (97, 140, 96), (60, 200, 111) -> 96^3: every flip bit, every k, non-zero shifts."""
     _, rows = ref.big_batch()

@@ -14,7 +14,11 @@ variant.  The 22 MB of source volumes stay cache-resident in every variant alike
   regression   icl_volume_feed of this build (`plain`, and `plain_again`: the same call a second time in every round, whose ratio to
                `plain` is the run-to-run spread of this box) against the same entry point of the build of the parent commit
                (`plain_parent`, only with --parent: the other library is loaded side by side with ctypes), at 96^3 (the quad
-               kernel) and at 96 x 96 x 90 (the one-voxel kernel).  Outputs compared bit for bit.
+               kernel) and at 96 x 96 x 90 (the one-voxel kernel).  Outputs compared bit for bit.  With --stages-out, the same
+               check for the other five gather entries: icl_volume_feed_origins, icl_volume_feed_affine with all flags 1 and with
+               all flags 0, icl_volume_feed_affine_origins, icl_crop_rotflip and icl_crop_rotflip_channels at C = 4, each with its
+               own `_again` and `_parent`; the band for this / parent is 1 +- twice the largest |again / first - 1| of the run
+               (the ratio of two independent medians carries the spread of both); written to <stages-out>.json.
   affine       icl_volume_feed_affine with every sample affine (angles in +-0.5 rad, anisotropic zoom in 0.7 .. 1.4) and with every
                flag 0 (the integer path inside the new kernel), against `plain`, and as a fraction of the device copy rate for the
                bytes written (`copy`: Tensor.copy_ of one image and one label buffer, device to device); `affine_identity`: every
@@ -42,6 +46,7 @@ import torch  # noqa: E402
 
 from icl_amd import _lib  # noqa: E402
 from icl_amd.dataloaders.amos import affine_matrix, amos_volume_store  # noqa: E402
+from icl_amd.dataloaders.brats2019 import DeviceVolumeStore, draw_rotflip_crop  # noqa: E402
 from icl_amd.utils.hashfill import hash_uniform_np  # noqa: E402
 
 SHAPES = [(130, 101, 70), (96, 96, 96), (97, 140, 96), (60, 200, 111)]
@@ -74,12 +79,117 @@ def window(fn, launches):
     return e0.elapsed_time(e1) * 1e3 / launches      # microseconds a call
 
 
+GATHER_ENTRIES = ("icl_volume_feed", "icl_volume_feed_origins", "icl_volume_feed_affine", "icl_volume_feed_affine_origins",
+                  "icl_crop_rotflip", "icl_crop_rotflip_channels")
+
+
 def load_parent(path):
+    """The parent commit's library beside this build's: the six gather entries, with the signatures of icl_amd/_lib.py (the ABI is shared)."""
     lib = ctypes.CDLL(path)
-    P, I = ctypes.c_void_p, ctypes.c_int
-    lib.icl_volume_feed.restype = ctypes.c_int
-    lib.icl_volume_feed.argtypes = [P, P, P, P, I, P, P, I, I, I, P]
+    for name in GATHER_ENTRIES:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _lib._SIGNATURES[name]
     return lib
+
+
+def measure_entries(L, parent, store, store4, dev, roi):
+    """The regression check of the five gather entries beside icl_volume_feed, on the batch of ``measure``: every entry of this build
+    (`x`, and `x_again` in the same round), against the parent's (`x_parent`), interleaved, outputs rotating and compared bit for bit."""
+    vols, rows, mats = make_rows(roi)
+    m = len(vols)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    ptrs = ctypes.c_void_p * m
+    images, labels = ptrs(*[store.images[j].data_ptr() for j in vols]), ptrs(*[store.labels[j].data_ptr() for j in vols])
+    images4 = ptrs(*[store4.images[j].data_ptr() for j in vols])
+    ints = (ctypes.c_int32 * (14 * m))(*[int(v) for r in rows for v in r[:14]])
+    floats = (ctypes.c_float * (2 * m))(*[float(v) for r in rows for v in r[14:16]])
+    affine_on = (ctypes.c_double * (10 * m))(*[float(v) for M in mats for v in (1.0, *M)])
+    affine_off = (ctypes.c_double * (10 * m))(*[float(v) for M in mats for v in (0.0, *M)])
+    origins = torch.tensor([r[3:6] for r in rows], dtype=torch.int32, device=dev)
+    np.random.seed(23)
+    crops = (ctypes.c_int32 * (11 * m))(*[int(v) for j in vols for v in draw_rotflip_crop(SHAPES[j], roi)])
+    channels = int(store4.channels)
+    sets = {c: [(torch.empty((m, c) + roi, device=dev), torch.empty((m,) + roi, dtype=torch.int64, device=dev)) for _ in range(SETS)]
+            for c in (1, channels)}
+    turn = {"n": 0}
+
+    def outs(c=1):
+        turn["n"] = (turn["n"] + 1) % SETS
+        i, l = sets[c][turn["n"]]
+        return i.data_ptr(), l.data_ptr()
+
+    calls = {
+        "volume_feed_origins": lambda lib: lib.icl_volume_feed_origins(images, labels, ints, floats, m, origins.data_ptr(), *outs(), *roi, stream),
+        "volume_feed_affine": lambda lib: lib.icl_volume_feed_affine(images, labels, ints, floats, affine_on, m, *outs(), *roi, stream),
+        "volume_feed_affine_flags_off": lambda lib: lib.icl_volume_feed_affine(images, labels, ints, floats, affine_off, m, *outs(), *roi, stream),
+        "volume_feed_affine_origins": lambda lib: lib.icl_volume_feed_affine_origins(images, labels, ints, floats, affine_on, m,
+                                                                                     origins.data_ptr(), *outs(), *roi, stream),
+        "crop_rotflip": lambda lib: lib.icl_crop_rotflip(images, labels, crops, m, *outs(), *roi, stream),
+        "crop_rotflip_channels": lambda lib: lib.icl_crop_rotflip_channels(images4, labels, crops, m, channels, *outs(channels), *roi, stream),
+    }
+
+    def run(name, lib):
+        if calls[name](lib) != 0:
+            raise SystemExit(f"{name} failed: {L.icl_last_error()}")
+
+    def result(name, lib):
+        c = channels if name == "crop_rotflip_channels" else 1
+        turn["n"] = SETS - 1                         # the next call writes set 0
+        run(name, lib)
+        torch.cuda.synchronize()
+        return sets[c][0][0].view(torch.int32).clone(), sets[c][0][1].clone()
+
+    equal, variants = {}, {}
+    for name in calls:
+        ours, theirs = result(name, L), result(name, parent)
+        equal[name] = bool(torch.equal(ours[0], theirs[0]) and torch.equal(ours[1], theirs[1]))
+        del ours, theirs
+        for suffix, lib in (("", L), ("_again", L), ("_parent", parent)):
+            variants[name + suffix] = (lambda name=name, lib=lib: run(name, lib))
+    for fn in variants.values():                     # warm-up: code objects loaded, every buffer touched
+        window(fn, 2 * SETS)
+    times = {k: [] for k in variants}
+    for _ in range(ROUNDS):
+        for k, fn in variants.items():
+            times[k].append(window(fn, LAUNCHES))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    return {"roi": list(roi), "batch": m, "channels_of_crop_rotflip_channels": channels,
+            "us_per_call": {k: {"median": round(med[k], 2), "min": round(min(v), 2), "max": round(max(v), 2)} for k, v in times.items()},
+            "again_over_first": {k: round(med[k + "_again"] / med[k], 4) for k in calls},
+            "now_over_parent": {k: round(med[k] / med[k + "_parent"], 4) for k in calls}, "equal": equal}
+
+
+def stages_record(device, blocks):
+    """profiles/feed_stages.json: per ROI the figures of ``measure`` (icl_volume_feed) and ``measure_entries``, the spread of the run
+    (the largest |again / first - 1| over every entry and ROI) and the band 1 +- twice that for median(this) / median(parent)."""
+    spread, entries = 0.0, []
+    for key, (plain, others) in blocks.items():
+        spread = max([spread, abs(plain["spread_plain_again_over_plain"] - 1)] + [abs(v - 1) for v in others["again_over_first"].values()])
+        entries.append((key, "volume_feed", plain["us_per_call"]["plain"]["median"], plain["us_per_call"]["plain_parent"]["median"],
+                        plain["spread_plain_again_over_plain"], plain["now_over_parent"], plain["equal"]["plain_parent"]))
+        for name in others["now_over_parent"]:
+            t = others["us_per_call"]
+            entries.append((key, name, t[name]["median"], t[name + "_parent"]["median"], others["again_over_first"][name],
+                            others["now_over_parent"][name], others["equal"][name]))
+    lo, hi = 1 - 2 * spread, 1 + 2 * spread
+    table = [{"roi": key, "entry": name, "median_us": now, "parent_median_us": par, "again_over_first": again, "now_over_parent": ratio,
+              "bit_equal_to_parent": eq, "verdict": "slower than the band" if ratio > hi else "faster than the band" if ratio < lo else "inside the band"}
+             for key, name, now, par, again, ratio, eq in entries]
+    return {"device": device, "sets": SETS, "launches_per_window": LAUNCHES, "rounds": ROUNDS, "spread": round(spread, 4),
+            "band": [round(lo, 4), round(hi, 4)], "entries": table,
+            "raw": {key: {"volume_feed": plain, "other_entries": others} for key, (plain, others) in blocks.items()}}
+
+
+def stages_markdown(rec):
+    lines = [f"Measured by `tools/affine_feed_time.py --parent ... --stages-out ...` on one {rec['device']}: {rec['rounds']} rounds of "
+             f"{rec['launches_per_window']} back-to-back calls per variant, variants interleaved, outputs rotating through {rec['sets']} sets.",
+             f"Spread of the run (largest |again / first - 1|): {rec['spread']}; band for now / parent: {rec['band'][0]} .. {rec['band'][1]}.", "",
+             "| ROI | entry | median µs | parent median µs | again / first | now / parent | bit-equal to parent | verdict |",
+             "|---|---|---|---|---|---|---|---|"]
+    for e in rec["entries"]:
+        lines.append(f"| {e['roi']} | `{e['entry']}` | {e['median_us']} | {e['parent_median_us']} | {e['again_over_first']} | "
+                     f"{e['now_over_parent']} | {e['bit_equal_to_parent']} | {e['verdict']} |")
+    return "\n".join(lines) + "\n"
 
 
 def make_rows(roi):
@@ -268,6 +378,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "affine_feed"), help="path without extension: .json and .md are written")
     ap.add_argument("--notes", default=os.path.join(ROOT, "profiles", "affine_feed_notes.md"),
                     help="a markdown file whose text is appended to the .md when it exists (what bounds the kernel, open work)")
+    ap.add_argument("--stages-out", default=None, help="with --parent: path without extension of the record of all six gather entries "
+                    "against the parent's (.json is written, its table is printed), e.g. profiles/feed_stages")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("affine_feed_time.py needs a HIP device")
@@ -277,6 +389,17 @@ def main():
     store = amos_volume_store([make_volume(j, s) for j, s in enumerate(SHAPES)], dev)
     big, rows, mats = measure(L, parent, store, dev, (96, 96, 96), True)
     odd, _, _ = measure(L, parent, store, dev, (96, 96, 90), False)
+    if parent is not None and a.stages_out:
+        store4 = DeviceVolumeStore([(np.stack([make_volume(j + 10 * c, s)[0] for c in range(4)]), make_volume(j, s)[1])
+                                    for j, s in enumerate(SHAPES)], dev)
+        rec = stages_record(torch.cuda.get_device_name(0), {"96 x 96 x 96": (big, measure_entries(L, parent, store, store4, dev, (96, 96, 96))),
+                                                            "96 x 96 x 90": (odd, measure_entries(L, parent, store, store4, dev, (96, 96, 90)))})
+        with open(a.stages_out + ".json", "w") as f:
+            json.dump(rec, f, indent=1)
+        print(stages_markdown(rec), flush=True)
+        bad = [f"{e['entry']} at {e['roi']}" for e in rec["entries"] if not e["bit_equal_to_parent"]]
+        if bad:
+            raise SystemExit(f"results differ from the parent's: {bad}")
     res = {"device": torch.cuda.get_device_name(0), "extents": [list(s) for s in SHAPES], "sets": SETS, "launches_per_window": LAUNCHES,
            "rounds": ROUNDS, "columns": ["now / parent"] if parent is not None else [], "roi_96": big, "roi_90": odd,
            "scipy_one_patch": scipy_context(rows, mats, (96, 96, 96))}

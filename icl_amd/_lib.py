@@ -120,6 +120,7 @@ _SIGNATURES = {
     "icl_attn_bwd_ws": (c_int, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, P]),
     "icl_crop_rotflip": (c_int, [P, P, P, I, P, P, I, I, I, P]),
     "icl_crop_rotflip_channels": (c_int, [P, P, P, I, I, P, P, I, I, I, P]),
+    "icl_crop_rotflip_affine": (c_int, [P, P, P, P, I, I, P, P, I, I, I, P]),
     "icl_channel_norm_stats": (c_int, [P, I, L, I, P, P, P]),
     "icl_channel_norm_apply": (c_int, [P, I, L, I, I, P, P]),
     "icl_volume_feed": (c_int, [P, P, P, P, I, P, P, I, I, I, P]),

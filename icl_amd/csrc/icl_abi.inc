@@ -2467,6 +2467,54 @@ int icl_crop_rotflip_channels(const void* const* images, const void* const* labe
   return check_launch("crop_rotflip_channels");
 }
 
+int icl_crop_rotflip_affine(const void* const* images, const void* const* labels, const int32_t* params, const double* affine_params, int batch,
+                            int channels, float* image_out, int64_t* label_out, int o0, int o1, int o2, void* stream) {
+  if (!images || !labels || !params || !image_out || !label_out) return fail(-1, "crop_rotflip_affine: null pointer");
+  if (!affine_params) return fail(-1, "crop_rotflip_affine: affine_params is a null pointer");
+  if (batch < 1 || batch > icl::kFeedMaxBatch)
+    return fail(-1, "crop_rotflip_affine: batch %d out of range (1 <= batch <= %d)", batch, icl::kFeedMaxBatch);
+  if (channels < 1 || channels > icl::kChannelNormMaxChannels)
+    return fail(-1, "crop_rotflip_affine: channels %d out of range (1 <= channels <= %d)", channels, icl::kChannelNormMaxChannels);
+  if (o0 < 1 || o1 < 1 || o2 < 1) return fail(-1, "crop_rotflip_affine: output extents %d x %d x %d (each must be >= 1)", o0, o1, o2);
+  if ((long)o0 * o1 * o2 > 0x7fffffffL)
+    return fail(-1, "crop_rotflip_affine: output extents %d x %d x %d (more than 2^31 - 1 voxels a sample)", o0, o1, o2);
+  icl::FeedBatch fb{};
+  const int bad = crop_feed_records(images, labels, params, batch, fb);
+  if (bad >= 0 && !(fb.s[bad].image && fb.s[bad].label)) return fail(-1, "crop_rotflip_affine: sample %d: null volume pointer", bad);
+  if (bad >= 0) return fail(-1, "crop_rotflip_affine: bad sample %d", bad);
+  icl::CropAffineBatch ab{};
+  for (int b = 0; b < batch; ++b) {
+    const double* q = affine_params + 10 * b;      // flag, M row-major
+    icl::CropAffineSample& s = ab.s[b];
+    s.f = fb.s[b];
+    if (!(q[0] == 0.0 || q[0] == 1.0)) return fail(-1, "crop_rotflip_affine: sample %d: affine flag %g (must be 0 or 1)", b, q[0]);
+    s.affine = q[0] == 1.0 ? 1 : 0;
+    for (int e = 0; e < 9; ++e) {
+      const double m = q[1 + e];
+      if (!std::isfinite(m))
+        return fail(-1, "crop_rotflip_affine: sample %d: affine matrix entry M[%d][%d] = %g is not finite", b, e / 3, e % 3, m);
+      if (std::fabs(m) > 16.0)
+        return fail(-1, "crop_rotflip_affine: sample %d: affine matrix entry M[%d][%d] = %g outside [-16, 16]", b, e / 3, e % 3, m);
+      s.m[e] = m;
+    }
+  }
+  static_assert(sizeof(icl::CropAffineBatch) == 16 * 144, "16 records of 144 B: 2,304 B of the 4 KB kernel-argument block");
+  const long voxels = (long)o0 * o1 * o2;      // per sample and channel; one grid row per sample
+  bool any = false;
+  for (int b = 0; b < batch; ++b) any = any || ab.s[b].affine;
+  // no affine sample: the grid of icl_crop_rotflip_channels.  Otherwise one thread per output voxel (the affine path's mapping, whatever
+  // V), up to 8192 workgroups a sample as for icl_volume_feed_affine; the threads an integer-path sample does not need leave at once
+  const int cap = any ? 8192 : 2048 / batch;
+  if ((o2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
+    ICL_LAUNCH(icl::crop_rotflip_affine_kernel<4>, dim3(grid_for(any ? voxels : voxels / 4, 256, cap), batch), dim3(256), 0, (hipStream_t)stream,
+               ab, image_out, (long long*)label_out, channels, o0, o1, o2);
+  } else {
+    ICL_LAUNCH(icl::crop_rotflip_affine_kernel<1>, dim3(grid_for(voxels, 256, cap), batch), dim3(256), 0, (hipStream_t)stream, ab, image_out,
+               (long long*)label_out, channels, o0, o1, o2);
+  }
+  return check_launch("crop_rotflip_affine");
+}
+
 namespace {
 
 int channel_norm_args(const char* what, const float* image, int channels, int64_t voxels, int mask_mode) {

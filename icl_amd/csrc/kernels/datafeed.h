@@ -616,4 +616,204 @@ __global__ __launch_bounds__(256) void volume_feed_affine_kernel(VolumeFeedAffin
   }
 }
 
+// ---- the BraTS chain (crop_rotflip_channels_kernel: rot90 -> flip -> zero padding -> crop, images [C][n0][n1][n2] with ONE label) with an
+// AFFINE stage about the patch centre.  The definition is in DESIGN.md §2 "Affine stage of the BraTS feed"; tests/crop_affine_ref.py
+// restates it in numpy.  Y = flip(rot90(x, k), axis) is the virtual rotated and flipped volume of extents (r0, r1, n2); it is never
+// materialised.  A sample either has the stage (`affine` = 1) or it does not: without it the sample takes the integer path, the body of
+// crop_rotflip_channels_kernel, and its values are copied.  With it, per output voxel q, every fp64 product and sum rounded on its own,
+//   u_a = q_a - (R_a - 1) / 2,  t_a = (c_a - p_a) + (R_a - 1) / 2                (both exact),
+//   x_a = t_a + ((M_a0 u_0 + M_a1 u_1) + M_a2 u_2)                               (a coordinate of the WHOLE of Y, not of the crop window),
+//   image, per channel: i_a = floor(x_a), f_a = x_a - i_a; the eight taps of Y in the order (0,0,0), (0,0,1), ..., (1,1,1), a tap outside
+//          [0, extent_a - 1] on any axis counting as 0 (which is the zero padding as well); sum of double(tap) * ((w_0 w_1) w_2),
+//          w_a = f_a for bit 1 and 1 - f_a for bit 0, left to right in double, rounded once to fp32; no mul / add;
+//   label: Y at rint(x_a) per axis (half to even); 0 when a rounded index is outside the extents.
+// An in-range index (a, c, d) of Y is mapped to the source as crop_rotflip_channels_kernel maps it, flip and then rot90_source(k, ., .,
+// n0, n1); that map is affine in (a, c), so it is an origin and one SIGNED source stride for each of the axes 0 and 1 (from crop_affine_row),
+// and stride 1 along depth.  Every range test is made on the DOUBLE, before any conversion to int (affine_axis), so no M can send a read
+// outside the volume (the launcher bounds |M_ab| by 16 all the same).
+struct CropAffineSample {
+  FeedSample f;              // as for crop_rotflip_channels_kernel
+  int affine;                // 1: the sample has the affine stage; 0: m is not read
+  double m[9];               // M, row-major
+};
+
+struct CropAffineBatch {
+  CropAffineSample s[kFeedMaxBatch];     // 144 B a record: 2,304 B of the 4 KB kernel-argument block
+};
+
+// source offset of the voxel (a, c, 0) of Y: the flip and the quarter turn of crop_rotflip_channels_kernel
+__device__ __forceinline__ long crop_affine_row(const FeedSample& s, int r0, int r1, int a, int c) {
+  if (s.flip_axis == 0) a = r0 - 1 - a;
+  else if (s.flip_axis == 1) c = r1 - 1 - c;
+  int sa, sc;
+  rot90_source(s.k, a, c, s.n0, s.n1, sa, sc);
+  return ((long)sa * s.n1 + sc) * s.n2;
+}
+
+// One axis of one voxel for crop_rotflip_affine_kernel: affine_axis's range tests, made on the double before any conversion to int,
+// with their results as integers.  j0, j1: an index INSIDE [0, n - 1] for each of the two taps floor(x), floor(x) + 1: its own where
+// its test let it in, else the other tap's, else 0 (n >= 1), so every tap has an address inside the volume whatever x is.
+struct CropAffineAxis {
+  double w0, w1;             // 1 - f, f
+  int j0, j1;
+  unsigned in;               // bit 0: tap floor(x) lies in [0, n - 1]; bit 1: tap floor(x) + 1 does
+  int nn;                    // rint(x), or -1 outside [0, n - 1]
+};
+
+__device__ __forceinline__ CropAffineAxis crop_affine_axis(double x, int n) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double top = (double)(n - 1);
+  const double fl = floor(x);
+  const double f = x - fl;
+  const bool in0 = fl >= 0.0 && fl <= top;            // on the double: a NaN or a huge x fails both
+  const bool in1 = fl >= -1.0 && fl <= top - 1.0;
+  const int i0 = (in0 || in1) ? (int)fl : 0;          // -1 .. n - 1
+  CropAffineAxis a;
+  a.j0 = in0 ? i0 : 0;                                // in1 alone: floor(x) = -1, and the other tap is 0
+  a.j1 = in1 ? i0 + 1 : a.j0;                         // in0 alone: floor(x) = n - 1 = j0
+  a.in = (in0 ? 1u : 0u) | (in1 ? 2u : 0u);
+  a.w0 = 1.0 - f;
+  a.w1 = f;
+  const double rn = rint(x);                          // half to even
+  a.nn = (rn >= 0.0 && rn <= top) ? (int)rn : -1;
+  return a;
+}
+
+// the loaded tap y where bit t of `in` is set, +0 where it is not: a select without a compare
+__device__ __forceinline__ float crop_affine_tap(float y, unsigned in, int t) {
+  return __uint_as_float(__float_as_uint(y) & (0u - ((in >> t) & 1u)));
+}
+
+// image_out [B][C][R0][R1][R2] fp32, label_out [B][R0][R1][R2] int64.  grid (x, B): one sample per blockIdx.y, so its record and `affine`
+// are wave-uniform.  V (4: R2 % 4 == 0 and both outputs 16-byte aligned) is the form of the INTEGER path, one thread per V consecutive
+// depth voxels as in crop_rotflip_channels_kernel<V>.  An affine sample takes one thread per output voxel in both instances.  Where
+// R1 % 8 == 0 and R2 % 8 == 0 a wave takes a compact 8 x 8 tile of (rows, depth), whose taps touch fewer cache lines under rotation than
+// those of 64 voxels in a line (it writes eight runs of 32 B a channel); otherwise 64 consecutive voxels.  The definition is per voxel,
+// so the result does not depend on the mapping.  Measured at 2 x 4 x 96^3 under rotation (profiles/crop_affine.md): one quad per thread
+// with guarded loads 266 us, one voxel per thread 122 us, with loads that need no branch 80 us, in tiles 71 us.  Per voxel the three
+// coordinates, the in-range bits, the four tap rows, the eight weights and the label come from the definition ONCE; the channel loop
+// then does eight fp32 loads and the eight-term double sum, with channel stride n0 n1 n2.  No LDS, no atomics.
+template <int V>
+__global__ __launch_bounds__(256) void crop_rotflip_affine_kernel(CropAffineBatch fb, float* __restrict__ image_out, long long* __restrict__ label_out,
+                                                                  int C, int R0, int R1, int R2) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  static_assert(V == 1 || V == 4, "one voxel or one quad per thread");
+  const int q2 = R2 / V;
+  const unsigned per = (unsigned)R0 * R1 * q2;                                // the launcher keeps R0 * R1 * R2 below 2^31
+  const int b = blockIdx.y;
+  const CropAffineSample& rec = fb.s[b];
+  const FeedSample& s = rec.f;
+  const long vox = (long)R0 * R1 * R2;                                        // channel stride of the output
+  const long cs = (long)s.n0 * s.n1 * s.n2;                                   // channel stride of the source
+  // extents after rot90: odd k swaps axes 0 and 1
+  const int r0 = (s.k & 1) ? s.n1 : s.n0, r1 = (s.k & 1) ? s.n0 : s.n1;
+  float* __restrict__ img = image_out + (long)b * C * vox;
+  long long* __restrict__ lab = label_out + (long)b * vox;
+  if (!rec.affine) {
+    // the integer path: crop_rotflip_channels_kernel<V>'s body
+    for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < per; r += gridDim.x * blockDim.x) {
+      const int l = (int)(r % q2) * V;
+      const unsigned rj = r / q2;
+      const int j = (int)(rj % R1), i = (int)(rj / R1);
+      const long e = (long)r * V;                                             // = (i * R1 + j) * R2 + l
+      const int a = s.c0 + i - s.p0, c = s.c1 + j - s.p1;
+      const int d = s.c2 + l - s.p2;
+      const bool row = a >= 0 && a < r0 && c >= 0 && c < r1;
+      const long base = row ? crop_affine_row(s, r0, r1, a, c) : 0;
+      bool in[V];
+      unsigned lv[V];
+#pragma unroll
+      for (int t = 0; t < V; ++t) {
+        in[t] = row && d + t >= 0 && d + t < s.n2;
+        lv[t] = in[t] ? (unsigned)s.label[base + d + t] : 0u;
+      }
+      const bool inside = V == 4 && row && d >= 0 && d + V <= s.n2;           // the whole quad lies in the row
+      for (int ch = 0; ch < C; ++ch) {
+        const float* __restrict__ src = s.image + ch * cs + base + d;         // dereferenced only where in[t]
+        float v[V];
+        if (inside && ((uintptr_t)src & 15) == 0) {
+          const float4 f = *reinterpret_cast<const float4*>(src);
+          v[0] = f.x;
+          if constexpr (V == 4) { v[1] = f.y; v[2] = f.z; v[3] = f.w; }
+        } else {
+#pragma unroll
+          for (int t = 0; t < V; ++t) v[t] = in[t] ? src[t] : 0.f;
+        }
+        if constexpr (V == 4) {
+          *reinterpret_cast<float4*>(img + ch * vox + e) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+          img[ch * vox + e] = v[0];
+        }
+      }
+      feed_store_labels<V>(lab + e, lv);
+    }
+    return;
+  }
+  // Y[a][c][d] = source[o00 + a * sa + c * sc + d]: the map is affine in (a, c), so three evaluations give it (they index nothing)
+  const long o00 = crop_affine_row(s, r0, r1, 0, 0);
+  const long sa = crop_affine_row(s, r0, r1, 1, 0) - o00, sc = crop_affine_row(s, r0, r1, 0, 1) - o00;
+  const double h0 = (double)(R0 - 1) * 0.5, h1 = (double)(R1 - 1) * 0.5, h2 = (double)(R2 - 1) * 0.5;
+  const double t0 = (double)(s.c0 - s.p0) + h0, t1 = (double)(s.c1 - s.p1) + h1, t2 = (double)(s.c2 - s.p2) + h2;
+  const unsigned voxels = (unsigned)R0 * R1 * R2;
+  const bool tiled = (R1 & 7) == 0 && (R2 & 7) == 0;
+  const unsigned tiles2 = (unsigned)R2 >> 3, tiles1 = (unsigned)R1 >> 3;
+  for (unsigned e = blockIdx.x * blockDim.x + threadIdx.x; e < voxels; e += gridDim.x * blockDim.x) {
+    int i, j, l;
+    if (tiled) {                                                              // a wave (64 consecutive e) takes rows j .. j + 7, depth l .. l + 7
+      const unsigned tile = e >> 6, lane = e & 63u;
+      l = (int)((tile % tiles2) << 3 | (lane & 7u));
+      const unsigned tj = tile / tiles2;
+      j = (int)((tj % tiles1) << 3 | (lane >> 3));
+      i = (int)(tj / tiles1);
+    } else {
+      l = (int)(e % R2);
+      const unsigned rj = e / R2;
+      j = (int)(rj % R1);
+      i = (int)(rj / R1);
+    }
+    const unsigned r = ((unsigned)i * R1 + j) * R2 + l;                       // the output voxel
+    // u_a = q_a - (R_a - 1) / 2 as (2 q_a - (R_a - 1)) / 2: an integer halved, exact like the difference
+    const double u0 = (double)(2 * i - (R0 - 1)) * 0.5, u1 = (double)(2 * j - (R1 - 1)) * 0.5, u2 = (double)(2 * l - (R2 - 1)) * 0.5;
+    const CropAffineAxis a0 = crop_affine_axis(t0 + ((rec.m[0] * u0 + rec.m[1] * u1) + rec.m[2] * u2), r0);      // every product and sum
+    const CropAffineAxis a1 = crop_affine_axis(t1 + ((rec.m[3] * u0 + rec.m[4] * u1) + rec.m[5] * u2), r1);      // rounded on its own
+    const CropAffineAxis a2 = crop_affine_axis(t2 + ((rec.m[6] * u0 + rec.m[7] * u1) + rec.m[8] * u2), s.n2);    // (contraction off)
+    // Every tap has an address inside the volume (crop_affine_axis), so the eight loads of a channel need no branch and are in flight
+    // together; the value of a tap outside Y is replaced by 0 after the load.
+    const long ra0 = o00 + (long)a0.j0 * sa, ra1 = o00 + (long)a0.j1 * sa, rc0 = (long)a1.j0 * sc + a2.j0, rc1 = (long)a1.j1 * sc + a2.j0;
+    const long b00 = ra0 + rc0, b01 = ra0 + rc1, b10 = ra1 + rc0, b11 = ra1 + rc1;                     // taps (0,0,0), (0,1,0), (1,0,0), (1,1,0)
+    const int dd = a2.j1 - a2.j0;                                                                      // 0 or 1: the step to tap (., ., 1)
+    // bit (4 b0 + 2 b1 + b2): tap (b0, b1, b2) is inside Y, the product of the three axes' bits.  One register for the channel loop, where
+    // bit t becomes an all-ones or all-zeros word that the loaded fp32 is ANDed with: a tap inside Y keeps every bit (a NaN its payload),
+    // a tap outside becomes +0.  Integer arithmetic throughout: a flag kept as a lane mask costs a scalar register pair.
+    const unsigned in01 = ((0u - (a0.in & 1u)) & a1.in) | (((0u - (a0.in >> 1)) & a1.in) << 2);        // bit (2 b0 + b1)
+    const unsigned in = ((0u - (in01 & 1u)) & a2.in) | (((0u - ((in01 >> 1) & 1u)) & a2.in) << 2) |
+                        (((0u - ((in01 >> 2) & 1u)) & a2.in) << 4) | (((0u - (in01 >> 3)) & a2.in) << 6);
+    const double w00 = a0.w0 * a1.w0, w01 = a0.w0 * a1.w1, w10 = a0.w1 * a1.w0, w11 = a0.w1 * a1.w1;
+    const double w000 = w00 * a2.w0, w001 = w00 * a2.w1, w010 = w01 * a2.w0, w011 = w01 * a2.w1;       // (w_0 w_1) w_2
+    const double w100 = w10 * a2.w0, w101 = w10 * a2.w1, w110 = w11 * a2.w0, w111 = w11 * a2.w1;
+    const int lin = (a0.nn | a1.nn | a2.nn) >= 0 ? 1 : 0;                                               // voxel (0, 0, 0) stands in otherwise
+    const unsigned lraw = s.label[o00 + (long)(a0.nn * lin) * sa + (long)(a1.nn * lin) * sc + a2.nn * lin];
+    const float* __restrict__ p = s.image;                                                             // channel ch of the source ...
+    float* __restrict__ o = img + r;                                                                   // ... and of the output voxel
+    for (int ch = 0; ch < C; ++ch, p += cs, o += vox) {
+      const float y000 = p[b00], y001 = p[b00 + dd], y010 = p[b01], y011 = p[b01 + dd];
+      const float y100 = p[b10], y101 = p[b10 + dd], y110 = p[b11], y111 = p[b11 + dd];
+      double acc = (double)crop_affine_tap(y000, in, 0) * w000;
+      acc = acc + (double)crop_affine_tap(y001, in, 1) * w001;
+      acc = acc + (double)crop_affine_tap(y010, in, 2) * w010;
+      acc = acc + (double)crop_affine_tap(y011, in, 3) * w011;
+      acc = acc + (double)crop_affine_tap(y100, in, 4) * w100;
+      acc = acc + (double)crop_affine_tap(y101, in, 5) * w101;
+      acc = acc + (double)crop_affine_tap(y110, in, 6) * w110;
+      acc = acc + (double)crop_affine_tap(y111, in, 7) * w111;
+      *o = (float)acc;
+    }
+    lab[r] = (long long)(lraw * (unsigned)lin);
+  }
+}
+
 }  // namespace icl

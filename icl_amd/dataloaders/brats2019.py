@@ -26,6 +26,7 @@ from torch.utils.data import Dataset
 from torch.utils.data.sampler import Sampler
 
 from .. import _lib
+from .affine import _affine_arguments, _affine_block, _affine_suffixes, _draw_affine
 from .intensity import _check_stage, _intensity_rows
 
 FEED_MAX_BATCH = 16         # samples per launch of the 3-D gather entries, icl_crop_rotflip* and icl_volume_feed* (kFeedMaxBatch)
@@ -227,19 +228,42 @@ class OnDeviceAugment:
     ``intensity``: None, or an ``IntensityAugment`` for ``patch_size`` (``dataloaders/intensity.py``; the reference's ``RandomNoise``,
     ``:150-161``, is its noise with ``noise_sigma=0.1, noise_clip=2``): its rows (``intensity_params``: one per sample, or with the
     stage's ``per_channel`` one per sample and channel, sample-major) are drawn after all geometric rows of the batch, from the
-    stage's own ``rng``, and it runs in place behind the gather on the same stream."""
+    stage's own ``rng``, and it runs in place behind the gather on the same stream.
 
-    def __init__(self, store: DeviceVolumeStore, patch_size: Sequence[int] = (96, 96, 96), intensity=None):
+    **Random rotation and zoom** (MONAI ``RandAffined``, nnU-Net's rotation and scaling; off by default: ``affine_prob=0``), the keywords
+    of the AMOS feeds (``affine_prob``, ``rotate_range`` in radians, ``zoom_range``, ``zoom_isotropic``; ``dataloaders/affine.py``), for
+    ``[W,H,D]`` and ``[C,W,H,D]`` stores alike.  A sample's affine is drawn from the global ``np.random`` directly after that sample's
+    ``draw_rotflip_crop`` (``rand() < affine_prob`` and, only if true, three angles and one or three zooms), and its row then carries the
+    nine entries of ``affine_matrix(theta, zoom)`` behind the 11 integers: 20 values.  With ``affine_prob=0`` nothing is drawn for the
+    stage, so every seed yields the rows it yielded without it.  The stage rotates and zooms the rotated and flipped volume about the
+    patch centre: trilinear for every channel of the image, nearest for the label, zeros outside the volume (DESIGN.md §2 "Affine stage of
+    the BraTS feed"; ``tests/crop_affine_ref.py`` restates it in numpy).  A launch of at most 16 samples in which no row has a matrix is
+    the launch described above; any other goes through ``icl_crop_rotflip_affine`` (a ``[W,H,D]`` store with ``channels = 1``), which
+    computes an output voxel's coordinates, tap offsets and weights once for all channels and the label."""
+
+    def __init__(self, store: DeviceVolumeStore, patch_size: Sequence[int] = (96, 96, 96), intensity=None, affine_prob: float = 0.0,
+                 rotate_range=(0, 0, 0), zoom_range=(1.0, 1.0), zoom_isotropic: bool = True):
         self.store = store
         self.patch = tuple(int(v) for v in patch_size)
         _check_stage(intensity, self.patch, "OnDeviceAugment")
         self.intensity = intensity
+        self.affine = _affine_arguments(affine_prob, rotate_range, zoom_range, zoom_isotropic)
 
-    def batch(self, indices: Sequence[int], params: Optional[Sequence[Sequence[int]]] = None, intensity_params=None):
+    def draw(self, indices: Sequence[int]) -> List[list]:
+        """The geometric rows of a batch, from the global ``np.random``: per sample ``draw_rotflip_crop`` and directly behind it the
+        affine draw (nothing with ``affine_prob == 0``).  11 values, or 20 for a sample that drew an affine."""
+        rows = []
+        for i in indices:
+            row = draw_rotflip_crop(self.store.images[i].shape[-3:], self.patch)
+            rows.append(row + list(_draw_affine(np.random, *self.affine)))
+        return rows
+
+    def batch(self, indices: Sequence[int], params: Optional[Sequence[Sequence[float]]] = None, intensity_params=None):
         st = self.store
         n = len(indices)
         if params is None:
-            params = [draw_rotflip_crop(st.images[i].shape[-3:], self.patch) for i in indices]
+            params = self.draw(indices)
+        suffixes = _affine_suffixes("OnDeviceAugment.batch", params, 11, "one parameter row of 11 values per index")
         channels = st.channels
         intensity_params = _intensity_rows(self.intensity, self.patch, n, intensity_params, "OnDeviceAugment.batch", channels)
         dev = st.device
@@ -247,17 +271,22 @@ class OnDeviceAugment:
         label = torch.empty((n,) + self.patch, dtype=torch.int64, device=dev)
         L = _lib.lib()
         stream = _lib.stream_of(dev)
-        for lo in range(0, n, FEED_MAX_BATCH):            # both entries take up to FEED_MAX_BATCH samples per launch
+        for lo in range(0, n, FEED_MAX_BATCH):            # every entry takes up to FEED_MAX_BATCH samples per launch
             chunk = list(indices[lo:lo + FEED_MAX_BATCH])
             m = len(chunk)
             ptrs = ctypes.c_void_p * m
-            flat = (ctypes.c_int32 * (11 * m))(*[int(v) for row in params[lo:lo + m] for v in row])
+            flat = (ctypes.c_int32 * (11 * m))(*[int(v) for row in params[lo:lo + m] for v in row[:11]])
             images, labels = ptrs(*[st.images[i].data_ptr() for i in chunk]), ptrs(*[st.labels[i].data_ptr() for i in chunk])
-            if st.multichannel:
+            affine = _affine_block(suffixes[lo:lo + m])
+            if st.multichannel or affine is not None:
                 for i, row in zip(chunk, params[lo:lo + m]):      # the kernel strides the channels by the row's extents
                     if tuple(int(v) for v in row[:3]) != tuple(st.images[i].shape[-3:]):
                         raise ValueError(f"OnDeviceAugment.batch: the row of volume {i} names the extents {tuple(row[:3])}, the volume "
                                          f"has {tuple(st.images[i].shape[-3:])}")
+            if affine is not None:
+                _lib.check(L.icl_crop_rotflip_affine(images, labels, flat, affine, m, channels, image[lo:].data_ptr(), label[lo:].data_ptr(),
+                                                     *self.patch, stream), "crop_rotflip_affine")
+            elif st.multichannel:
                 _lib.check(L.icl_crop_rotflip_channels(images, labels, flat, m, channels, image[lo:].data_ptr(), label[lo:].data_ptr(),
                                                        *self.patch, stream), "crop_rotflip_channels")
             else:

@@ -495,6 +495,21 @@ int icl_crop_rotflip(const void* const* images, const void* const* labels, const
 int icl_crop_rotflip_channels(const void* const* images, const void* const* labels, const int32_t* params, int batch, int channels,
                               float* image_out, int64_t* label_out, int o0, int o1, int o2, void* stream);
 
+/* ---- the same chain with an AFFINE stage about the patch centre (arbitrary rotation and zoom: MONAI RandAffined, nnU-Net's rotation
+ * and scaling), for one or many channels (crop_rotflip_affine_kernel, csrc/kernels/datafeed.h; the definition is in DESIGN.md "Affine
+ * stage of the BraTS feed").  The arguments of icl_crop_rotflip_channels, plus affine_params: HOST double [batch][10] = {flag, M row-major
+ * (3x3)}.  flag 0: the sample is gathered as icl_crop_rotflip_channels gathers it, bit for bit.  flag 1: with Y = flip(rot90(x, k), axis)
+ * of extents (r0, r1, n2), never materialised, x_a = t_a + ((M_a0 u_0 + M_a1 u_1) + M_a2 u_2), u_a = q_a - (o_a - 1) / 2 and
+ * t_a = (c_a - p_a) + (o_a - 1) / 2, in double, every product and sum rounded on its own; every channel of the image is interpolated
+ * trilinearly in Y (eight taps in the order (0,0,0) .. (1,1,1), a tap outside Y counting as 0, summed left to right in double, one
+ * rounding to fp32) and the label is Y at rint(x_a) (half to even; 0 outside).  x is a coordinate of the WHOLE of Y: voxels outside the
+ * crop window are read.  Coordinates, tap offsets and weights are computed once per output voxel and used for every channel and the label.
+ * Returns -1, launching nothing, for whatever icl_crop_rotflip_channels refuses and for a null affine_params, a flag other than 0 or 1,
+ * or an entry of M (of any sample, whatever its flag) that is not finite or exceeds 16 in magnitude.  All range tests of the kernel are
+ * made on the double coordinate, so no M can cause a read outside the volume. */
+int icl_crop_rotflip_affine(const void* const* images, const void* const* labels, const int32_t* params, const double* affine_params, int batch,
+                            int channels, float* image_out, int64_t* label_out, int o0, int o1, int o2, void* stream);
+
 /* ---- channel-wise intensity normalisation of a resident volume, in place (MONAI's NormalizeIntensityd(nonzero=True,
  * channel_wise=True): mask 0, apply 0; the reference's itensity_normalize_one_volume, dataloaders/brats_proprecessing.py:62-78:
  * mask 1, apply 1).  image: DEVICE fp32 [channels][voxels], channels in 1..16, voxels in 1..2^31 - 1.  mask_mode: 0 x != 0, 1 x > 0,

@@ -2412,8 +2412,8 @@ int icl_linear_wgrad_small(const float* gy, const float* x, float* dw, void* ws,
 
 namespace {
 
-// The record of icl_crop_rotflip / icl_crop_rotflip_channels from the caller's rows of 11 integers.  Returns -1, or the first sample
-// that is refused (a null volume pointer or a value of its row out of range): each entry words its own refusal.
+// The record of the crop entries from the caller's rows of 11 integers.  Returns -1, or the first sample that is refused (a null
+// volume pointer or a value of its row out of range): each entry words its own refusal.
 int crop_feed_records(const void* const* images, const void* const* labels, const int32_t* params, int batch, icl::FeedBatch& fb) {
   for (int b = 0; b < batch; ++b) {
     const int32_t* q = params + 11 * b;
@@ -2425,6 +2425,36 @@ int crop_feed_records(const void* const* images, const void* const* labels, cons
     if (!s.image || !s.label || s.n0 < 1 || s.n1 < 1 || s.n2 < 1 || s.k < 0 || s.k > 3 || s.flip_axis > 1 || s.p0 < 0 || s.p1 < 0 || s.p2 < 0) return b;
   }
   return -1;
+}
+
+// Every check of the channel entries icl_crop_rotflip_channels / icl_crop_rotflip_affine (`what`: the entry's name), and their record.
+int crop_channels_records(const char* what, const void* const* images, const void* const* labels, const int32_t* params, int batch, int channels,
+                          const float* image_out, const int64_t* label_out, int o0, int o1, int o2, icl::FeedBatch& fb) {
+  if (!images || !labels || !params || !image_out || !label_out) return fail(-1, "%s: null pointer", what);
+  if (batch < 1 || batch > icl::kFeedMaxBatch) return fail(-1, "%s: batch %d out of range (1 <= batch <= %d)", what, batch, icl::kFeedMaxBatch);
+  if (channels < 1 || channels > icl::kChannelNormMaxChannels)
+    return fail(-1, "%s: channels %d out of range (1 <= channels <= %d)", what, channels, icl::kChannelNormMaxChannels);
+  if (o0 < 1 || o1 < 1 || o2 < 1) return fail(-1, "%s: output extents %d x %d x %d (each must be >= 1)", what, o0, o1, o2);
+  if ((long)o0 * o1 * o2 > 0x7fffffffL) return fail(-1, "%s: output extents %d x %d x %d (more than 2^31 - 1 voxels a sample)", what, o0, o1, o2);
+  const int bad = crop_feed_records(images, labels, params, batch, fb);
+  if (bad >= 0 && !(fb.s[bad].image && fb.s[bad].label)) return fail(-1, "%s: sample %d: null volume pointer", what, bad);
+  if (bad >= 0) return fail(-1, "%s: bad sample %d", what, bad);
+  return 0;
+}
+
+// Row b of the affine rows of icl_crop_rotflip_affine / icl_volume_feed_affine[_origins]: flag in {0, 1}, then M row-major, nine finite
+// entries with |M_ab| <= 16.
+int affine_rows(const char* what, const double* affine_params, int b, int& flag_out, double (&m_out)[9]) {
+  const double* q = affine_params + 10 * b;
+  if (!(q[0] == 0.0 || q[0] == 1.0)) return fail(-1, "%s: sample %d: affine flag %g (must be 0 or 1)", what, b, q[0]);
+  flag_out = q[0] == 1.0 ? 1 : 0;
+  for (int e = 0; e < 9; ++e) {
+    const double m = q[1 + e];
+    if (!std::isfinite(m)) return fail(-1, "%s: sample %d: affine matrix entry M[%d][%d] = %g is not finite", what, b, e / 3, e % 3, m);
+    if (std::fabs(m) > 16.0) return fail(-1, "%s: sample %d: affine matrix entry M[%d][%d] = %g outside [-16, 16]", what, b, e / 3, e % 3, m);
+    m_out[e] = m;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -2443,18 +2473,9 @@ int icl_crop_rotflip(const void* const* images, const void* const* labels, const
 
 int icl_crop_rotflip_channels(const void* const* images, const void* const* labels, const int32_t* params, int batch, int channels,
                               float* image_out, int64_t* label_out, int o0, int o1, int o2, void* stream) {
-  if (!images || !labels || !params || !image_out || !label_out) return fail(-1, "crop_rotflip_channels: null pointer");
-  if (batch < 1 || batch > icl::kFeedMaxBatch)
-    return fail(-1, "crop_rotflip_channels: batch %d out of range (1 <= batch <= %d)", batch, icl::kFeedMaxBatch);
-  if (channels < 1 || channels > icl::kChannelNormMaxChannels)
-    return fail(-1, "crop_rotflip_channels: channels %d out of range (1 <= channels <= %d)", channels, icl::kChannelNormMaxChannels);
-  if (o0 < 1 || o1 < 1 || o2 < 1) return fail(-1, "crop_rotflip_channels: output extents %d x %d x %d (each must be >= 1)", o0, o1, o2);
-  if ((long)o0 * o1 * o2 > 0x7fffffffL)
-    return fail(-1, "crop_rotflip_channels: output extents %d x %d x %d (more than 2^31 - 1 voxels a sample)", o0, o1, o2);
   icl::FeedBatch fb{};
-  const int bad = crop_feed_records(images, labels, params, batch, fb);
-  if (bad >= 0 && !(fb.s[bad].image && fb.s[bad].label)) return fail(-1, "crop_rotflip_channels: sample %d: null volume pointer", bad);
-  if (bad >= 0) return fail(-1, "crop_rotflip_channels: bad sample %d", bad);
+  if (const int rc = crop_channels_records("crop_rotflip_channels", images, labels, params, batch, channels, image_out, label_out, o0, o1, o2, fb))
+    return rc;
   const long voxels = (long)o0 * o1 * o2;      // per sample and channel; one grid row per sample
   const int cap = 2048 / batch;                // 2048 workgroups of 256 threads: every wave slot of the 256 CUs once, the rest by stride
   if ((o2 & 3) == 0 && aligned16(image_out) && aligned16(label_out)) {
@@ -2469,39 +2490,21 @@ int icl_crop_rotflip_channels(const void* const* images, const void* const* labe
 
 int icl_crop_rotflip_affine(const void* const* images, const void* const* labels, const int32_t* params, const double* affine_params, int batch,
                             int channels, float* image_out, int64_t* label_out, int o0, int o1, int o2, void* stream) {
-  if (!images || !labels || !params || !image_out || !label_out) return fail(-1, "crop_rotflip_affine: null pointer");
-  if (!affine_params) return fail(-1, "crop_rotflip_affine: affine_params is a null pointer");
-  if (batch < 1 || batch > icl::kFeedMaxBatch)
-    return fail(-1, "crop_rotflip_affine: batch %d out of range (1 <= batch <= %d)", batch, icl::kFeedMaxBatch);
-  if (channels < 1 || channels > icl::kChannelNormMaxChannels)
-    return fail(-1, "crop_rotflip_affine: channels %d out of range (1 <= channels <= %d)", channels, icl::kChannelNormMaxChannels);
-  if (o0 < 1 || o1 < 1 || o2 < 1) return fail(-1, "crop_rotflip_affine: output extents %d x %d x %d (each must be >= 1)", o0, o1, o2);
-  if ((long)o0 * o1 * o2 > 0x7fffffffL)
-    return fail(-1, "crop_rotflip_affine: output extents %d x %d x %d (more than 2^31 - 1 voxels a sample)", o0, o1, o2);
+  // a null among the other pointers is refused first, by the shared checks
+  if (!affine_params && images && labels && params && image_out && label_out)
+    return fail(-1, "crop_rotflip_affine: affine_params is a null pointer");
   icl::FeedBatch fb{};
-  const int bad = crop_feed_records(images, labels, params, batch, fb);
-  if (bad >= 0 && !(fb.s[bad].image && fb.s[bad].label)) return fail(-1, "crop_rotflip_affine: sample %d: null volume pointer", bad);
-  if (bad >= 0) return fail(-1, "crop_rotflip_affine: bad sample %d", bad);
+  if (const int rc = crop_channels_records("crop_rotflip_affine", images, labels, params, batch, channels, image_out, label_out, o0, o1, o2, fb))
+    return rc;
   icl::CropAffineBatch ab{};
+  bool any = false;
   for (int b = 0; b < batch; ++b) {
-    const double* q = affine_params + 10 * b;      // flag, M row-major
-    icl::CropAffineSample& s = ab.s[b];
-    s.f = fb.s[b];
-    if (!(q[0] == 0.0 || q[0] == 1.0)) return fail(-1, "crop_rotflip_affine: sample %d: affine flag %g (must be 0 or 1)", b, q[0]);
-    s.affine = q[0] == 1.0 ? 1 : 0;
-    for (int e = 0; e < 9; ++e) {
-      const double m = q[1 + e];
-      if (!std::isfinite(m))
-        return fail(-1, "crop_rotflip_affine: sample %d: affine matrix entry M[%d][%d] = %g is not finite", b, e / 3, e % 3, m);
-      if (std::fabs(m) > 16.0)
-        return fail(-1, "crop_rotflip_affine: sample %d: affine matrix entry M[%d][%d] = %g outside [-16, 16]", b, e / 3, e % 3, m);
-      s.m[e] = m;
-    }
+    ab.s[b].f = fb.s[b];
+    if (const int rc = affine_rows("crop_rotflip_affine", affine_params, b, ab.s[b].affine, ab.s[b].m)) return rc;
+    any = any || ab.s[b].affine;
   }
   static_assert(sizeof(icl::CropAffineBatch) == 16 * 144, "16 records of 144 B: 2,304 B of the 4 KB kernel-argument block");
   const long voxels = (long)o0 * o1 * o2;      // per sample and channel; one grid row per sample
-  bool any = false;
-  for (int b = 0; b < batch; ++b) any = any || ab.s[b].affine;
   // no affine sample: the grid of icl_crop_rotflip_channels.  Otherwise one thread per output voxel (the affine path's mapping, whatever
   // V), up to 8192 workgroups a sample as for icl_volume_feed_affine; the threads an integer-path sample does not need leave at once
   const int cap = any ? 8192 : 2048 / batch;
@@ -2606,11 +2609,16 @@ int volume_feed_records(const char* what, const void* const* images, const void*
 extern "C++" template <int V, bool DEV, typename Batch>
 void volume_feed_launch_as(const Batch& fb, int batch, const int32_t* origins, float* image_out, int64_t* label_out, int R0, int R1, int R2,
                            void* stream) {
-  const dim3 grid(grid_for((long)R0 * R1 * R2 / V, 256, 8192), batch);      // one grid row per sample
+  const long voxels = (long)R0 * R1 * R2;
   if constexpr (std::is_same_v<Batch, icl::VolumeFeedBatch>) {
+    const dim3 grid(grid_for(voxels / V, 256, 8192), batch);      // one grid row per sample
     ICL_LAUNCH((icl::volume_feed_kernel<V, DEV>), grid, dim3(256), 0, (hipStream_t)stream, fb, (const int*)origins, image_out,
                (long long*)label_out, R0, R1, R2);
   } else {
+    // an affine sample takes one thread per output voxel whatever V, as for icl_crop_rotflip_affine; with none, volume_feed_kernel's grid
+    bool any = false;
+    for (int b = 0; b < batch; ++b) any = any || fb.s[b].affine;
+    const dim3 grid(grid_for(any ? voxels : voxels / V, 256, 8192), batch);
     ICL_LAUNCH((icl::volume_feed_affine_kernel<V, DEV>), grid, dim3(256), 0, (hipStream_t)stream, fb, (const int*)origins, image_out,
                (long long*)label_out, R0, R1, R2);
   }
@@ -2665,23 +2673,14 @@ namespace {
 int volume_feed_affine_records(const char* what, const void* const* images, const void* const* labels, const int32_t* int_params,
                                const float* float_params, const double* affine_params, int batch, int R0, int R1, int R2, bool device_origins,
                                icl::VolumeFeedAffineBatch& ab) {
+  static_assert(sizeof(icl::VolumeFeedAffineBatch) == 16 * 160, "16 records of 160 B: 2,560 B of the 4 KB kernel-argument block");
   if (!affine_params) return fail(-1, "%s: affine_params is a null pointer", what);
   icl::VolumeFeedBatch fb{};
   if (const int rc = volume_feed_records(what, images, labels, int_params, float_params, batch, R0, R1, R2, device_origins, fb)) return rc;
   for (int b = 0; b < batch; ++b) {
-    const double* q = affine_params + 10 * b;      // flag, M row-major
-    icl::VolumeFeedAffineSample& s = ab.s[b];
-    s.f = fb.s[b];
-    s.n0 = int_params[14 * b];
-    if (!(q[0] == 0.0 || q[0] == 1.0)) return fail(-1, "%s: sample %d: affine flag %g (must be 0 or 1)", what, b, q[0]);
-    s.affine = q[0] == 1.0 ? 1 : 0;
-    for (int e = 0; e < 9; ++e) {
-      const double m = q[1 + e];
-      if (!std::isfinite(m)) return fail(-1, "%s: sample %d: affine matrix entry M[%d][%d] = %g is not finite", what, b, e / 3, e % 3, m);
-      if (std::fabs(m) > 16.0)
-        return fail(-1, "%s: sample %d: affine matrix entry M[%d][%d] = %g outside [-16, 16]", what, b, e / 3, e % 3, m);
-      s.m[e] = m;
-    }
+    ab.s[b].f = fb.s[b];
+    ab.s[b].n0 = int_params[14 * b];
+    if (const int rc = affine_rows(what, affine_params, b, ab.s[b].affine, ab.s[b].m)) return rc;
   }
   return 0;
 }

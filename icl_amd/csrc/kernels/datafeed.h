@@ -35,6 +35,17 @@ __device__ __forceinline__ void rot90_source(int k, int a, int c, int e0, int e1
   }
 }
 
+// The crop chain's map into the source, stated once: Y = flip(rot90(x, k), flip_axis) is the rotated and flipped volume of extents
+// (r0, r1, n2), r0 and r1 being n0 and n1 swapped for odd k; this is the source offset of its voxel (a, c, 0).  The map is affine in
+// (a, c): an origin and one SIGNED source stride for each of the axes 0 and 1, and stride 1 along depth.
+__device__ __forceinline__ long crop_feed_row(const FeedSample& s, int r0, int r1, int a, int c) {
+  if (s.flip_axis == 0) a = r0 - 1 - a;
+  else if (s.flip_axis == 1) c = r1 - 1 - c;
+  int sa, sc;
+  rot90_source(s.k, a, c, s.n0, s.n1, sa, sc);
+  return ((long)sa * s.n1 + sc) * s.n2;
+}
+
 // V labels (0..255) as int64 at p; V = 4: p is 16-byte aligned, two 16-byte stores whose high dwords are 0
 template <int V>
 __device__ __forceinline__ void feed_store_labels(long long* p, const unsigned (&lab)[V]) {
@@ -72,16 +83,11 @@ __global__ __launch_bounds__(256) void crop_rotflip_kernel(FeedBatch fb, float* 
     // extents after rot90: odd k swaps axes 0 and 1
     const int r0 = (s.k & 1) ? s.n1 : s.n0, r1 = (s.k & 1) ? s.n0 : s.n1;
     // crop -> padded coordinates -> unpadded (rotated + flipped) coordinates
-    int a = s.c0 + i - s.p0, c = s.c1 + j - s.p1;
-    const int d = s.c2 + l - s.p2;
+    const int a = s.c0 + i - s.p0, c = s.c1 + j - s.p1, d = s.c2 + l - s.p2;
     float v = 0.f;
     long long lab = 0;
     if (a >= 0 && a < r0 && c >= 0 && c < r1 && d >= 0 && d < s.n2) {
-      if (s.flip_axis == 0) a = r0 - 1 - a;
-      else if (s.flip_axis == 1) c = r1 - 1 - c;
-      int sa, sc;
-      rot90_source(s.k, a, c, s.n0, s.n1, sa, sc);
-      const long src = ((long)sa * s.n1 + sc) * s.n2 + d;
+      const long src = crop_feed_row(s, r0, r1, a, c) + d;
       v = s.image[src];
       lab = (long long)s.label[src];
     }
@@ -93,11 +99,52 @@ __global__ __launch_bounds__(256) void crop_rotflip_kernel(FeedBatch fb, float* 
 // ---- multi-modal volumes: the chain of crop_rotflip_kernel on images [C][n0][n1][n2] (co-registered channels, BraTS's four MR
 // modalities) with ONE label [n0][n1][n2].  The map output voxel -> crop -> padding -> flip -> rot90 -> source index does not depend on
 // the channel, so it is computed once per output position and used for all C channels (channel stride n0 * n1 * n2) and for the
-// label, which is read and written once.  image_out [B][C][o0][o1][o2] fp32, label_out [B][o0][o1][o2] int64.  grid (x, B): one sample
-// per blockIdx.y, so its record is wave-uniform.  One thread per V consecutive depth voxels (V = 4: o2 % 4 == 0 and both outputs 16-byte
-// aligned; the store is always a quad per channel and feed_store_labels; the load is a quad where the four sources lie inside
-// the row at a 16-byte aligned address, four guarded scalar loads otherwise: the scheme of window_gather_kernel<4>).  No LDS, no
-// atomics.  With C = 1 the result is crop_rotflip_kernel's bit for bit (the values are copied, never computed with).
+// label, which is read and written once.
+//
+// The integer gather of that chain, the only one of crop_rotflip_channels_kernel and the path of a sample without the affine stage in
+// crop_rotflip_affine_kernel: V consecutive output depth voxels from (i, j, l) on, for all C channels, stored at `img` (channel stride
+// `vox`) and `lab`, which point at the output voxel.  V = 4: the store is always a quad per channel and feed_store_labels; the load is
+// a quad where the four sources lie inside the row at a 16-byte aligned address, four guarded scalar loads otherwise (the scheme of
+// window_gather_kernel<4>).  The values are copied, never computed with.
+template <int V>
+__device__ __forceinline__ void crop_feed_gather(const FeedSample& s, int r0, int r1, int C, int i, int j, int l, float* __restrict__ img, long vox,
+                                                 long long* __restrict__ lab) {
+  const long cs = (long)s.n0 * s.n1 * s.n2;                                   // channel stride of the source
+  // crop -> padded coordinates -> unpadded (rotated + flipped) coordinates
+  const int a = s.c0 + i - s.p0, c = s.c1 + j - s.p1, d = s.c2 + l - s.p2;
+  const bool row = a >= 0 && a < r0 && c >= 0 && c < r1;
+  const long base = row ? crop_feed_row(s, r0, r1, a, c) : 0;
+  bool in[V];
+  unsigned lv[V];
+#pragma unroll
+  for (int t = 0; t < V; ++t) {
+    in[t] = row && d + t >= 0 && d + t < s.n2;
+    lv[t] = in[t] ? (unsigned)s.label[base + d + t] : 0u;
+  }
+  const bool inside = V == 4 && row && d >= 0 && d + V <= s.n2;               // the whole quad lies in the row
+  for (int ch = 0; ch < C; ++ch) {
+    const float* __restrict__ src = s.image + ch * cs + base + d;             // dereferenced only where in[t]
+    float v[V];
+    if (inside && ((uintptr_t)src & 15) == 0) {
+      const float4 f = *reinterpret_cast<const float4*>(src);
+      v[0] = f.x;
+      if constexpr (V == 4) { v[1] = f.y; v[2] = f.z; v[3] = f.w; }
+    } else {
+#pragma unroll
+      for (int t = 0; t < V; ++t) v[t] = in[t] ? src[t] : 0.f;
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(img + ch * vox) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+      img[ch * vox] = v[0];
+    }
+  }
+  feed_store_labels<V>(lab, lv);
+}
+
+// image_out [B][C][o0][o1][o2] fp32, label_out [B][o0][o1][o2] int64.  grid (x, B): one sample per blockIdx.y, so its record is
+// wave-uniform.  One thread per V consecutive depth voxels (V = 4: o2 % 4 == 0 and both outputs 16-byte aligned).  No LDS, no atomics.
+// With C = 1 the result is crop_rotflip_kernel's bit for bit.
 template <int V>
 __global__ __launch_bounds__(256) void crop_rotflip_channels_kernel(FeedBatch fb, float* __restrict__ image_out, long long* __restrict__ label_out,
                                                                     int C, int o0, int o1, int o2) {
@@ -107,7 +154,6 @@ __global__ __launch_bounds__(256) void crop_rotflip_channels_kernel(FeedBatch fb
   const int b = blockIdx.y;
   const FeedSample& s = fb.s[b];
   const long vox = (long)o0 * o1 * o2;                                        // channel stride of the output
-  const long cs = (long)s.n0 * s.n1 * s.n2;                                   // channel stride of the source
   // extents after rot90: odd k swaps axes 0 and 1
   const int r0 = (s.k & 1) ? s.n1 : s.n0, r1 = (s.k & 1) ? s.n0 : s.n1;
   float* __restrict__ img = image_out + (long)b * C * vox;
@@ -115,46 +161,8 @@ __global__ __launch_bounds__(256) void crop_rotflip_channels_kernel(FeedBatch fb
   for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < per; r += gridDim.x * blockDim.x) {
     const int l = (int)(r % q2) * V;
     const unsigned rj = r / q2;
-    const int j = (int)(rj % o1), i = (int)(rj / o1);
     const long e = (long)r * V;                                               // = (i * o1 + j) * o2 + l
-    // crop -> padded coordinates -> unpadded (rotated + flipped) coordinates
-    int a = s.c0 + i - s.p0, c = s.c1 + j - s.p1;
-    const int d = s.c2 + l - s.p2;
-    const bool row = a >= 0 && a < r0 && c >= 0 && c < r1;
-    long base = 0;
-    if (row) {
-      if (s.flip_axis == 0) a = r0 - 1 - a;
-      else if (s.flip_axis == 1) c = r1 - 1 - c;
-      int sa, sc;
-      rot90_source(s.k, a, c, s.n0, s.n1, sa, sc);
-      base = ((long)sa * s.n1 + sc) * s.n2;
-    }
-    bool in[V];
-    unsigned lv[V];
-#pragma unroll
-    for (int t = 0; t < V; ++t) {
-      in[t] = row && d + t >= 0 && d + t < s.n2;
-      lv[t] = in[t] ? (unsigned)s.label[base + d + t] : 0u;
-    }
-    const bool inside = V == 4 && row && d >= 0 && d + V <= s.n2;             // the whole quad lies in the row
-    for (int ch = 0; ch < C; ++ch) {
-      const float* __restrict__ src = s.image + ch * cs + base + d;           // dereferenced only where in[t]
-      float v[V];
-      if (inside && ((uintptr_t)src & 15) == 0) {
-        const float4 f = *reinterpret_cast<const float4*>(src);
-        v[0] = f.x;
-        if constexpr (V == 4) { v[1] = f.y; v[2] = f.z; v[3] = f.w; }
-      } else {
-#pragma unroll
-        for (int t = 0; t < V; ++t) v[t] = in[t] ? src[t] : 0.f;
-      }
-      if constexpr (V == 4) {
-        *reinterpret_cast<float4*>(img + ch * vox + e) = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
-        img[ch * vox + e] = v[0];
-      }
-    }
-    feed_store_labels<V>(lab + e, lv);
+    crop_feed_gather<V>(s, r0, r1, C, (int)(rj / o1), (int)(rj % o1), l, img + e, vox, lab + e);
   }
 }
 
@@ -487,19 +495,154 @@ __global__ __launch_bounds__(256) void volume_feed_kernel(VolumeFeedBatch fb, co
   }
 }
 
-// ---- the same chain with an AFFINE stage between the pad and the flips (MONAI RandAffined, nnU-Net's rotation and scaling):
-// crop -> symmetric pad -> affine about the patch centre -> flips -> rot90 -> intensity.  The definition is in DESIGN.md §2 "Affine
-// stage of the 3-D feed"; tests/affine_feed_ref.py restates it in numpy.  A sample either has the stage (`affine` = 1) or it does not:
-// without it the sample goes through volume_feed_gather, as in volume_feed_kernel.  With it, the output voxel is mapped back through
-// rot90 and the flips to integer patch coordinates p as above, and then, every fp64 product and sum rounded on its own,
-//   u_a = p_a - (R_a - 1) / 2,  t_a = (c_a - l_a) + (R_a - 1) / 2                (both exact),
-//   x_a = t_a + ((M_a0 u_0 + M_a1 u_1) + M_a2 u_2)                               (a coordinate of the WHOLE volume, not of the crop),
+// ---- the AFFINE stage of both 3-D chains (MONAI RandAffined, nnU-Net's rotation and scaling): one trilinear sampler about the patch
+// centre, used by volume_feed_affine_kernel (AMOS) and crop_rotflip_affine_kernel (BraTS).  The definition is in DESIGN.md §2 "Affine
+// stage of the 3-D feed"; tests/affine_feed_ref.py and tests/crop_affine_ref.py restate it in numpy.  For the integer patch coordinates
+// p of a voxel, every fp64 product and sum rounded on its own,
+//   u_a = p_a - (R_a - 1) / 2,  t_a = (c_a - pad_a) + (R_a - 1) / 2              (both exact),
+//   x_a = t_a + ((M_a0 u_0 + M_a1 u_1) + M_a2 u_2)                               (a coordinate of the WHOLE sampled volume, not of the crop),
 //   image: i_a = floor(x_a), f_a = x_a - i_a; the eight taps in the order (0,0,0), (0,0,1), ..., (1,1,1), a tap outside [0, n_a - 1]
 //          on any axis counting as 0; sum of double(tap) * ((w_0 w_1) w_2), w_a = f_a for bit 1 and 1 - f_a for bit 0, left to right
-//          in double, rounded once to fp32; then fp32(fp32(v * mul) + add);
+//          in double, rounded once to fp32;
 //   label: the voxel at rint(x_a) per axis (half to even); 0 when a rounded index is outside [0, n_a - 1].
-// Every range test is made on the DOUBLE, before any conversion to int, so no M and no content of `origins` can send a read outside
-// the volume (the launcher bounds |M_ab| by 16 all the same, which keeps |x| far below 2^31).
+// Every range test is made on the DOUBLE, before any conversion to int, so no M and no content of a device buffer can send a read outside
+// the volume (the launchers bound |M_ab| by 16 all the same, which keeps |x| far below 2^31).  The definition is per voxel, so the result
+// does not depend on how threads are mapped to voxels.  Each function repeats the pragma: it binds to the compound statement it stands in.
+
+// The sampled volume: extents, and the element offset of its voxel (a, c, d) = origin + a * stride0 + c * stride1 + d (signed strides)
+struct AffineVolume {
+  int n0, n1, n2;
+  long origin, stride0, stride1;
+};
+
+// what the voxels of a sample share: the doubled half extents 2 h_a = R_a - 1, and t_a = (c_a - pad_a) + h_a
+struct AffineFrame {
+  int hh0, hh1, hh2;
+  double t0, t1, t2;
+};
+
+__device__ __forceinline__ AffineFrame affine_frame(int R0, int R1, int R2, int d0, int d1, int d2) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  AffineFrame f;
+  f.hh0 = R0 - 1; f.hh1 = R1 - 1; f.hh2 = R2 - 1;
+  f.t0 = (double)d0 + (double)f.hh0 * 0.5; f.t1 = (double)d1 + (double)f.hh1 * 0.5; f.t2 = (double)d2 + (double)f.hh2 * 0.5;
+  return f;
+}
+
+// One axis of one voxel.  j0, j1: an index INSIDE [0, n - 1] for each of the two taps floor(x), floor(x) + 1: its own where its range
+// test let it in, else the other tap's, else 0 (n >= 1), so every tap has an address inside the volume whatever x is.
+struct AffineAxis {
+  double w0, w1;             // 1 - f, f
+  int j0, j1;
+  unsigned in;               // bit 0: tap floor(x) lies in [0, n - 1]; bit 1: tap floor(x) + 1 does
+  int nn;                    // rint(x), or -1 outside [0, n - 1]
+};
+
+__device__ __forceinline__ AffineAxis affine_axis(double x, int n) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double top = (double)(n - 1);
+  const double fl = floor(x);
+  const double f = x - fl;
+  const bool in0 = fl >= 0.0 && fl <= top;            // on the double: a NaN or a huge x fails both
+  const bool in1 = fl >= -1.0 && fl <= top - 1.0;
+  const int i0 = (in0 || in1) ? (int)fl : 0;          // -1 .. n - 1
+  AffineAxis a;
+  a.j0 = in0 ? i0 : 0;                                // in1 alone: floor(x) = -1, and the other tap is 0
+  a.j1 = in1 ? i0 + 1 : a.j0;                         // in0 alone: floor(x) = n - 1 = j0
+  a.in = (in0 ? 1u : 0u) | (in1 ? 2u : 0u);
+  a.w0 = 1.0 - f;
+  a.w1 = f;
+  const double rn = rint(x);                          // half to even
+  a.nn = (rn >= 0.0 && rn <= top) ? (int)rn : -1;
+  return a;
+}
+
+// The taps of one voxel, from the definition ONCE for all channels.  Every tap has an address inside the volume (affine_axis), so the
+// loads need no branch and are in flight together; the value of a tap outside is replaced by 0 after the load (affine_value).
+struct AffineTaps {
+  long row[4];               // offsets of the taps (0,0,0), (0,1,0), (1,0,0), (1,1,0)
+  int step;                  // 0 or 1: from tap (., ., 0) to tap (., ., 1)
+  unsigned in;               // bit (4 b0 + 2 b1 + b2): tap (b0, b1, b2) is inside the volume
+  double w[8];               // (w_0 w_1) w_2 of tap (4 b0 + 2 b1 + b2)
+  long label;                // offset of the label's voxel; voxel (0, 0, 0) stands in where `labelled` is 0
+  unsigned labelled;         // 1: every rounded index is inside; 0: the label is 0
+};
+
+__device__ __forceinline__ AffineTaps affine_taps(int p0, int p1, int p2, const double (&m)[9], const AffineFrame& f, const AffineVolume& vol) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  // u_a = p_a - h_a as (2 p_a - 2 h_a) / 2: an integer halved, exact like the difference
+  const double u0 = (double)(2 * p0 - f.hh0) * 0.5, u1 = (double)(2 * p1 - f.hh1) * 0.5, u2 = (double)(2 * p2 - f.hh2) * 0.5;
+  const AffineAxis a0 = affine_axis(f.t0 + ((m[0] * u0 + m[1] * u1) + m[2] * u2), vol.n0);      // every product and sum
+  const AffineAxis a1 = affine_axis(f.t1 + ((m[3] * u0 + m[4] * u1) + m[5] * u2), vol.n1);      // rounded on its own
+  const AffineAxis a2 = affine_axis(f.t2 + ((m[6] * u0 + m[7] * u1) + m[8] * u2), vol.n2);      // (contraction off)
+  AffineTaps t;
+  const long ra0 = vol.origin + (long)a0.j0 * vol.stride0, ra1 = vol.origin + (long)a0.j1 * vol.stride0;
+  const long rc0 = (long)a1.j0 * vol.stride1 + a2.j0, rc1 = (long)a1.j1 * vol.stride1 + a2.j0;
+  t.row[0] = ra0 + rc0; t.row[1] = ra0 + rc1; t.row[2] = ra1 + rc0; t.row[3] = ra1 + rc1;
+  t.step = a2.j1 - a2.j0;
+  // The product of the three axes' bits, in integer arithmetic throughout: a flag kept as a lane mask costs a scalar register pair.
+  const unsigned in01 = ((0u - (a0.in & 1u)) & a1.in) | (((0u - (a0.in >> 1)) & a1.in) << 2);        // bit (2 b0 + b1)
+  t.in = ((0u - (in01 & 1u)) & a2.in) | (((0u - ((in01 >> 1) & 1u)) & a2.in) << 2) |
+         (((0u - ((in01 >> 2) & 1u)) & a2.in) << 4) | (((0u - (in01 >> 3)) & a2.in) << 6);
+  const double w00 = a0.w0 * a1.w0, w01 = a0.w0 * a1.w1, w10 = a0.w1 * a1.w0, w11 = a0.w1 * a1.w1;
+  t.w[0] = w00 * a2.w0; t.w[1] = w00 * a2.w1; t.w[2] = w01 * a2.w0; t.w[3] = w01 * a2.w1;
+  t.w[4] = w10 * a2.w0; t.w[5] = w10 * a2.w1; t.w[6] = w11 * a2.w0; t.w[7] = w11 * a2.w1;
+  const int lin = (a0.nn | a1.nn | a2.nn) >= 0 ? 1 : 0;
+  t.labelled = (unsigned)lin;
+  t.label = vol.origin + (long)(a0.nn * lin) * vol.stride0 + (long)(a1.nn * lin) * vol.stride1 + a2.nn * lin;
+  return t;
+}
+
+// The value of one channel `p` at the taps: eight unconditional fp32 loads; bit k of `in` becomes an all-ones or all-zeros word that
+// tap k is ANDed with (a select without a compare: a tap inside keeps every bit, a NaN its payload; a tap outside becomes +0); then
+// the eight-term sum, left to right in double, rounded once.
+__device__ __forceinline__ float affine_value(const float* __restrict__ p, const AffineTaps& t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  float y[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) y[k] = p[t.row[k >> 1] + (k & 1) * t.step];
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const double term = (double)__uint_as_float(__float_as_uint(y[k]) & (0u - ((t.in >> k) & 1u))) * t.w[k];
+    acc = k == 0 ? term : acc + term;
+  }
+  return (float)acc;
+}
+
+// The output voxel (i, j, l) of thread e of an affine sample, one thread per voxel.  Where R1 % 8 == 0 and R2 % 8 == 0 a wave (64
+// consecutive e) takes a compact 8 x 8 tile of (rows, depth): rows j .. j + 7, depth l .. l + 7, whose taps touch fewer cache lines
+// under rotation than those of 64 voxels in a line (it writes eight runs of 32 B a channel); otherwise 64 consecutive voxels.
+// Measured on crop_rotflip_affine_kernel at 2 x 4 x 96^3 under rotation (profiles/crop_affine.md): one quad per thread with guarded
+// loads 266 us, one voxel per thread 122 us, with loads that need no branch 80 us, in tiles 71 us.
+__device__ __forceinline__ void affine_thread_voxel(unsigned e, int R1, int R2, int& i, int& j, int& l) {
+  if ((R1 & 7) == 0 && (R2 & 7) == 0) {
+    const unsigned tiles2 = (unsigned)R2 >> 3, tiles1 = (unsigned)R1 >> 3;
+    const unsigned tile = e >> 6, lane = e & 63u;
+    l = (int)((tile % tiles2) << 3 | (lane & 7u));
+    const unsigned tj = tile / tiles2;
+    j = (int)((tj % tiles1) << 3 | (lane >> 3));
+    i = (int)(tj / tiles1);
+  } else {
+    l = (int)(e % R2);
+    const unsigned rj = e / R2;
+    j = (int)(rj % R1);
+    i = (int)(rj / R1);
+  }
+}
+
+// ---- the AMOS chain with the stage between the pad and the flips: crop -> symmetric pad -> affine about the patch centre -> flips ->
+// rot90 -> intensity.  A sample either has the stage (`affine` = 1) or it does not: without it the sample goes through
+// volume_feed_gather, as in volume_feed_kernel.  With it, the output voxel is mapped back through rot90 and the flips to integer patch
+// coordinates p as there, the sampler reads the whole source volume (strides n1 n2 and n2), and fp32(fp32(v * mul) + add) follows.
 struct VolumeFeedAffineSample {
   VolumeFeedSample f;        // as for volume_feed_kernel
   int n0;                    // source extent of axis 0: the affine gather reads the whole volume
@@ -511,36 +654,11 @@ struct VolumeFeedAffineBatch {
   VolumeFeedAffineSample s[kFeedMaxBatch];     // 160 B a record: 2,560 B of the 4 KB kernel-argument block
 };
 
-// one axis of one voxel: the two image taps i0, i0 + 1 with their weights, and the label's index
-struct AffineAxis {
-  double w0, w1;             // 1 - f, f
-  int i0;                    // floor(x) where one of the taps is inside, else 0 (and both flags are false)
-  int nn;                    // rint(x), or -1 outside [0, n - 1]
-  bool in0, in1;             // tap i0 / i0 + 1 lies in [0, n - 1]
-};
-
-__device__ __forceinline__ AffineAxis affine_axis(double x, int n) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  const double top = (double)(n - 1);
-  const double fl = floor(x);
-  const double f = x - fl;
-  AffineAxis a;
-  a.in0 = fl >= 0.0 && fl <= top;                    // on the double: a NaN or a huge x fails both
-  a.in1 = fl >= -1.0 && fl <= top - 1.0;
-  a.i0 = (a.in0 || a.in1) ? (int)fl : 0;             // -1 .. n - 1
-  a.w0 = 1.0 - f;
-  a.w1 = f;
-  const double rn = rint(x);                         // half to even
-  a.nn = (rn >= 0.0 && rn <= top) ? (int)rn : -1;
-  return a;
-}
-
-// Arguments, grid and stores of volume_feed_kernel<V, DEV>; one sample per blockIdx.y, so `affine` is wave-uniform.  An affine sample
-// takes one thread per V consecutive OUTPUT depth voxels as well: every voxel's coordinates come from the definition (the part of x_a
-// that the V voxels share, M_a0 u_0 + M_a1 u_1, is the same value for each of them), eight fp32 tap loads and one label load a voxel.
-// DEV = true: t_a is formed on the device from the clamped origin (clamp_device_origin).  No LDS, no atomics.
+// Arguments and stores of volume_feed_kernel<V, DEV>; grid (x, B), one sample per blockIdx.y, so its record and `affine` are
+// wave-uniform.  V is the form of the INTEGER path.  An affine sample takes one thread per output voxel in both instances
+// (affine_thread_voxel); the launcher sizes the grid for that when the launch has an affine sample, and the threads an integer-path
+// sample does not need leave at once.  DEV = true: t_a is formed on the device from the clamped origin (clamp_device_origin).
+// No LDS, no atomics.
 template <int V, bool DEV>
 __global__ __launch_bounds__(256) void volume_feed_affine_kernel(VolumeFeedAffineBatch fb, const int* __restrict__ origins,
                                                                  float* __restrict__ image_out, long long* __restrict__ label_out, int R0, int R1,
@@ -549,88 +667,52 @@ __global__ __launch_bounds__(256) void volume_feed_affine_kernel(VolumeFeedAffin
 #pragma clang fp contract(off)
 #endif
   static_assert(V == 1 || V == 4, "one voxel or one quad per thread");
-  const int q2 = R2 / V;
-  const unsigned per = (unsigned)R0 * R1 * q2;                                // the launcher keeps R0 * R1 * R2 below 2^31
+  const unsigned voxels = (unsigned)R0 * R1 * R2;                             // the launcher keeps R0 * R1 * R2 below 2^31
   const int b = blockIdx.y;
   const VolumeFeedAffineSample& rec = fb.s[b];
   const VolumeFeedSample& s = rec.f;
   int c0 = s.c0, c1 = s.c1, c2 = s.c2;
   if constexpr (DEV) clamp_device_origin(origins, b, c0, c1, c2);
-  const bool affine = rec.affine != 0;
-  const double h0 = (double)(R0 - 1) * 0.5, h1 = (double)(R1 - 1) * 0.5, h2 = (double)(R2 - 1) * 0.5;
-  const double t0 = (double)(c0 - s.l0) + h0, t1 = (double)(c1 - s.l1) + h1, t2 = (double)(c2 - s.l2) + h2;
-  const bool rev = (s.flip & 4) != 0;
-  for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < per; r += gridDim.x * blockDim.x) {
-    const long e = (long)b * per + r;
-    const int l = (int)(r % q2) * V;
-    const unsigned rj = r / q2;
-    const int j = (int)(rj % R1), i = (int)(rj / R1);
+  float* __restrict__ img = image_out + (long)b * voxels;
+  long long* __restrict__ lab = label_out + (long)b * voxels;
+  if (!rec.affine) {
+    const int q2 = R2 / V;
+    for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < voxels / V; r += gridDim.x * blockDim.x) {
+      const int l = (int)(r % q2) * V;
+      const unsigned rj = r / q2;
+      int fa, fc;                                                             // out[i][j] = flipped[fa][fc]
+      rot90_source(s.k, (int)(rj / R1), (int)(rj % R1), R0, R1, fa, fc);
+      if (s.flip & 1) fa = R0 - 1 - fa;
+      if (s.flip & 2) fc = R1 - 1 - fc;
+      float v[V];
+      unsigned lv[V];
+      volume_feed_gather<V>(s, c0, c1, c2, fa, fc, l, R2, v, lv);
+      feed_store<V>(img + (long)r * V, lab + (long)r * V, v, lv);
+    }
+    return;
+  }
+  const AffineFrame frame = affine_frame(R0, R1, R2, c0 - s.l0, c1 - s.l1, c2 - s.l2);
+  const AffineVolume vol = {rec.n0, s.n1, s.n2, 0, (long)s.n1 * s.n2, s.n2};
+  for (unsigned e = blockIdx.x * blockDim.x + threadIdx.x; e < voxels; e += gridDim.x * blockDim.x) {
+    int i, j, l;
+    affine_thread_voxel(e, R1, R2, i, j, l);
     int fa, fc;                                                               // out[i][j] = flipped[fa][fc]
     rot90_source(s.k, i, j, R0, R1, fa, fc);
     if (s.flip & 1) fa = R0 - 1 - fa;
     if (s.flip & 2) fc = R1 - 1 - fc;
-    float v[V];
-    unsigned lab[V];
-    if (!affine) {
-      volume_feed_gather<V>(s, c0, c1, c2, fa, fc, l, R2, v, lab);
-    } else {
-      const double u0 = (double)fa - h0, u1 = (double)fc - h1;
-      const double g0 = rec.m[0] * u0 + rec.m[1] * u1;                         // two products and a sum, each rounded (contraction off)
-      const double g1 = rec.m[3] * u0 + rec.m[4] * u1;
-      const double g2 = rec.m[6] * u0 + rec.m[7] * u1;
-#pragma unroll
-      for (int t = 0; t < V; ++t) {
-        const int p2 = rev ? R2 - 1 - (l + t) : l + t;
-        const double u2 = (double)p2 - h2;
-        const AffineAxis a0 = affine_axis(t0 + (g0 + rec.m[2] * u2), rec.n0);
-        const AffineAxis a1 = affine_axis(t1 + (g1 + rec.m[5] * u2), s.n1);
-        const AffineAxis a2 = affine_axis(t2 + (g2 + rec.m[8] * u2), s.n2);
-        const long r00 = ((long)a0.i0 * s.n1 + a1.i0) * s.n2 + a2.i0;          // tap (0,0,0); read only where its flags allow
-        const long d0s = (long)s.n1 * s.n2, d1s = s.n2;
-        const bool k00 = a0.in0 && a1.in0, k01 = a0.in0 && a1.in1, k10 = a0.in1 && a1.in0, k11 = a0.in1 && a1.in1;
-        const double x000 = k00 && a2.in0 ? (double)s.image[r00] : 0.0;
-        const double x001 = k00 && a2.in1 ? (double)s.image[r00 + 1] : 0.0;
-        const double x010 = k01 && a2.in0 ? (double)s.image[r00 + d1s] : 0.0;
-        const double x011 = k01 && a2.in1 ? (double)s.image[r00 + d1s + 1] : 0.0;
-        const double x100 = k10 && a2.in0 ? (double)s.image[r00 + d0s] : 0.0;
-        const double x101 = k10 && a2.in1 ? (double)s.image[r00 + d0s + 1] : 0.0;
-        const double x110 = k11 && a2.in0 ? (double)s.image[r00 + d0s + d1s] : 0.0;
-        const double x111 = k11 && a2.in1 ? (double)s.image[r00 + d0s + d1s + 1] : 0.0;
-        const double w00 = a0.w0 * a1.w0, w01 = a0.w0 * a1.w1, w10 = a0.w1 * a1.w0, w11 = a0.w1 * a1.w1;
-        double acc = x000 * (w00 * a2.w0);
-        acc = acc + x001 * (w00 * a2.w1);
-        acc = acc + x010 * (w01 * a2.w0);
-        acc = acc + x011 * (w01 * a2.w1);
-        acc = acc + x100 * (w10 * a2.w0);
-        acc = acc + x101 * (w10 * a2.w1);
-        acc = acc + x110 * (w11 * a2.w0);
-        acc = acc + x111 * (w11 * a2.w1);
-        const float x = (float)acc;
-        const float m = x * s.mul;
-        v[t] = m + s.add;
-        lab[t] = 0u;
-        if (a0.nn >= 0 && a1.nn >= 0 && a2.nn >= 0) lab[t] = s.label[((long)a0.nn * s.n1 + a1.nn) * s.n2 + a2.nn];
-      }
-    }
-    feed_store<V>(image_out + e * V, label_out + e * V, v, lab);
+    const AffineTaps taps = affine_taps(fa, fc, (s.flip & 4) ? R2 - 1 - l : l, rec.m, frame, vol);
+    const unsigned r = ((unsigned)i * R1 + j) * R2 + l;                       // the output voxel
+    const float m = affine_value(s.image, taps) * s.mul;                      // two roundings
+    img[r] = m + s.add;
+    lab[r] = (long long)(s.label[taps.label] * taps.labelled);
   }
 }
 
-// ---- the BraTS chain (crop_rotflip_channels_kernel: rot90 -> flip -> zero padding -> crop, images [C][n0][n1][n2] with ONE label) with an
-// AFFINE stage about the patch centre.  The definition is in DESIGN.md §2 "Affine stage of the BraTS feed"; tests/crop_affine_ref.py
-// restates it in numpy.  Y = flip(rot90(x, k), axis) is the virtual rotated and flipped volume of extents (r0, r1, n2); it is never
-// materialised.  A sample either has the stage (`affine` = 1) or it does not: without it the sample takes the integer path, the body of
-// crop_rotflip_channels_kernel, and its values are copied.  With it, per output voxel q, every fp64 product and sum rounded on its own,
-//   u_a = q_a - (R_a - 1) / 2,  t_a = (c_a - p_a) + (R_a - 1) / 2                (both exact),
-//   x_a = t_a + ((M_a0 u_0 + M_a1 u_1) + M_a2 u_2)                               (a coordinate of the WHOLE of Y, not of the crop window),
-//   image, per channel: i_a = floor(x_a), f_a = x_a - i_a; the eight taps of Y in the order (0,0,0), (0,0,1), ..., (1,1,1), a tap outside
-//          [0, extent_a - 1] on any axis counting as 0 (which is the zero padding as well); sum of double(tap) * ((w_0 w_1) w_2),
-//          w_a = f_a for bit 1 and 1 - f_a for bit 0, left to right in double, rounded once to fp32; no mul / add;
-//   label: Y at rint(x_a) per axis (half to even); 0 when a rounded index is outside the extents.
-// An in-range index (a, c, d) of Y is mapped to the source as crop_rotflip_channels_kernel maps it, flip and then rot90_source(k, ., .,
-// n0, n1); that map is affine in (a, c), so it is an origin and one SIGNED source stride for each of the axes 0 and 1 (from crop_affine_row),
-// and stride 1 along depth.  Every range test is made on the DOUBLE, before any conversion to int (affine_axis), so no M can send a read
-// outside the volume (the launcher bounds |M_ab| by 16 all the same).
+// ---- the BraTS chain (crop_rotflip_channels_kernel: rot90 -> flip -> zero padding -> crop, images [C][n0][n1][n2] with ONE label) with the
+// stage about the patch centre (DESIGN.md §2 "Affine stage of the BraTS feed").  The sampled volume is Y = flip(rot90(x, k), axis) of
+// extents (r0, r1, n2); it is never materialised: crop_feed_row gives its origin and its signed strides in the source.  A tap outside Y
+// counts as 0, which is the zero padding as well.  A sample either has the stage (`affine` = 1) or it does not: without it the sample
+// goes through crop_feed_gather, as in crop_rotflip_channels_kernel, and its values are copied.  No mul / add.
 struct CropAffineSample {
   FeedSample f;              // as for crop_rotflip_channels_kernel
   int affine;                // 1: the sample has the affine stage; 0: m is not read
@@ -641,178 +723,48 @@ struct CropAffineBatch {
   CropAffineSample s[kFeedMaxBatch];     // 144 B a record: 2,304 B of the 4 KB kernel-argument block
 };
 
-// source offset of the voxel (a, c, 0) of Y: the flip and the quarter turn of crop_rotflip_channels_kernel
-__device__ __forceinline__ long crop_affine_row(const FeedSample& s, int r0, int r1, int a, int c) {
-  if (s.flip_axis == 0) a = r0 - 1 - a;
-  else if (s.flip_axis == 1) c = r1 - 1 - c;
-  int sa, sc;
-  rot90_source(s.k, a, c, s.n0, s.n1, sa, sc);
-  return ((long)sa * s.n1 + sc) * s.n2;
-}
-
-// One axis of one voxel for crop_rotflip_affine_kernel: affine_axis's range tests, made on the double before any conversion to int,
-// with their results as integers.  j0, j1: an index INSIDE [0, n - 1] for each of the two taps floor(x), floor(x) + 1: its own where
-// its test let it in, else the other tap's, else 0 (n >= 1), so every tap has an address inside the volume whatever x is.
-struct CropAffineAxis {
-  double w0, w1;             // 1 - f, f
-  int j0, j1;
-  unsigned in;               // bit 0: tap floor(x) lies in [0, n - 1]; bit 1: tap floor(x) + 1 does
-  int nn;                    // rint(x), or -1 outside [0, n - 1]
-};
-
-__device__ __forceinline__ CropAffineAxis crop_affine_axis(double x, int n) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  const double top = (double)(n - 1);
-  const double fl = floor(x);
-  const double f = x - fl;
-  const bool in0 = fl >= 0.0 && fl <= top;            // on the double: a NaN or a huge x fails both
-  const bool in1 = fl >= -1.0 && fl <= top - 1.0;
-  const int i0 = (in0 || in1) ? (int)fl : 0;          // -1 .. n - 1
-  CropAffineAxis a;
-  a.j0 = in0 ? i0 : 0;                                // in1 alone: floor(x) = -1, and the other tap is 0
-  a.j1 = in1 ? i0 + 1 : a.j0;                         // in0 alone: floor(x) = n - 1 = j0
-  a.in = (in0 ? 1u : 0u) | (in1 ? 2u : 0u);
-  a.w0 = 1.0 - f;
-  a.w1 = f;
-  const double rn = rint(x);                          // half to even
-  a.nn = (rn >= 0.0 && rn <= top) ? (int)rn : -1;
-  return a;
-}
-
-// the loaded tap y where bit t of `in` is set, +0 where it is not: a select without a compare
-__device__ __forceinline__ float crop_affine_tap(float y, unsigned in, int t) {
-  return __uint_as_float(__float_as_uint(y) & (0u - ((in >> t) & 1u)));
-}
-
 // image_out [B][C][R0][R1][R2] fp32, label_out [B][R0][R1][R2] int64.  grid (x, B): one sample per blockIdx.y, so its record and `affine`
 // are wave-uniform.  V (4: R2 % 4 == 0 and both outputs 16-byte aligned) is the form of the INTEGER path, one thread per V consecutive
-// depth voxels as in crop_rotflip_channels_kernel<V>.  An affine sample takes one thread per output voxel in both instances.  Where
-// R1 % 8 == 0 and R2 % 8 == 0 a wave takes a compact 8 x 8 tile of (rows, depth), whose taps touch fewer cache lines under rotation than
-// those of 64 voxels in a line (it writes eight runs of 32 B a channel); otherwise 64 consecutive voxels.  The definition is per voxel,
-// so the result does not depend on the mapping.  Measured at 2 x 4 x 96^3 under rotation (profiles/crop_affine.md): one quad per thread
-// with guarded loads 266 us, one voxel per thread 122 us, with loads that need no branch 80 us, in tiles 71 us.  Per voxel the three
-// coordinates, the in-range bits, the four tap rows, the eight weights and the label come from the definition ONCE; the channel loop
-// then does eight fp32 loads and the eight-term double sum, with channel stride n0 n1 n2.  No LDS, no atomics.
+// depth voxels as in crop_rotflip_channels_kernel<V>.  An affine sample takes one thread per output voxel in both instances
+// (affine_thread_voxel): the taps come from the definition once, the channel loop is affine_value with channel stride n0 n1 n2.
+// No LDS, no atomics.
 template <int V>
 __global__ __launch_bounds__(256) void crop_rotflip_affine_kernel(CropAffineBatch fb, float* __restrict__ image_out, long long* __restrict__ label_out,
                                                                   int C, int R0, int R1, int R2) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
   static_assert(V == 1 || V == 4, "one voxel or one quad per thread");
-  const int q2 = R2 / V;
-  const unsigned per = (unsigned)R0 * R1 * q2;                                // the launcher keeps R0 * R1 * R2 below 2^31
   const int b = blockIdx.y;
   const CropAffineSample& rec = fb.s[b];
   const FeedSample& s = rec.f;
-  const long vox = (long)R0 * R1 * R2;                                        // channel stride of the output
-  const long cs = (long)s.n0 * s.n1 * s.n2;                                   // channel stride of the source
+  const unsigned voxels = (unsigned)R0 * R1 * R2;                             // channel stride of the output; the launcher keeps it below 2^31
   // extents after rot90: odd k swaps axes 0 and 1
   const int r0 = (s.k & 1) ? s.n1 : s.n0, r1 = (s.k & 1) ? s.n0 : s.n1;
-  float* __restrict__ img = image_out + (long)b * C * vox;
-  long long* __restrict__ lab = label_out + (long)b * vox;
+  float* __restrict__ img = image_out + (long)b * C * voxels;
+  long long* __restrict__ lab = label_out + (long)b * voxels;
   if (!rec.affine) {
-    // the integer path: crop_rotflip_channels_kernel<V>'s body
-    for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < per; r += gridDim.x * blockDim.x) {
+    const int q2 = R2 / V;
+    for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < voxels / V; r += gridDim.x * blockDim.x) {
       const int l = (int)(r % q2) * V;
       const unsigned rj = r / q2;
-      const int j = (int)(rj % R1), i = (int)(rj / R1);
       const long e = (long)r * V;                                             // = (i * R1 + j) * R2 + l
-      const int a = s.c0 + i - s.p0, c = s.c1 + j - s.p1;
-      const int d = s.c2 + l - s.p2;
-      const bool row = a >= 0 && a < r0 && c >= 0 && c < r1;
-      const long base = row ? crop_affine_row(s, r0, r1, a, c) : 0;
-      bool in[V];
-      unsigned lv[V];
-#pragma unroll
-      for (int t = 0; t < V; ++t) {
-        in[t] = row && d + t >= 0 && d + t < s.n2;
-        lv[t] = in[t] ? (unsigned)s.label[base + d + t] : 0u;
-      }
-      const bool inside = V == 4 && row && d >= 0 && d + V <= s.n2;           // the whole quad lies in the row
-      for (int ch = 0; ch < C; ++ch) {
-        const float* __restrict__ src = s.image + ch * cs + base + d;         // dereferenced only where in[t]
-        float v[V];
-        if (inside && ((uintptr_t)src & 15) == 0) {
-          const float4 f = *reinterpret_cast<const float4*>(src);
-          v[0] = f.x;
-          if constexpr (V == 4) { v[1] = f.y; v[2] = f.z; v[3] = f.w; }
-        } else {
-#pragma unroll
-          for (int t = 0; t < V; ++t) v[t] = in[t] ? src[t] : 0.f;
-        }
-        if constexpr (V == 4) {
-          *reinterpret_cast<float4*>(img + ch * vox + e) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-          img[ch * vox + e] = v[0];
-        }
-      }
-      feed_store_labels<V>(lab + e, lv);
+      crop_feed_gather<V>(s, r0, r1, C, (int)(rj / R1), (int)(rj % R1), l, img + e, voxels, lab + e);
     }
     return;
   }
-  // Y[a][c][d] = source[o00 + a * sa + c * sc + d]: the map is affine in (a, c), so three evaluations give it (they index nothing)
-  const long o00 = crop_affine_row(s, r0, r1, 0, 0);
-  const long sa = crop_affine_row(s, r0, r1, 1, 0) - o00, sc = crop_affine_row(s, r0, r1, 0, 1) - o00;
-  const double h0 = (double)(R0 - 1) * 0.5, h1 = (double)(R1 - 1) * 0.5, h2 = (double)(R2 - 1) * 0.5;
-  const double t0 = (double)(s.c0 - s.p0) + h0, t1 = (double)(s.c1 - s.p1) + h1, t2 = (double)(s.c2 - s.p2) + h2;
-  const unsigned voxels = (unsigned)R0 * R1 * R2;
-  const bool tiled = (R1 & 7) == 0 && (R2 & 7) == 0;
-  const unsigned tiles2 = (unsigned)R2 >> 3, tiles1 = (unsigned)R1 >> 3;
+  const long cs = (long)s.n0 * s.n1 * s.n2;                                   // channel stride of the source
+  // Y[a][c][d] = source[origin + a * stride0 + c * stride1 + d]: the map is affine in (a, c), so three evaluations give it (they index nothing)
+  const long origin = crop_feed_row(s, r0, r1, 0, 0);
+  const AffineVolume vol = {r0, r1, s.n2, origin, crop_feed_row(s, r0, r1, 1, 0) - origin, crop_feed_row(s, r0, r1, 0, 1) - origin};
+  const AffineFrame frame = affine_frame(R0, R1, R2, s.c0 - s.p0, s.c1 - s.p1, s.c2 - s.p2);
   for (unsigned e = blockIdx.x * blockDim.x + threadIdx.x; e < voxels; e += gridDim.x * blockDim.x) {
     int i, j, l;
-    if (tiled) {                                                              // a wave (64 consecutive e) takes rows j .. j + 7, depth l .. l + 7
-      const unsigned tile = e >> 6, lane = e & 63u;
-      l = (int)((tile % tiles2) << 3 | (lane & 7u));
-      const unsigned tj = tile / tiles2;
-      j = (int)((tj % tiles1) << 3 | (lane >> 3));
-      i = (int)(tj / tiles1);
-    } else {
-      l = (int)(e % R2);
-      const unsigned rj = e / R2;
-      j = (int)(rj % R1);
-      i = (int)(rj / R1);
-    }
+    affine_thread_voxel(e, R1, R2, i, j, l);
+    const AffineTaps taps = affine_taps(i, j, l, rec.m, frame, vol);
     const unsigned r = ((unsigned)i * R1 + j) * R2 + l;                       // the output voxel
-    // u_a = q_a - (R_a - 1) / 2 as (2 q_a - (R_a - 1)) / 2: an integer halved, exact like the difference
-    const double u0 = (double)(2 * i - (R0 - 1)) * 0.5, u1 = (double)(2 * j - (R1 - 1)) * 0.5, u2 = (double)(2 * l - (R2 - 1)) * 0.5;
-    const CropAffineAxis a0 = crop_affine_axis(t0 + ((rec.m[0] * u0 + rec.m[1] * u1) + rec.m[2] * u2), r0);      // every product and sum
-    const CropAffineAxis a1 = crop_affine_axis(t1 + ((rec.m[3] * u0 + rec.m[4] * u1) + rec.m[5] * u2), r1);      // rounded on its own
-    const CropAffineAxis a2 = crop_affine_axis(t2 + ((rec.m[6] * u0 + rec.m[7] * u1) + rec.m[8] * u2), s.n2);    // (contraction off)
-    // Every tap has an address inside the volume (crop_affine_axis), so the eight loads of a channel need no branch and are in flight
-    // together; the value of a tap outside Y is replaced by 0 after the load.
-    const long ra0 = o00 + (long)a0.j0 * sa, ra1 = o00 + (long)a0.j1 * sa, rc0 = (long)a1.j0 * sc + a2.j0, rc1 = (long)a1.j1 * sc + a2.j0;
-    const long b00 = ra0 + rc0, b01 = ra0 + rc1, b10 = ra1 + rc0, b11 = ra1 + rc1;                     // taps (0,0,0), (0,1,0), (1,0,0), (1,1,0)
-    const int dd = a2.j1 - a2.j0;                                                                      // 0 or 1: the step to tap (., ., 1)
-    // bit (4 b0 + 2 b1 + b2): tap (b0, b1, b2) is inside Y, the product of the three axes' bits.  One register for the channel loop, where
-    // bit t becomes an all-ones or all-zeros word that the loaded fp32 is ANDed with: a tap inside Y keeps every bit (a NaN its payload),
-    // a tap outside becomes +0.  Integer arithmetic throughout: a flag kept as a lane mask costs a scalar register pair.
-    const unsigned in01 = ((0u - (a0.in & 1u)) & a1.in) | (((0u - (a0.in >> 1)) & a1.in) << 2);        // bit (2 b0 + b1)
-    const unsigned in = ((0u - (in01 & 1u)) & a2.in) | (((0u - ((in01 >> 1) & 1u)) & a2.in) << 2) |
-                        (((0u - ((in01 >> 2) & 1u)) & a2.in) << 4) | (((0u - (in01 >> 3)) & a2.in) << 6);
-    const double w00 = a0.w0 * a1.w0, w01 = a0.w0 * a1.w1, w10 = a0.w1 * a1.w0, w11 = a0.w1 * a1.w1;
-    const double w000 = w00 * a2.w0, w001 = w00 * a2.w1, w010 = w01 * a2.w0, w011 = w01 * a2.w1;       // (w_0 w_1) w_2
-    const double w100 = w10 * a2.w0, w101 = w10 * a2.w1, w110 = w11 * a2.w0, w111 = w11 * a2.w1;
-    const int lin = (a0.nn | a1.nn | a2.nn) >= 0 ? 1 : 0;                                               // voxel (0, 0, 0) stands in otherwise
-    const unsigned lraw = s.label[o00 + (long)(a0.nn * lin) * sa + (long)(a1.nn * lin) * sc + a2.nn * lin];
-    const float* __restrict__ p = s.image;                                                             // channel ch of the source ...
-    float* __restrict__ o = img + r;                                                                   // ... and of the output voxel
-    for (int ch = 0; ch < C; ++ch, p += cs, o += vox) {
-      const float y000 = p[b00], y001 = p[b00 + dd], y010 = p[b01], y011 = p[b01 + dd];
-      const float y100 = p[b10], y101 = p[b10 + dd], y110 = p[b11], y111 = p[b11 + dd];
-      double acc = (double)crop_affine_tap(y000, in, 0) * w000;
-      acc = acc + (double)crop_affine_tap(y001, in, 1) * w001;
-      acc = acc + (double)crop_affine_tap(y010, in, 2) * w010;
-      acc = acc + (double)crop_affine_tap(y011, in, 3) * w011;
-      acc = acc + (double)crop_affine_tap(y100, in, 4) * w100;
-      acc = acc + (double)crop_affine_tap(y101, in, 5) * w101;
-      acc = acc + (double)crop_affine_tap(y110, in, 6) * w110;
-      acc = acc + (double)crop_affine_tap(y111, in, 7) * w111;
-      *o = (float)acc;
-    }
-    lab[r] = (long long)(lraw * (unsigned)lin);
+    const unsigned lraw = s.label[taps.label];
+    const float* __restrict__ p = s.image;                                    // channel ch of the source ...
+    float* __restrict__ o = img + r;                                          // ... and of the output voxel
+    for (int ch = 0; ch < C; ++ch, p += cs, o += voxels) *o = affine_value(p, taps);
+    lab[r] = (long long)(lraw * taps.labelled);
   }
 }
 

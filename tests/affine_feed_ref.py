@@ -23,23 +23,39 @@ from icl_amd.dataloaders.amos import OnDeviceAugmentAMOS, affine_matrix
 from icl_amd.dataloaders.brats2019 import DeviceVolumeStore
 
 ROI_SCALAR = aref.ROI_SCALAR          # (6, 6, 5): one thread per voxel
-ROI_QUAD = aref.ROI_QUAD              # (6, 6, 8): one thread per four depth voxels
+ROI_QUAD = aref.ROI_QUAD              # (6, 6, 8): one thread per four depth voxels on the integer path
+ROI_TILED = (8, 8, 8)                 # R1 % 8 == 0 and R2 % 8 == 0: an affine sample's waves take 8 x 8 tiles of (rows, depth); two workgroups
+ROIS = (ROI_SCALAR, ROI_QUAD, ROI_TILED)
 IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
 CUBES = [(8, 8, 8), (5, 5, 5)]        # source == roi: the quad path with an even centre (3.5), the scalar path with an odd one (2)
 RANDOM_SOURCES = [(7, 5, 9), (12, 11, 4), (9, 9, 8), (13, 12, 11)]
-RANDOM_ROIS = [(8, 8, 8), (6, 6, 5)]
+RANDOM_ROIS = [ROI_TILED, ROI_SCALAR]
+
+
+def coordinates(row, M, roi):
+    """x_a of every voxel of the PATCH grid (before the flips and the quarter turn), three float64 arrays: the formula, operation by
+    operation."""
+    c, left = row[3:6], row[9:12]
+    M = np.asarray(M, dtype=np.float64).reshape(3, 3)
+    p = np.meshgrid(*[np.arange(r, dtype=np.float64) for r in roi], indexing="ij")
+    u = [p[a] - (roi[a] - 1) / 2 for a in range(3)]
+    t = [np.float64(int(c[a]) - int(left[a])) + (roi[a] - 1) / 2 for a in range(3)]
+    return [t[a] + ((M[a, 0] * u[0] + M[a, 1] * u[1]) + M[a, 2] * u[2]) for a in range(3)]
+
+
+def forwards(y, row):
+    """A patch-grid array through the flips and the quarter turn of ``row``, forwards."""
+    for a in range(3):
+        if int(row[12]) >> a & 1:
+            y = np.flip(y, a)
+    return np.rot90(y, int(row[13]), axes=(0, 1))
 
 
 def affine_chain(image, label, row, M, roi):
     """(image [1, *roi] fp32, label [1, *roi] int64) of one sample with the affine stage.  ``row``: the 16 feed values; ``M``: 3x3."""
     n = image.shape
-    c, left, flip, k = row[3:6], row[9:12], int(row[12]), int(row[13])
     mul, add = np.float32(row[14]), np.float32(row[15])
-    M = np.asarray(M, dtype=np.float64).reshape(3, 3)
-    p = np.meshgrid(*[np.arange(r, dtype=np.float64) for r in roi], indexing="ij")
-    u = [p[a] - (roi[a] - 1) / 2 for a in range(3)]
-    t = [np.float64(int(c[a]) - int(left[a])) + (roi[a] - 1) / 2 for a in range(3)]
-    x = [t[a] + ((M[a, 0] * u[0] + M[a, 1] * u[1]) + M[a, 2] * u[2]) for a in range(3)]
+    x = coordinates(row, M, roi)
     fl = [np.floor(x[a]) for a in range(3)]
     f = [x[a] - fl[a] for a in range(3)]
     w = [(1.0 - f[a], f[a]) for a in range(3)]
@@ -60,15 +76,9 @@ def affine_chain(image, label, row, M, roi):
         inside &= (rn[a] >= 0) & (rn[a] <= n[a] - 1)
     at = tuple(np.where(inside, rn[a], 0).astype(np.int64) for a in range(3))
     lab = np.where(inside, label[at], 0).astype(np.int64)
-    out = []
-    for y in (img, lab):
-        for a in range(3):
-            if flip >> a & 1:
-                y = np.flip(y, a)
-        out.append(np.rot90(y, k, axes=(0, 1)))
-    y = (out[0] * mul).astype(np.float32)        # rounded ...
-    y = (y + add).astype(np.float32)             # ... and rounded again
-    return np.ascontiguousarray(y)[None], np.ascontiguousarray(out[1])[None]
+    y = (forwards(img, row) * mul).astype(np.float32)        # rounded ...
+    y = (y + add).astype(np.float32)                         # ... and rounded again
+    return np.ascontiguousarray(y)[None], np.ascontiguousarray(forwards(lab, row))[None]
 
 
 def same(got, want):
@@ -258,12 +268,93 @@ def check_random(store, roi):
     return len(cases)
 
 
+# ---- 5. non-finite voxels -------------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def nonfinite_volume(v):
+    """random_volume(v) with a NaN at voxel (0, 0, 0), which stands in for a tap outside the volume inside the kernel, +inf at the last
+    voxel and -inf at the central one."""
+    image, label = random_volume(v)
+    image = image.copy()
+    image[0, 0, 0] = np.nan
+    image[-1, -1, -1] = np.inf
+    image[tuple(n // 2 for n in image.shape)] = -np.inf
+    return image, label
+
+
+def nonfinite_store(device):
+    return DeviceVolumeStore([nonfinite_volume(v) for v in range(len(RANDOM_SOURCES))], device)
+
+
+NONFINITE_SEED = 0
+
+
+@functools.lru_cache(maxsize=None)
+def nonfinite_cases(roi, seed=NONFINITE_SEED):
+    """Six matrices per source as in random_cases, seeded; the crop at the corner of voxel (0, 0, 0), at the opposite corner and in the
+    middle in turn (the three voxels of nonfinite_volume); flips and quarter turns vary; mul = 1 and add = 0, so that a voxel without a
+    tap stays +0.  The seed was chosen so that check_nonfinite's conditions hold at all three ROIS."""
+    rng = np.random.RandomState(seed)
+    cases = []
+    for v, shape in enumerate(RANDOM_SOURCES):
+        span = [max(n - r, 0) for n, r in zip(shape, roi)]
+        for q in range(6):
+            M = affine_matrix(rng.uniform(-0.5, 0.5, 3), rng.uniform(0.7, 1.4, 3))
+            origin = [(0, span[a], span[a] // 2)[q % 3] for a in range(3)]
+            m = 6 * v + q
+            cases.append((v, aref.make_row(shape, roi, origin, (m * 3 + 1) % 8, m % 4, 1.0, 0.0), tuple(M.reshape(-1))))
+    return tuple(cases)
+
+
+def check_nonfinite(store, roi):
+    """A tap outside the volume counts as 0 whatever the stand-in voxel holds; a tap inside carries its value even where its weight is 0
+    (0 * inf is a NaN in the definition too).  Through icl_volume_feed_affine and icl_volume_feed_affine_origins, aligned outputs and
+    outputs 4 / 8 bytes off: equal to the restatement, a NaN equal to a NaN.  What the case list must hold is asserted on the restatement
+    alone: voxels with a tap outside the volume on each axis and on all three at once, a NaN carried by an inside tap at voxel (0, 0, 0), and a voxel all of whose
+    eight taps are outside and whose value is +0."""
+    cases = nonfinite_cases(roi)
+    outside_on_axis, outside_on_all, nan_from_origin, untouched = [0, 0, 0], 0, 0, 0
+    want = []
+    for v, row, M in cases:
+        image, label = nonfinite_volume(v)
+        with np.errstate(invalid="ignore"):                              # 0 * inf and inf - inf are part of the case
+            want.append(affine_chain(image, label, row, M, roi))
+        fl = [np.floor(x) for x in coordinates(row, M, roi)]
+        out = [[(fl[a] + bit < 0) | (fl[a] + bit > image.shape[a] - 1) for bit in (0, 1)] for a in range(3)]
+        for a in range(3):
+            outside_on_axis[a] += int((out[a][0] | out[a][1]).sum())
+        outside_on_all += int(np.logical_and.reduce([out[a][0] | out[a][1] for a in range(3)]).sum())
+        # tap (0, 0, 0) of the volume is among the eight: floor(x_a) is 0 or -1 on every axis
+        at_origin = np.logical_and.reduce([(fl[a] == 0) | (fl[a] == -1) for a in range(3)])
+        carried = want[-1][0][0][forwards(at_origin, row)]                # the mask is on the patch grid, the output flipped and turned
+        assert np.isnan(carried).all()
+        nan_from_origin += carried.size
+        # every tap is outside where both taps of one axis are
+        none = forwards(np.logical_or.reduce([out[a][0] & out[a][1] for a in range(3)]), row)
+        value = want[-1][0][0][none]
+        assert (value == 0).all() and not np.signbit(value).any()
+        untouched += int(none.sum())
+    print(f"roi {roi}: voxels with a tap outside per axis {outside_on_axis}, on all three {outside_on_all}; NaN from voxel (0, 0, 0) "
+          f"{nan_from_origin}; no tap inside {untouched}")
+    assert min(outside_on_axis) > 0 and outside_on_all > 0 and nan_from_origin > 0 and untouched > 0
+    want = np.stack([w[0] for w in want]), np.stack([w[1] for w in want])
+    origins = torch.tensor([c[1][3:6] for c in cases], dtype=torch.int32, device=store.device)
+    for misaligned in (False, True):
+        for dev_origins in (False, True):
+            for lo in range(0, len(cases), 16):
+                part = cases[lo:lo + 16]
+                rc, image, label = raw_affine(store, roi, [c[0] for c in part], [c[1] for c in part], [c[2] for c in part], misaligned=misaligned,
+                                              origins=origins[lo:lo + 16].contiguous() if dev_origins else None)
+                assert rc == 0, _lib.lib().icl_last_error()
+                check_cases((image.cpu().numpy(), label.cpu().numpy()[:, None]), part, (want[0][lo:lo + 16], want[1][lo:lo + 16]))
+    return len(cases)
+
+
 # ---- 6. mixed batch -------------------------------------------------------------------------------------------------------------------
 
-def check_mixed_batch(store):
+def check_mixed_batch(store, roi=ROI_TILED):
     """17 samples, plain and affine rows alternating: two launches (16 through the affine entry, the last, plain one through
     icl_volume_feed).  Plain samples equal icl_volume_feed's, affine ones the restatement; a second run is bit-equal."""
-    roi = (8, 8, 8)
     cases = random_cases(roi)[:17]
     want = reference(random_cases(roi), "random", roi)
     indices = [c[0] for c in cases]
@@ -293,7 +384,7 @@ def check_device_origins(device):
     from icl_amd.dataloaders.amos import ForegroundIndex, OnDeviceAugmentPosNeg
     store = pref.small_store(device)
     index = ForegroundIndex(store, pref.THRESHOLD)
-    for roi in (ROI_QUAD, ROI_SCALAR):
+    for roi in (ROI_QUAD, ROI_SCALAR, ROI_TILED):
         feed = OnDeviceAugmentPosNeg(store, index, roi, num_samples=2, rng=np.random.RandomState(11), flip_prob=0.5, rot_prob=0.5, affine_prob=1.0,
                                      rotate_range=0.5, zoom_range=(0.7, 1.4), zoom_isotropic=False)
         vols = [2, 0, 3, 1]

@@ -272,10 +272,12 @@ def check_mixed_flags(lib, device, channels, patch):
 
 # ---- 3. against the single-channel kernel on the materialised Y -----------------------------------------------------------------------
 
-def check_against_volume_feed_affine(lib, device, patch, channels=3):
+def check_against_volume_feed_affine(lib, device, patch, channels=3, misaligned_amos=False):
     """Y = flip(rot90(x, k), axis) is materialised on the host for each channel and goes through icl_volume_feed_affine with origin
     max(c - p, 0), left pad max(p - c, 0), the matching size, no flips, k = 0, mul = 1, add = 0 and the same M (so t_a is the same
-    number): the new kernel on x equals it channel by channel; the label is compared once.  Returns the number of cases."""
+    number): this kernel on x equals it channel by channel; the label is compared once.  ``misaligned_amos``: the outputs of the
+    single-channel entry are 4 bytes off, so the two sides run the shared sampler from different instances (V = 1 there).  Returns the
+    number of cases."""
     cases = random_cases(patch)
     vols = random_volumes(channels)
     got = run_cases(lib, to_tensors(vols, device), list(cases), channels, patch)
@@ -294,7 +296,7 @@ def check_against_volume_feed_affine(lib, device, patch, channels=3):
         tlab = torch.as_tensor(ylab).to(device)
         for c in range(channels):
             timg = torch.as_tensor(np.ascontiguousarray(virtual_volume(vols[si][0][c], k, axis))).to(device)
-            image, label = sentinel_outputs(1, 1, patch, device)
+            image, label = sentinel_outputs(1, 1, patch, device, misaligned_amos)
             rc = lib.icl_volume_feed_affine(one(timg.data_ptr()), one(tlab.data_ptr()), ints, floats, affine, 1, image.data_ptr(),
                                             label.data_ptr(), *patch, _stream(device))
             assert rc == 0, lib.icl_last_error()

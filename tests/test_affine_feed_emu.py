@@ -93,6 +93,11 @@ def test_random_matrices_against_scipy(random_store, roi):
     assert left_out <= total / 1000
 
 
+@pytest.mark.parametrize("roi", ref.ROIS)
+def test_nonfinite_voxels_count_only_where_a_tap_is_inside(emu_library, roi):
+    assert ref.check_nonfinite(ref.nonfinite_store("cpu"), roi) == 24
+
+
 def test_mixed_batch_of_17_is_two_launches(random_store):
     ref.check_mixed_batch(random_store)
 

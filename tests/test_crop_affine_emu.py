@@ -61,12 +61,13 @@ def test_a_tap_outside_the_volume_is_zero_whatever_the_volume_holds(emu, patch):
 
 
 def test_the_tiled_thread_mapping_of_the_affine_path(emu):
-    """Patch (6, 8, 8): identity against the plain entry, a mixed launch, the single-channel kernel, the restatement (random, dyadic,
-    misaligned outputs) and non-finite volumes."""
+    """Patch (6, 8, 8): identity against the plain entry, a mixed launch, the single-channel kernel (aligned and misaligned outputs on its
+    side), the restatement (random, dyadic, misaligned outputs) and non-finite volumes."""
     ref.check_identity(emu, CPU, 3, ref.PATCH_TILED)
     ref.check_identity(emu, CPU, None, ref.PATCH_TILED, misaligned=True)
     ref.check_mixed_flags(emu, CPU, 4, ref.PATCH_TILED)
     assert ref.check_against_volume_feed_affine(emu, CPU, ref.PATCH_TILED) == 12
+    assert ref.check_against_volume_feed_affine(emu, CPU, ref.PATCH_TILED, misaligned_amos=True) == 12
     assert ref.check_reference(emu, CPU, ref.PATCH_TILED) == 18
     ref.check_nonfinite(emu, CPU, ref.PATCH_TILED)
 

@@ -67,6 +67,11 @@ def test_random_matrices_equal_the_restatement_on_both_kernels(random_store, roi
     assert ref.check_random(random_store, roi) == 24
 
 
+@pytest.mark.parametrize("roi", ref.ROIS)
+def test_nonfinite_voxels_count_only_where_a_tap_is_inside(dev, roi):
+    assert ref.check_nonfinite(ref.nonfinite_store(dev), roi) == 24
+
+
 def test_mixed_batch_of_17_is_two_launches_and_repeats_bit_for_bit(random_store):
     ref.check_mixed_batch(random_store)
 

@@ -64,12 +64,13 @@ def test_a_tap_outside_the_volume_is_zero_whatever_the_volume_holds_on_the_gpu(l
 
 
 def test_the_tiled_thread_mapping_of_the_affine_path_on_the_gpu(lib, dev):
-    """Patch (6, 8, 8): identity against the plain entry, a mixed launch, the single-channel kernel, the restatement (random, dyadic,
-    misaligned outputs) and non-finite volumes."""
+    """Patch (6, 8, 8): identity against the plain entry, a mixed launch, the single-channel kernel (aligned and misaligned outputs on its
+    side), the restatement (random, dyadic, misaligned outputs) and non-finite volumes."""
     ref.check_identity(lib, dev, 3, ref.PATCH_TILED)
     ref.check_identity(lib, dev, None, ref.PATCH_TILED, misaligned=True)
     ref.check_mixed_flags(lib, dev, 4, ref.PATCH_TILED)
     assert ref.check_against_volume_feed_affine(lib, dev, ref.PATCH_TILED) == 12
+    assert ref.check_against_volume_feed_affine(lib, dev, ref.PATCH_TILED, misaligned_amos=True) == 12
     assert ref.check_reference(lib, dev, ref.PATCH_TILED) == 18
     ref.check_nonfinite(lib, dev, ref.PATCH_TILED)
 

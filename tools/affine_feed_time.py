@@ -15,9 +15,9 @@ variant.  The 22 MB of source volumes stay cache-resident in every variant alike
                `plain` is the run-to-run spread of this box) against the same entry point of the build of the parent commit
                (`plain_parent`, only with --parent: the other library is loaded side by side with ctypes), at 96^3 (the quad
                kernel) and at 96 x 96 x 90 (the one-voxel kernel).  Outputs compared bit for bit.  With --stages-out, the same
-               check for the other five gather entries: icl_volume_feed_origins, icl_volume_feed_affine with all flags 1 and with
-               all flags 0, icl_volume_feed_affine_origins, icl_crop_rotflip and icl_crop_rotflip_channels at C = 4, each with its
-               own `_again` and `_parent`; the band for this / parent is 1 +- twice the largest |again / first - 1| of the run
+               check for the other six gather entries: icl_volume_feed_origins, icl_volume_feed_affine with all flags 1 and with
+               all flags 0, icl_volume_feed_affine_origins, icl_crop_rotflip, icl_crop_rotflip_channels at C = 4 and
+               icl_crop_rotflip_affine at C = 4 with all flags 1 and with all flags 0, each with its own `_again` and `_parent`; the band for this / parent is 1 +- twice the largest |again / first - 1| of the run
                (the ratio of two independent medians carries the spread of both); written to <stages-out>.json.
   affine       icl_volume_feed_affine with every sample affine (angles in +-0.5 rad, anisotropic zoom in 0.7 .. 1.4) and with every
                flag 0 (the integer path inside the new kernel), against `plain`, and as a fraction of the device copy rate for the
@@ -80,11 +80,11 @@ def window(fn, launches):
 
 
 GATHER_ENTRIES = ("icl_volume_feed", "icl_volume_feed_origins", "icl_volume_feed_affine", "icl_volume_feed_affine_origins",
-                  "icl_crop_rotflip", "icl_crop_rotflip_channels")
+                  "icl_crop_rotflip", "icl_crop_rotflip_channels", "icl_crop_rotflip_affine")
 
 
 def load_parent(path):
-    """The parent commit's library beside this build's: the six gather entries, with the signatures of icl_amd/_lib.py (the ABI is shared)."""
+    """The parent commit's library beside this build's: the seven gather entries, with the signatures of icl_amd/_lib.py (the ABI is shared)."""
     lib = ctypes.CDLL(path)
     for name in GATHER_ENTRIES:
         fn = getattr(lib, name)
@@ -93,7 +93,7 @@ def load_parent(path):
 
 
 def measure_entries(L, parent, store, store4, dev, roi):
-    """The regression check of the five gather entries beside icl_volume_feed, on the batch of ``measure``: every entry of this build
+    """The regression check of the six gather entries beside icl_volume_feed, on the batch of ``measure``: every entry of this build
     (`x`, and `x_again` in the same round), against the parent's (`x_parent`), interleaved, outputs rotating and compared bit for bit."""
     vols, rows, mats = make_rows(roi)
     m = len(vols)
@@ -126,14 +126,18 @@ def measure_entries(L, parent, store, store4, dev, roi):
                                                                                      origins.data_ptr(), *outs(), *roi, stream),
         "crop_rotflip": lambda lib: lib.icl_crop_rotflip(images, labels, crops, m, *outs(), *roi, stream),
         "crop_rotflip_channels": lambda lib: lib.icl_crop_rotflip_channels(images4, labels, crops, m, channels, *outs(channels), *roi, stream),
+        "crop_rotflip_affine": lambda lib: lib.icl_crop_rotflip_affine(images4, labels, crops, affine_on, m, channels, *outs(channels), *roi, stream),
+        "crop_rotflip_affine_flags_off": lambda lib: lib.icl_crop_rotflip_affine(images4, labels, crops, affine_off, m, channels, *outs(channels),
+                                                                                 *roi, stream),
     }
+    multi = ("crop_rotflip_channels", "crop_rotflip_affine", "crop_rotflip_affine_flags_off")      # the entries that write C channels
 
     def run(name, lib):
         if calls[name](lib) != 0:
             raise SystemExit(f"{name} failed: {L.icl_last_error()}")
 
     def result(name, lib):
-        c = channels if name == "crop_rotflip_channels" else 1
+        c = channels if name in multi else 1
         turn["n"] = SETS - 1                         # the next call writes set 0
         run(name, lib)
         torch.cuda.synchronize()
@@ -153,7 +157,7 @@ def measure_entries(L, parent, store, store4, dev, roi):
         for k, fn in variants.items():
             times[k].append(window(fn, LAUNCHES))
     med = {k: statistics.median(v) for k, v in times.items()}
-    return {"roi": list(roi), "batch": m, "channels_of_crop_rotflip_channels": channels,
+    return {"roi": list(roi), "batch": m, "channels_of_crop_rotflip_channels": channels, "channels_of_crop_rotflip_affine": channels,
             "us_per_call": {k: {"median": round(med[k], 2), "min": round(min(v), 2), "max": round(max(v), 2)} for k, v in times.items()},
             "again_over_first": {k: round(med[k + "_again"] / med[k], 4) for k in calls},
             "now_over_parent": {k: round(med[k] / med[k + "_parent"], 4) for k in calls}, "equal": equal}
@@ -378,7 +382,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "affine_feed"), help="path without extension: .json and .md are written")
     ap.add_argument("--notes", default=os.path.join(ROOT, "profiles", "affine_feed_notes.md"),
                     help="a markdown file whose text is appended to the .md when it exists (what bounds the kernel, open work)")
-    ap.add_argument("--stages-out", default=None, help="with --parent: path without extension of the record of all six gather entries "
+    ap.add_argument("--stages-out", default=None, help="with --parent: path without extension of the record of all seven gather entries "
                     "against the parent's (.json is written, its table is printed), e.g. profiles/feed_stages")
     a = ap.parse_args()
     if not torch.cuda.is_available():

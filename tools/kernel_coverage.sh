@@ -4,7 +4,8 @@
 # (rank_count_kernel, rank_scan_kernel, rank_select_kernel of rankindex.h and volume_feed_kernel<1, true> and <4, true> of datafeed.h, the
 #  pos/neg feed, are launched by tests/test_gpu_posneg_feed.py: the index and select tests, and the (6, 6, 5) and (6, 6, 8) batches)
 # (volume_feed_affine_kernel<1, false>, <4, false>, <1, true> and <4, true> of datafeed.h, the affine stage of both feeds, are launched by
-#  tests/test_gpu_affine_feed.py: the random-matrix cases on aligned and misaligned outputs, and the device-origin test at both ROIs)
+#  tests/test_gpu_affine_feed.py: the random-matrix cases on aligned and misaligned outputs, and the device-origin and non-finite tests at
+#  (6, 6, 5), (6, 6, 8) and (8, 8, 8), the last with the affine path's 8 x 8 tiles)
 # (intensity_noise_kernel<1> and <4>, intensity_blur_strided_kernel, intensity_blur_line_kernel<1> and <4>, intensity_stats_partial_kernel,
 #  intensity_stats_finish_kernel, intensity_point_kernel<1> and <4> of intensity.h, the intensity stage of the 3-D feeds, are launched by
 #  tests/test_gpu_intensity_feed.py: every check runs (7, 9, 10) for the one-voxel kernels and (8, 12, 16) for the quad kernels, and the

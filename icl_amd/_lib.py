@@ -146,6 +146,9 @@ _SIGNATURES = {
     "icl_sgd_factored_split_ws_bytes": (c_int64, [I, I, I]),
     "icl_sgd_step_factored_split": (c_int, [P, P, P, P, P, I, I, I, F, F, F, I, P, P]),
     "icl_sgd_step_multi": (c_int, [P, P, P, P, I, F, F, F, I, P, P]),
+    "icl_adamw_step": (c_int, [P, P, P, P, L, F, F, F, F, F, F, F, I, P, P]),
+    "icl_adamw_step_multi": (c_int, [P, P, P, P, P, I, F, F, F, F, F, F, F, I, P, P]),
+    "icl_adamw_step_factored": (c_int, [P, P, P, P, P, I, I, I, F, F, F, F, F, F, F, I, P, P]),
     "icl_loss_bwd": (c_int, [P, P, P, P, P, P, P, P, I, I, L, I, I, P]),
     "icl_loss_fwd_multi": (c_int, [P, I, P]),
     "icl_loss_bwd_multi": (c_int, [P, I, P]),

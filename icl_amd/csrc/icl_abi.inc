@@ -17,6 +17,7 @@
 #include "kernels/misc.h"
 #include "kernels/loss.h"
 #include "kernels/optim.h"
+#include "kernels/adamw.h"
 #include "kernels/winattn.h"
 #include "kernels/linear_wgrad.h"
 #include "kernels/token.h"
@@ -2339,6 +2340,54 @@ int icl_sgd_step_multi(void* const* p, const void* const* g, void* const* m, con
     if (rc) return rc;
   }
   return 0;
+}
+
+// ---- AdamW (kernels/adamw.h).  Bad arguments launch nothing.
+int icl_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float decay, float step_size, float bc2_sqrt, float beta2,
+                   float omb1, float omb2, float eps, int first, const float* hyper_dev, void* stream) {
+  if (!p || !g || !m || !v || n < 1) return fail(-1, "adamw_step: bad argument (null pointer or n < 1)");
+  const icl::AdamwHyper h{decay, step_size, bc2_sqrt, beta2, omb1, omb2, eps};
+  ICL_LAUNCH(icl::adamw_kernel, dim3(grid_for((n + 3) / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, h, first,
+             hyper_dev);
+  return check_launch("adamw_step");
+}
+
+int icl_adamw_step_multi(void* const* p, const void* const* g, void* const* m, void* const* v, const int64_t* n, int count, float decay,
+                         float step_size, float bc2_sqrt, float beta2, float omb1, float omb2, float eps, int first,
+                         const float* hyper_dev, void* stream) {
+  if (!p || !g || !m || !v || !n || count < 1) return fail(-1, "adamw_step_multi: bad argument");
+  for (int i = 0; i < count; ++i)      // the whole list is checked before the first launch: a bad entry leaves every tensor untouched
+    if (!p[i] || !g[i] || !m[i] || !v[i] || n[i] < 1) return fail(-1, "adamw_step_multi: bad tensor %d (null pointer or n < 1)", i);
+  const icl::AdamwHyper h{decay, step_size, bc2_sqrt, beta2, omb1, omb2, eps};
+  for (int base = 0; base < count; base += icl::kAdamwMulti) {
+    icl::AdamwMulti t{};
+    const int k = count - base < icl::kAdamwMulti ? count - base : icl::kAdamwMulti;
+    long nmax = 1;
+    for (int i = 0; i < k; ++i) {
+      t.p[i] = (float*)p[base + i];
+      t.g[i] = (const float*)g[base + i];
+      t.m[i] = (float*)m[base + i];
+      t.v[i] = (float*)v[base + i];
+      t.n[i] = (long)n[base + i];
+      if (t.n[i] > nmax) nmax = t.n[i];
+    }
+    ICL_LAUNCH(icl::adamw_multi_kernel, dim3(grid_for((nmax + 3) / 4, 256, 64), k), dim3(256), 0, (hipStream_t)stream, t, h, first, hyper_dev);
+    const int rc = check_launch("adamw_step_multi");
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int icl_adamw_step_factored(float* p, float* m, float* v, const float* g, const float* x, int rows, int n, int k, float decay,
+                            float step_size, float bc2_sqrt, float beta2, float omb1, float omb2, float eps, int first,
+                            const float* hyper_dev, void* stream) {
+  if (!p || !m || !v || !g || !x || rows < 1 || n < 1 || k < 4 || (k & 3))
+    return fail(-1, "adamw_step_factored: bad argument (null pointer, rows < 1, n < 1 or k %% 4 != 0)");
+  if (!aligned16(p) || !aligned16(m) || !aligned16(v) || !aligned16(x)) return fail(-1, "adamw_step_factored: p, m, v and x need 16-byte alignment");
+  const icl::AdamwHyper h{decay, step_size, bc2_sqrt, beta2, omb1, omb2, eps};
+  const dim3 grid((k + icl::kAvCols - 1) / icl::kAvCols, (n + icl::kAvRows - 1) / icl::kAvRows);
+  ICL_LAUNCH(icl::adamw_factored_kernel, grid, dim3(256), 0, (hipStream_t)stream, p, m, v, g, x, rows, n, k, h, first, hyper_dev);
+  return check_launch("adamw_step_factored");
 }
 
 int64_t icl_gemm_ws_bytes(int64_t m, int n, int k, int batch) { return gemm_ws_bytes_impl((long)m, n, k, batch < 1 ? 1 : batch); }

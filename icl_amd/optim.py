@@ -4,11 +4,14 @@ Counterpart of ``optim.SGD(model.parameters(), lr, momentum=0.9, weight_decay=1e
 (/root/reference/code/train_inherent_consistent_unet_3D_BraTS.py:85-86).  It is a ``torch.optim.Optimizer`` so the
 trainers' ``for g in optimizer.param_groups: g['lr'] = lr_`` schedule (:117-119) keeps working.  Parameters whose
 ``.grad`` is None are skipped entirely — no weight decay, no momentum — exactly like torch.
+
+FusedAdamW (at the end of the file) is the same for ``torch.optim.AdamW``, the usual optimiser of the Swin families.
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import struct
 import weakref
 
 import torch
@@ -48,7 +51,7 @@ def _no_hook(module, args):
 
 
 class _ScopePreHook:
-    """The forward pre-hook that opens FusedSGD's step scope.  A module-level class holding a weak reference (the model does not keep
+    """The forward pre-hook that opens the step scope of a FusedSGD or FusedAdamW.  A module-level class holding a weak reference (the model does not keep
     its optimiser alive); pickling a hooked model stores a no-op in its place."""
 
     def __init__(self, opt):
@@ -682,3 +685,235 @@ def _install_graphed_forward(opt, model):
         return st.run(args)
 
     model.forward = forward
+
+
+# ------------------------------------------------------------------------------------------------ FusedAdamW
+ADAMW_FACTORED_MAX_ROWS = 160   # factor rows up to which the update runs from the factors (icl_adamw_step_factored: plain VALU products, 24 B
+                                # per weight); above, the factors are multiplied out (ops._tall_atb) and the dense kernel runs.  Measured at
+                                # 13,824^2 (tools/adamw_probe.py, profiles/adamw.md section 2), factored against multiplied out: 64 rows
+                                # 1056 / 1495 us, 128 rows 1499 / 1691 us, 192 rows 2042 / 1882 us, 256 rows 2538 / 2076 us — the lines
+                                # cross at ~163 rows (8.5 against 3.0 us per row between 128 and 192)
+
+
+def _f32(x: float) -> float:
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def adamw_scalars(lr, weight_decay, beta1, beta2, eps, t):
+    """(decay, step_size, bc2_sqrt, beta2, omb1, omb2, eps) of step ``t`` as the kernels take them: each formed in double — the
+    expressions of torch.optim.AdamW's single-tensor path — and rounded ONCE to fp32.  ``1 - beta`` is never formed in fp32."""
+    return (_f32(1.0 - lr * weight_decay), _f32(lr / (1.0 - beta1 ** t)), _f32((1.0 - beta2 ** t) ** 0.5), _f32(beta2), _f32(1.0 - beta1),
+            _f32(1.0 - beta2), _f32(eps))
+
+
+class FusedAdamW(torch.optim.Optimizer):
+    """``torch.optim.AdamW(params, lr, betas, eps, weight_decay)`` (amsgrad=False, maximize=False) on one HIP pass per parameter
+    (csrc/kernels/adamw.h), a one-line swap.  State per parameter as torch keeps it — ``step`` (CPU fp32 scalar tensor), ``exp_avg``,
+    ``exp_avg_sq`` — so ``state_dict()`` / ``load_state_dict()`` interchange with torch.optim.AdamW in both directions.  Parameters
+    whose ``.grad`` is None and that have no factored gradient are skipped entirely: no decay, ``step`` does not advance.
+
+    ``step_scope`` (default on): as FusedSGD — when the parameters belong to ONE icl_amd model built by the factories, a forward
+    pre-hook of that model opens the step scope and ``step()`` closes it: packed convolution weights, the weight-gradient lane,
+    deferred bias sums and factored gradients of the token-axis matrices on a single process (packed weights only under a multi-rank
+    process group).  There is no update inside backward: the factored matrices are updated in ``step()``, from their factors
+    (icl_adamw_step_factored) up to ``ADAMW_FACTORED_MAX_ROWS`` rows and from the multiplied-out gradient above.
+
+    ``hyper_dev`` (None, or a device fp32 tensor of 3; hipGraph replay): the kernels read {decay, step_size, bc2_sqrt} from it.  One
+    param group; every parameter updated in a step shares one ``step`` value.  ``write_device_hyper()`` stores the scalars of the NEXT
+    update (outside any capture); a ``step()`` under stream capture launches the kernels without advancing the host's ``step``
+    counters, and ``advance_captured_step()`` advances them after every replay."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, step_scope: bool = True):
+        if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"FusedAdamW: invalid hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
+        # the group keys of this torch's own AdamW (amsgrad, maximize, foreach, capturable, ...) with its defaults, so that a
+        # state_dict of either loads into the other; step() refuses the two it does not implement should a loaded dict switch them on
+        defaults = dict(torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr, betas=tuple(betas), eps=eps,
+                                          weight_decay=weight_decay).defaults)
+        super().__init__(params, defaults)
+        self.hyper_dev = None
+        self._touched = None         # the parameters of the last step(): those a captured update touches (advance_captured_step)
+        self._scope_packed = None
+        if step_scope:
+            models = {id(m): m for m in (model_of(p) for g in self.param_groups for p in g["params"]) if m is not None}
+            if len(models) == 1:
+                (model,) = models.values()
+                model.register_forward_pre_hook(_ScopePreHook(self))
+
+    def _clear_factors(self):
+        for group in self.param_groups:
+            for p in group["params"]:
+                if getattr(p, "_icl_factors", None) is not None:
+                    p._icl_factors = None
+
+    def zero_grad(self, set_to_none: bool = True):
+        self._clear_factors()
+        super().zero_grad(set_to_none=set_to_none)
+
+    def abandon_step(self):
+        """Discard what an iteration that will not reach ``step()`` left behind: factored gradients and the open step scope."""
+        self._clear_factors()
+        self._close_scope(flush=False)
+
+    # ---- step scope: FusedSGD's, without the update inside backward
+    def _open_scope(self, module):
+        from . import ops
+        if not module.training or not torch.is_grad_enabled():
+            return
+        scope = StepScope.current
+        if scope is not None:
+            if scope.owner() is self:
+                scope.packed.begin_step()      # a second training forward before step(): the scope stays open, weights are re-packed
+            return                             # (somebody else — ICLTrainer — has a step open)
+        if self._scope_packed is None:
+            self._scope_packed = ops.PackedWeights()
+        try:
+            import torch.distributed as dist
+            single = not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+        except Exception:                # noqa: BLE001
+            single = True
+        StepScope.open(self._scope_packed, owner=self, lane_open=single, deferrals=single, complete_at_backward_end=single,
+                       factored=True if single else None, fused_optimizer=None)
+
+    def _close_scope(self, flush: bool = True):
+        scope = StepScope.current
+        if scope is not None and scope.owner() is self:
+            scope.close(flush)
+
+    # ---- hipGraph replay
+    def _hyper_group(self):
+        h = self.hyper_dev
+        if h is None or h.dtype != torch.float32 or h.numel() != 3 or not h.is_contiguous():
+            raise RuntimeError("FusedAdamW.hyper_dev must be a contiguous fp32 tensor of 3 elements")
+        if len(self.param_groups) != 1:
+            raise RuntimeError(f"FusedAdamW.hyper_dev serves exactly one param group, this optimiser has {len(self.param_groups)}")
+        return self.param_groups[0]
+
+    def _name(self, p):
+        for gi, group in enumerate(self.param_groups):
+            for i, q in enumerate(group["params"]):
+                if q is p:
+                    return f"parameter {i} of group {gi} (shape {tuple(p.shape)})"
+        return f"a parameter of shape {tuple(p.shape)}"
+
+    def _common_step(self, params):
+        """The one ``step`` value the given parameters share (0 for parameters without state); raises, naming a parameter, otherwise."""
+        t = None
+        for p in params:
+            s = float(self.state[p]["step"]) if "step" in self.state.get(p, {}) else 0.0
+            if t is None:
+                t, p0 = s, p
+            elif s != t:
+                raise RuntimeError(f"FusedAdamW.hyper_dev: one set of device scalars serves the whole update, but {self._name(p)} is at "
+                                   f"step {s:g} and {self._name(p0)} at step {t:g}")
+        return 0.0 if t is None else t
+
+    def _store_hyper(self, group, t):
+        b1, b2 = group["betas"]
+        s = adamw_scalars(float(group["lr"]), float(group["weight_decay"]), b1, b2, float(group["eps"]), t)
+        self.hyper_dev.copy_(torch.tensor(s[:3], dtype=torch.float32))
+
+    def write_device_hyper(self):
+        """Store {decay, step_size, bc2_sqrt} of the NEXT update in ``hyper_dev`` — from the group's current lr and the ``step`` the
+        updated parameters share — with stream-ordered work; call it outside any capture, before the replay that reads them."""
+        group = self._hyper_group()
+        params = self._touched if self._touched is not None else [p for p in group["params"] if "step" in self.state.get(p, {})]
+        self._store_hyper(group, self._common_step(params) + 1.0)
+
+    def advance_captured_step(self):
+        """After a replay of the captured update: ``step`` of every parameter it touched moves on by one, so the host's state — the
+        next ``write_device_hyper()``, a checkpoint — stays right."""
+        if self._touched is None:
+            raise RuntimeError("FusedAdamW.advance_captured_step(): no step() has run, captured or eager")
+        for p in self._touched:
+            self.state[p]["step"] += 1
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from . import ops
+        L = _lib.lib()
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._close_scope()                     # lane joined, deferred bias gradients assigned, packed weights released
+        work = []                               # (group, parameter, dense gradient or None, factors or None)
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise RuntimeError("FusedAdamW implements amsgrad=False, maximize=False")
+            for p in group["params"]:
+                g, fac = p.grad, getattr(p, "_icl_factors", None)
+                if g is None and not fac:
+                    continue
+                if getattr(p, "_icl_shard", None) is not None:
+                    raise RuntimeError("FusedAdamW: row-sharded data-parallel updates (_icl_shard) are not implemented")
+                if not (p.is_contiguous() and p.dtype == torch.float32 and (g is None or (g.is_contiguous() and g.dtype == torch.float32))):
+                    raise RuntimeError("FusedAdamW needs contiguous fp32 parameters and gradients")
+                if not p.is_cuda and not _lib.host_pointers_ok():
+                    raise RuntimeError("FusedAdamW needs device tensors (no CPU fallback)")
+                work.append((group, p, g, fac))
+        if not work:
+            return loss
+        p0 = work[0][1]
+        capturing = p0.is_cuda and torch.cuda.is_current_stream_capturing()
+        hp = None
+        if self.hyper_dev is not None:
+            group = self._hyper_group()
+            t = self._common_step([w[1] for w in work]) + 1.0
+            if not capturing:
+                self._store_hyper(group, t)      # an eager step reads them too
+            hp = self.hyper_dev.data_ptr()
+        elif capturing:
+            raise RuntimeError("FusedAdamW.step() under stream capture needs hyper_dev: the scalars of a step change with its number")
+        stream = ctypes.c_void_p(torch.cuda.current_stream(p0.device).cuda_stream) if p0.is_cuda else None
+        small = {}                               # (id(group), first, t) -> [group, [(p, g, m, v), ...]]
+        for group, p, g, fac in work:
+            st = self.state[p]
+            if "step" not in st:
+                if capturing:
+                    raise RuntimeError(f"FusedAdamW: {self._name(p)} has no state yet: run a real step before the capture, otherwise "
+                                       "the captured kernels would re-initialise it at every replay")
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"], st["exp_avg_sq"] = torch.empty_like(p), torch.empty_like(p)      # never read in the first step
+            first = 1 if float(st["step"]) == 0.0 else 0
+            if not capturing:
+                st["step"] += 1
+            t = float(st["step"]) + (1.0 if capturing else 0.0)
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            if not (m.is_contiguous() and v.is_contiguous() and m.dtype == torch.float32 and v.dtype == torch.float32):
+                raise RuntimeError("FusedAdamW needs contiguous fp32 state")
+            b1, b2 = group["betas"]
+            sc = adamw_scalars(float(group["lr"]), float(group["weight_decay"]), b1, b2, float(group["eps"]), t)
+            if fac:
+                rows = sum(f[0].shape[0] for f in fac)
+                n, k = p.shape
+                if any(f[0].shape[1] != n or f[1].shape[1] != k or f[0].shape[0] != f[1].shape[0] for f in fac):
+                    raise RuntimeError("FusedAdamW: factored gradient does not match its parameter")
+                if g is None and rows <= ADAMW_FACTORED_MAX_ROWS and k % 4 == 0:
+                    gf = (fac[0][0] if len(fac) == 1 else torch.cat([f[0] for f in fac], 0)).contiguous()
+                    xf = (fac[0][1] if len(fac) == 1 else torch.cat([f[1] for f in fac], 0)).contiguous()
+                    with ops._timed("adamw_factored_kernel", 2.0 * rows * n * k, 24.0 * n * k, p):
+                        _lib.check(L.icl_adamw_step_factored(p.data_ptr(), m.data_ptr(), v.data_ptr(), gf.data_ptr(), xf.data_ptr(), rows, n,
+                                                             k, *sc, first, hp, stream), "adamw_step_factored")
+                    p._icl_factors = None
+                    continue
+                # many factor rows, or a weight with a factored use AND a dense one in the same step: the factors are multiplied out
+                # into the dense gradient (csrc/kernels/gemm.h) and the ordinary update runs
+                for gf, xf in fac:
+                    d = ops._tall_atb(gf, xf, False)[0]
+                    g = d if g is None else g + d
+                p.grad = g
+                p._icl_factors = None
+            if p.numel() >= _BIG:
+                _lib.check(L.icl_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), *sc, first, hp, stream),
+                           "adamw_step")
+            else:
+                small.setdefault((id(group), first, t), [sc, []])[1].append((p, g, m, v))
+        for (_, first, _t), (sc, items) in small.items():
+            n = len(items)
+            arr = ctypes.c_void_p * n
+            P_, G_, M_, V_ = (arr(*[it[j].data_ptr() for it in items]) for j in range(4))
+            N_ = (ctypes.c_int64 * n)(*[it[0].numel() for it in items])
+            _lib.check(L.icl_adamw_step_multi(P_, G_, M_, V_, N_, n, *sc, first, hp, stream), "adamw_step_multi")
+        self._touched = [w[1] for w in work]
+        return loss

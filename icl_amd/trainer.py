@@ -20,7 +20,7 @@ from torch.nn.modules.loss import CrossEntropyLoss
 
 from . import ops
 from .networks.layers import BatchNormAct
-from .optim import FusedSGD
+from .optim import FusedAdamW, FusedSGD
 from .utils import losses as L
 
 
@@ -37,13 +37,25 @@ class ICLConfig:
     patch_size: tuple = (96, 96, 96)   # (256, 256) selects the 2-D losses (AuxLoss / PseudoSoftLoss)
     factored_mlp2_grads: bool = True   # keep the 13,824^2 mlp2 weight gradients factored (ops.FactoredGrads)
     update_in_backward: bool = True    # single rank: SGD step of those matrices inside their backward pass (one read of the matrix)
+    optimizer: str = "sgd"             # "adamw": icl_amd.optim.FusedAdamW, base_lr / weight_decay as given, same poly schedule (one process)
+    betas: tuple = (0.9, 0.999)        # of "adamw"
+    eps: float = 1e-8                  # of "adamw"
 
 
 class ICLTrainer:
     def __init__(self, model: torch.nn.Module, cfg: ICLConfig, ddp=None):
         self.model, self.cfg, self.ddp = model, cfg, ddp
-        self.optimizer = FusedSGD(model.parameters(), lr=cfg.base_lr, momentum=cfg.momentum,
-                                  weight_decay=cfg.weight_decay, step_scope=False)      # this class opens the step scope itself
+        if cfg.optimizer == "adamw":
+            if ddp is not None and ddp.active:
+                raise ValueError("ICLConfig.optimizer='adamw' is single-process: FusedAdamW has no row-sharded or gathered-factor update")
+            self.optimizer = FusedAdamW(model.parameters(), lr=cfg.base_lr, betas=cfg.betas, eps=cfg.eps, weight_decay=cfg.weight_decay,
+                                        step_scope=False)
+        elif cfg.optimizer == "sgd":
+            self.optimizer = FusedSGD(model.parameters(), lr=cfg.base_lr, momentum=cfg.momentum,
+                                      weight_decay=cfg.weight_decay, step_scope=False)      # this class opens the step scope itself
+        else:
+            raise ValueError(f"ICLConfig.optimizer: 'sgd' or 'adamw', not {cfg.optimizer!r}")
+        self.adamw = cfg.optimizer == "adamw"
         self.ce_loss = CrossEntropyLoss()
         self.dice_loss = L.DiceLoss(cfg.num_classes)
         if len(cfg.patch_size) == 3:
@@ -65,6 +77,7 @@ class ICLTrainer:
         self.time_phases = False
         self._phase_events = None
         self.lr_dev = None
+        self.hyper_dev = None     # "adamw" after capture(): FusedAdamW.hyper_dev
 
     def compute_loss(self, outputs, label_batch):
         cfg = self.cfg
@@ -111,7 +124,7 @@ class ICLTrainer:
         ddp = self.ddp if (self.ddp is not None and self.ddp.active) else None
         ops.StepRNG.begin_step()
         # without gradient exchange the factors of a layer are final when its backward runs: update there (FusedSGD.update_in_backward)
-        fuse = cfg.factored_mlp2_grads and cfg.update_in_backward and ddp is None
+        fuse = cfg.factored_mlp2_grads and cfg.update_in_backward and ddp is None and not self.adamw
         # leaving the block joins the lane and reduces what was deferred, one launch each — or drops it, if the step raised
         with ops.StepScope.open(self.packed, factored=cfg.factored_mlp2_grads, world=ddp.world if ddp is not None else 1,
                                 max_rows_gathered=ddp.max_rows_gathered if ddp is not None else None,
@@ -168,10 +181,13 @@ class ICLTrainer:
         ~21 ms of host time, on par with the GPU time."""
         if self.lr_dev is not None:       # after capture() the kernels read the learning rate from device memory, replayed or not
             self.lr_dev.fill_(self.optimizer.param_groups[0]["lr"])
+        replay = self.graph is not None and self.use_graph
+        if self.adamw and replay:
+            self.optimizer.write_device_hyper()      # the scalars of this step: the lr just scheduled, the bias corrections of its number
         if self.graph_update is not None and not self.use_graph:
             raise RuntimeError("a data-parallel trainer that has been captured cannot step eagerly (the reducer's buffers belong to "
                                "the graphs); build a second trainer for eager steps")
-        if self.graph is not None and self.use_graph:
+        if replay:
             if volume_batch.data_ptr() != self.static_vol.data_ptr():
                 self.static_vol.copy_(volume_batch)
             if label_batch.data_ptr() != self.static_lab.data_ptr():
@@ -195,6 +211,8 @@ class ICLTrainer:
                 self.ddp.finish_post_update()
                 if ev:
                     ev[3].record()
+            if self.adamw:
+                self.optimizer.advance_captured_step()
             parts = self.static_out
         else:
             parts = self._step_body(volume_batch, label_batch)
@@ -234,7 +252,10 @@ class ICLTrainer:
         self.static_vol = volume_batch.clone()
         self.static_lab = label_batch.clone()
         self.lr_dev = torch.full((1,), float(self.optimizer.param_groups[0]["lr"]), dtype=torch.float32, device=dev)
-        self.optimizer.lr_dev = self.lr_dev
+        if self.adamw:      # {decay, step_size, bc2_sqrt}: FusedAdamW.step() writes them in eager steps, step() above before a replay
+            self.hyper_dev = self.optimizer.hyper_dev = torch.zeros(3, dtype=torch.float32, device=dev)
+        else:
+            self.optimizer.lr_dev = self.lr_dev
         ops.StepRNG.enable(dev)
         if ddp is not None:
             ddp.static = True

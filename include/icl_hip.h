@@ -683,6 +683,30 @@ int icl_sgd_step_factored_narrow(float* p, float* m, const float* g, const float
 int icl_sgd_step_multi(void* const* p, const void* const* g, void* const* m, const int64_t* n, int count, float lr,
                        float momentum, float weight_decay, int first, const float* lr_dev, void* stream);
 
+/* ---- fused AdamW step, torch.optim.AdamW semantics (amsgrad = False, maximize = False), per fp32 element (csrc/kernels/adamw.h):
+ *   p1 = p*decay;  m' = m + (g - m)*omb1;  v' = v*beta2 + omb2*g*g;  denom = sqrt(v')/bc2_sqrt + eps;  p' = p1 - step_size*(m'/denom)
+ * The caller forms decay = 1 - lr*wd, step_size = lr/(1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), omb1 = 1 - beta1, omb2 = 1 - beta2
+ * in double and rounds each ONCE to fp32 (1 - beta is never formed in fp32).  IEEE sqrt and division.
+ * first != 0: m and v count as 0 and are never read (the state may be uninitialised memory); they are written.
+ * hyper_dev (may be NULL): when given, {decay, step_size, bc2_sqrt} are read from these three device floats instead of the by-value
+ * arguments (hipGraph replay, as lr_dev of the SGD entries).
+ * Bad arguments — a null p / g / m / v, n < 1 — return non-zero with icl_last_error() set and launch nothing. */
+int icl_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float decay, float step_size, float bc2_sqrt, float beta2,
+                   float omb1, float omb2, float eps, int first, const float* hyper_dev, void* stream);
+/* The same step for `count` tensors: HOST arrays of device pointers and element counts, 48 tensors per launch (longer lists are split).
+ * One set of scalars and one `first` serve the whole list.  Bad arguments — a null array, count < 1, a null pointer or n[i] < 1 in
+ * ANY entry — return non-zero with icl_last_error() set and launch nothing (the list is checked before the first launch). */
+int icl_adamw_step_multi(void* const* p, const void* const* g, void* const* m, void* const* v, const int64_t* n, int count, float decay,
+                         float step_size, float bc2_sqrt, float beta2, float omb1, float omb2, float eps, int first,
+                         const float* hyper_dev, void* stream);
+/* The same step for a Linear weight p [n, k] whose gradient is still factored, gg[n][k] = sum_{r < rows} g[r][n] * x[r][k] (g [rows, n],
+ * x [rows, k]; fp32 sums in row order): one pass over p, m and v (24 B per weight) without ever forming the gradient.  Any rows >= 1.
+ * Bad arguments — a null pointer, rows < 1, n < 1, k % 4 != 0, or p / m / v / x not 16-byte aligned — return non-zero with
+ * icl_last_error() set and launch nothing. */
+int icl_adamw_step_factored(float* p, float* m, float* v, const float* g, const float* x, int rows, int n, int k, float decay,
+                            float step_size, float bc2_sqrt, float beta2, float omb1, float omb2, float eps, int first,
+                            const float* hyper_dev, void* stream);
+
 /* ---- the aligner's QUERY chain as fused stages (round 6; csrc/kernels/qchain.h).  Replaces, per resolution level of
  * InherentConsistent, the operator-by-operator mirror of Class_Decoder's query half — norm1_query -> attn.fc_q -> [read-out of
  * softmax(QK^T)V: icl_attn_fwd / icl_attn_bwd_ws] -> attn.proj -> q + drop_path(q) -> norm2 -> mlp.fc1 -> GELU -> mlp.fc2 ->

@@ -149,6 +149,12 @@ _SIGNATURES = {
     "icl_adamw_step": (c_int, [P, P, P, P, L, F, F, F, F, F, F, F, I, P, P]),
     "icl_adamw_step_multi": (c_int, [P, P, P, P, P, I, F, F, F, F, F, F, F, I, P, P]),
     "icl_adamw_step_factored": (c_int, [P, P, P, P, P, I, I, I, F, F, F, F, F, F, F, I, P, P]),
+    "icl_gradclip_sumsq": (c_int, [P, P, I, I, P, P]),
+    "icl_gradclip_factored_ws_bytes": (c_int64, [I, I, I]),
+    "icl_gradclip_factored_parts": (c_int, [I]),
+    "icl_gradclip_sumsq_factored": (c_int, [P, P, I, I, I, P, P, P]),
+    "icl_gradclip_finish": (c_int, [P, L, F, P, P]),
+    "icl_gradclip_scale": (c_int, [P, P, P, I, I, P, P]),
     "icl_loss_bwd": (c_int, [P, P, P, P, P, P, P, P, I, I, L, I, I, P]),
     "icl_loss_fwd_multi": (c_int, [P, I, P]),
     "icl_loss_bwd_multi": (c_int, [P, I, P]),

@@ -18,6 +18,7 @@
 #include "kernels/loss.h"
 #include "kernels/optim.h"
 #include "kernels/adamw.h"
+#include "kernels/gradclip.h"
 #include "kernels/winattn.h"
 #include "kernels/linear_wgrad.h"
 #include "kernels/token.h"
@@ -2388,6 +2389,96 @@ int icl_adamw_step_factored(float* p, float* m, float* v, const float* g, const 
   const dim3 grid((k + icl::kAvCols - 1) / icl::kAvCols, (n + icl::kAvRows - 1) / icl::kAvRows);
   ICL_LAUNCH(icl::adamw_factored_kernel, grid, dim3(256), 0, (hipStream_t)stream, p, m, v, g, x, rows, n, k, h, first, hyper_dev);
   return check_launch("adamw_step_factored");
+}
+
+// ---- gradient clipping by the global 2-norm (kernels/gradclip.h).  Bad arguments launch nothing.
+namespace {
+struct GcGramPlan { int pairs, slab_g, slab_x, nslab_g, nslab_x; };
+constexpr int kGcMaxRows = 1024, kGcMaxChunks = 4096;
+
+// slabs of the long axes: whole 128-column pieces, about 256 workgroups per side over all pairs of row chunks and at most 64 slabs (the
+// combine kernel walks an entry's slabs in one thread; tools/gradclip_probe.py: with 108 slabs that walk was the whole cost at 8 rows)
+GcGramPlan gc_gram_plan(int rows, int n, int k) {
+  GcGramPlan p;
+  const int nch = (rows + icl::kGcRows - 1) / icl::kGcRows;
+  p.pairs = nch * (nch + 1) / 2;
+  const int target = 256 / p.pairs > 64 ? 64 : (256 / p.pairs < 4 ? 4 : 256 / p.pairs);
+  p.slab_g = round_up((int)cdivl(n, target), icl::kGcCols);
+  p.slab_x = round_up((int)cdivl(k, target), icl::kGcCols);
+  p.nslab_g = (int)cdivl(n, p.slab_g);
+  p.nslab_x = (int)cdivl(k, p.slab_x);
+  return p;
+}
+}  // namespace
+
+int64_t icl_gradclip_factored_ws_bytes(int rows, int n, int k) {
+  if (rows < 1 || rows > kGcMaxRows || n < 1 || k < 1) return 0;
+  const GcGramPlan p = gc_gram_plan(rows, n, k);
+  return (int64_t)(p.nslab_g + p.nslab_x) * rows * rows * 8;
+}
+
+int icl_gradclip_factored_parts(int rows) { return rows < 1 || rows > kGcMaxRows ? 0 : (rows * rows + 255) / 256; }
+
+int icl_gradclip_sumsq(const void* const* g, const int64_t* n, int count, int chunks, double* partial, void* stream) {
+  if (!g || !n || !partial || count < 1 || chunks < 1 || chunks > kGcMaxChunks || ((uintptr_t)partial & 7))
+    return fail(-1, "gradclip_sumsq: bad argument (null pointer, count < 1, chunks outside 1..%d or partial not 8-byte aligned)", kGcMaxChunks);
+  for (int i = 0; i < count; ++i)      // the whole list is checked before the first launch
+    if (!g[i] || n[i] < 1) return fail(-1, "gradclip_sumsq: bad tensor %d (null pointer or n < 1)", i);
+  for (int base = 0; base < count; base += icl::kGcMulti) {
+    icl::GcSumsqMulti t{};
+    const int k = count - base < icl::kGcMulti ? count - base : icl::kGcMulti;
+    for (int i = 0; i < k; ++i) {
+      t.g[i] = (const float*)g[base + i];
+      t.n[i] = (long)n[base + i];
+    }
+    ICL_LAUNCH(icl::gradclip_sumsq_multi_kernel, dim3(chunks, k), dim3(256), 0, (hipStream_t)stream, t, partial + (long)base * chunks);
+    const int rc = check_launch("gradclip_sumsq");
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int icl_gradclip_sumsq_factored(const float* g, const float* x, int rows, int n, int k, void* ws, double* partial, void* stream) {
+  if (!g || !x || !ws || !partial || rows < 1 || rows > kGcMaxRows || n < 1 || k < 1 || ((uintptr_t)ws & 7) || ((uintptr_t)partial & 7))
+    return fail(-1, "gradclip_sumsq_factored: bad argument (null pointer, rows outside 1..%d, n < 1, k < 1 or ws / partial not 8-byte aligned)",
+                kGcMaxRows);
+  const GcGramPlan p = gc_gram_plan(rows, n, k);
+  const int nslab = p.nslab_g > p.nslab_x ? p.nslab_g : p.nslab_x;
+  ICL_LAUNCH(icl::gradclip_gram_kernel, dim3(nslab, p.pairs, 2), dim3(256), 0, (hipStream_t)stream, g, x, rows, n, k, p.slab_g, p.slab_x,
+             p.nslab_g, p.nslab_x, (double*)ws);
+  int rc = check_launch("gradclip_sumsq_factored");
+  if (rc) return rc;
+  ICL_LAUNCH(icl::gradclip_gram_combine_kernel, dim3(icl_gradclip_factored_parts(rows)), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
+             rows, p.nslab_g, p.nslab_x, partial);
+  return check_launch("gradclip_sumsq_factored");
+}
+
+int icl_gradclip_finish(const double* partial, int64_t count, float max_norm, float* clip_dev, void* stream) {
+  if (!partial || !clip_dev || count < 1 || ((uintptr_t)partial & 7))
+    return fail(-1, "gradclip_finish: bad argument (null pointer, count < 1 or partial not 8-byte aligned)");
+  ICL_LAUNCH(icl::gradclip_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, (long)count, max_norm, clip_dev);
+  return check_launch("gradclip_finish");
+}
+
+int icl_gradclip_scale(void* const* dst, const void* const* src, const int64_t* n, int count, int chunks, const float* clip_dev,
+                       void* stream) {
+  if (!dst || !src || !n || !clip_dev || count < 1 || chunks < 1 || chunks > kGcMaxChunks)
+    return fail(-1, "gradclip_scale: bad argument (null pointer, count < 1 or chunks outside 1..%d)", kGcMaxChunks);
+  for (int i = 0; i < count; ++i)
+    if (!dst[i] || !src[i] || n[i] < 1) return fail(-1, "gradclip_scale: bad tensor %d (null pointer or n < 1)", i);
+  for (int base = 0; base < count; base += icl::kGcMulti) {
+    icl::GcScaleMulti t{};
+    const int k = count - base < icl::kGcMulti ? count - base : icl::kGcMulti;
+    for (int i = 0; i < k; ++i) {
+      t.dst[i] = (float*)dst[base + i];
+      t.src[i] = (const float*)src[base + i];
+      t.n[i] = (long)n[base + i];
+    }
+    ICL_LAUNCH(icl::gradclip_scale_multi_kernel, dim3(chunks, k), dim3(256), 0, (hipStream_t)stream, t, clip_dev);
+    const int rc = check_launch("gradclip_scale");
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 int64_t icl_gemm_ws_bytes(int64_t m, int n, int k, int batch) { return gemm_ws_bytes_impl((long)m, n, k, batch < 1 ? 1 : batch); }

@@ -70,6 +70,188 @@ def _load_no_hook():
     return _no_hook
 
 
+# ------------------------------------------------------------------------------------------------ gradient clipping by the global norm
+_FUSED_SGDS = weakref.WeakSet()      # every live FusedSGD (clip_grad_norm_: which parameters were already updated inside backward)
+_CLIP_ENTRIES = ("icl_gradclip_sumsq", "icl_gradclip_sumsq_factored", "icl_gradclip_finish", "icl_gradclip_scale")
+
+
+def _require_single_process(what: str):
+    try:
+        import torch.distributed as dist
+        many = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    except Exception:                # noqa: BLE001
+        many = False
+    if many:
+        raise ValueError(f"{what}: clipping by the global gradient norm is single-process — under a process group the norm would have to "
+                         "be taken after the gradient exchange (gathered factors), which is not implemented")
+
+
+def _clip_option(who: str, max_grad_norm):
+    """(max_grad_norm, last_grad_norm, buffers) of an optimiser's constructor."""
+    if max_grad_norm is None:
+        return None, None, None
+    max_grad_norm = float(max_grad_norm)
+    if not max_grad_norm > 0.0:
+        raise ValueError(f"{who}: max_grad_norm must be a positive number or None, not {max_grad_norm}")
+    _require_single_process(f"{who}(max_grad_norm=...)")
+    return max_grad_norm, None, _ClipBuffers()
+
+
+class _ClipBuffers:
+    """The persistent device memory of a clipping optimiser: ``clip_dev`` = {total_norm, coef} and the workspace of doubles.  Created
+    (and grown) by eager steps only: a captured step finds them in place."""
+
+    def __init__(self):
+        self.clip_dev, self.ws = None, None
+
+    def ensure(self, doubles: int, dev, capturing: bool):
+        if self.clip_dev is not None and self.clip_dev.device == dev and self.ws.numel() >= doubles:
+            return
+        if capturing:
+            raise RuntimeError("gradient clipping under stream capture: run one eager step first, it creates the buffers the captured "
+                               "kernels write (nothing is allocated during a capture)")
+        if self.clip_dev is None or self.clip_dev.device != dev:
+            self.clip_dev = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.ws = torch.empty(doubles, dtype=torch.float64, device=dev)
+
+
+def _clip_chunks(numel: int, cap: int) -> int:
+    """Workgroups per tensor of the sum-of-squares and scale launches: one per 1,024 elements (256 threads x float4), at most ``cap``."""
+    return max(1, min(cap, (numel + 1023) // 1024))
+
+
+@torch.no_grad()
+def _clip_gradients(params, max_norm: float, buf: _ClipBuffers, error_if_nonfinite: bool = False):
+    """The body of ``clip_grad_norm_``: measure dense and factored gradients together, scale both; returns total_norm (0-dim, device)."""
+    from . import ops
+    _require_single_process("clip_grad_norm_")
+    ids = {id(p) for p in params}
+    for sgd in list(_FUSED_SGDS):
+        if sgd._updated_in_backward & ids:
+            raise RuntimeError("clip_grad_norm_: a parameter's update already ran inside its backward pass in this iteration "
+                               "(FusedSGD update_in_backward): its gradient no longer exists and the others would be clipped by a partial "
+                               "norm.  Build the optimiser with max_grad_norm=... or update_in_backward=False")
+    L = _lib.lib()
+    dense, factored = [], []      # gradients; (parameter, g rows, x rows, whether the g rows are a tensor of this function's own)
+    for p in params:
+        g, fac = p.grad, getattr(p, "_icl_factors", None)
+        if g is None and not fac:
+            continue
+        if fac:
+            n, k = p.shape
+            if any(f[0].shape[1] != n or f[1].shape[1] != k or f[0].shape[0] != f[1].shape[0] for f in fac):
+                raise RuntimeError("clip_grad_norm_: factored gradient does not match its parameter")
+            if g is None and sum(f[0].shape[0] for f in fac) <= ADAMW_FACTORED_MAX_ROWS:
+                gf = fac[0][0] if len(fac) == 1 else torch.cat([f[0] for f in fac], 0)
+                xf = fac[0][1] if len(fac) == 1 else torch.cat([f[1] for f in fac], 0)
+                own = len(fac) > 1 or not gf.is_contiguous()
+                factored.append((p, gf.contiguous(), xf.contiguous(), own))
+                continue
+            # many factor rows, or a factored use AND a dense one: multiplied out (csrc/kernels/gemm.h) and treated as dense
+            for gf, xf in fac:
+                d = ops._tall_atb(gf, xf, False)[0]
+                g = d if g is None else g + d
+            p.grad = g
+            p._icl_factors = None
+        dense.append(g)
+    tensors = dense + [t for f in factored for t in f[1:3]]
+    if not tensors:
+        dev = params[0].device if params else torch.device("cpu")
+        return torch.zeros((), dtype=torch.float32, device=dev)
+    dev = tensors[0].device
+    for t in tensors:
+        if not (t.is_contiguous() and t.dtype == torch.float32 and t.layout == torch.strided and t.device == dev):
+            raise RuntimeError("clip_grad_norm_ needs contiguous fp32 gradients on one device")
+    if dev.type != "cuda" and not _lib.host_pointers_ok():
+        raise RuntimeError("clip_grad_norm_ needs device tensors (no CPU fallback)")
+    capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+    if error_if_nonfinite and capturing:
+        raise RuntimeError("clip_grad_norm_(error_if_nonfinite=True) reads the norm on the host and cannot be captured")
+    # plan: the slots of every partial sum, then the Gram scratch (reused by the factored weights one after the other)
+    small = [g for g in dense if g.numel() < _BIG]
+    big = [g for g in dense if g.numel() >= _BIG]
+    chunks_small = _clip_chunks(max((g.numel() for g in small), default=1), 64)
+    slots = len(small) * chunks_small + sum(_clip_chunks(g.numel(), 1024) for g in big)
+    slots += sum(L.icl_gradclip_factored_parts(f[1].shape[0]) for f in factored)
+    scratch = max((L.icl_gradclip_factored_ws_bytes(f[1].shape[0], f[1].shape[1], f[2].shape[1]) for f in factored), default=0)
+    if buf is None:
+        buf = _ClipBuffers()
+    buf.ensure(slots + (scratch + 7) // 8, dev, capturing)
+    partial, stream = buf.ws.data_ptr(), _lib.stream_of(dev)
+    scratch_ptr = partial + 8 * slots
+
+    def many(entry, lists, chunks, *tail):
+        n = len(lists[0])
+        arr = ctypes.c_void_p * n
+        ptrs = [arr(*[t.data_ptr() for t in ts]) for ts in lists]
+        _lib.check(getattr(L, entry)(*ptrs, (ctypes.c_int64 * n)(*[t.numel() for t in lists[0]]), n, chunks, *tail, stream), entry[4:])
+
+    at = 0
+    if small:
+        many("icl_gradclip_sumsq", [small], chunks_small, partial)
+        at += len(small) * chunks_small
+    for g in big:
+        c = _clip_chunks(g.numel(), 1024)
+        many("icl_gradclip_sumsq", [[g]], c, partial + 8 * at)
+        at += c
+    for p, gf, xf, own in factored:
+        rows = gf.shape[0]
+        _lib.check(L.icl_gradclip_sumsq_factored(gf.data_ptr(), xf.data_ptr(), rows, gf.shape[1], xf.shape[1], scratch_ptr, partial + 8 * at,
+                                                 stream), "gradclip_sumsq_factored")
+        at += L.icl_gradclip_factored_parts(rows)
+    assert at == slots
+    _lib.check(L.icl_gradclip_finish(partial, slots, max_norm, buf.clip_dev.data_ptr(), stream), "gradclip_finish")
+    total_norm = buf.clip_dev[0]
+    if error_if_nonfinite and not bool(torch.isfinite(total_norm)):
+        raise RuntimeError("The total norm of order 2.0 for gradients from `parameters` is non-finite, so it cannot be clipped. To disable "
+                           "this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+    # scale: dense gradients in place; factor rows g into a tensor of this function's own ((c g)^T x = c (g^T x)) — the factors may be
+    # saved activations, static capture buffers or shared between parameters and are never written
+    pairs = [(g, g) for g in dense]
+    for p, gf, xf, own in factored:
+        gs = gf if own else torch.empty_like(gf)
+        pairs.append((gs, gf))
+        p._icl_factors = [(gs, xf)]
+    small = [pr for pr in pairs if pr[0].numel() < _BIG]
+    if small:
+        many("icl_gradclip_scale", [[d for d, _ in small], [s_ for _, s_ in small]], _clip_chunks(max(d.numel() for d, _ in small), 64),
+             buf.clip_dev.data_ptr())
+    for d, s_ in pairs:
+        if d.numel() >= _BIG:
+            many("icl_gradclip_scale", [[d], [s_]], _clip_chunks(d.numel(), 1024), buf.clip_dev.data_ptr())
+    return total_norm
+
+
+def clip_grad_norm_(params_or_optimizer, max_norm, norm_type=2.0, error_if_nonfinite: bool = False):
+    """``torch.nn.utils.clip_grad_norm_`` for gradients that are partly FACTORED: between ``loss.backward()`` and ``optimizer.step()``,
+    with the parameters (an iterable or one tensor) or with the optimiser.  torch's function sees only ``.grad`` — here 3 % of the ICL
+    models: the token-axis matrices keep their gradient as factor pairs ``_icl_factors`` (G = sum g^T x) — and would measure and scale
+    only that.  This one measures dense gradients and factors together, the factors through their Gram matrices
+    (|g^T x|_F^2 = sum_rs (g_r . g_s)(x_r . x_s), in double: csrc/kernels/gradclip.h) without multiplying them out, and scales the dense
+    gradients in place and the g rows of the factors into a tensor of its own (``_icl_factors`` is rebound; the original factor
+    tensors are never written).  A weight with more than ``ADAMW_FACTORED_MAX_ROWS`` factor rows, or with a dense and a factored use, is
+    multiplied out first and treated as dense.  The gradients of an open step scope are completed first (lane joined, deferred bias
+    sums assigned).
+
+    Returns total_norm as a 0-dim fp32 device tensor; nothing is read on the host unless ``error_if_nonfinite`` (which raises as torch
+    does and cannot be captured).  Limits: the 2-norm only (``ValueError`` otherwise) and one process (``ValueError`` under a process
+    group of more than one rank).  ``RuntimeError`` if a parameter's update already ran inside backward in this iteration
+    (FusedSGD(update_in_backward=True)): a partial gradient is never clipped silently."""
+    if float(norm_type) != 2.0:
+        raise ValueError(f"clip_grad_norm_: only the 2-norm is implemented, not norm_type={norm_type}")
+    _require_single_process("clip_grad_norm_")
+    if isinstance(params_or_optimizer, torch.optim.Optimizer):
+        params = [p for group in params_or_optimizer.param_groups for p in group["params"]]
+    elif isinstance(params_or_optimizer, torch.Tensor):
+        params = [params_or_optimizer]
+    else:
+        params = list(params_or_optimizer)
+    scope = StepScope.current
+    if scope is not None:
+        scope.end_of_backward()
+    return _clip_gradients(params, float(max_norm), None, error_if_nonfinite)
+
+
 class FusedSGD(torch.optim.Optimizer):
     """``step_scope`` (default on): when the parameters belong to ONE icl_amd model built by ``net_factory_3d`` / ``net_factory``, the
     optimiser opens — from a forward pre-hook of that model, in training mode with gradients enabled — the step scope (``ops.StepScope``)
@@ -80,14 +262,24 @@ class FusedSGD(torch.optim.Optimizer):
     /root/reference/code/train_inherent_consistent_unet_3D_BraTS.py:103-115) then runs the fast path with the one-line optimiser swap of
     INTEGRATION.md §2.  Requirement it inherits from ``update_in_backward``: every ``loss.backward()`` of a training-mode forward is
     followed by ``optimizer.step()`` (the big matrices are updated inside their backward pass); pass ``update_in_backward=False`` for
-    loops that accumulate gradients over several backward passes, ``step_scope=False`` to get a plain fused optimiser."""
+    loops that accumulate gradients over several backward passes, ``step_scope=False`` to get a plain fused optimiser.
+
+    ``max_grad_norm`` (None, or a positive number; single process): ``step()`` first clips the global 2-norm of all gradients — dense and
+    factored, measured without multiplying the factors out (``clip_grad_norm_`` below) — and keeps the norm, a device scalar, in
+    ``last_grad_norm`` (a view of a persistent buffer that every step overwrites).  A clipped update needs the whole gradient before the
+    first weight moves, so the option forces ``update_in_backward`` off: no update inside backward, no deferred update, no narrow update
+    stream.  What that costs: one more read of the big token-axis matrices per step (their input gradient and their update each read the
+    matrix, 4 + 16 B per weight in two passes instead of 20 B in one).  Nothing is read on the host, so ``graph=True`` and
+    ``ICLTrainer.capture()`` work with it.  None takes the code path without clipping: no launches, no buffers."""
 
     def __init__(self, params, lr=0.01, momentum=0.9, weight_decay=0.0, step_scope: bool = True, update_in_backward: bool = True,
-                 graph: bool = False, graph_warmup: int = 3):
+                 graph: bool = False, graph_warmup: int = 3, max_grad_norm=None):
         if momentum <= 0:
             raise ValueError("FusedSGD implements the momentum form used by the ICL trainers")
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
-        self._scope_update_in_backward = bool(update_in_backward)
+        self.max_grad_norm, self.last_grad_norm, self._clip = _clip_option("FusedSGD", max_grad_norm)
+        self._scope_update_in_backward = bool(update_in_backward) and self.max_grad_norm is None
+        _FUSED_SGDS.add(self)           # clip_grad_norm_ asks every live FusedSGD which parameters it has already updated inside backward
         self._scope_packed = None
         # graph=True (round 5, needs the step scope): after `graph_warmup` eager training iterations the model's forward and backward
         # are captured into two hipGraphs (the step scope's bookkeeping inside them) and every later `model(x_lab, x_unlab)` /
@@ -138,6 +330,11 @@ class FusedSGD(torch.optim.Optimizer):
         self._deferred = []          # (parameter, g, x, event after the input-gradient kernel)
         self._update_stream = None
         self._update_stream_used = False
+
+    @property
+    def clip_dev(self):
+        """{total_norm, coef} of the last clipped step (device fp32, 2 elements); None without ``max_grad_norm`` or before the first step."""
+        return None if self._clip is None else self._clip.clip_dev
 
     def zero_grad(self, set_to_none: bool = True):
         for group in self.param_groups:
@@ -428,6 +625,8 @@ class FusedSGD(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         self._close_scope()                     # lane joined, deferred bias gradients assigned, packed weights released
+        if self.max_grad_norm is not None:
+            self.last_grad_norm = _clip_gradients([p for group in self.param_groups for p in group["params"]], self.max_grad_norm, self._clip)
         if self._graph_state is not None and self.lr_dev is not None and not (
                 self.lr_dev.is_cuda and torch.cuda.is_current_stream_capturing()):
             # graph mode: a batch whose shape the graphs do not match ran eagerly — its update must not read the learning rate the
@@ -721,9 +920,14 @@ class FusedAdamW(torch.optim.Optimizer):
     ``hyper_dev`` (None, or a device fp32 tensor of 3; hipGraph replay): the kernels read {decay, step_size, bc2_sqrt} from it.  One
     param group; every parameter updated in a step shares one ``step`` value.  ``write_device_hyper()`` stores the scalars of the NEXT
     update (outside any capture); a ``step()`` under stream capture launches the kernels without advancing the host's ``step``
-    counters, and ``advance_captured_step()`` advances them after every replay."""
+    counters, and ``advance_captured_step()`` advances them after every replay.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, step_scope: bool = True):
+    ``max_grad_norm`` (None, or a positive number; single process): ``step()`` first clips the global 2-norm of all gradients, dense and
+    factored (``clip_grad_norm_`` below), and keeps the norm, a device scalar, in ``last_grad_norm`` (a view of a persistent buffer that
+    every step overwrites).  The coefficient stays in device memory (``clip_dev``), so a captured step clips every replay by that
+    replay's own norm; the buffers are created by the first eager step.  None: no launches, no buffers."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, step_scope: bool = True, max_grad_norm=None):
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"FusedAdamW: invalid hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         # the group keys of this torch's own AdamW (amsgrad, maximize, foreach, capturable, ...) with its defaults, so that a
@@ -731,6 +935,7 @@ class FusedAdamW(torch.optim.Optimizer):
         defaults = dict(torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr, betas=tuple(betas), eps=eps,
                                           weight_decay=weight_decay).defaults)
         super().__init__(params, defaults)
+        self.max_grad_norm, self.last_grad_norm, self._clip = _clip_option("FusedAdamW", max_grad_norm)
         self.hyper_dev = None
         self._touched = None         # the parameters of the last step(): those a captured update touches (advance_captured_step)
         self._scope_packed = None
@@ -739,6 +944,11 @@ class FusedAdamW(torch.optim.Optimizer):
             if len(models) == 1:
                 (model,) = models.values()
                 model.register_forward_pre_hook(_ScopePreHook(self))
+
+    @property
+    def clip_dev(self):
+        """{total_norm, coef} of the last clipped step (device fp32, 2 elements); None without ``max_grad_norm`` or before the first step."""
+        return None if self._clip is None else self._clip.clip_dev
 
     def _clear_factors(self):
         for group in self.param_groups:
@@ -837,6 +1047,8 @@ class FusedAdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         self._close_scope()                     # lane joined, deferred bias gradients assigned, packed weights released
+        if self.max_grad_norm is not None:
+            self.last_grad_norm = _clip_gradients([p for group in self.param_groups for p in group["params"]], self.max_grad_norm, self._clip)
         work = []                               # (group, parameter, dense gradient or None, factors or None)
         for group in self.param_groups:
             if group.get("amsgrad") or group.get("maximize"):

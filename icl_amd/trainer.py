@@ -40,19 +40,24 @@ class ICLConfig:
     optimizer: str = "sgd"             # "adamw": icl_amd.optim.FusedAdamW, base_lr / weight_decay as given, same poly schedule (one process)
     betas: tuple = (0.9, 0.999)        # of "adamw"
     eps: float = 1e-8                  # of "adamw"
+    max_grad_norm: Optional[float] = None   # clip the global gradient 2-norm, dense and factored, before every update (one process); for
+                                            # "sgd" this also switches the update inside backward off; the step's result gains "grad_norm"
 
 
 class ICLTrainer:
     def __init__(self, model: torch.nn.Module, cfg: ICLConfig, ddp=None):
         self.model, self.cfg, self.ddp = model, cfg, ddp
+        if cfg.max_grad_norm is not None and ddp is not None and ddp.active:
+            raise ValueError("ICLConfig.max_grad_norm is single-process: the norm would have to be taken after the gradient exchange")
         if cfg.optimizer == "adamw":
             if ddp is not None and ddp.active:
                 raise ValueError("ICLConfig.optimizer='adamw' is single-process: FusedAdamW has no row-sharded or gathered-factor update")
             self.optimizer = FusedAdamW(model.parameters(), lr=cfg.base_lr, betas=cfg.betas, eps=cfg.eps, weight_decay=cfg.weight_decay,
-                                        step_scope=False)
+                                        step_scope=False, max_grad_norm=cfg.max_grad_norm)
         elif cfg.optimizer == "sgd":
             self.optimizer = FusedSGD(model.parameters(), lr=cfg.base_lr, momentum=cfg.momentum,
-                                      weight_decay=cfg.weight_decay, step_scope=False)      # this class opens the step scope itself
+                                      weight_decay=cfg.weight_decay, step_scope=False,      # this class opens the step scope itself
+                                      max_grad_norm=cfg.max_grad_norm)
         else:
             raise ValueError(f"ICLConfig.optimizer: 'sgd' or 'adamw', not {cfg.optimizer!r}")
         self.adamw = cfg.optimizer == "adamw"
@@ -124,7 +129,8 @@ class ICLTrainer:
         ddp = self.ddp if (self.ddp is not None and self.ddp.active) else None
         ops.StepRNG.begin_step()
         # without gradient exchange the factors of a layer are final when its backward runs: update there (FusedSGD.update_in_backward)
-        fuse = cfg.factored_mlp2_grads and cfg.update_in_backward and ddp is None and not self.adamw
+        # (a clipped update needs the whole gradient first: max_grad_norm keeps every update in step())
+        fuse = cfg.factored_mlp2_grads and cfg.update_in_backward and ddp is None and not self.adamw and cfg.max_grad_norm is None
         # leaving the block joins the lane and reduces what was deferred, one launch each — or drops it, if the step raised
         with ops.StepScope.open(self.packed, factored=cfg.factored_mlp2_grads, world=ddp.world if ddp is not None else 1,
                                 max_rows_gathered=ddp.max_rows_gathered if ddp is not None else None,
@@ -166,6 +172,8 @@ class ICLTrainer:
             self.ddp.finish_post_update()
         else:
             self._apply_update()
+        if self.cfg.max_grad_norm is not None:
+            parts["grad_norm"] = self.optimizer.last_grad_norm      # device scalar, overwritten by the next step
         return parts
 
     def _advance_lr(self):

@@ -707,6 +707,32 @@ int icl_adamw_step_factored(float* p, float* m, float* v, const float* g, const 
                             float step_size, float bc2_sqrt, float beta2, float omb1, float omb2, float eps, int first,
                             const float* hyper_dev, void* stream);
 
+/* ---- gradient clipping by the global 2-norm, torch.nn.utils.clip_grad_norm_ semantics (csrc/kernels/gradclip.h).  The norm is measured
+ * from dense gradients and from gradients that are still factored (G = g^T x) without multiplying them out:
+ *   |g^T x|_F^2 = sum_{r,s} (g_r . g_s)(x_r . x_s)
+ * Every square, product and sum is formed in double; every workgroup writes one double to a slot fixed by its index (no atomics, fixed
+ * summation order: two runs give the same bits).  The caller lays the partial sums of all its calls out in ONE array of doubles and
+ * finishes with icl_gradclip_finish; the scale kernels read the coefficient from device memory, so nothing returns to the host.
+ * Bad arguments return non-zero with icl_last_error() set and launch nothing.
+ *
+ * icl_gradclip_sumsq: `count` tensors (HOST arrays of device pointers and element counts, 48 per launch), `chunks` workgroups each
+ * (1 .. 4096): partial[i * chunks + c] = workgroup c's share of sum g_i^2; writes count * chunks doubles.  A pointer that is not
+ * 16-byte aligned takes a scalar path. */
+int icl_gradclip_sumsq(const void* const* g, const int64_t* n, int count, int chunks, double* partial, void* stream);
+/* g [rows, n], x [rows, k] (fp32, contiguous; 1 <= rows <= 1024, any n >= 1, k >= 1): partial Gram entries per slab of the long axes in
+ * `ws` (icl_gradclip_factored_ws_bytes bytes, 8-byte aligned), summed in slab order and combined to icl_gradclip_factored_parts(rows)
+ * doubles in `partial`, whose sum is |g^T x|_F^2. */
+int64_t icl_gradclip_factored_ws_bytes(int rows, int n, int k);
+int icl_gradclip_factored_parts(int rows);
+int icl_gradclip_sumsq_factored(const float* g, const float* x, int rows, int n, int k, void* ws, double* partial, void* stream);
+/* One workgroup: clip_dev[0] = total_norm = (float)sqrt(sum of partial[0 .. count)), rounded once; clip_dev[1] = coef =
+ * min(1, max_norm / (total_norm + 1e-6f)) evaluated in fp32 (torch's operations; a NaN norm gives a NaN coefficient, an infinite one 0). */
+int icl_gradclip_finish(const double* partial, int64_t count, float max_norm, float* clip_dev, void* stream);
+/* dst[i] = src[i] * clip_dev[1] for `count` tensors (48 per launch, `chunks` workgroups each), in place (dst == src) or out of place.
+ * In place with a coefficient of exactly 1 nothing is read or written. */
+int icl_gradclip_scale(void* const* dst, const void* const* src, const int64_t* n, int count, int chunks, const float* clip_dev,
+                       void* stream);
+
 /* ---- the aligner's QUERY chain as fused stages (round 6; csrc/kernels/qchain.h).  Replaces, per resolution level of
  * InherentConsistent, the operator-by-operator mirror of Class_Decoder's query half — norm1_query -> attn.fc_q -> [read-out of
  * softmax(QK^T)V: icl_attn_fwd / icl_attn_bwd_ws] -> attn.proj -> q + drop_path(q) -> norm2 -> mlp.fc1 -> GELU -> mlp.fc2 ->

@@ -1,11 +1,15 @@
-"""FusedSGD — torch.optim.SGD(momentum, weight_decay) semantics on one HIP pass per parameter.
+"""FusedSGD and FusedAdamW: the optimisers of the ICL trainers on one HIP pass per parameter, and ``clip_grad_norm_``.
 
-Counterpart of ``optim.SGD(model.parameters(), lr, momentum=0.9, weight_decay=1e-4)`` in the reference trainers
-(/root/reference/code/train_inherent_consistent_unet_3D_BraTS.py:85-86).  It is a ``torch.optim.Optimizer`` so the
-trainers' ``for g in optimizer.param_groups: g['lr'] = lr_`` schedule (:117-119) keeps working.  Parameters whose
-``.grad`` is None are skipped entirely — no weight decay, no momentum — exactly like torch.
+FusedSGD is the counterpart of ``optim.SGD(model.parameters(), lr, momentum=0.9, weight_decay=1e-4)`` in the reference trainers
+(/root/reference/code/train_inherent_consistent_unet_3D_BraTS.py:85-86).  It is a ``torch.optim.Optimizer`` so the trainers'
+``for g in optimizer.param_groups: g['lr'] = lr_`` schedule (:117-119) keeps working.  Parameters whose ``.grad`` is None are skipped
+entirely — no weight decay, no momentum — exactly like torch.  FusedAdamW is the same for ``torch.optim.AdamW``, the
+usual optimiser of the Swin families.
 
-FusedAdamW (at the end of the file) is the same for ``torch.optim.AdamW``, the usual optimiser of the Swin families.
+What they share is written once: ``_many_ranks`` (the single-process decision), ``_Gradient`` (what backward left on a parameter: dense
+gradient, factor pairs, their concatenation, shape check and multiply-out — WHEN to multiply out stays with each caller),
+``_launch_many`` (a multi-tensor launch) and ``_ScopedOptimizer`` (the base class: the step scope of the forward pre-hook,
+``max_grad_norm``, the head of ``step()``).  The graphed loop of FusedSGD(graph=True) lives in graphed_step.py.
 """
 from __future__ import annotations
 
@@ -22,6 +26,11 @@ from .step_scope import StepScope
 _BIG = 1 << 20
 SPLIT_MIN_ROWS = 192    # factor rows from which d = g^T x runs on split products (tools/sgd_probe.py, 13,824^2: 128 rows 769 -> 720 us
                         # but +2 small launches: a wash inside the step; 256 rows 1244 -> 1029 us, 512 rows 2158 -> 1770 us)
+ADAMW_FACTORED_MAX_ROWS = 160   # factor rows up to which the update runs from the factors (icl_adamw_step_factored: plain VALU products, 24 B
+                                # per weight); above, the factors are multiplied out (ops._tall_atb) and the dense kernel runs.  Measured at
+                                # 13,824^2 (tools/adamw_probe.py, profiles/adamw.md section 2), factored against multiplied out: 64 rows
+                                # 1056 / 1495 us, 128 rows 1499 / 1691 us, 192 rows 2042 / 1882 us, 256 rows 2538 / 2076 us — the lines
+                                # cross at ~163 rows (8.5 against 3.0 us per row between 128 and 192)
 
 
 _MODEL_OF = {}     # id(parameter) -> (weak reference to the parameter, weak reference to its model)
@@ -70,18 +79,81 @@ def _load_no_hook():
     return _no_hook
 
 
+def _many_ranks() -> bool:
+    """More than one rank in a live process group.  ``torch.distributed`` is looked up at every call."""
+    try:
+        import torch.distributed as dist
+        return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    except Exception:                # noqa: BLE001
+        return False
+
+
+# ------------------------------------------------------------------------------------------------ what backward left on a parameter
+class _Gradient:
+    """The gradient of one parameter as its backward pass left it: ``dense`` (``p.grad`` or None) and ``pairs`` (the factor pairs (g, x)
+    of ops.FactoredGrads, dW = sum g^T x; None when there are none), checked against the parameter's shape, with ``rows`` factor rows
+    in all.  ``who`` (FusedSGD, FusedAdamW, clip_grad_norm_) opens every refusal.  ``pairs`` may be handed in (FusedSGD's deferred
+    updates hold their factors themselves).  Built only for parameters that have factors: a step walks hundreds of dense ones."""
+    __slots__ = ("who", "p", "dense", "pairs", "rows")
+
+    def __init__(self, who: str, p, pairs=None):
+        self.who, self.p, self.dense = who, p, p.grad
+        self.pairs = pairs or getattr(p, "_icl_factors", None) or None
+        self.rows = 0
+        if self.pairs:
+            n, k = p.shape
+            if any(g.shape[1] != n or x.shape[1] != k or g.shape[0] != x.shape[0] for g, x in self.pairs):
+                raise RuntimeError(f"{who}: factored gradient does not match its parameter")
+            self.rows = sum(g.shape[0] for g, _ in self.pairs)
+
+    def concatenated(self):
+        """(g, x, own): all factor rows as two contiguous matrices; ``own`` if g is a tensor made here and not one of the pairs'."""
+        fac = self.pairs
+        g = fac[0][0] if len(fac) == 1 else torch.cat([f[0] for f in fac], 0)
+        x = fac[0][1] if len(fac) == 1 else torch.cat([f[1] for f in fac], 0)
+        own = len(fac) > 1 or not g.is_contiguous()
+        return g.contiguous(), x.contiguous(), own
+
+    def multiply_out(self):
+        """The factors multiplied out (csrc/kernels/gemm.h) and added to the dense gradient, which becomes ``p.grad``; returns it."""
+        from . import ops
+        g = self.dense
+        for gf, xf in self.pairs:
+            d = ops._tall_atb(gf, xf, False)[0]
+            g = d if g is None else g + d
+        self.p.grad = self.dense = g
+        self.drop_factors()
+        return g
+
+    def drop_factors(self):
+        self.p._icl_factors = self.pairs = None
+
+
+def _require_fp32(who: str, p, g):
+    if not (p.is_contiguous() and p.dtype == torch.float32 and (g is None or (g.is_contiguous() and g.dtype == torch.float32))):
+        raise RuntimeError(f"{who} needs contiguous fp32 parameters and gradients")
+
+
+def _require_device(who: str, dev):
+    if dev.type != "cuda" and not _lib.host_pointers_ok():
+        raise RuntimeError(f"{who} needs device tensors (no CPU fallback)")
+
+
+def _launch_many(entry: str, lists, *tail):
+    """One multi-tensor launch: a pointer array per list of tensors, the sizes of the first list, the count, ``tail`` (the stream last)."""
+    n = len(lists[0])
+    arr = ctypes.c_void_p * n
+    ptrs = [arr(*[t.data_ptr() for t in ts]) for ts in lists]
+    _lib.check(getattr(_lib.lib(), entry)(*ptrs, (ctypes.c_int64 * n)(*[t.numel() for t in lists[0]]), n, *tail), entry[4:])
+
+
 # ------------------------------------------------------------------------------------------------ gradient clipping by the global norm
 _FUSED_SGDS = weakref.WeakSet()      # every live FusedSGD (clip_grad_norm_: which parameters were already updated inside backward)
 _CLIP_ENTRIES = ("icl_gradclip_sumsq", "icl_gradclip_sumsq_factored", "icl_gradclip_finish", "icl_gradclip_scale")
 
 
 def _require_single_process(what: str):
-    try:
-        import torch.distributed as dist
-        many = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-    except Exception:                # noqa: BLE001
-        many = False
-    if many:
+    if _many_ranks():
         raise ValueError(f"{what}: clipping by the global gradient norm is single-process — under a process group the norm would have to "
                          "be taken after the gradient exchange (gathered factors), which is not implemented")
 
@@ -123,7 +195,6 @@ def _clip_chunks(numel: int, cap: int) -> int:
 @torch.no_grad()
 def _clip_gradients(params, max_norm: float, buf: _ClipBuffers, error_if_nonfinite: bool = False):
     """The body of ``clip_grad_norm_``: measure dense and factored gradients together, scale both; returns total_norm (0-dim, device)."""
-    from . import ops
     _require_single_process("clip_grad_norm_")
     ids = {id(p) for p in params}
     for sgd in list(_FUSED_SGDS):
@@ -134,26 +205,15 @@ def _clip_gradients(params, max_norm: float, buf: _ClipBuffers, error_if_nonfini
     L = _lib.lib()
     dense, factored = [], []      # gradients; (parameter, g rows, x rows, whether the g rows are a tensor of this function's own)
     for p in params:
-        g, fac = p.grad, getattr(p, "_icl_factors", None)
-        if g is None and not fac:
-            continue
-        if fac:
-            n, k = p.shape
-            if any(f[0].shape[1] != n or f[1].shape[1] != k or f[0].shape[0] != f[1].shape[0] for f in fac):
-                raise RuntimeError("clip_grad_norm_: factored gradient does not match its parameter")
-            if g is None and sum(f[0].shape[0] for f in fac) <= ADAMW_FACTORED_MAX_ROWS:
-                gf = fac[0][0] if len(fac) == 1 else torch.cat([f[0] for f in fac], 0)
-                xf = fac[0][1] if len(fac) == 1 else torch.cat([f[1] for f in fac], 0)
-                own = len(fac) > 1 or not gf.is_contiguous()
-                factored.append((p, gf.contiguous(), xf.contiguous(), own))
+        g = p.grad
+        if getattr(p, "_icl_factors", None):
+            gr = _Gradient("clip_grad_norm_", p)
+            if g is None and gr.rows <= ADAMW_FACTORED_MAX_ROWS:
+                factored.append((p, *gr.concatenated()))
                 continue
-            # many factor rows, or a factored use AND a dense one: multiplied out (csrc/kernels/gemm.h) and treated as dense
-            for gf, xf in fac:
-                d = ops._tall_atb(gf, xf, False)[0]
-                g = d if g is None else g + d
-            p.grad = g
-            p._icl_factors = None
-        dense.append(g)
+            g = gr.multiply_out()     # many factor rows, or a factored use AND a dense one: treated as dense
+        if g is not None:
+            dense.append(g)
     tensors = dense + [t for f in factored for t in f[1:3]]
     if not tensors:
         dev = params[0].device if params else torch.device("cpu")
@@ -162,8 +222,7 @@ def _clip_gradients(params, max_norm: float, buf: _ClipBuffers, error_if_nonfini
     for t in tensors:
         if not (t.is_contiguous() and t.dtype == torch.float32 and t.layout == torch.strided and t.device == dev):
             raise RuntimeError("clip_grad_norm_ needs contiguous fp32 gradients on one device")
-    if dev.type != "cuda" and not _lib.host_pointers_ok():
-        raise RuntimeError("clip_grad_norm_ needs device tensors (no CPU fallback)")
+    _require_device("clip_grad_norm_", dev)
     capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
     if error_if_nonfinite and capturing:
         raise RuntimeError("clip_grad_norm_(error_if_nonfinite=True) reads the norm on the host and cannot be captured")
@@ -179,20 +238,13 @@ def _clip_gradients(params, max_norm: float, buf: _ClipBuffers, error_if_nonfini
     buf.ensure(slots + (scratch + 7) // 8, dev, capturing)
     partial, stream = buf.ws.data_ptr(), _lib.stream_of(dev)
     scratch_ptr = partial + 8 * slots
-
-    def many(entry, lists, chunks, *tail):
-        n = len(lists[0])
-        arr = ctypes.c_void_p * n
-        ptrs = [arr(*[t.data_ptr() for t in ts]) for ts in lists]
-        _lib.check(getattr(L, entry)(*ptrs, (ctypes.c_int64 * n)(*[t.numel() for t in lists[0]]), n, chunks, *tail, stream), entry[4:])
-
     at = 0
     if small:
-        many("icl_gradclip_sumsq", [small], chunks_small, partial)
+        _launch_many("icl_gradclip_sumsq", [small], chunks_small, partial, stream)
         at += len(small) * chunks_small
     for g in big:
         c = _clip_chunks(g.numel(), 1024)
-        many("icl_gradclip_sumsq", [[g]], c, partial + 8 * at)
+        _launch_many("icl_gradclip_sumsq", [[g]], c, partial + 8 * at, stream)
         at += c
     for p, gf, xf, own in factored:
         rows = gf.shape[0]
@@ -214,11 +266,11 @@ def _clip_gradients(params, max_norm: float, buf: _ClipBuffers, error_if_nonfini
         p._icl_factors = [(gs, xf)]
     small = [pr for pr in pairs if pr[0].numel() < _BIG]
     if small:
-        many("icl_gradclip_scale", [[d for d, _ in small], [s_ for _, s_ in small]], _clip_chunks(max(d.numel() for d, _ in small), 64),
-             buf.clip_dev.data_ptr())
+        _launch_many("icl_gradclip_scale", [[d for d, _ in small], [s_ for _, s_ in small]], _clip_chunks(max(d.numel() for d, _ in small), 64),
+                     buf.clip_dev.data_ptr(), stream)
     for d, s_ in pairs:
         if d.numel() >= _BIG:
-            many("icl_gradclip_scale", [[d], [s_]], _clip_chunks(d.numel(), 1024), buf.clip_dev.data_ptr())
+            _launch_many("icl_gradclip_scale", [[d], [s_]], _clip_chunks(d.numel(), 1024), buf.clip_dev.data_ptr(), stream)
     return total_norm
 
 
@@ -252,7 +304,100 @@ def clip_grad_norm_(params_or_optimizer, max_norm, norm_type=2.0, error_if_nonfi
     return _clip_gradients(params, float(max_norm), None, error_if_nonfinite)
 
 
-class FusedSGD(torch.optim.Optimizer):
+# ------------------------------------------------------------------------------------------------ what FusedSGD and FusedAdamW share
+class _ScopedOptimizer(torch.optim.Optimizer):
+    """The base of FusedSGD and FusedAdamW: the step scope a forward pre-hook of the parameters' model opens and ``step()`` closes
+    (``step_scope.StepScope``: packed convolution weights, and on a single process the weight-gradient lane, deferred bias sums and
+    factored gradients), the ``max_grad_norm`` option, and the handling of ``_icl_factors``.  ``_who`` names the class in refusals."""
+    _who = None
+
+    def __init__(self, params, defaults, max_grad_norm):
+        super().__init__(params, defaults)
+        self.max_grad_norm, self.last_grad_norm, self._clip = _clip_option(self._who, max_grad_norm)
+        self._scope_packed = None
+
+    @property
+    def clip_dev(self):
+        """{total_norm, coef} of the last clipped step (device fp32, 2 elements); None without ``max_grad_norm`` or before the first step."""
+        return None if self._clip is None else self._clip.clip_dev
+
+    def _all_params(self):
+        return [p for group in self.param_groups for p in group["params"]]
+
+    def _clear_factors(self):
+        for p in self._all_params():
+            if getattr(p, "_icl_factors", None) is not None:
+                p._icl_factors = None
+
+    def zero_grad(self, set_to_none: bool = True):
+        self._clear_factors()
+        super().zero_grad(set_to_none=set_to_none)
+
+    def abandon_step(self):
+        """Discard what an iteration that will not reach ``step()`` left behind: factored gradients and the open step scope."""
+        self._clear_factors()
+        self._close_scope(flush=False)
+
+    def _attach_scope(self):
+        """Registers the pre-hook that opens the scope on the ONE model the parameters belong to (``tag_model_parameters``); returns that
+        model, or None (untagged parameters, or several models: a plain fused optimiser)."""
+        models = {id(m): m for m in (model_of(p) for p in self._all_params()) if m is not None}
+        if len(models) != 1:
+            return None
+        (model,) = models.values()
+        model.register_forward_pre_hook(_ScopePreHook(self))
+        return model
+
+    def _open_scope(self, module, fused_optimizer=None):
+        """``fused_optimizer``: what applies the update of the big token-axis matrices inside their backward pass (FusedSGD only)."""
+        from . import ops
+        if not module.training or not torch.is_grad_enabled():
+            return
+        scope = StepScope.current
+        if scope is not None and scope.owner() is not self:
+            return                       # somebody else (ICLTrainer) has a step open
+        if scope is not None:
+            # A second training forward before step() (ADVICE round 5): gradient accumulation over micro-batches, or several forward
+            # passes whose losses are summed before ONE backward.  The scope stays open — use counts, queued bias gradients and
+            # factored gradients keep accumulating, exactly as `.grad` does — and the packed weights are refreshed (one launch; the
+            # weights may have been touched between the calls).
+            self._second_forward()
+            scope.packed.begin_step()
+            return
+        if self._scope_packed is None:
+            self._scope_packed = ops.PackedWeights()
+        # single process: weight gradients of the deep levels on a lane, bias / LayerNorm gradients reduced by one launch — both
+        # completed when the backward pass ENDS (ops.BackwardEnd), so `.grad` is whole when loss.backward() returns — and factored
+        # gradients.  Multi-process (a data-parallel wrapper around the unchanged loop): dense `.grad` tensors that pass through
+        # autograd's own accumulation — a wrapper's accumulator hooks fire for every parameter and bucket nothing that another stream
+        # is still writing — so neither the lane nor the deferrals nor the factored gradients are opened; packed weights and the
+        # BatchNorm counters (forward-only) still are
+        single = not _many_ranks()
+        StepScope.open(self._scope_packed, owner=self, lane_open=single, deferrals=single, complete_at_backward_end=single,
+                       factored=True if single else None, fused_optimizer=fused_optimizer if single else None)
+
+    def _second_forward(self):
+        """Called before the open scope of this optimiser takes another training forward: the place to refuse it."""
+
+    def _close_scope(self, flush: bool = True):
+        scope = StepScope.current
+        if scope is not None and scope.owner() is self:
+            scope.close(flush)
+
+    def _begin_step(self, closure):
+        """The head of ``step()``: the closure, the scope closed (lane joined, deferred bias gradients assigned, packed weights
+        released), the gradients clipped if asked; returns the closure's loss."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._close_scope()
+        if self.max_grad_norm is not None:
+            self.last_grad_norm = _clip_gradients(self._all_params(), self.max_grad_norm, self._clip)
+        return loss
+
+
+class FusedSGD(_ScopedOptimizer):
     """``step_scope`` (default on): when the parameters belong to ONE icl_amd model built by ``net_factory_3d`` / ``net_factory``, the
     optimiser opens — from a forward pre-hook of that model, in training mode with gradients enabled — the step scope (``ops.StepScope``)
     that ``ICLTrainer`` opens around its iteration, and closes it in ``step()``: packed convolution weights (``ops.PackedWeights``), factored
@@ -265,39 +410,35 @@ class FusedSGD(torch.optim.Optimizer):
     loops that accumulate gradients over several backward passes, ``step_scope=False`` to get a plain fused optimiser.
 
     ``max_grad_norm`` (None, or a positive number; single process): ``step()`` first clips the global 2-norm of all gradients — dense and
-    factored, measured without multiplying the factors out (``clip_grad_norm_`` below) — and keeps the norm, a device scalar, in
+    factored, measured without multiplying the factors out (``clip_grad_norm_`` above) — and keeps the norm, a device scalar, in
     ``last_grad_norm`` (a view of a persistent buffer that every step overwrites).  A clipped update needs the whole gradient before the
     first weight moves, so the option forces ``update_in_backward`` off: no update inside backward, no deferred update, no narrow update
     stream.  What that costs: one more read of the big token-axis matrices per step (their input gradient and their update each read the
     matrix, 4 + 16 B per weight in two passes instead of 20 B in one).  Nothing is read on the host, so ``graph=True`` and
     ``ICLTrainer.capture()`` work with it.  None takes the code path without clipping: no launches, no buffers."""
+    _who = "FusedSGD"
 
     def __init__(self, params, lr=0.01, momentum=0.9, weight_decay=0.0, step_scope: bool = True, update_in_backward: bool = True,
                  graph: bool = False, graph_warmup: int = 3, max_grad_norm=None):
         if momentum <= 0:
             raise ValueError("FusedSGD implements the momentum form used by the ICL trainers")
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
-        self.max_grad_norm, self.last_grad_norm, self._clip = _clip_option("FusedSGD", max_grad_norm)
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay), max_grad_norm)
         self._scope_update_in_backward = bool(update_in_backward) and self.max_grad_norm is None
         _FUSED_SGDS.add(self)           # clip_grad_norm_ asks every live FusedSGD which parameters it has already updated inside backward
-        self._scope_packed = None
         # graph=True (round 5, needs the step scope): after `graph_warmup` eager training iterations the model's forward and backward
         # are captured into two hipGraphs (the step scope's bookkeeping inside them) and every later `model(x_lab, x_unlab)` /
         # `loss.backward()` of the UNCHANGED loop replays them; the losses, `optimizer.zero_grad()`, `optimizer.step()` and the
-        # `.item()` reads of the loop stay eager.  See _GraphedStep.
+        # `.item()` reads of the loop stay eager.  See graphed_step._GraphedStep.
         self._graph_on = bool(graph) and bool(step_scope)
         self._graph_warmup = max(int(graph_warmup), 1)
         self._graph_state = None
         self._graph_failed = None
         self._train_calls = 0
-        self._cap_stream = None      # the stream of every training forward before AND during the capture (see _install_graphed_forward)
-        if step_scope:
-            models = {id(m): m for m in (model_of(p) for g in self.param_groups for p in g["params"]) if m is not None}
-            if len(models) == 1:
-                (model,) = models.values()
-                model.register_forward_pre_hook(_ScopePreHook(self))
-                if self._graph_on:
-                    _install_graphed_forward(self, model)
+        self._cap_stream = None      # the stream of every training forward before AND during the capture (graphed_step._install_graphed_forward)
+        model = self._attach_scope() if step_scope else None
+        if model is not None and self._graph_on:
+            from .graphed_step import _install_graphed_forward
+            _install_graphed_forward(self, model)
         self.lr_dev = None   # optional device scalar read by the kernels instead of group['lr'] (hipGraph replay)
         self._groups = None  # id(parameter) -> its group (update_in_backward)
         self._updated_in_backward = set()   # ids of the parameters whose update of this step already ran inside backward
@@ -327,27 +468,26 @@ class FusedSGD(torch.optim.Optimizer):
         # dependent 5 us launches even a half-chip stream costs more (HBM latency under load) than the 0.58 ms head start returns
         self.update_early = os.environ.get("ICL_UPDATE_EARLY", "0") != "0"
         self._gate_event = None
-        self._deferred = []          # (parameter, g, x, event after the input-gradient kernel)
+        self._deferred = []          # (parameter, g, x, event after the input-gradient kernel, gate)
         self._update_stream = None
         self._update_stream_used = False
 
-    @property
-    def clip_dev(self):
-        """{total_norm, coef} of the last clipped step (device fp32, 2 elements); None without ``max_grad_norm`` or before the first step."""
-        return None if self._clip is None else self._clip.clip_dev
-
     def zero_grad(self, set_to_none: bool = True):
-        for group in self.param_groups:
-            for p in group["params"]:
-                if getattr(p, "_icl_factors", None) is not None:
-                    p._icl_factors = None
         # a step that was skipped or failed after its backward pass must not make the next one raise "updated twice"
         self._updated_in_backward.clear()
         if self._deferred or self._update_stream_used:
+            self._clear_factors()
             raise RuntimeError("FusedSGD.zero_grad(): updates queued by the previous backward pass were never applied; call step() "
                                "after every backward pass when update_placement is 'tail' (the default), 'gated' or 'free' — or "
                                "abandon_step() to discard what a failed iteration left behind")
         super().zero_grad(set_to_none=set_to_none)
+
+    def _forget_backward(self):
+        """Drops the Python-side traces of a backward pass: queued updates, the gate, the "updated inside backward" marks."""
+        self._deferred = []
+        self._gate_event = None
+        self._update_stream_used = False
+        self._updated_in_backward.clear()
 
     def abandon_step(self):
         """Discard what an iteration that will not reach ``step()`` left behind (an exception between backward and step, a skipped
@@ -356,86 +496,46 @@ class FusedSGD(torch.optim.Optimizer):
         (placement 'fused') keep it: that pass cannot be undone.  ICLTrainer calls this when its step raises."""
         if self._update_stream is not None and self._update_stream_used:
             torch.cuda.current_stream(self._update_stream.device).wait_stream(self._update_stream)
-        self._deferred = []
-        self._gate_event = None
-        self._update_stream_used = False
-        self._updated_in_backward.clear()
-        for group in self.param_groups:
-            for p in group["params"]:
-                if getattr(p, "_icl_factors", None) is not None:
-                    p._icl_factors = None
-        self._close_scope(flush=False)
+        self._forget_backward()
+        super().abandon_step()
 
     # ---- step scope (see the class docstring; the state itself is an ops.StepScope)
     def _open_scope(self, module, capturing: bool = False):
-        from . import ops
-        if not module.training or not torch.is_grad_enabled():
-            return
         if self._graph_state is not None and not capturing:
             return                       # the captured graphs carry the scope's work; nothing runs eagerly
-        scope = StepScope.current
-        if scope is not None and scope.owner() is not self:
-            return                       # somebody else (ICLTrainer) has a step open
-        if scope is not None:
-            # A second training forward before step() (ADVICE round 5): gradient accumulation over micro-batches, or several forward
-            # passes whose losses are summed before ONE backward.  The scope stays open — use counts, queued bias gradients and
-            # factored gradients keep accumulating, exactly as `.grad` does — and the packed weights are refreshed (one launch; the
-            # weights may have been touched between the calls).  The one thing that cannot continue: a backward pass that has already
-            # applied this step's update of the big matrices (update_in_backward) followed by another forward without step().
-            if self._updated_in_backward or self._deferred or self._update_stream_used:
-                raise RuntimeError(
-                    "FusedSGD: a training forward pass started after a backward pass that already applied this step's update of the "
-                    "token-axis matrices (update_in_backward=True) and before optimizer.step(): the second micro-batch would see "
-                    "half-updated weights.  Call optimizer.step() after every loss.backward(), or build the optimiser with "
-                    "update_in_backward=False for loops that accumulate gradients over several backward passes (or abandon_step() "
-                    "to discard a failed iteration)")
-            scope.packed.begin_step()
-            return
-        if self._scope_packed is None:
-            self._scope_packed = ops.PackedWeights()
-        try:
-            import torch.distributed as dist
-            single = not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
-        except Exception:                # noqa: BLE001
-            single = True
-        # single process: weight gradients of the deep levels on a lane, bias / LayerNorm gradients reduced by one launch — both
-        # completed when the backward pass ENDS (ops.BackwardEnd), so `.grad` is whole when loss.backward() returns — and factored
-        # gradients.  Multi-process (a data-parallel wrapper around the unchanged loop): dense `.grad` tensors that pass through
-        # autograd's own accumulation — a wrapper's accumulator hooks fire for every parameter and bucket nothing that another stream
-        # is still writing — so neither the lane nor the deferrals nor the factored gradients are opened; packed weights and the
-        # BatchNorm counters (forward-only) still are
-        StepScope.open(self._scope_packed, owner=self, lane_open=single, deferrals=single, complete_at_backward_end=single,
-                       factored=True if single else None,
-                       fused_optimizer=weakref.proxy(self) if (single and self._scope_update_in_backward) else None)
+        super()._open_scope(module, weakref.proxy(self) if self._scope_update_in_backward else None)
 
-    def _close_scope(self, flush: bool = True):
-        scope = StepScope.current
-        if scope is not None and scope.owner() is self:
-            scope.close(flush)
+    def _second_forward(self):
+        # The one thing that cannot continue: a backward pass that has already applied this step's update of the big matrices
+        # (update_in_backward) followed by another forward without step().
+        if self._updated_in_backward or self._deferred or self._update_stream_used:
+            raise RuntimeError(
+                "FusedSGD: a training forward pass started after a backward pass that already applied this step's update of the "
+                "token-axis matrices (update_in_backward=True) and before optimizer.step(): the second micro-batch would see "
+                "half-updated weights.  Call optimizer.step() after every loss.backward(), or build the optimiser with "
+                "update_in_backward=False for loops that accumulate gradients over several backward passes (or abandon_step() "
+                "to discard a failed iteration)")
 
-    def _step_factored(self, L, p, factors, lr, mom, wd, narrow: int = 0):
-        """dW = sum over entries of g^T x, applied without forming it (ops.FactoredGrads, csrc/kernels/optim.h)."""
-        g = factors[0][0] if len(factors) == 1 else torch.cat([f[0] for f in factors], 0)
-        x = factors[0][1] if len(factors) == 1 else torch.cat([f[1] for f in factors], 0)
+    def _step_factored(self, gr: _Gradient, group, narrow: int = 0):
+        """dW = sum over entries of g^T x, applied without forming it (ops.FactoredGrads, csrc/kernels/optim.h).  Never multiplied out
+        by row count: from SPLIT_MIN_ROWS the split kernel keeps the update an HBM stream."""
+        L, p = _lib.lib(), gr.p
+        lr, mom, wd = float(group["lr"]), float(group["momentum"]), float(group["weight_decay"])
+        g, x, _ = gr.concatenated()
         n, k = p.shape
-        if g.shape[1] != n or x.shape[1] != k or g.shape[0] != x.shape[0] or not p.is_contiguous():
+        if not p.is_contiguous():
             raise RuntimeError("FusedSGD: factored gradient does not match its parameter")
-        if not p.is_cuda and not _lib.host_pointers_ok():
-            raise RuntimeError("FusedSGD needs device tensors (no CPU fallback)")
+        _require_device("FusedSGD", p.device)
         st = self.state[p]
         shard = getattr(p, "_icl_shard", None)
         p._icl_shard = None      # the decision belongs to THIS step's factors (ddp.GradientReducer.rebind sets it per step)
-        first = 0
-        if "momentum_buffer" not in st:
-            # row-sharded: the other ranks' rows are never written here, so they must be zeros, not uninitialised memory
-            st["momentum_buffer"] = torch.zeros_like(p) if shard is not None else torch.empty_like(p)
-            first = 1
-        elif st.get("momentum_shard") != shard and st.get("momentum_shard") is not None:
+        # row-sharded: the other ranks' rows are never written here, so they must be zeros, not uninitialised memory
+        m, first = self._momentum(p, zeros=shard is not None)
+        if st.get("momentum_shard") != shard and st.get("momentum_shard") is not None:
             self._gather_momentum(p)      # the shard decision flipped: make every row of the buffer valid first
-        m = st["momentum_buffer"]
         if shard is not None:
             st["momentum_shard"] = tuple(shard)      # only rows [r N/W, (r+1) N/W) of the buffer are this parameter's momentum
-        stream = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream) if p.is_cuda else None
+        stream = _lib.stream_of(p.device)
         lrp = self.lr_dev.data_ptr() if self.lr_dev is not None else None
         pv, mv = p, m
         if shard is not None:
@@ -443,11 +543,10 @@ class FusedSGD(torch.optim.Optimizer):
             # 1/W of the MFMA-bound rank-(M W) product — and the ranks all-gather the updated rows afterwards (post_update)
             rank, world = shard
             r0, r1 = rank * (n // world), (rank + 1) * (n // world)
-            pv, mv, g = p[r0:r1], m[r0:r1], g[:, r0:r1]
+            pv, mv, g = p[r0:r1], m[r0:r1], g[:, r0:r1].contiguous()
             n = r1 - r0
-        g, x = g.contiguous(), x.contiguous()
         from . import ops   # KernelTimer bracket: the update streams p and m in and out (16 B per weight), HBM-bound
-        rows = g.shape[0]
+        rows = gr.rows
         with ops._timed("sgd_factored_kernel", 2.0 * rows * n * k, 16.0 * n * k, p):
             if narrow and shard is None and pv.is_contiguous():
                 rc = L.icl_sgd_step_factored_narrow(pv.data_ptr(), mv.data_ptr(), g.data_ptr(), x.data_ptr(), rows, n, k, lr, mom, wd, first,
@@ -465,6 +564,14 @@ class FusedSGD(torch.optim.Optimizer):
             else:
                 _lib.check(L.icl_sgd_step_factored(pv.data_ptr(), mv.data_ptr(), g.data_ptr(), x.data_ptr(), rows, n, k, lr, mom, wd,
                                                    first, lrp, stream), "sgd_step_factored")
+
+    def _momentum(self, p, zeros: bool = False):
+        """(the momentum buffer of p, 1 if this call created it — the kernels then write it without reading it — else 0)."""
+        st = self.state[p]
+        first = int("momentum_buffer" not in st)
+        if first:
+            st["momentum_buffer"] = torch.zeros_like(p) if zeros else torch.empty_like(p)
+        return st["momentum_buffer"], first
 
     def _gather_momentum(self, p):
         """Row-sharded data-parallel updates (ddp.GradientReducer, `_icl_shard`) keep only this rank's rows of the momentum buffer
@@ -487,10 +594,9 @@ class FusedSGD(torch.optim.Optimizer):
 
     def consolidate_momentum(self):
         """Collective: completes every row-sharded momentum buffer (all ranks call it together)."""
-        for group in self.param_groups:
-            for p in group["params"]:
-                if self.state.get(p, {}).get("momentum_shard") is not None:
-                    self._gather_momentum(p)
+        for p in self._all_params():
+            if self.state.get(p, {}).get("momentum_shard") is not None:
+                self._gather_momentum(p)
 
     def state_dict(self):
         """LOCAL, like torch.optim.Optimizer.state_dict (the usual `if rank == 0: torch.save(opt.state_dict())` must not deadlock).
@@ -539,19 +645,13 @@ class FusedSGD(torch.optim.Optimizer):
         lr, mom, wd = float(group["lr"]), float(group["momentum"]), float(group["weight_decay"])
         n, k = p.shape
         rows = g.shape[0]
-        st = self.state[p]
-        first = 0
-        if "momentum_buffer" not in st:
-            st["momentum_buffer"] = torch.empty_like(p)
-            first = 1
-        m = st["momentum_buffer"]
+        m, first = self._momentum(p)
         gx = torch.empty((rows, k), dtype=torch.float32, device=g.device)
         ws = ops._ws(L.icl_linear_ws_bytes(rows, k, n, 3), g)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream) if p.is_cuda else None
         lrp = self.lr_dev.data_ptr() if self.lr_dev is not None else None
         with ops._timed("linear_dgrad_sgd_kernel", 4.0 * rows * n * k, 16.0 * n * k, p):
             _lib.check(L.icl_linear_dgrad_sgd(g.data_ptr(), x.data_ptr(), p.data_ptr(), m.data_ptr(), gx.data_ptr(), ws.data_ptr(), rows, k, n,
-                                              lr, mom, wd, first, lrp, stream), "linear_dgrad_sgd")
+                                              lr, mom, wd, first, lrp, _lib.stream_of(p.device)), "linear_dgrad_sgd")
         # the kernel wrote the weight through its raw pointer: tell autograd, so that any other node of this graph that saved the
         # weight (a second use that the use count missed: F.linear, a tied weight, a hook) raises instead of differentiating
         # through the already-updated matrix
@@ -579,7 +679,6 @@ class FusedSGD(torch.optim.Optimizer):
         if not todo:
             return
         self._deferred = [e for e in self._deferred if not (only is None or e[4] == only)]
-        L = _lib.lib()
         dev = todo[0][0].device
         if self._update_stream is None:
             # (stream priorities measured without effect on this step: profiles/r4_schedule_experiments.txt)
@@ -593,9 +692,7 @@ class FusedSGD(torch.optim.Optimizer):
             s.wait_event(ev)
         with torch.cuda.stream(s):
             for p, g, x, ev, where in todo:
-                group = self._group_of()[id(p)]
-                self._step_factored(L, p, [(g, x)], float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]),
-                                    narrow=self.update_wgs if where == "deep" else 0)
+                self._step_factored(_Gradient("FusedSGD", p, [(g, x)]), self._group_of()[id(p)], narrow=self.update_wgs if where == "deep" else 0)
                 g.record_stream(s)
                 x.record_stream(s)
         self._update_stream_used = True
@@ -605,28 +702,20 @@ class FusedSGD(torch.optim.Optimizer):
         """The factored update of the given parameters only, now; ``step()`` afterwards finds nothing left to do for them.  Used by the
         data-parallel step for the ROW-SHARDED matrices: their updates run first so that the all-gather of the updated rows
         (ddp.GradientReducer.post_update) travels over xGMI while ``step()`` updates everything else."""
-        L = _lib.lib()
         groups = self._group_of()
         for p in params:
-            fac = getattr(p, "_icl_factors", None)
-            if not fac:
+            gr = _Gradient("FusedSGD", p)
+            if not gr.pairs:
                 continue
-            if p.grad is not None or id(p) in self._updated_in_backward:
+            if gr.dense is not None or id(p) in self._updated_in_backward:
                 continue              # a mixed / already applied gradient: left to step(), which knows how to merge or refuse it
-            group = groups[id(p)]
-            self._step_factored(L, p, fac, float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]))
-            p._icl_factors = None
+            self._step_factored(gr, groups[id(p)])
+            gr.drop_factors()
 
     @torch.no_grad()
     def step(self, closure=None):
         L = _lib.lib()
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._close_scope()                     # lane joined, deferred bias gradients assigned, packed weights released
-        if self.max_grad_norm is not None:
-            self.last_grad_norm = _clip_gradients([p for group in self.param_groups for p in group["params"]], self.max_grad_norm, self._clip)
+        loss = self._begin_step(closure)
         if self._graph_state is not None and self.lr_dev is not None and not (
                 self.lr_dev.is_cuda and torch.cuda.is_current_stream_capturing()):
             # graph mode: a batch whose shape the graphs do not match ran eagerly — its update must not read the learning rate the
@@ -637,263 +726,44 @@ class FusedSGD(torch.optim.Optimizer):
         if self._update_stream_used:
             torch.cuda.current_stream(self._update_stream.device).wait_stream(self._update_stream)
             self._update_stream_used = False
+        lrp = self.lr_dev.data_ptr() if self.lr_dev is not None else None
         for group in self.param_groups:
             lr, mom, wd = float(group["lr"]), float(group["momentum"]), float(group["weight_decay"])
-            small = {0: [], 1: []}
+            small = {0: ([], [], []), 1: ([], [], [])}      # first -> (parameters, gradients, momentum buffers) of one multi-tensor launch
             for p in group["params"]:
                 g = p.grad
-                fac = getattr(p, "_icl_factors", None)
-                if id(p) in self._updated_in_backward and (g is not None or fac):
+                gr = _Gradient("FusedSGD", p) if getattr(p, "_icl_factors", None) else None
+                if id(p) in self._updated_in_backward and (g is not None or gr is not None):
                     raise RuntimeError("FusedSGD: a parameter that was updated inside its backward pass (update_in_backward) also "
                                        "received a gradient from another use in the same step; this step's update would be applied "
                                        "twice.  Turn ICLConfig.update_in_backward off for models that reuse such a weight")
-                if fac and g is not None:
-                    # a weight with a factored use AND a dense one in the same step (ops.linear with few rows and with many): the
-                    # factors are multiplied out into the dense gradient (csrc/kernels/gemm.h) and the ordinary update runs
-                    from . import ops
-                    for gf, xf in fac:
-                        g = g + ops._tall_atb(gf, xf, False)[0]
-                    p.grad = g
-                    p._icl_factors = fac = None
-                if fac:
-                    self._step_factored(L, p, fac, lr, mom, wd)
-                    p._icl_factors = None
+                if gr is not None and g is None:
+                    self._step_factored(gr, group)
+                    gr.drop_factors()
                     continue
+                if gr is not None:
+                    # a weight with a factored use AND a dense one in the same step (ops.linear with few rows and with many): the
+                    # factors are multiplied out into the dense gradient and the ordinary update runs
+                    g = gr.multiply_out()
                 if g is None:
                     continue
-                if not (p.is_contiguous() and g.is_contiguous() and p.dtype == torch.float32):
-                    raise RuntimeError("FusedSGD needs contiguous fp32 parameters and gradients")
-                if not p.is_cuda and not _lib.host_pointers_ok():
-                    raise RuntimeError("FusedSGD needs device tensors (no CPU fallback)")
-                st = self.state[p]
-                first = 0
-                if "momentum_buffer" not in st:
-                    st["momentum_buffer"] = torch.empty_like(p)
-                    first = 1
-                m = st["momentum_buffer"]
+                _require_fp32("FusedSGD", p, g)
+                _require_device("FusedSGD", p.device)
+                m, first = self._momentum(p)
                 if p.numel() >= _BIG:
-                    stream = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream) if p.is_cuda else None
-                    lrp = self.lr_dev.data_ptr() if self.lr_dev is not None else None
-                    _lib.check(L.icl_sgd_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), p.numel(), lr, mom, wd, first, lrp, stream),
-                               "sgd_step")
+                    _lib.check(L.icl_sgd_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), p.numel(), lr, mom, wd, first, lrp,
+                                              _lib.stream_of(p.device)), "sgd_step")
                 else:
-                    small[first].append((p, g, m))
-            for first, items in small.items():
-                if not items:
-                    continue
-                n = len(items)
-                arr = ctypes.c_void_p * n
-                P_ = arr(*[it[0].data_ptr() for it in items])
-                G_ = arr(*[it[1].data_ptr() for it in items])
-                M_ = arr(*[it[2].data_ptr() for it in items])
-                N_ = (ctypes.c_int64 * n)(*[it[0].numel() for it in items])
-                p0 = items[0][0]
-                stream = ctypes.c_void_p(torch.cuda.current_stream(p0.device).cuda_stream) if p0.is_cuda else None
-                lrp = self.lr_dev.data_ptr() if self.lr_dev is not None else None
-                _lib.check(L.icl_sgd_step_multi(P_, G_, M_, N_, n, lr, mom, wd, first, lrp, stream), "sgd_step_multi")
+                    for ts, t in zip(small[first], (p, g, m)):
+                        ts.append(t)
+            for first, lists in small.items():
+                if lists[0]:
+                    _launch_many("icl_sgd_step_multi", lists, lr, mom, wd, first, lrp, _lib.stream_of(lists[0][0].device))
         self._updated_in_backward.clear()
         return loss
 
 
-# ------------------------------------------------------------------------------------------------ graphed forward / backward of the unchanged loop
-def _flatten_outputs(out):
-    """(tensors, rebuild): the tensors of a nested tuple / list output in order, and a function that rebuilds the structure."""
-    flat = []
-
-    def walk(o):
-        if isinstance(o, torch.Tensor):
-            flat.append(o)
-            return ("t", len(flat) - 1)
-        if isinstance(o, (list, tuple)):
-            return ("l" if isinstance(o, list) else "u", [walk(v) for v in o])
-        return ("c", o)
-
-    spec = walk(out)
-
-    def rebuild(ts, node=spec):
-        kind, v = node
-        if kind == "t":
-            return ts[v]
-        if kind == "c":
-            return v
-        seq = [rebuild(ts, n) for n in v]
-        return seq if kind == "l" else tuple(seq)
-
-    return flat, rebuild
-
-
-class _GraphedFn(torch.autograd.Function):
-    """Connects the replayed forward graph's static outputs to autograd: backward copies the incoming gradients into the static
-    gradient buffers, replays the backward graph and re-binds the parameters' (static) gradients and factored gradients — the loop's
-    `optimizer.zero_grad()` between forward and backward has dropped the references, the buffers themselves belong to the graphs."""
-
-    @staticmethod
-    def forward(ctx, state, anchor, *outs):
-        ctx.state = state
-        ctx.set_materialize_grads(False)
-        return tuple(o.detach() for o in outs)
-
-    @staticmethod
-    def backward(ctx, *gs):
-        st = ctx.state
-        with torch.no_grad():
-            for buf, g in zip(st.gouts, gs):
-                if g is None:
-                    buf.zero_()
-                else:
-                    buf.copy_(g)
-            opt = st.opt()
-            opt.lr_dev.fill_(float(opt.param_groups[0]["lr"]))
-            st.gb.replay()
-            for p, g in st.grads:
-                p.grad = g
-            for p, f in st.factors:
-                p._icl_factors = list(f)
-        return (None, None) + (None,) * len(gs)
-
-
-class _GraphedStep:
-    """Forward and backward of ONE icl_amd model as two hipGraphs, driven by the unchanged reference loop (FusedSGD(graph=True)).
-
-    Capture (at the first training forward after the warm-up iterations, on the tensors of that call): graph F = the step scope's opening
-    (all convolution weights packed and split in one launch each, dropout counter) + `model.forward`; graph B = `torch.autograd.backward`
-    of the outputs against static gradient buffers + the scope's closing (lane join, BatchNorm counters, deferred bias gradients) + the
-    join of FusedSGD's update stream.  The big token-axis matrices are updated INSIDE graph B (update_in_backward), everything else by the
-    loop's own eager `optimizer.step()` from gradients that live in the graphs' memory pool.  Two graphs, not one, because forked streams
-    that wait on each other in both directions crash hipStreamEndCapture on ROCm 7.2 (trainer.ICLTrainer.capture)."""
-
-    def __init__(self, opt, module, orig_forward, args):
-        from . import ops
-        self.opt = weakref.ref(opt)
-        dev = args[0].device
-        opt._close_scope(flush=False)           # the pre-hook opened an eager scope for this call: the captured one replaces it
-        params = [p for g in opt.param_groups for p in g["params"]]
-        for p in params:
-            p.grad = None
-            if getattr(p, "_icl_factors", None) is not None:
-                p._icl_factors = None
-        torch.cuda.synchronize(dev)
-        if ops.StepRNG.tensor is None or ops.StepRNG.tensor.device != dev:
-            ops.StepRNG.enable(dev)
-        if opt.lr_dev is None:
-            opt.lr_dev = torch.full((1,), float(opt.param_groups[0]["lr"]), dtype=torch.float32, device=dev)
-        self.static_in = [a.detach().clone() for a in args]
-        self.shapes = [tuple(a.shape) for a in args]
-        pool = torch.cuda.graph_pool_handle()
-        self.gf, self.gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.gf, pool=pool, stream=opt._cap_stream):
-            ops.StepRNG.begin_step()
-            opt._open_scope(module, capturing=True)
-            out = orig_forward(*self.static_in)
-        flat, self.rebuild = _flatten_outputs(out)
-        if not flat or not all(t.requires_grad for t in flat):
-            raise RuntimeError("graphed step: every output of the training forward is expected to require grad")
-        self.outs = flat
-        self.souts = [t.detach() for t in flat]      # the static output buffers, cut loose from the autograd graph of the capture
-        self.gouts = [torch.zeros_like(t) for t in flat]
-        with torch.cuda.graph(self.gb, pool=pool, stream=opt._cap_stream):
-            torch.autograd.backward(flat, self.gouts)
-            opt._close_scope()
-            opt.flush_deferred(gate=True)
-            if opt._update_stream_used:
-                torch.cuda.current_stream(dev).wait_stream(opt._update_stream)
-            ops.StepRNG.end_step()
-        # nothing of the capture has run: forget the Python-side traces of a backward pass that never executed
-        opt._deferred = []
-        opt._gate_event = None
-        opt._update_stream_used = False
-        opt._updated_in_backward.clear()
-        self.grads = [(p, p.grad) for p in params if p.grad is not None]
-        self.factors = [(p, list(p._icl_factors)) for p in params if getattr(p, "_icl_factors", None)]
-        self.anchor = next(p for p in params if p.requires_grad)
-        self.outs = None      # (drops the autograd graph of the capture: its kernels live in the hipGraphs, its buffers in their pool)
-        for p in params:
-            p.grad = None
-            if getattr(p, "_icl_factors", None) is not None:
-                p._icl_factors = None
-
-    def matches(self, args) -> bool:
-        return len(args) == len(self.shapes) and all(isinstance(a, torch.Tensor) and tuple(a.shape) == s for a, s in zip(args, self.shapes))
-
-    def run(self, args):
-        with torch.no_grad():
-            for buf, a in zip(self.static_in, args):
-                if a.data_ptr() != buf.data_ptr():
-                    buf.copy_(a)
-        self.gf.replay()
-        outs = _GraphedFn.apply(self, self.anchor, *self.souts)
-        return self.rebuild(list(outs))
-
-
-def _install_graphed_forward(opt, model):
-    """Instance-level `forward` of the model: eager for inference / evaluation / the warm-up iterations, graph replay afterwards."""
-    orig = model.forward
-    me = weakref.ref(opt)
-
-    def forward(*args, **kwargs):
-        o = me()
-        train = (o is not None and o._graph_on and o._graph_failed is None and model.training and torch.is_grad_enabled() and not kwargs
-                 and len(args) == 2 and all(isinstance(a, torch.Tensor) and a.is_cuda for a in args))
-        if not train:
-            return orig(*args, **kwargs)
-        st = o._graph_state
-        if st is None:
-            o._train_calls += 1
-            dev = args[0].device
-            if o._cap_stream is None:
-                o._cap_stream = torch.cuda.Stream(device=dev)
-            if o._train_calls <= o._graph_warmup:
-                # Eager iterations (allocator warm-up, momentum buffers, one-time kernel attributes) — on the stream the capture will
-                # use.  A parameter's AccumulateGrad node keeps the stream of the forward pass that created it, and the loop's own
-                # variables (`outputs`, `loss` of the previous iteration) keep that node alive into the next forward: created on the
-                # default stream it would run there during the capture of the backward graph, which hipStreamEndCapture does not survive.
-                cur = torch.cuda.current_stream(dev)
-                o._cap_stream.wait_stream(cur)
-                with torch.cuda.stream(o._cap_stream):
-                    out = orig(*args)
-                cur.wait_stream(o._cap_stream)
-                for t in _flatten_outputs(out)[0]:
-                    t.record_stream(cur)
-                return out
-            try:
-                st = _GraphedStep(o, model, orig, args)
-            except Exception as e:          # noqa: BLE001 — a model that cannot be captured keeps training eagerly
-                o._graph_failed = repr(e)
-                o._graph_state = None
-                import warnings
-                warnings.warn(f"FusedSGD(graph=True): capture failed, staying eager: {e!r}")
-                # nothing of the aborted capture has run: drop every Python-side trace of it (queued updates, "updated in backward"
-                # marks, gradients and factors that point into the failed capture's pool, the device learning rate the captured
-                # kernels would have read) before the eager scope reopens — the loop's next zero_grad() / step() must find a clean
-                # optimiser (ADVICE round 5)
-                o._deferred = []
-                o._update_stream_used = False
-                o._updated_in_backward.clear()
-                o._close_scope(flush=False)
-                for g_ in o.param_groups:
-                    for p_ in g_["params"]:
-                        p_.grad = None
-                        if getattr(p_, "_icl_factors", None) is not None:
-                            p_._icl_factors = None
-                o.lr_dev = None
-                o._open_scope(model)
-                return orig(*args)
-            o._graph_state = st
-        if not st.matches(args):
-            return orig(*args)              # another batch shape: eager (the pre-hook's scope stayed closed: plain autograd path)
-        return st.run(args)
-
-    model.forward = forward
-
-
 # ------------------------------------------------------------------------------------------------ FusedAdamW
-ADAMW_FACTORED_MAX_ROWS = 160   # factor rows up to which the update runs from the factors (icl_adamw_step_factored: plain VALU products, 24 B
-                                # per weight); above, the factors are multiplied out (ops._tall_atb) and the dense kernel runs.  Measured at
-                                # 13,824^2 (tools/adamw_probe.py, profiles/adamw.md section 2), factored against multiplied out: 64 rows
-                                # 1056 / 1495 us, 128 rows 1499 / 1691 us, 192 rows 2042 / 1882 us, 256 rows 2538 / 2076 us — the lines
-                                # cross at ~163 rows (8.5 against 3.0 us per row between 128 and 192)
-
-
 def _f32(x: float) -> float:
     return struct.unpack("f", struct.pack("f", x))[0]
 
@@ -905,7 +775,7 @@ def adamw_scalars(lr, weight_decay, beta1, beta2, eps, t):
             _f32(1.0 - beta2), _f32(eps))
 
 
-class FusedAdamW(torch.optim.Optimizer):
+class FusedAdamW(_ScopedOptimizer):
     """``torch.optim.AdamW(params, lr, betas, eps, weight_decay)`` (amsgrad=False, maximize=False) on one HIP pass per parameter
     (csrc/kernels/adamw.h), a one-line swap.  State per parameter as torch keeps it — ``step`` (CPU fp32 scalar tensor), ``exp_avg``,
     ``exp_avg_sq`` — so ``state_dict()`` / ``load_state_dict()`` interchange with torch.optim.AdamW in both directions.  Parameters
@@ -923,9 +793,10 @@ class FusedAdamW(torch.optim.Optimizer):
     counters, and ``advance_captured_step()`` advances them after every replay.
 
     ``max_grad_norm`` (None, or a positive number; single process): ``step()`` first clips the global 2-norm of all gradients, dense and
-    factored (``clip_grad_norm_`` below), and keeps the norm, a device scalar, in ``last_grad_norm`` (a view of a persistent buffer that
+    factored (``clip_grad_norm_`` above), and keeps the norm, a device scalar, in ``last_grad_norm`` (a view of a persistent buffer that
     every step overwrites).  The coefficient stays in device memory (``clip_dev``), so a captured step clips every replay by that
     replay's own norm; the buffers are created by the first eager step.  None: no launches, no buffers."""
+    _who = "FusedAdamW"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, step_scope: bool = True, max_grad_norm=None):
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
@@ -934,61 +805,11 @@ class FusedAdamW(torch.optim.Optimizer):
         # state_dict of either loads into the other; step() refuses the two it does not implement should a loaded dict switch them on
         defaults = dict(torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr, betas=tuple(betas), eps=eps,
                                           weight_decay=weight_decay).defaults)
-        super().__init__(params, defaults)
-        self.max_grad_norm, self.last_grad_norm, self._clip = _clip_option("FusedAdamW", max_grad_norm)
+        super().__init__(params, defaults, max_grad_norm)
         self.hyper_dev = None
         self._touched = None         # the parameters of the last step(): those a captured update touches (advance_captured_step)
-        self._scope_packed = None
         if step_scope:
-            models = {id(m): m for m in (model_of(p) for g in self.param_groups for p in g["params"]) if m is not None}
-            if len(models) == 1:
-                (model,) = models.values()
-                model.register_forward_pre_hook(_ScopePreHook(self))
-
-    @property
-    def clip_dev(self):
-        """{total_norm, coef} of the last clipped step (device fp32, 2 elements); None without ``max_grad_norm`` or before the first step."""
-        return None if self._clip is None else self._clip.clip_dev
-
-    def _clear_factors(self):
-        for group in self.param_groups:
-            for p in group["params"]:
-                if getattr(p, "_icl_factors", None) is not None:
-                    p._icl_factors = None
-
-    def zero_grad(self, set_to_none: bool = True):
-        self._clear_factors()
-        super().zero_grad(set_to_none=set_to_none)
-
-    def abandon_step(self):
-        """Discard what an iteration that will not reach ``step()`` left behind: factored gradients and the open step scope."""
-        self._clear_factors()
-        self._close_scope(flush=False)
-
-    # ---- step scope: FusedSGD's, without the update inside backward
-    def _open_scope(self, module):
-        from . import ops
-        if not module.training or not torch.is_grad_enabled():
-            return
-        scope = StepScope.current
-        if scope is not None:
-            if scope.owner() is self:
-                scope.packed.begin_step()      # a second training forward before step(): the scope stays open, weights are re-packed
-            return                             # (somebody else — ICLTrainer — has a step open)
-        if self._scope_packed is None:
-            self._scope_packed = ops.PackedWeights()
-        try:
-            import torch.distributed as dist
-            single = not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
-        except Exception:                # noqa: BLE001
-            single = True
-        StepScope.open(self._scope_packed, owner=self, lane_open=single, deferrals=single, complete_at_backward_end=single,
-                       factored=True if single else None, fused_optimizer=None)
-
-    def _close_scope(self, flush: bool = True):
-        scope = StepScope.current
-        if scope is not None and scope.owner() is self:
-            scope.close(flush)
+            self._attach_scope()     # the scope of the base class as it is: there is no update inside backward
 
     # ---- hipGraph replay
     def _hyper_group(self):
@@ -1042,14 +863,8 @@ class FusedAdamW(torch.optim.Optimizer):
     def step(self, closure=None):
         from . import ops
         L = _lib.lib()
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._close_scope()                     # lane joined, deferred bias gradients assigned, packed weights released
-        if self.max_grad_norm is not None:
-            self.last_grad_norm = _clip_gradients([p for group in self.param_groups for p in group["params"]], self.max_grad_norm, self._clip)
-        work = []                               # (group, parameter, dense gradient or None, factors or None)
+        loss = self._begin_step(closure)
+        work = []                               # (group, parameter, its factored gradient or None)
         for group in self.param_groups:
             if group.get("amsgrad") or group.get("maximize"):
                 raise RuntimeError("FusedAdamW implements amsgrad=False, maximize=False")
@@ -1059,11 +874,9 @@ class FusedAdamW(torch.optim.Optimizer):
                     continue
                 if getattr(p, "_icl_shard", None) is not None:
                     raise RuntimeError("FusedAdamW: row-sharded data-parallel updates (_icl_shard) are not implemented")
-                if not (p.is_contiguous() and p.dtype == torch.float32 and (g is None or (g.is_contiguous() and g.dtype == torch.float32))):
-                    raise RuntimeError("FusedAdamW needs contiguous fp32 parameters and gradients")
-                if not p.is_cuda and not _lib.host_pointers_ok():
-                    raise RuntimeError("FusedAdamW needs device tensors (no CPU fallback)")
-                work.append((group, p, g, fac))
+                _require_fp32("FusedAdamW", p, g)
+                _require_device("FusedAdamW", p.device)
+                work.append((group, p, _Gradient("FusedAdamW", p) if fac else None))
         if not work:
             return loss
         p0 = work[0][1]
@@ -1077,9 +890,9 @@ class FusedAdamW(torch.optim.Optimizer):
             hp = self.hyper_dev.data_ptr()
         elif capturing:
             raise RuntimeError("FusedAdamW.step() under stream capture needs hyper_dev: the scalars of a step change with its number")
-        stream = ctypes.c_void_p(torch.cuda.current_stream(p0.device).cuda_stream) if p0.is_cuda else None
-        small = {}                               # (id(group), first, t) -> [group, [(p, g, m, v), ...]]
-        for group, p, g, fac in work:
+        stream = _lib.stream_of(p0.device)
+        small = {}                               # (id(group), first, t) -> [scalars, (parameters, gradients, exp_avg, exp_avg_sq)]
+        for group, p, gr in work:
             st = self.state[p]
             if "step" not in st:
                 if capturing:
@@ -1096,36 +909,26 @@ class FusedAdamW(torch.optim.Optimizer):
                 raise RuntimeError("FusedAdamW needs contiguous fp32 state")
             b1, b2 = group["betas"]
             sc = adamw_scalars(float(group["lr"]), float(group["weight_decay"]), b1, b2, float(group["eps"]), t)
-            if fac:
-                rows = sum(f[0].shape[0] for f in fac)
+            g = p.grad
+            if gr is not None:
                 n, k = p.shape
-                if any(f[0].shape[1] != n or f[1].shape[1] != k or f[0].shape[0] != f[1].shape[0] for f in fac):
-                    raise RuntimeError("FusedAdamW: factored gradient does not match its parameter")
-                if g is None and rows <= ADAMW_FACTORED_MAX_ROWS and k % 4 == 0:
-                    gf = (fac[0][0] if len(fac) == 1 else torch.cat([f[0] for f in fac], 0)).contiguous()
-                    xf = (fac[0][1] if len(fac) == 1 else torch.cat([f[1] for f in fac], 0)).contiguous()
-                    with ops._timed("adamw_factored_kernel", 2.0 * rows * n * k, 24.0 * n * k, p):
-                        _lib.check(L.icl_adamw_step_factored(p.data_ptr(), m.data_ptr(), v.data_ptr(), gf.data_ptr(), xf.data_ptr(), rows, n,
-                                                             k, *sc, first, hp, stream), "adamw_step_factored")
-                    p._icl_factors = None
+                if gr.dense is None and gr.rows <= ADAMW_FACTORED_MAX_ROWS and k % 4 == 0:
+                    gf, xf, _ = gr.concatenated()
+                    with ops._timed("adamw_factored_kernel", 2.0 * gr.rows * n * k, 24.0 * n * k, p):
+                        _lib.check(L.icl_adamw_step_factored(p.data_ptr(), m.data_ptr(), v.data_ptr(), gf.data_ptr(), xf.data_ptr(), gr.rows,
+                                                             n, k, *sc, first, hp, stream), "adamw_step_factored")
+                    gr.drop_factors()
                     continue
-                # many factor rows, or a weight with a factored use AND a dense one in the same step: the factors are multiplied out
-                # into the dense gradient (csrc/kernels/gemm.h) and the ordinary update runs
-                for gf, xf in fac:
-                    d = ops._tall_atb(gf, xf, False)[0]
-                    g = d if g is None else g + d
-                p.grad = g
-                p._icl_factors = None
+                # many factor rows, rows the factored kernel does not take (k % 4), or a weight with a factored use AND a dense one in
+                # the same step: the factors are multiplied out into the dense gradient and the ordinary update runs
+                g = gr.multiply_out()
             if p.numel() >= _BIG:
                 _lib.check(L.icl_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), *sc, first, hp, stream),
                            "adamw_step")
             else:
-                small.setdefault((id(group), first, t), [sc, []])[1].append((p, g, m, v))
-        for (_, first, _t), (sc, items) in small.items():
-            n = len(items)
-            arr = ctypes.c_void_p * n
-            P_, G_, M_, V_ = (arr(*[it[j].data_ptr() for it in items]) for j in range(4))
-            N_ = (ctypes.c_int64 * n)(*[it[0].numel() for it in items])
-            _lib.check(L.icl_adamw_step_multi(P_, G_, M_, V_, N_, n, *sc, first, hp, stream), "adamw_step_multi")
+                for ts, t_ in zip(small.setdefault((id(group), first, t), [sc, ([], [], [], [])])[1], (p, g, m, v)):
+                    ts.append(t_)
+        for (_, first, _t), (sc, lists) in small.items():
+            _launch_many("icl_adamw_step_multi", lists, *sc, first, hp, stream)
         self._touched = [w[1] for w in work]
         return loss

@@ -158,6 +158,12 @@ _SIGNATURES = {
     "icl_loss_bwd": (c_int, [P, P, P, P, P, P, P, P, I, I, L, I, I, P]),
     "icl_loss_fwd_multi": (c_int, [P, I, P]),
     "icl_loss_bwd_multi": (c_int, [P, I, P]),
+    "icl_kl_fwd": (c_int, [P, P, P, P, L, I, L, F, F, P]),
+    "icl_kl_bwd": (c_int, [P, P, P, P, P, L, I, L, F, F, P]),
+    "icl_entropy_fwd": (c_int, [P, P, P, P, L, I, L, I, F, P]),
+    "icl_entropy_bwd": (c_int, [P, P, P, P, L, I, L, I, F, P]),
+    "icl_focal_fwd": (c_int, [P, P, P, P, P, L, I, L, F, I, P]),
+    "icl_focal_bwd": (c_int, [P, P, P, P, P, L, I, L, F, I, P]),
     "icl_qchain_stage": (c_int, [P, P]),
     "icl_qchain_wgrad": (c_int, [P, P, P, P, P, P, P, P, I, P]),
     "icl_seg_metrics_ws_bytes": (c_int64, [I, I, I, I]),

@@ -16,6 +16,7 @@
 #include "kernels/conv_cin1.h"
 #include "kernels/misc.h"
 #include "kernels/loss.h"
+#include "kernels/loss_point.h"
 #include "kernels/optim.h"
 #include "kernels/adamw.h"
 #include "kernels/gradclip.h"
@@ -1894,6 +1895,99 @@ int icl_loss_bwd(const float* a, const float* b, const int64_t* labels, const fl
                inv_elems, a_is_prob);
   }
   return check_launch("loss_grad");
+}
+
+// ---- voxel-wise losses (kernels/loss_point.h): class groups as above — registers for <= 4 and <= 16 classes, the class-walking body for
+// 17 .. 256 (or any count under ICL_LOSS_GENERIC=1).  POINT_DISPATCH launches `kern<4 | 16 | 0>` with the arguments behind it.
+#define ICL_POINT_DISPATCH(kern, nc, grid, st, ...)                                            \
+  do {                                                                                         \
+    if ((nc) > 16 || loss_force_generic()) ICL_LAUNCH((icl::kern<0>), grid, dim3(256), 0, st, __VA_ARGS__); \
+    else if ((nc) <= 4) ICL_LAUNCH((icl::kern<4>), grid, dim3(256), 0, st, __VA_ARGS__);       \
+    else ICL_LAUNCH((icl::kern<16>), grid, dim3(256), 0, st, __VA_ARGS__);                     \
+  } while (0)
+
+static int point_loss_shape(const char* who, int64_t outer, int nc, int64_t inner) {
+  if (nc < 1 || nc > icl::kLossMaxNc) return fail(-1, "%s: %d classes (1 .. %d)", who, nc, icl::kLossMaxNc);
+  if (outer < 1 || inner < 1) return fail(-1, "%s: bad argument", who);
+  return 0;
+}
+static int point_loss_finish(const char* who, hipStream_t st, const float* part, int nblk, float* out, double scale) {
+  int rc = check_launch(who);
+  if (rc) return rc;
+  ICL_LAUNCH(icl::point_finalize_kernel, dim3(1), dim3(256), 0, st, part, nblk, out, scale);
+  return check_launch("point_finalize");
+}
+
+int icl_kl_fwd(const float* a, const float* b, float* ws, float* out, int64_t outer, int nc, int64_t inner, float w_fwd, float w_rev,
+               void* stream) {
+  int rc = point_loss_shape("kl_fwd", outer, nc, inner);
+  if (rc) return rc;
+  if (!a || !b || !ws || !out) return fail(-1, "kl_fwd: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const long total = (long)outer * inner;
+  const int nblk = grid_for(total, 256, ICL_LOSS_MAX_BLOCKS);
+  ICL_POINT_DISPATCH(point_kl_fwd_kernel, nc, dim3(nblk), st, a, b, ws, (long)outer, nc, (long)inner, w_fwd, w_rev);
+  return point_loss_finish("kl_fwd", st, ws, nblk, out, 1.0 / ((double)total * (double)nc));
+}
+
+int icl_kl_bwd(const float* a, const float* b, const float* gout, float* ga, float* gb, int64_t outer, int nc, int64_t inner, float w_fwd,
+               float w_rev, void* stream) {
+  int rc = point_loss_shape("kl_bwd", outer, nc, inner);
+  if (rc) return rc;
+  if (!a || !b || !gout || (!ga && !gb)) return fail(-1, "kl_bwd: bad argument");
+  const long total = (long)outer * inner;
+  ICL_POINT_DISPATCH(point_kl_bwd_kernel, nc, dim3(grid_for(total, 256, 4096)), (hipStream_t)stream, a, b, gout, ga, gb, (long)outer, nc,
+                     (long)inner, w_fwd, w_rev, 1.0f / ((float)total * (float)nc));
+  return check_launch("kl_bwd");
+}
+
+int icl_entropy_fwd(const float* x, float* ws, float* out, float* map, int64_t outer, int nc, int64_t inner, int from_logits, float scale,
+                    void* stream) {
+  int rc = point_loss_shape("entropy_fwd", outer, nc, inner);
+  if (rc) return rc;
+  if (!x || (!out && !map)) return fail(-1, "entropy_fwd: bad argument");
+  if (out && !ws) return fail(-1, "entropy_fwd: the mean needs the workspace");
+  hipStream_t st = (hipStream_t)stream;
+  const long total = (long)outer * inner;
+  const int nblk = grid_for(total, 256, ICL_LOSS_MAX_BLOCKS);
+  ICL_POINT_DISPATCH(point_entropy_fwd_kernel, nc, dim3(nblk), st, x, out ? ws : (float*)nullptr, map, (long)outer, nc, (long)inner, from_logits,
+                     scale);
+  if (!out) return check_launch("entropy_fwd");
+  return point_loss_finish("entropy_fwd", st, ws, nblk, out, (double)scale / (double)total);
+}
+
+int icl_entropy_bwd(const float* x, const float* gout, const float* gmap, float* gx, int64_t outer, int nc, int64_t inner, int from_logits,
+                    float scale, void* stream) {
+  int rc = point_loss_shape("entropy_bwd", outer, nc, inner);
+  if (rc) return rc;
+  if (!x || !gx || (!gout && !gmap)) return fail(-1, "entropy_bwd: bad argument");
+  const long total = (long)outer * inner;
+  ICL_POINT_DISPATCH(point_entropy_bwd_kernel, nc, dim3(grid_for(total, 256, 4096)), (hipStream_t)stream, x, gout, gmap, gx, (long)outer, nc,
+                     (long)inner, from_logits, scale, 1.0f / (float)total);
+  return check_launch("entropy_bwd");
+}
+
+int icl_focal_fwd(const float* a, const int64_t* labels, const float* alpha, float* ws, float* out, int64_t outer, int nc, int64_t inner,
+                  float gamma, int mean, void* stream) {
+  int rc = point_loss_shape("focal_fwd", outer, nc, inner);
+  if (rc) return rc;
+  if (!a || !labels || !ws || !out || !(gamma >= 0.f)) return fail(-1, "focal_fwd: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const long total = (long)outer * inner;
+  const int nblk = grid_for(total, 256, ICL_LOSS_MAX_BLOCKS);
+  ICL_POINT_DISPATCH(point_focal_fwd_kernel, nc, dim3(nblk), st, a, (const long long*)labels, alpha, ws, (long)outer, nc, (long)inner, gamma);
+  return point_loss_finish("focal_fwd", st, ws, nblk, out, mean ? 1.0 / (double)total : 1.0);
+}
+
+int icl_focal_bwd(const float* a, const int64_t* labels, const float* alpha, const float* gout, float* ga, int64_t outer, int nc,
+                  int64_t inner, float gamma, int mean, void* stream) {
+  int rc = point_loss_shape("focal_bwd", outer, nc, inner);
+  if (rc) return rc;
+  if (!a || !labels || !gout || !ga || !(gamma >= 0.f)) return fail(-1, "focal_bwd: bad argument");
+  const long total = (long)outer * inner;
+  ICL_POINT_DISPATCH(point_focal_bwd_kernel, nc, dim3(grid_for(total, 256, 4096)), (hipStream_t)stream, a, (const long long*)labels, alpha,
+                     gout, ga, (long)outer, nc, (long)inner, gamma, mean ? 1.0f / (float)total : 1.0f);
+  return check_launch("focal_bwd");
 }
 
 int icl_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int64_t rows,

@@ -2644,6 +2644,149 @@ def softmax_mse(a: torch.Tensor, b: torch.Tensor):
 
 
 # --------------------------------------------------------------------------------------
+# Voxel-wise losses (utils/losses.py: softmax_kl_loss :93-112, compute_kl_loss :334-346, the entropy functions :33-39, :62-65, :321-331,
+# FocalLoss :149-183): csrc/kernels/loss_point.h — one pass and a one-block finalize forward, one pass backward, nothing kept between them
+# --------------------------------------------------------------------------------------
+
+def _class_axis(t: torch.Tensor, dim: int, what: str):
+    """(outer, nc, inner) of a contiguous tensor whose class axis is ``dim``."""
+    if t.dim() < 2:
+        raise ValueError(f"icl_amd {what}: needs a class axis, got shape {tuple(t.shape)}")
+    dim = dim % t.dim()
+    nc = t.shape[dim]
+    _check_classes(nc, what)
+    outer = math.prod(t.shape[:dim])
+    inner = math.prod(t.shape[dim + 1:])
+    if outer * inner < 1:
+        raise ValueError(f"icl_amd {what}: empty tensor {tuple(t.shape)}")
+    return outer, nc, inner
+
+
+def _point_ws(like: torch.Tensor) -> torch.Tensor:
+    return torch.empty(LOSS_MAX_BLOCKS, dtype=torch.float32, device=like.device)      # ICL_POINT_LOSS_WS_FLOATS
+
+
+class _SoftmaxKL(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, w_fwd, w_rev, dim):
+        _require(a, b)
+        assert a.shape == b.shape and a.dtype == torch.float32 and b.dtype == torch.float32, "softmax_kl: two fp32 tensors of one shape"
+        a, b = a.contiguous(), b.contiguous()
+        geo = _class_axis(a, dim, "softmax_kl")
+        out, ws = torch.empty(1, dtype=torch.float32, device=a.device), _point_ws(a)
+        _lib.check(_lib.lib().icl_kl_fwd(_ptr(a), _ptr(b), _ptr(ws), _ptr(out), *geo, w_fwd, w_rev, _stream(a)), "kl_fwd")
+        ctx.save_for_backward(a, b)
+        ctx.cfg = (geo, w_fwd, w_rev)
+        ctx.set_materialize_grads(False)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None
+        a, b = ctx.saved_tensors
+        geo, w_fwd, w_rev = ctx.cfg
+        g = g.contiguous()
+        ga = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        gb = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        _lib.check(_lib.lib().icl_kl_bwd(_ptr(a), _ptr(b), _ptr(g), _ptr(ga), _ptr(gb), *geo, w_fwd, w_rev, _stream(a)), "kl_bwd")
+        return ga, gb, None, None, None
+
+
+def softmax_kl(a: torch.Tensor, b: torch.Tensor, w_fwd: float = 1.0, w_rev: float = 0.0, dim: int = 1) -> torch.Tensor:
+    """w_fwd * mean KL(q || p) + w_rev * mean KL(p || q) with p = softmax(a, dim), q = softmax(b, dim); the mean is over ALL elements, as
+    F.kl_div(log_softmax(a), softmax(b), reduction='mean') takes it (losses.py:106-110).  The gradient reaches ``b`` when, and only
+    when, it requires one: the reference's softmax_kl_loss does not detach its target."""
+    return _SoftmaxKL.apply(a, b, float(w_fwd), float(w_rev), int(dim))
+
+
+class _Entropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, from_logits, scale, want_mean, want_map):
+        _require(x)
+        assert x.dtype == torch.float32, "entropy: fp32 input"
+        x = x.contiguous()
+        geo = _class_axis(x, 1, "entropy")
+        mean = torch.empty(1, dtype=torch.float32, device=x.device) if want_mean else None
+        emap = torch.empty((x.shape[0], 1) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device) if want_map else None
+        ws = _point_ws(x) if want_mean else None
+        _lib.check(_lib.lib().icl_entropy_fwd(_ptr(x), _ptr(ws), _ptr(mean), _ptr(emap), *geo,
+                                              int(from_logits), scale, _stream(x)), "entropy_fwd")
+        ctx.save_for_backward(x)
+        ctx.cfg = (geo, int(from_logits), scale)
+        ctx.set_materialize_grads(False)
+        return (mean[0] if want_mean else None), emap
+
+    @staticmethod
+    def backward(ctx, gmean, gmap):
+        if gmean is None and gmap is None:
+            return None, None, None, None, None
+        x, = ctx.saved_tensors
+        geo, from_logits, scale = ctx.cfg
+        gmean = gmean.contiguous() if gmean is not None else None
+        gmap = gmap.contiguous() if gmap is not None else None
+        gx = torch.empty_like(x)
+        _lib.check(_lib.lib().icl_entropy_bwd(_ptr(x), _ptr(gmean), _ptr(gmap), _ptr(gx), *geo, from_logits, scale, _stream(x)),
+                   "entropy_bwd")
+        return gx, None, None, None, None
+
+
+def entropy(p: torch.Tensor, from_logits: bool = False, scale: float = 1.0, want: str = "mean"):
+    """H_v = -sum_c p_c log(p_c + 1e-6) over dim 1 of [B, nc, ...] probabilities (``from_logits``: of softmax(p, 1), fused), times
+    ``scale`` (1, or 1 / log C for entropy_loss): want = "mean" the mean over the voxels (0-dim), "map" the [B, 1, ...] map, "both" the
+    pair from one pass."""
+    if want not in ("mean", "map", "both"):
+        raise ValueError(f"icl_amd entropy: want = 'mean', 'map' or 'both', not {want!r}")
+    mean, emap = _Entropy.apply(p, bool(from_logits), float(scale), want != "map", want != "mean")
+    return mean if want == "mean" else (emap if want == "map" else (mean, emap))
+
+
+class _Focal(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, alpha, gamma, mean, dim):
+        _require(logits, labels, alpha)
+        assert logits.dtype == torch.float32, "focal_loss: fp32 logits"
+        logits, labels = logits.contiguous(), labels.contiguous()
+        geo = _class_axis(logits, dim, "focal_loss")
+        assert labels.dtype == torch.int64 and labels.numel() == geo[0] * geo[2], "focal_loss: int64 labels, one per voxel"
+        out, ws = torch.empty(1, dtype=torch.float32, device=logits.device), _point_ws(logits)
+        _lib.check(_lib.lib().icl_focal_fwd(_ptr(logits), _ptr(labels), _ptr(alpha), _ptr(ws), _ptr(out), *geo, gamma,
+                                            int(mean), _stream(logits)), "focal_fwd")
+        ctx.save_for_backward(logits, labels, alpha)
+        ctx.cfg = (geo, gamma, int(mean))
+        ctx.set_materialize_grads(False)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None, None, None
+        logits, labels, alpha = ctx.saved_tensors
+        geo, gamma, mean = ctx.cfg
+        g = g.contiguous()
+        ga = torch.empty_like(logits)
+        _lib.check(_lib.lib().icl_focal_bwd(_ptr(logits), _ptr(labels), _ptr(alpha), _ptr(g), _ptr(ga), *geo, gamma, mean,
+                                            _stream(logits)), "focal_bwd")
+        return ga, None, None, None, None, None
+
+
+def focal_loss(logits: torch.Tensor, labels: torch.Tensor, gamma: float = 2.0, alpha: Optional[torch.Tensor] = None,
+               size_average: bool = True) -> torch.Tensor:
+    """FocalLoss.forward (losses.py:160-183): -alpha_y (1 - pt)^gamma log pt per voxel, pt = softmax(logits, 1)_y, mean or sum over the
+    voxels.  ``logits`` [N, C, ...] or [M, C], ``labels`` int64 with one entry per voxel, ``alpha`` None or a float tensor of at least C
+    entries on the logits' device.  (1 - pt)^gamma is a constant of the backward pass, as in the reference (pt from ``.data``).
+    A label outside [0, C) indexes nothing — its voxel adds 0 to the value and to the gradient and still counts in the mean — where the
+    reference's gather raises on the CPU."""
+    if gamma < 0:
+        raise ValueError(f"icl_amd focal_loss: gamma >= 0, not {gamma}")
+    if alpha is not None:
+        if alpha.numel() < logits.shape[1]:
+            raise ValueError(f"icl_amd focal_loss: alpha has {alpha.numel()} entries for {logits.shape[1]} classes")
+        alpha = alpha.detach().to(device=logits.device, dtype=torch.float32).contiguous()
+    return _Focal.apply(logits, labels, alpha, float(gamma), bool(size_average), 1)
+
+
+# --------------------------------------------------------------------------------------
 # Validation metrics — cal_metric / calculate_metric_percase of every foreground class (val_3D.py:85-97, val_2D.py:10-22)
 # --------------------------------------------------------------------------------------
 

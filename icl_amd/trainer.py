@@ -42,6 +42,9 @@ class ICLConfig:
     eps: float = 1e-8                  # of "adamw"
     max_grad_norm: Optional[float] = None   # clip the global gradient 2-norm, dense and factored, before every update (one process); for
                                             # "sgd" this also switches the update inside backward off; the step's result gains "grad_norm"
+    consistency: str = "mse"           # "kl": the consistency leaves are softmax KL divergences (ops.softmax_kl), targets detached as for MSE
+    w_ent: float = 0.0                 # weight of the entropy of the unlabelled prediction (ops.entropy(outputs[1], from_logits=True)) as one
+                                       # more leaf; non-zero: the step's result gains "ent"
 
 
 class ICLTrainer:
@@ -49,6 +52,8 @@ class ICLTrainer:
         self.model, self.cfg, self.ddp = model, cfg, ddp
         if cfg.max_grad_norm is not None and ddp is not None and ddp.active:
             raise ValueError("ICLConfig.max_grad_norm is single-process: the norm would have to be taken after the gradient exchange")
+        if cfg.consistency not in ("mse", "kl"):
+            raise ValueError(f"ICLConfig.consistency: 'mse' or 'kl', not {cfg.consistency!r}")
         if cfg.optimizer == "adamw":
             if ddp is not None and ddp.active:
                 raise ValueError("ICLConfig.optimizer='adamw' is single-process: FusedAdamW has no row-sharded or gathered-factor update")
@@ -88,40 +93,50 @@ class ICLTrainer:
         cfg = self.cfg
         lab = label_batch[:cfg.labeled_bs]
         # CrossEntropyLoss()(out0, y) and DiceLoss(softmax(out0), y) (…BraTS.py:105-108) from one fused pass
-        n_terms = 1 + len(outputs[2]) + len(outputs[3]) + len(outputs[4])
+        kl = cfg.consistency == "kl"       # the KL pairs are launches of their own beside ops.fused_losses
+        n_terms = 1 + len(outputs[2]) + len(outputs[3]) + (0 if kl else len(outputs[4]))
         if hasattr(self.aux_loss, "terms") and hasattr(self.pse_loss, "terms") and n_terms <= ops.LOSS_MULTI_MAX:
             # round 6: the ten reductions of the objective — CE + Dice on the logits, the AuxLoss3D / PseudoSoftLoss3D maps, the
             # softmax-MSE pairs — in ONE statistics launch + one finalize (and one gradient launch in backward): ops.fused_losses
             terms = ([(outputs[0], lab, 1)] + self.aux_loss.terms(outputs[2], lab) + self.pse_loss.terms(outputs[3], outputs[1])
-                     + [(a, b, 3) for a, b in zip(outputs[3], outputs[4])])
+                     + ([] if kl else [(a, b, 3) for a, b in zip(outputs[3], outputs[4])]))
             pairs = ops.fused_losses(terms)
             na_, np_ = len(outputs[2]), len(outputs[3])
             loss_ce, loss_dice = pairs[0]
             aux = [v for p in pairs[1:1 + na_] for v in p]                     # [ce_0, dice_0, ce_1, ...]
             pse = [p[1] for p in pairs[1 + na_:1 + na_ + np_]]
-            con = [p[0] for p in pairs[1 + na_ + np_:]]
+            con = L.softmax_kl_leaves(outputs[3], outputs[4]) if kl else [p[0] for p in pairs[1 + na_ + np_:]]
         else:
             loss_ce, loss_dice = ops.cross_entropy_dice_parts(outputs[0], lab, cfg.num_classes)
             aux = self.aux_loss.leaves(outputs[2], lab)
             pse = self.pse_loss.leaves(outputs[3], outputs[1])
-            con = L.softmax_mse_leaves(outputs[3], outputs[4])
+            con = (L.softmax_kl_leaves if kl else L.softmax_mse_leaves)(outputs[3], outputs[4])
         # every term of the five-part objective as a leaf scalar, the weighted sums (loss = dice + ce + aux + w_pse pse + w_con con,
         # aux / pse / con = means over the scales) in ONE launch: out = [loss, aux, pse, con]
-        leaves = [loss_dice, loss_ce] + aux + pse + con
+        ent = [ops.entropy(outputs[1], from_logits=True)] if cfg.w_ent != 0.0 else []
+        leaves = [loss_dice, loss_ce] + aux + pse + con + ent
         if len(leaves) > 16:      # more scales than the combine kernel takes: the class-level means, then the sum
             loss_aux = self.aux_loss(outputs[2], lab)
             loss_pse = self.pse_loss(outputs[3], outputs[1])
-            loss_con = L.softmax_mse_loss(outputs[3], outputs[4])
+            loss_con = L._mean_of(con) if kl else L.softmax_mse_loss(outputs[3], outputs[4])
             loss = loss_dice + loss_ce + loss_aux + cfg.w_pse * loss_pse + cfg.w_con * loss_con
-            return loss, dict(dice=loss_dice, ce=loss_ce, aux=loss_aux, pse=loss_pse, con=loss_con)
+            parts = dict(dice=loss_dice, ce=loss_ce, aux=loss_aux, pse=loss_pse, con=loss_con)
+            if ent:
+                loss = loss + cfg.w_ent * ent[0]
+                parts["ent"] = ent[0]
+            return loss, parts
         na, npse, ncon = len(aux), len(pse), len(con)
         nmaps = max(len(outputs[2]), 1)
         wa, wp, wc = [1.0 / nmaps] * na, [1.0 / max(npse, 1)] * npse, [1.0 / max(ncon, 1)] * ncon
         z = lambda k: [0.0] * k      # noqa: E731
-        W = [[1.0, 1.0] + wa + [cfg.w_pse * v for v in wp] + [cfg.w_con * v for v in wc],
-             z(2) + wa + z(npse) + z(ncon), z(2) + z(na) + wp + z(ncon), z(2) + z(na) + z(npse) + wc]
+        ne = len(ent)
+        W = [[1.0, 1.0] + wa + [cfg.w_pse * v for v in wp] + [cfg.w_con * v for v in wc] + [cfg.w_ent] * ne,
+             z(2) + wa + z(npse) + z(ncon) + z(ne), z(2) + z(na) + wp + z(ncon) + z(ne), z(2) + z(na) + z(npse) + wc + z(ne)]
         out = ops.combine_scalars(leaves, W)
-        return out[0], dict(dice=loss_dice, ce=loss_ce, aux=out[1], pse=out[2], con=out[3])
+        parts = dict(dice=loss_dice, ce=loss_ce, aux=out[1], pse=out[2], con=out[3])
+        if ent:
+            parts["ent"] = ent[0]
+        return out[0], parts
 
     def _forward_backward(self, volume_batch, label_batch, boundary=None):
         """``boundary()`` (capture only) is called between the loss and ``loss.backward()``."""

@@ -5,8 +5,17 @@ tensor attached to autograd.
 
 Differences from the reference that do not change results: no per-class ``.item()`` host syncs
 (losses.py:229 forces nc device→host round trips per call), and the trilinear resize runs on the HIP kernel.
+
+The rest of the reference's module — softmax_kl_loss :93-112, compute_kl_loss :334-346, entropy_loss :33-39, entropy_loss_map :62-65,
+entropy_minmization :321-325, entropy_map :328-331, FocalLoss :149-183 — runs on the voxel-wise kernels (ops.softmax_kl, ops.entropy,
+ops.focal_loss); dice_loss :11-19 is a torch expression like dice_loss1.
+
+Out of scope: KD_Loss, symmetric_mse_loss, cos_sim_loss and EAMLoss (their loops index element 0 or keep only the last iterate in the
+reference, and no trainer calls them), and the ``sigmoid=True`` branches.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 import torch.nn as nn
@@ -21,6 +30,14 @@ def dice_loss1(score, target):
     smooth = 1e-5
     intersect = torch.sum(score * target)
     return 1 - (2 * intersect + smooth) / (torch.sum(score) + torch.sum(target) + smooth)
+
+
+def dice_loss(score, target):
+    """losses.py:11-19 — squared sums in the denominator."""
+    target = target.float()
+    smooth = 1e-5
+    intersect = torch.sum(score * target)
+    return 1 - (2 * intersect + smooth) / (torch.sum(score * score) + torch.sum(target * target) + smooth)
 
 
 def softmax_dice_loss(input_logits, target_logits):
@@ -46,6 +63,68 @@ def softmax_mse_loss(input_logits, target_logits, sigmoid=False):
     if sigmoid:
         raise NotImplementedError("the ICL trainers never pass sigmoid=True")
     return _mean_of(softmax_mse_leaves(input_logits, target_logits))
+
+
+def softmax_kl_loss(input_logits, target_logits, sigmoid=False):
+    """losses.py:93-112: F.kl_div(log_softmax(input, 1), softmax(target, 1), reduction='mean'), the mean over ALL elements.  The
+    reference does not detach its target, whatever its docstring says: ``target_logits`` gets a gradient when it requires one."""
+    assert input_logits.size() == target_logits.size()
+    if sigmoid:
+        raise NotImplementedError("softmax_kl_loss(sigmoid=True) is not built")
+    return ops.softmax_kl(input_logits, target_logits, 1.0, 0.0, dim=1)
+
+
+def softmax_kl_leaves(input_logits, target_logits):
+    """Per-scale KL consistency terms against detached targets (the trainer's consistency="kl")."""
+    return [ops.softmax_kl(a, b.detach()) for a, b in zip(input_logits, target_logits)]
+
+
+def compute_kl_loss(p, q):
+    """losses.py:334-346: lists of logits, soft-max over the last axis; per pair (mean KL(q||p) + mean KL(p||q)) / 2, then the mean
+    over the list.  Gradients reach both arguments."""
+    return _mean_of([ops.softmax_kl(a, b, 0.5, 0.5, dim=-1) for a, b in zip(p, q)])
+
+
+def entropy_loss(p, C=2):
+    """losses.py:33-39: mean over the voxels of -sum_c p log(p + 1e-6) / log C; ``p`` holds probabilities [N, C, ...]."""
+    return ops.entropy(p, scale=1.0 / math.log(C), want="mean")
+
+
+def entropy_loss_map(p, C=2):
+    """losses.py:62-65: the [N, 1, ...] map of -sum_c p log(p + 1e-6) / log C."""
+    return ops.entropy(p, scale=1.0 / math.log(C), want="map")
+
+
+def entropy_minmization(p):
+    """losses.py:321-325 (the reference's spelling): mean over the voxels of -sum_c p log(p + 1e-6)."""
+    return ops.entropy(p, want="mean")
+
+
+def entropy_map(p):
+    """losses.py:328-331: the [N, 1, ...] map of -sum_c p log(p + 1e-6)."""
+    return ops.entropy(p, want="map")
+
+
+class FocalLoss(nn.Module):
+    """losses.py:149-183.  A float ``alpha`` becomes [alpha, 1 - alpha], a list is used as given; input [N, C, ...] or [M, C], target
+    integer class ids, one per voxel.  (1 - pt)^gamma is a constant of the backward pass, as in the reference (pt from ``.data``).
+    A label outside [0, C) adds 0 to the value and to the gradient and still counts in the mean; the reference's gather raises on it on
+    the CPU."""
+
+    def __init__(self, gamma=2, alpha=None, size_average=True):
+        super().__init__()
+        self.gamma = gamma
+        self.alpha = alpha
+        if isinstance(alpha, (float, int)):
+            self.alpha = torch.Tensor([alpha, 1 - alpha])
+        if isinstance(alpha, list):
+            self.alpha = torch.Tensor(alpha)
+        self.size_average = size_average
+
+    def forward(self, input, target):
+        if self.alpha is not None and (self.alpha.device != input.device or self.alpha.dtype != torch.float32):
+            self.alpha = self.alpha.to(device=input.device, dtype=torch.float32)      # once, as the reference's type_as
+        return ops.focal_loss(input, target.long(), self.gamma, self.alpha, self.size_average)
 
 
 class DiceLoss(nn.Module):

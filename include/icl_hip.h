@@ -306,6 +306,33 @@ typedef struct IclLossJob {
 int icl_loss_fwd_multi(const IclLossJob* jobs, int count, void* stream);
 int icl_loss_bwd_multi(const IclLossJob* jobs, int count, void* stream);
 
+/* ---- voxel-wise losses (utils/losses.py: softmax_kl_loss :93-112, compute_kl_loss :334-346, entropy_loss :33-39, entropy_loss_map
+ * :62-65, entropy_minmization :321-325, entropy_map :328-331, FocalLoss :149-183), forward and backward.  Tensors are (outer, nc, inner):
+ * the class axis has stride `inner` (inner = S: dim 1 of [B, nc, ...]; inner = 1: the last axis of [M, nc]).  1 <= nc <= 256 with the
+ * class groups of icl_loss_fwd; outside that range, on a NULL pointer or on outputs that do not fit the call -1 is returned and nothing
+ * is launched.  ws: ICL_POINT_LOSS_WS_FLOATS floats of per-workgroup partials, summed in a fixed order (no atomics, nothing to zero,
+ * bit-reproducible); nothing is kept from the forward for the backward pass.  out / gout: one float.
+ *   KL       out = w_fwd mean KL(q||p) + w_rev mean KL(p||q), p = softmax(a), q = softmax(b), mean over the outer*nc*inner elements
+ *            (F.kl_div(reduction='mean')); logs are v - lse (an underflowed class adds 0).  ga or gb may be NULL (no gradient wanted there), not both.
+ *   entropy  H_v = -sum_c p_c log(p_c + 1e-6), p = x or softmax(x) (from_logits); out = scale * mean_v H_v and / or map[v] = scale * H_v
+ *            (either may be NULL, not both); gout / gmap: their upstream gradients (either may be NULL, not both).
+ *   focal    loss_v = -alpha_y (1 - pt)^gamma log pt, pt = softmax(a)_y; out = mean (mean != 0) or sum over the voxels; alpha (nc floats)
+ *            may be NULL.  (1 - pt)^gamma is a constant of the backward pass, as in the reference (pt from .data).  A label outside
+ *            [0, nc) indexes nothing: its voxel adds 0 to the value and gets a zero gradient, and still counts in the mean. */
+#define ICL_POINT_LOSS_WS_FLOATS ICL_LOSS_MAX_BLOCKS
+int icl_kl_fwd(const float* a, const float* b, float* ws, float* out, int64_t outer, int nc, int64_t inner, float w_fwd, float w_rev,
+               void* stream);
+int icl_kl_bwd(const float* a, const float* b, const float* gout, float* ga, float* gb, int64_t outer, int nc, int64_t inner, float w_fwd,
+               float w_rev, void* stream);
+int icl_entropy_fwd(const float* x, float* ws, float* out, float* map, int64_t outer, int nc, int64_t inner, int from_logits, float scale,
+                    void* stream);
+int icl_entropy_bwd(const float* x, const float* gout, const float* gmap, float* gx, int64_t outer, int nc, int64_t inner, int from_logits,
+                    float scale, void* stream);
+int icl_focal_fwd(const float* a, const int64_t* labels, const float* alpha, float* ws, float* out, int64_t outer, int nc, int64_t inner,
+                  float gamma, int mean, void* stream);
+int icl_focal_bwd(const float* a, const int64_t* labels, const float* alpha, const float* gout, float* ga, int64_t outer, int nc,
+                  int64_t inner, float gamma, int mean, void* stream);
+
 /* ---- aligner token operators (networks/unet_3D_icl.py:244-315)
  * LayerNorm over the last axis c of [rows, c] (nn.LayerNorm, eps 1e-5); mean/rstd [rows] are saved for the backward;
  * dgamma/dbeta (may both be NULL) are overwritten: row-chunk partial sums go to `ws` (icl_layernorm_bwd_ws_bytes) and are added in
